@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- generator+D step throughput of the PDGN hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 35] [--no-cpu-baseline] [--eval]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 35] [--dump-outputs DIR] [--full [--no-cpu-baseline]] [--eval]
 
 A "step" is one complete training iteration of models/PDGNet_v2.py:171-256 (generator forward
 x2, four discriminator updates, six local-pair shape losses, generator backward, five Adam
@@ -12,6 +12,18 @@ N > 1: one rank per GPU over RCCL.  Launched through torch.distributed.run (the 
 are already there; launched as plain `python bench.py --gpus N`, this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD -- before anything here has
 touched a GPU -- relays rank 0's JSON line and exits with the child's code.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps and prints the headline line (points/s, ms_per_step).  --full adds what
+else the line has carried: the executed flops of one extra iteration, ms_per_step_x3, the roofline kernels and gemm_accuracy,
+eval_c5 and cpu_baseline (each still left out by its --no-* option).  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy: the six losses it returns.  So that they repeat from run to run with the same arguments, that
+step starts from the seeded initial state (weights, BatchNorm statistics, fresh Adam moments), restored off the clock after step
+K-1: float atomics and kNN ties let a trajectory of several iterations drift apart from run to run, one iteration from a fixed
+state does not (measured: d_loss1-4 bit for bit, g_loss and similar_loss within 1.3e-4 relative).  The weights it updates are
+not written: from fresh moments Adam moves a weight whose gradient is at rounding level by +-lr, so they differ from run to run
+by more than rounding.  A dumping run's ms_per_step includes one drain of the device: its last step starts on an idle GPU after
+the restore, where a plain run's overlaps the issue of its launches with the step before (measured at K = 30, alternating with
+plain runs: +0.07 and +0.09 ms per step).
 
 --eval times configuration C5 instead (evaluation path: Chamfer + approximate EMD on 512 pairs of
 2048-point clouds, evaluation/evaluation_metrics.py:26-45, 85-121) and prints its own JSON line.
@@ -50,6 +62,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=35, help="per-GPU batch (BASELINE.json: 35)")
     ap.add_argument("--base-points", type=int, default=128, help="128: 256->2048 (reference); 256: 512->4096")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: executed flops, ms_per_step_x3, roofline + gemm_accuracy, eval_c5, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the six losses of the last timed step, run from the seeded initial state, as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-batch", type=int, default=35,
                     help="batch of the CPU-baseline sample: 35 = the batch the metric is quoted on (one iteration, ~18 s on "
@@ -304,9 +320,10 @@ def emd_issue_model(elements):
     return cyc / 64.0, ins / tot, trans / cyc
 
 
-def eval_c5(pairs=512, steps=5, warmup=1):
+def eval_c5(pairs=512, steps=5, warmup=1, dump=None):
     """Config C5: Chamfer (nn_distance) + approximate EMD (fused pdgn_emd_cost) on `pairs` pairs of 2048 x 2048 points,
-    evaluation/evaluation_metrics.py:26-45, 85-121.  Returns the fields of its bench line."""
+    evaluation/evaluation_metrics.py:26-45, 85-121.  Returns the fields of its bench line; `dump`: a directory that receives
+    the last timed step's per-pair Chamfer and EMD (cd.npy, emd.npy)."""
     import torch
     from pdgn_amd.structural_losses import emd_cost, nn_distance
     P, N = pairs, 2048
@@ -326,6 +343,8 @@ def eval_c5(pairs=512, steps=5, warmup=1):
         cd, emd = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    if dump:
+        write_outputs(dump, {"cd": cd, "emd": emd})
     ms_emd, ms_cd = _event_ms(lambda: emd_cost(a, b)), _event_ms(lambda: nn_distance(a, b))
     # emd_cost_kernel is bound by vector-instruction ISSUE, not by HBM (inputs: 25 MB) and not by the transcendental
     # unit alone: `peak` = the pair rate at which the instruction stream it EXECUTES on this input (the sorted sweeps skip
@@ -358,7 +377,7 @@ def eval_main(args):
     """bench.py --eval: config C5 as a line of its own."""
     import torch
     torch.cuda.set_device(0)
-    r = eval_c5(args.eval_pairs, args.steps, args.warmup)
+    r = eval_c5(args.eval_pairs, args.steps, args.warmup, dump=args.dump_outputs)
     P = r["pairs"]
     line = {"metric": "Chamfer + approx-EMD structural losses, pairs/sec (2048-pt pairs, B=%d)" % P,
             "value": r["pairs_per_s"], "unit": "pairs/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -405,6 +424,37 @@ def main():
         dist.destroy_process_group()
 
 
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every tensor in `arrays` (float32 / float64, from the device after a synchronise)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
+def initial_state(trainer):
+    """Copies of the parameters and buffers of G and D1..D4 before the first iteration: the seeded initial weights and BatchNorm
+    statistics (the optimizers hold no state yet)."""
+    return [t.detach().clone() for net in [trainer.G] + trainer.D for t in list(net.parameters()) + list(net.buffers())]
+
+
+def restore_initial_state(trainer, initial):
+    """Put the trainer back to where `initial_state` found it, in place (a recorded launch list keeps its pointers): the weights
+    and buffers copied back, every Adam moment and step counter zero, as in a fresh optimizer.  The float atomics of the weight
+    gradients and ties in the kNN graphs make two runs' trajectories drift apart from the second iteration on; an iteration from
+    this state returns the same losses in every run, to rounding."""
+    import torch
+    with torch.no_grad():
+        for t, v in zip([t for net in [trainer.G] + trainer.D for t in list(net.parameters()) + list(net.buffers())], initial):
+            t.copy_(v)
+        for opt in [trainer.optG] + trainer.optD:
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+
+
 def x3_leg(args, device, reals, zs, steps=10, warmup=3):
     """The same iteration with every contraction on three bf16 parts (six bf16 MFMA products per fp32 product: the arithmetic that
     needs no operand scale at all, PDGN_GEMM=x3), from a second trainer built in that mode, issued as a launch list like the
@@ -442,6 +492,9 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
     import torch
     import torch.distributed as dist
     B = args.batch
+    full = getattr(args, "full", False)         # everything beside the headline (executed flops, x3 leg, roofline, C5, CPU)
+    # --dump-outputs: the seeded initial state, restored in front of the last timed step (see restore_initial_state)
+    initial = initial_state(trainer) if getattr(args, "dump_outputs", None) else None
     step, graphed = trainer.step, False
     if args.graph and not args.no_graph and not trainer.distributed:
         try:                                   # one hipGraph per iteration (trainer.capture)
@@ -477,7 +530,7 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
     # the dominant kernel (conv2's dense half, stage 4, forward: one launch per generator pass) timed INSIDE the timed steps: HIP
     # events around each of its launches, on the stream the launch list issues it on (csrc/replay.hip)
     in_step = None
-    if issue == "list" and not getattr(args, "no_roofline", False):
+    if issue == "list" and full and not getattr(args, "no_roofline", False):
         try:
             from pdgn_amd import roofline as _rf
             spans = _rf.conv2_in_step_spans(trainer._list, args.batch, args.base_points)
@@ -487,11 +540,17 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
         except Exception as e:
             print("in-step kernel timing unavailable (%r)" % (e,), file=sys.stderr)
     barrier()
-    t0 = time.perf_counter()
+    t0, paused = time.perf_counter(), 0.0
     for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:        # (off the clock: every rank restores its own replicas)
+            barrier()
+            t1 = time.perf_counter()
+            restore_initial_state(trainer, initial)
+            barrier()
+            paused = time.perf_counter() - t1
         out = step(reals, *zs[args.warmup + i])
     barrier()
-    dt_local = time.perf_counter() - t0
+    dt_local = time.perf_counter() - t0 - paused
     if in_step:
         try:
             in_step = trainer._list.timed_ms()
@@ -507,11 +566,13 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
         dts = [x.item() for x in all_t]
         dt = max(dts)
     finite = all(torch.isfinite(v).item() for v in out.values())
+    if rank == 0 and initial is not None:                        # before any further iteration changes the weights
+        write_outputs(args.dump_outputs, out)
 
     # The flop-logging iteration is a full trainer.step(): under data parallelism it issues the gradient all-reduces, so
     # EVERY rank runs it (rank 0 alone would wait for collectives nobody else joins); only rank 0's log is reported.
     flops = None
-    if not graphed:
+    if full and not graphed:
         try:
             flops = executed_flops(trainer, reals, *zs[0])
         except Exception as e:
@@ -559,14 +620,14 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
             line["step_frac_of_fp32_instruction_peak"] = total / (ms * 1e-3) / (MFMA_F32_PEAK_TFLOPS * 1e12)
             line["direct_form_flops_per_step"] = DIRECT_FORM_FLOPS_PER_SAMPLE * B
             line["algebraic_saving"] = DIRECT_FORM_FLOPS_PER_SAMPLE * B / total if total else None
-        if world == 1 and not graphed and not getattr(args, "no_x3_leg", False) and not args.no_roofline:      # (traces run with --no-roofline: one trainer's kernels only)
+        if full and world == 1 and not graphed and not getattr(args, "no_x3_leg", False) and not args.no_roofline:      # (traces run with --no-roofline: one trainer's kernels only)
             try:
                 from pdgn_amd import _lib as _l
                 if _l.gemm_mode() == "x2":
                     line["ms_per_step_x3"] = x3_leg(args, device, reals, zs)
             except Exception as e:                               # never lose the headline number
                 line["ms_per_step_x3"] = {"error": repr(e)}
-        if not args.no_roofline:
+        if full and not args.no_roofline:
             try:
                 from pdgn_amd import roofline
                 line["roofline"] = roofline.measure(args.batch, args.base_points, device)
@@ -575,12 +636,12 @@ def measure_and_report(args, trainer, reals, zs, world, rank, device, res):
                 line["gemm_accuracy"] = roofline.gemm_accuracy(device)        # both kernels against fp64, same operands
             except Exception as e:                               # never lose the headline number
                 line["roofline"] = {"error": repr(e)}
-        if world == 1 and not args.no_eval_c5:               # BASELINE.json configs[4], ~0.3 s: Chamfer + EMD, 512 pairs
+        if full and world == 1 and not args.no_eval_c5:               # BASELINE.json configs[4], ~0.3 s: Chamfer + EMD, 512 pairs
             try:
                 line["eval_c5"] = eval_c5()
             except Exception as e:
                 line["eval_c5"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:          # host baseline: rank 0, N = 1 only
+        if full and not args.no_cpu_baseline and world == 1:          # host baseline: rank 0, N = 1 only
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_batch)
         print(json.dumps(line), flush=True)
         return line

@@ -43,17 +43,29 @@ def test_reference_import_lines_resolve_to_pdgn_amd(compat_path):
     assert match_cost is sl.match_cost and nn_distance is sl.nn_distance
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/evaluation"), reason="reference checkout not on this machine")
-def test_reference_modules_import_through_compat():
-    """The reference's evaluation_metrics.py and models/PDGNet_v2.py imported UNEDITED, compat/ in front of the reference on
-    sys.path (a child process: the reference wants `h5py`, absent here, which gets an empty stand-in module)."""
+def test_reference_modules_import_through_compat(tmp_path):
+    """The reference's evaluation_metrics.py and models/PDGNet_v2.py imported through compat/ (a child process), with compat/ in
+    front of the reference tree on sys.path.  The tree is a stand-in under tmp_path that holds the reference's own import lines
+    (evaluation/evaluation_metrics.py:9-10, models/PDGNet_v2.py:17, 21): evaluation_metrics must come from that tree although
+    compat/ shadows its package (the extend_path of compat/evaluation and compat/lib), and its names must be pdgn_amd's."""
+    ref = tmp_path / "reference"
+    for d in ("evaluation", "lib", "models"):
+        (ref / d).mkdir(parents=True)
+    (ref / "evaluation" / "__init__.py").write_text("")
+    (ref / "lib" / "__init__.py").write_text("")
+    (ref / "evaluation" / "evaluation_metrics.py").write_text(
+        "from evaluation.StructuralLosses.match_cost import match_cost\n"
+        "from evaluation.StructuralLosses.nn_distance import nn_distance\n")
+    (ref / "models" / "PDGNet_v2.py").write_text(
+        "from lib.pointops.functions import pointops\n"
+        "from evaluation.evaluation_metrics import *\n")
     code = (
-        "import sys, types; sys.modules['h5py'] = types.ModuleType('h5py');"
-        "sys.path[:0] = [%r, %r, '/root/reference'];"
+        "import sys; sys.path[:0] = [%r, %r, %r];"
         "import evaluation.evaluation_metrics as em, models.PDGNet_v2 as net, pdgn_amd.pointops as po, pdgn_amd.structural_losses as sl;"
         "assert em.match_cost is sl.match_cost and em.nn_distance is sl.nn_distance;"
+        "assert net.match_cost is sl.match_cost and net.nn_distance is sl.nn_distance;"
         "assert net.pointops.knnquery is po.knnquery and net.pointops.Gen_QueryAndGroupXYZ is po.Gen_QueryAndGroupXYZ;"
-        "assert em.__file__.startswith('/root/reference'); print('ok')" % (COMPAT, ROOT))
+        "assert em.__file__.startswith(%r); print('ok')" % (COMPAT, ROOT, str(ref), str(ref)))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 

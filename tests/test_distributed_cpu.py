@@ -268,7 +268,8 @@ def _worker_bench(rank, world, port, out_dir):
     res = (32, 64, 128, 256)
     reals = [torch.randn(B, 3, n, generator=g) for n in res]
     args = argparse.Namespace(batch=B, steps=1, warmup=0, graph=False, no_graph=False, no_roofline=True,
-                              no_cpu_baseline=True, base_points=16, cpu_sample_batch=2)
+                              no_cpu_baseline=True, base_points=16, cpu_sample_batch=2, full=True,
+                              dump_outputs=os.path.join(out_dir, "dump"))
     zs = [(torch.randn(B, 128, generator=g) * 0.2, torch.randn(B, 128, generator=g) * 0.2)]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
@@ -289,6 +290,7 @@ def test_bench_measurement_with_two_ranks_gloo():
     with tempfile.TemporaryDirectory() as d:
         mp.spawn(_worker_bench, args=(world, _free_port(), d), nprocs=world, join=True)
         r = [dict(np.load(os.path.join(d, "bench%d.npz" % i))) for i in range(world)]
+        dump = {f[:-4]: np.load(os.path.join(d, "dump", f)) for f in os.listdir(os.path.join(d, "dump"))}
     assert bool(r[0]["has_line"]) and not bool(r[1]["has_line"]) and str(r[1]["printed"]) == ""
     lines = [l for l in str(r[0]["printed"]).splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -296,6 +298,9 @@ def test_bench_measurement_with_two_ranks_gloo():
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["config"]["global_batch"] == 8
     assert line["config"]["losses_finite"] is True and line["ms_per_step_min_rank"] <= line["ms_per_step_max_rank"]
     assert "error" not in json.dumps(line.get("executed_flops_per_step"))
+    # --dump-outputs: rank 0 wrote the six losses of its last timed step
+    assert sorted(dump) == sorted(["d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss"])
+    assert all(a.dtype == np.float32 and a.shape == () and np.isfinite(a) for a in dump.values())
 
 
 def _worker_late_gradient(rank, world, port, out_dir):

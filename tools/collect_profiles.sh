@@ -6,8 +6,8 @@ OUT=${1:-gpurun_out/prof}; TAG=${2:-r06}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 # the bench line as the driver runs it (launch-list issue, cpu_baseline at B = 35), and the same with every launch issued from Python
-python3 bench.py --steps 30 --warmup 5 > $OUT/${TAG}_bench_full.json 2> $OUT/bench.err
-python3 bench.py --steps 30 --warmup 5 --issue eager --no-cpu-baseline --no-eval-c5 > $OUT/${TAG}_bench_eager.json 2>> $OUT/bench.err
+python3 bench.py --steps 30 --warmup 5 --full > $OUT/${TAG}_bench_full.json 2> $OUT/bench.err
+python3 bench.py --steps 30 --warmup 5 --full --issue eager --no-cpu-baseline --no-eval-c5 > $OUT/${TAG}_bench_eager.json 2>> $OUT/bench.err
 python3 bench.py --eval --steps 10 --warmup 2 > $OUT/${TAG}_eval_c5.json 2>> $OUT/bench.err
 # kernel trace + stats of the bench command (the launch-list step) and its reductions
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_bench -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-eval-c5 > $OUT/kt_bench.log 2>&1
@@ -41,7 +41,7 @@ for c in 0 4 5; do python3 -u tools/list_progress.py 10 $c 2>&1 | grep -v amdgpu
 python3 tools/host_time.py > $OUT/${TAG}_host_time.txt 2>&1
 python3 tools/phase_events.py > $OUT/${TAG}_phases_overlapped.txt 2>&1
 python3 tools/finalize_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_finalize_bench.txt
-python3 bench.py --base-points 256 --steps 10 --warmup 3 --no-cpu-baseline --no-eval-c5 > $OUT/${TAG}_bench_c4.json 2>> $OUT/bench.err
+python3 bench.py --base-points 256 --steps 10 --warmup 3 --full --no-cpu-baseline --no-eval-c5 > $OUT/${TAG}_bench_c4.json 2>> $OUT/bench.err
 # round 5: both bf16 matrix instructions (x3_check with the shape forced), the launch list under a one-rank RCCL group, the
 # torch-native / library launches with their owners, the block fixtures' backward error, the register table of the shipped library
 PDGN_GEMM=x3 python3 tools/x3_check.py 16 2>&1 | grep -v amdgpu.ids > $OUT/${TAG}_x3_check_16x16x32.txt
