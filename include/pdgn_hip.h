@@ -653,6 +653,30 @@ int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *co
  * replaces torch._foreach_copy_. */
 int pdgn_copy_multi(int ntensors, void *const *dst, const void *const *src, const long long *n, pdgn_stream_t stream);
 
+/* ------------------------------------------------------------------ deterministic mode
+ * pdgn_set_deterministic: process-wide switch, like pdgn_gemm_set_mode.  -1 queries the current value; any other value
+ * sets it (non-zero: on) and returns the previous one.  PDGN_DETERMINISTIC=1 in the environment at first use turns it on;
+ * the default is off.  The _det entry points below are the fixed-order forms of the scatter-add adjoints above: bitwise
+ * repeatable (each output sums its contributions in increasing index order, with no float atomics), same arguments plus
+ * an integer workspace of the caller's.  The Python layer picks them while the mode is on (pdgn_amd._lib.deterministic). */
+int pdgn_set_deterministic(int on);
+/* Ints of workspace one CSR transpose of an index tensor takes: b * (2 * targets + 1 + edges). */
+long long pdgn_det_workspace_ints(int b, int targets, long long edges);
+/* pdgn_grouping_backward, fixed order: ws = pdgn_det_workspace_ints(b, n, m * nsample) ints; grad_points ACCUMULATED. */
+int pdgn_grouping_backward_det(int b, int c, int n, int m, int nsample, const float *grad_out, const int32_t *idx,
+                               int32_t *ws, float *grad_points, pdgn_stream_t stream);
+/* pdgn_interpolation_backward, fixed order: ws = pdgn_det_workspace_ints(b, m, 3 * n) ints; grad_points ACCUMULATED. */
+int pdgn_interpolation_backward_det(int b, int c, int n, int m, const float *grad_out, const int32_t *idx,
+                                    const float *weight, int32_t *ws, float *grad_points, pdgn_stream_t stream);
+/* pdgn_gathering_backward, fixed order: ws = pdgn_det_workspace_ints(b, n, m) ints; grad_points ACCUMULATED. */
+int pdgn_gathering_backward_det(int b, int c, int n, int m, const float *grad_out, const int32_t *idx, int32_t *ws,
+                                float *grad_points, pdgn_stream_t stream);
+/* pdgn_nndistance_grad, fixed order (a point's own term first, then those of the other cloud's points whose nearest it
+ * is, in their index order): ws = pdgn_det_workspace_ints(b, n, m) + pdgn_det_workspace_ints(b, m, n) ints. */
+int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float *xyz2, const float *grad_dist1,
+                             const int32_t *idx1, const float *grad_dist2, const int32_t *idx2, int32_t *ws,
+                             float *grad_xyz1, float *grad_xyz2, pdgn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,3 +8,12 @@ Sub-modules mirror the reference's plugin boundary:
 All device code is hand-written HIP for gfx950 behind the C ABI in include/pdgn_hip.h.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # deterministic mode (DESIGN.md section 5), re-exported lazily: importing the package (pdgn_amd.build among others)
+    # loads neither torch nor the library
+    if name in ("deterministic", "set_deterministic"):
+        from . import _lib
+        return getattr(_lib, name)
+    raise AttributeError("module 'pdgn_amd' has no attribute %r" % name)

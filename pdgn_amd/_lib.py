@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libpdgn_hip.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 
@@ -31,6 +31,7 @@ def lib():
         got = handle.pdgn_abi_version()
         if got != ABI_VERSION:
             raise PdgnHipError("libpdgn_hip.so ABI %d != expected %d: rebuild" % (got, ABI_VERSION))
+        handle.pdgn_det_workspace_ints.restype = ctypes.c_longlong
         _lib = handle
         if handle.pdgn_gemm_set_mode(-1) == 2:                     # the default mode: a ring on the current device now (raw ctypes callers);
             ensure_scale_slots(handle=handle)                      # the wrappers move it if the contractions run on another one
@@ -128,3 +129,45 @@ def set_gemm_config(cfg):
     """Force a tile configuration of pdgn_gemm_nt / _nn (0 .. 3; None or -1: the launch model's pick).  Measurement / tests.
     Returns the previous value (-1: automatic)."""
     return lib().pdgn_gemm_set_config(-1 if cfg is None else int(cfg))
+
+
+# ---------------------------------------------------------------------------- deterministic mode
+_DET_EXPLICIT = bool(os.environ.get("PDGN_DETERMINISTIC"))       # the environment counts as an explicit setting (the library reads it too)
+_det_synced = None                                               # the value last handed to the library while following torch's flag
+
+
+def deterministic():
+    """Whether the library's deterministic mode is in force: the value set by `set_deterministic` (or PDGN_DETERMINISTIC in the
+    environment); with neither, torch.are_deterministic_algorithms_enabled() at call time; pdgn_set_deterministic holds the value.
+    What the mode covers: the backward of pointops grouping / interpolation / gathering and of nn_distance run in a fixed order
+    (bitwise repeatable).  The training step is NOT covered yet: PDGNTrainer.step / capture_list warn (DeterminismWarning)
+    when they run with the mode on."""
+    global _det_synced
+    if _DET_EXPLICIT:
+        return bool(lib().pdgn_set_deterministic(-1))
+    on = torch.are_deterministic_algorithms_enabled()
+    if on != _det_synced:                                        # the library's own choices follow the same value
+        lib().pdgn_set_deterministic(int(on))
+        _det_synced = on
+    return on
+
+
+def set_deterministic(on):
+    """Turn the deterministic mode on (True) or off (False) for this process, overriding torch's flag; None returns to following
+    torch.are_deterministic_algorithms_enabled().  Returns the previous value (True / False, what `deterministic()` said)."""
+    global _DET_EXPLICIT, _det_synced
+    old = deterministic()
+    if on is None:
+        _DET_EXPLICIT, _det_synced = False, None
+        deterministic()
+    else:
+        lib().pdgn_set_deterministic(1 if on else 0)
+        _DET_EXPLICIT = True
+    return old
+
+
+def det_workspace(device, *transposes):
+    """Integer workspace of a fixed-order scatter adjoint: pdgn_det_workspace_ints per (b, targets, edges) transpose it makes."""
+    L = lib()
+    ints = sum(L.pdgn_det_workspace_ints(int(b), int(t), ctypes.c_longlong(e)) for b, t, e in transposes)
+    return torch.empty(ints, dtype=torch.int32, device=device)

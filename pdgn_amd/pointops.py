@@ -88,6 +88,12 @@ class Grouping(Function):
         b, c, m, nsample = grad_out.size()
         grad_features = torch.zeros((b, c, n), dtype=F32, device=grad_out.device)
         grad_out_data = grad_out.data.contiguous()
+        if _lib.deterministic():                         # fixed order: a gather over the sorted transpose of idx
+            ws = _lib.det_workspace(grad_out.device, (b, n, m * nsample))
+            check(_lib.lib().pdgn_grouping_backward_det(b, c, n, m, nsample, ptr(grad_out_data), ptr(idx), ptr(ws),
+                                                        ptr(grad_features), stream_of(grad_out_data)),
+                  "pdgn_grouping_backward_det")
+            return grad_features, None
         check(_lib.lib().pdgn_grouping_backward(b, c, n, m, nsample, ptr(grad_out_data), ptr(idx),
                                                 ptr(grad_features), stream_of(grad_out_data)),
               "pdgn_grouping_backward")
@@ -144,6 +150,12 @@ class Interpolation(Function):
         b, c, n = grad_out.size()
         grad_features = torch.zeros((b, c, m), dtype=F32, device=grad_out.device)
         grad_out_data = grad_out.data.contiguous()
+        if _lib.deterministic():
+            ws = _lib.det_workspace(grad_out.device, (b, m, 3 * n))
+            check(_lib.lib().pdgn_interpolation_backward_det(b, c, n, m, ptr(grad_out_data), ptr(idx), ptr(weight), ptr(ws),
+                                                             ptr(grad_features), stream_of(grad_out_data)),
+                  "pdgn_interpolation_backward_det")
+            return grad_features, None, None
         check(_lib.lib().pdgn_interpolation_backward(b, c, n, m, ptr(grad_out_data), ptr(idx), ptr(weight),
                                                      ptr(grad_features), stream_of(grad_out_data)),
               "pdgn_interpolation_backward")
@@ -202,6 +214,11 @@ class Gathering(Function):
         b, m = idx.shape
         grad_out = grad_out.contiguous()
         grad = torch.zeros((b, c, n), dtype=F32, device=grad_out.device)
+        if _lib.deterministic():
+            ws = _lib.det_workspace(grad_out.device, (b, n, m))
+            check(_lib.lib().pdgn_gathering_backward_det(b, c, n, m, ptr(grad_out), ptr(idx), ptr(ws), ptr(grad),
+                                                         stream_of(grad_out)), "pdgn_gathering_backward_det")
+            return grad, None
         check(_lib.lib().pdgn_gathering_backward(b, c, n, m, ptr(grad_out), ptr(idx), ptr(grad), stream_of(grad_out)),
               "pdgn_gathering_backward")
         return grad, None

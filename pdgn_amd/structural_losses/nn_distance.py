@@ -34,6 +34,12 @@ def NNDistanceGrad(set_d, set_q, idx1, idx2, grad_dist1, grad_dist2):
     grad_dist2 = grad_dist2.contiguous()
     grad1 = torch.empty((b, n, 3), dtype=F32, device=set_d.device)
     grad2 = torch.empty((b, m, 3), dtype=F32, device=set_d.device)
+    if _lib.deterministic():                             # fixed order: own term, then the other cloud's in index order
+        ws = _lib.det_workspace(set_d.device, (b, n, m), (b, m, n))
+        check(_lib.lib().pdgn_nndistance_grad_det(b, n, ptr(set_d), m, ptr(set_q), ptr(grad_dist1), ptr(idx1),
+                                                  ptr(grad_dist2), ptr(idx2), ptr(ws), ptr(grad1), ptr(grad2),
+                                                  stream_of(set_d)), "pdgn_nndistance_grad_det")
+        return [grad1, grad2]
     check(_lib.lib().pdgn_nndistance_grad(b, n, ptr(set_d), m, ptr(set_q), ptr(grad_dist1), ptr(idx1),
                                           ptr(grad_dist2), ptr(idx2), ptr(grad1), ptr(grad2),
                                           stream_of(set_d)), "pdgn_nndistance_grad")

@@ -7,11 +7,13 @@ as ONE flat fp32 buffer per network (G: 50.8 MB, D1-4: 6.8 MB) -- parameters' ``
 are views into that buffer, so there is no bucket copy in or out.
 """
 import os
+import warnings
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import _lib
 from . import streams as _streams
 from .fused import clear_zero_colsum, flush_bn_counters, hold_bn_counters, release_zero_arena, reset_zero_arena
 from .generator import PointDiscriminator, PointGenerator
@@ -193,6 +195,20 @@ def _recorder(device):
     from . import replay
     rec = replay.recorder()
     return rec if rec is not None and _capturing(device) else None
+
+
+class DeterminismWarning(UserWarning):
+    """The library's deterministic mode is on, but the operation at hand has no fixed-order form yet."""
+
+
+def _warn_if_deterministic(what):
+    """The deterministic mode (pdgn_amd.set_deterministic, or torch's flag) covers the reference-compatible pointops /
+    nn_distance adjoints; the training step still sums with float atomics: say so instead of
+    letting a user who asked for repeatable runs believe they have them."""
+    if _lib.deterministic():
+        warnings.warn("PDGNTrainer.%s: deterministic mode is on, but the training step has no fixed-order form yet -- its "
+                      "weight gradients and adjoints still sum with float atomics, so runs are not bitwise repeatable "
+                      "(DESIGN.md section 5)" % what, DeterminismWarning, stacklevel=3)
 
 
 def world_size():
@@ -541,6 +557,7 @@ class PDGNTrainer:
     def step(self, reals, z1, z2):
         """reals: four tensors (B,3,N_k); z1 / z2: noise (B,128) of the two generator passes
         (:178, :228).  Returns dict of 0-dim device tensors (no host sync inside the step)."""
+        _warn_if_deterministic("step")
         if self.overlap:
             return self._step_overlapped(reals, z1, z2)
         st = self._state(reals, z1, z2)
@@ -772,6 +789,7 @@ class PDGNTrainer:
         from . import replay
         if not self.overlap:
             raise RuntimeError("capture_list: stream-overlapped schedule only")
+        _warn_if_deterministic("capture_list")
         self._static = self._state([r.clone() for r in reals], z1.clone(), z2.clone())
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
