@@ -677,6 +677,33 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
                              const int32_t *idx1, const float *grad_dist2, const int32_t *idx2, int32_t *ws,
                              float *grad_xyz1, float *grad_xyz2, pdgn_stream_t stream);
 
+/* ------------------------------------------------------------------ batch feeder
+ * One launch fills one training batch from a device-resident data set: replaces ShapeNetCore.__getitem__'s three
+ * np.random.choice sub-samplings and the DataLoader's shuffled collate (datasets_4point.py:370-380), the unpacking, the four
+ * transposes and the two np.random.normal(0, 0.2) draws of the training loop (models/PDGNet_v2.py:171-178, 184, 195, 206, 217,
+ * 228).  data (S,N,3) normalised clouds; order (S) int32, the epoch's permutation of [0, S) (entries are clamped to that
+ * range); local row b takes cloud c = order[first + b]:
+ *   p4[b] (3,N)     = data[c] transposed;
+ *   pk[b,:,j]       = data[c, i, :], i uniform in [0, N) drawn WITH replacement, independently per row, resolution, iteration;
+ *   z1, z2 (B,128)  ~ N(0, sigma^2).
+ * Randomness is Philox4x32-10 (Salmon et al., SC'11), counter-based and a pure function of the arguments -- no device state,
+ * no dependence on grid shape or launch order:
+ *   key     = (seed low 32, seed high 32)
+ *   counter = (group j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8)
+ *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order)
+ * A group is the four output words of one counter.  Index streams: word e of group j is column 4j + e, i = (word * N) >> 32
+ * (bias of a point's probability at most N / 2^32 relative: 4.8e-7 at N = 2048).  Noise: group j gives columns 4j .. 4j+3 as
+ * two Box-Muller pairs (words 0,1 and 2,3): u1 = ((w >> 8) + 1) * 2^-24 in (0, 1], u2 = (w' >> 8) * 2^-24 in [0, 1),
+ * (sigma * sqrt(-2 ln u1) * cos(2 pi u2), sigma * sqrt(-2 ln u1) * sin(2 pi u2)), evaluated in fp32 with the accurate logf /
+ * sincosf.  With the GLOBAL row (row0 = rank * B) and the global iteration t, W ranks at local batch B draw exactly what one
+ * rank draws at batch B * W.  The clouds are bit-exact copies; one thread writes four consecutive columns (16-byte stores
+ * where the row length is a multiple of 4 and the base 16-byte aligned).
+ * PDGN_ERR_INVALID: B <= 0 or > 65535, S, N or an r <= 0, first < 0, first + B > S, row0 < 0 or row0 + B > 2^32, a null
+ * pointer, z1 / z2 not 16-byte aligned.  All of these are checked on the host before anything is launched. */
+int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
+                    unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2, float *p3,
+                    float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,163 @@
+// feed.hip -- pdgn_feed_batch: one launch writes a whole training batch (the four real resolutions and the two noise
+// tensors) from a device-resident data set into the buffers the training step reads.  Replaces, per iteration, the
+// DataLoader's shuffle + collate, ShapeNetCore.__getitem__'s three np.random.choice sub-samplings
+// (datasets_4point.py:370-380), the four transposes (models/PDGNet_v2.py:184,195,206,217) and the two np.random.normal
+// draws (:178, :228).  Randomness: Philox4x32-10, counter-based, a pure function of the arguments (layout in
+// include/pdgn_hip.h); the host mirror of the tests (tests/feed_mirror.py) spells the same function in numpy.
+//
+// One thread = one 4-word Philox group = four consecutive output columns of one row: four gathered points (12 floats
+// in, one 16-byte store per channel), four points of the transposed full cloud (48 contiguous bytes in, one 16-byte
+// store per channel) or four normals (one 16-byte store).  A wave therefore writes 1 KiB contiguous per channel.
+// No LDS, no atomics.
+#include "common.h"
+
+#define FEED_THREADS 256
+#define FEED_NOISE_DIM 128                                      // (B,128): models/PDGNet_v2.py:178 with main.py:23's default
+#define FEED_TAG_Z1 3u
+#define FEED_TAG_Z2 4u
+
+struct FeedArgs {
+    int S, N, r[3];
+    int g[6];                                                    // exclusive prefix of the groups of one row: p1 p2 p3 p4 z1 z2 (g[5] + 32 = all)
+    int groups;
+    int vec;                                                     // bit k: output k (p1 p2 p3 p4) takes 16-byte stores; bit 4: the cloud rows take 16-byte loads
+    const float *data;
+    const int *order;
+    long long first;
+    unsigned k0, k1, t_lo, t_hi24;
+    unsigned row0;
+    float sigma;
+    float *p[4];
+    float *z[2];
+};
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+// two normals from two words: u1 in (0, 1], u2 in [0, 1), both exact in fp32; the accurate logf / sincosf (the tests bound the
+// deviation from an fp64 evaluation by a multiple of an fp32 host evaluation's own)
+__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float sigma, float &n0, float &n1) {
+    float u1 = (float)((wa >> 8) + 1u) * 5.9604644775390625e-8f;
+    float u2 = (float)(wb >> 8) * 5.9604644775390625e-8f;
+    float rad = sqrtf(-2.0f * logf(u1));
+    float s, c;
+    sincosf(6.2831855f * u2, &s, &c);
+    n0 = sigma * (rad * c);
+    n1 = sigma * (rad * s);
+}
+
+__device__ __forceinline__ void store4(float *dst, int cols, bool vec, float a, float b, float c, float d) {
+    if (vec) {                                                   // (vec: the row length is a multiple of 4, so cols == 4 here)
+        *reinterpret_cast<float4 *>(dst) = make_float4(a, b, c, d);
+    } else {
+        dst[0] = a;
+        if (cols > 1) dst[1] = b;
+        if (cols > 2) dst[2] = c;
+        if (cols > 3) dst[3] = d;
+    }
+}
+
+__global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
+    const int q = blockIdx.x * FEED_THREADS + threadIdx.x;       // the group of row b this thread owns
+    const int b = blockIdx.y;
+    if (q >= a.groups) return;
+    const unsigned row = a.row0 + (unsigned)b;
+    unsigned w[4];
+    if (q >= a.g[4]) {                                           // ---- noise: group j of z1 / z2 -> columns 4j .. 4j+3
+        const int which = q >= a.g[5];
+        const int j = q - a.g[4 + which];
+        philox4x32_10((unsigned)j, row, a.t_lo, (which ? FEED_TAG_Z2 : FEED_TAG_Z1) | (a.t_hi24 << 8), a.k0, a.k1, w);
+        float n0, n1, n2, n3;
+        box_muller(w[0], w[1], a.sigma, n0, n1);
+        box_muller(w[2], w[3], a.sigma, n2, n3);
+        *reinterpret_cast<float4 *>(a.z[which] + (size_t)b * FEED_NOISE_DIM + 4 * j) = make_float4(n0, n1, n2, n3);   // (128 floats per row: 16-byte aligned whenever the base is; checked on the host)
+        return;
+    }
+    const int c = min(max(a.order[a.first + b], 0), a.S - 1);    // (a permutation of [0, S) by contract; clamped so that a bad one cannot read outside data)
+    const float *cloud = a.data + (size_t)c * a.N * 3;
+    if (q >= a.g[3]) {                                           // ---- the full cloud, transposed: points 4j .. 4j+3
+        const int j = q - a.g[3];
+        const int cols = min(4, a.N - 4 * j);
+        const float *src = cloud + (size_t)12 * j;
+        float v[12];
+        if (a.vec & 16) {
+            const float4 *s4 = reinterpret_cast<const float4 *>(src);
+            float4 x = s4[0], y = s4[1], z = s4[2];
+            v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w, v[4] = y.x, v[5] = y.y, v[6] = y.z, v[7] = y.w;
+            v[8] = z.x, v[9] = z.y, v[10] = z.z, v[11] = z.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) v[i] = i < 3 * cols ? src[i] : 0.f;
+        }
+        float *dst = a.p[3] + (size_t)b * 3 * a.N + 4 * j;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            store4(dst + (size_t)ch * a.N, cols, a.vec & 8, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
+        return;
+    }
+    // ---- a sub-resolution: columns 4j .. 4j+3 of p_k[b] are the points i = umulhi(word, N), drawn with replacement
+    const int k = (q >= a.g[1]) + (q >= a.g[2]);
+    const int j = q - a.g[k];
+    const int r = a.r[k];
+    const int cols = min(4, r - 4 * j);
+    philox4x32_10((unsigned)j, row, a.t_lo, (unsigned)k | (a.t_hi24 << 8), a.k0, a.k1, w);
+    float v[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float *pt = cloud + (size_t)__umulhi(w[i], (unsigned)a.N) * 3;
+        v[3 * i] = pt[0], v[3 * i + 1] = pt[1], v[3 * i + 2] = pt[2];
+    }
+    float *dst = a.p[k] + (size_t)b * 3 * r + 4 * j;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        store4(dst + (size_t)ch * r, cols, (a.vec >> k) & 1, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
+}
+
+extern "C" int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
+                               unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
+                               float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
+    // host-side checks only: nothing here touches the device
+    if (B <= 0 || B > 65535 || S <= 0 || N <= 0 || r1 <= 0 || r2 <= 0 || r3 <= 0) return PDGN_ERR_INVALID;
+    if (first < 0 || first > (long long)S - B) return PDGN_ERR_INVALID;                       // first + B > S
+    if (row0 < 0 || row0 + B > 0x100000000LL) return PDGN_ERR_INVALID;                        // the global row is one 32-bit counter word
+    if (!data || !order || !p1 || !p2 || !p3 || !p4 || !z1 || !z2) return PDGN_ERR_INVALID;
+    if ((((uintptr_t)z1 | (uintptr_t)z2) & 15) || (((uintptr_t)data | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)p4) & 3))
+        return PDGN_ERR_INVALID;
+    if ((long long)N > 0x7fffffffLL / 3 || (long long)r1 + r2 + r3 + N > 0x7fffff00LL) return PDGN_ERR_INVALID;
+    FeedArgs a;
+    a.S = S, a.N = N, a.r[0] = r1, a.r[1] = r2, a.r[2] = r3;
+    const int len[4] = {r1, r2, r3, N};
+    float *const out[4] = {p1, p2, p3, p4};
+    int at = 0;
+    a.vec = 0;
+    for (int k = 0; k < 4; ++k) {
+        a.g[k] = at;
+        at += (len[k] + 3) / 4;
+        a.p[k] = out[k];
+        if (len[k] % 4 == 0 && !((uintptr_t)out[k] & 15)) a.vec |= 1 << k;
+    }
+    if (N % 4 == 0 && !((uintptr_t)data & 15)) a.vec |= 16;
+    a.g[4] = at, a.g[5] = at + FEED_NOISE_DIM / 4;
+    a.groups = at + 2 * (FEED_NOISE_DIM / 4);
+    a.data = data, a.order = order, a.first = first;
+    a.k0 = (unsigned)seed, a.k1 = (unsigned)(seed >> 32);
+    a.t_lo = (unsigned)t, a.t_hi24 = (unsigned)(t >> 32) & 0xffffffu;
+    a.row0 = (unsigned)row0;
+    a.sigma = sigma;
+    a.z[0] = z1, a.z[1] = z2;
+    dim3 grid(cdiv(a.groups, FEED_THREADS), B);
+    hipLaunchKernelGGL(feed_batch_kernel, grid, dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    return pdgn_launch_status();
+}

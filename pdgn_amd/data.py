@@ -5,7 +5,12 @@ The reference normalises cloud by cloud in a Python loop at load time; here the 
 tensor expressions over a (S, N, 3) stack.  `ShapeNetCore` reads the same HDF5 layout
 (`f[synsetid][split] -> (S, N, 3)`) -- from a path when `h5py` is installed, or from any mapping with that
 shape (which is also how the tests drive it: this image has no h5py).
+
+`BatchFeeder` is the training-side feed: the whole split stays on the device and ONE launch (csrc/feed.hip,
+pdgn_feed_batch) writes a batch -- shuffled clouds, the three sub-samplings, the transposes and both noise draws --
+into the buffers the training step reads.
 """
+import ctypes
 import os
 import random
 
@@ -138,3 +143,127 @@ class ShapeNetCore(torch.utils.data.Dataset):
         """All clouds of the split as one (S,N,3) tensor in data-set order (the test phase's `ref_pcs`, :293-298)."""
         pcs = torch.stack([d["pointcloud"] for d in self.pointclouds], 0)
         return pcs.to(device) if device is not None else pcs
+
+
+# ---------------------------------------------------------------------------- the training feed (csrc/feed.hip)
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_TAG_ORDER = 5                                                  # stream tags 0..4 belong to pdgn_feed_batch (include/pdgn_hip.h)
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on numpy arrays of 32-bit words held in uint64 -> four arrays of words."""
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & mask, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & mask
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def epoch_order(seed, epoch, S):
+    """The permutation of [0, S) an epoch visits the clouds in (the DataLoader's shuffle=True, models/PDGNet_v2.py:78):
+    a stable argsort of S Philox words, key (seed lo, seed hi), counter (group, epoch lo, epoch hi, tag 5).  A pure function of
+    its arguments, computed on the host: resuming at an epoch boundary needs no saved generator state."""
+    seed, epoch, S = int(seed), int(epoch), int(S)
+    g = np.arange((S + 3) // 4, dtype=np.uint64)
+    full = lambda v: np.full_like(g, v)
+    words = _philox4x32_10(g, full(epoch & 0xFFFFFFFF), full((epoch >> 32) & 0xFFFFFFFF), full(_TAG_ORDER),
+                           seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    return np.argsort(np.stack(words, axis=1).reshape(-1)[:S], kind="stable").astype(np.int32)
+
+
+def batches_per_epoch(S, B, world=1):
+    """Full batches only, as the reference does (models/PDGNet_v2.py:79, :169); the global batch is B * world."""
+    return int(S) // (int(B) * int(world))
+
+
+class BatchFeeder:
+    """A device-resident split and the launch that turns it into training batches.
+
+    clouds: (S, N, 3) fp32 device tensor (`ShapeNetCore.stack(device)`; `from_dataset` does that and refuses a data set with a
+    per-item `transform`, for which the device path has no hook).  sizes: the three sub-resolutions (a fourth entry must
+    equal N).  Batch i of `epoch` on `rank` of `world` takes the clouds order[(i * world + rank) * B ...] of
+    `epoch_order(seed, epoch, S)`; global rows rank * B + b and the global iteration (epoch - 1) * batches_per_epoch + i index
+    the random streams, so that `world` ranks at batch B draw what one rank draws at batch B * world."""
+
+    NOISE_DIM = 128
+
+    def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2):
+        from . import _lib
+        if not isinstance(clouds, torch.Tensor):
+            if getattr(clouds, "transform", None) is not None:
+                raise ValueError("BatchFeeder: the data set has a per-item transform; the device feed has no per-item Python hook")
+            raise TypeError("BatchFeeder takes the (S,N,3) device tensor of a split (ShapeNetCore.stack(device), or "
+                            "BatchFeeder.from_dataset)")
+        _lib.require(clouds, "clouds", torch.float32, 3)
+        if clouds.shape[2] != 3:
+            raise ValueError("clouds must be (S,N,3), got %s" % (tuple(clouds.shape),))
+        sizes = tuple(int(r) for r in sizes)
+        if len(sizes) == 4 and sizes[3] == clouds.shape[1]:
+            sizes = sizes[:3]
+        if len(sizes) != 3 or min(sizes) < 1:
+            raise ValueError("sizes: the three sub-resolutions (optionally followed by N), got %r" % (sizes,))
+        self.clouds, self.sizes = clouds, sizes
+        self.S, self.N = int(clouds.shape[0]), int(clouds.shape[1])
+        self.B, self.seed, self.rank, self.world, self.sigma = int(batch_size), int(seed), int(rank), int(world), float(sigma)
+        if self.B < 1 or self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError("batch_size >= 1 and 0 <= rank < world, got %d, %d, %d" % (self.B, self.rank, self.world))
+        self.batches_per_epoch = batches_per_epoch(self.S, self.B, self.world)
+        if self.batches_per_epoch < 1:
+            raise ValueError("%d clouds do not make one batch of %d x %d" % (self.S, self.B, self.world))
+        self._order = torch.empty(self.S, dtype=torch.int32, device=clouds.device)
+        self._order_host = torch.empty(self.S, dtype=torch.int32).pin_memory()
+        self._order_epoch = None
+        self._fn = _lib.lib().pdgn_feed_batch
+        self._check = None
+
+    @classmethod
+    def from_dataset(cls, dataset, device, batch_size, sizes=(256, 512, 1024), seed=0, **kw):
+        if getattr(dataset, "transform", None) is not None:
+            raise ValueError("BatchFeeder: the data set has a per-item transform; the device feed has no per-item Python hook")
+        return cls(dataset.stack(device).float().contiguous(), batch_size, sizes, seed, **kw)
+
+    def shapes(self):
+        """Shapes of (p1, p2, p3, p4, z)."""
+        return [(self.B, 3, r) for r in self.sizes + (self.N,)] + [(self.B, self.NOISE_DIM)]
+
+    def buffers(self):
+        """Fresh (reals, z1, z2) of the right shapes on the clouds' device."""
+        sh = self.shapes()
+        new = lambda s: torch.empty(s, dtype=torch.float32, device=self.clouds.device)
+        return [new(s) for s in sh[:4]], new(sh[4]), new(sh[4])
+
+    def _upload_order(self, epoch):
+        # the previous epoch's upload may not have run yet, and it reads the pinned staging buffer when it runs
+        if self._order_epoch is not None:
+            self._order_copied.synchronize()
+        self._order_host.copy_(torch.from_numpy(epoch_order(self.seed, epoch, self.S)))
+        self._order.copy_(self._order_host, non_blocking=True)
+        self._order_copied = torch.cuda.Event()
+        self._order_copied.record(torch.cuda.current_stream(self.clouds.device))
+        self._order_epoch = epoch
+
+    def fill(self, epoch, i, reals, z1, z2):
+        """Batch i (0-based) of `epoch` (1-based) into the given tensors, on the current stream: one launch."""
+        from . import _lib
+        key = (tuple(t.data_ptr() for t in reals), z1.data_ptr(), z2.data_ptr())
+        if key != self._check:                                   # (the same static buffers every iteration: checked once)
+            if len(reals) != 4:
+                raise ValueError("reals: four tensors (B,3,r1) (B,3,r2) (B,3,r3) (B,3,N)")
+            for t, name, shape in zip(list(reals) + [z1, z2], ("p1", "p2", "p3", "p4", "z1", "z2"), self.shapes() + [self.shapes()[4]]):
+                _lib.require(t, name, torch.float32, len(shape))
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+                if t.device != self.clouds.device:
+                    raise _lib.PdgnHipError("%s is on %s, the clouds on %s" % (name, t.device, self.clouds.device))
+            self._check = key
+        if not 0 <= i < self.batches_per_epoch or epoch < 1:
+            raise IndexError("batch %d of epoch %d: an epoch has %d batches, epochs count from 1" % (i, epoch, self.batches_per_epoch))
+        if epoch != self._order_epoch:
+            self._upload_order(epoch)
+        ll, ull = ctypes.c_longlong, ctypes.c_ulonglong
+        _lib.check(self._fn(self.B, self.S, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(self.clouds),
+                            _lib.ptr(self._order), ll((i * self.world + self.rank) * self.B), ull(self.seed & 0xFFFFFFFFFFFFFFFF),
+                            ull((epoch - 1) * self.batches_per_epoch + i), ll(self.rank * self.B), ctypes.c_float(self.sigma),
+                            _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
+                            _lib.stream_of(self.clouds)), "pdgn_feed_batch")

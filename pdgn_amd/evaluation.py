@@ -210,11 +210,12 @@ def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
 
 # ---------------------------------------------------------------------------- the test phase (models/PDGNet_v2.py:296-331)
 @torch.no_grad()
-def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=None, with_jsd=True):
+def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=None, with_jsd=True, return_raw=False):
     """PDGNet_v2.test: draw ceil(N_ref / batch_size) batches of z ~ N(0, 1) (:304 -- sigma 1, unlike training's
     0.2), keep the finest cloud of each, truncate to N_ref, normalise like the reference set (`normalize` =
     the data set's scale mode: shape_unit / shape_bbox / None), then compute_all_metrics (+ 'jsd').
-    Returns (generated clouds (N_ref, N, 3), results dict of floats-on-device)."""
+    Returns (generated clouds (N_ref, N, 3), results dict of floats-on-device); with return_raw also, third, the clouds as
+    generated, before the normalisation (the reference's `nonormal_out.npy`, :309)."""
     from .data import normalize_point_clouds
     dev = ref_pcs.device
     n_ref = ref_pcs.shape[0]
@@ -222,9 +223,9 @@ def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=No
     for _ in range((n_ref + batch_size - 1) // batch_size):
         z = torch.randn(batch_size, 128, generator=rng, device=dev if rng is None or rng.device.type != "cpu" else "cpu").to(dev)
         gen.append(generator(z)[3].transpose(2, 1).contiguous())
-    gen_pcs = torch.cat(gen, dim=0)[:n_ref].contiguous()
-    gen_pcs = normalize_point_clouds(gen_pcs, normalize)
+    raw = torch.cat(gen, dim=0)[:n_ref].contiguous()
+    gen_pcs = normalize_point_clouds(raw, normalize)
     results = compute_all_metrics(gen_pcs, ref_pcs, batch_size)
     if with_jsd:
         results["jsd"] = jsd_between_point_cloud_sets(gen_pcs, ref_pcs)
-    return gen_pcs, results
+    return (gen_pcs, results, raw) if return_raw else (gen_pcs, results)

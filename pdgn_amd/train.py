@@ -1,0 +1,189 @@
+"""`python -m pdgn_amd.train`: the reference's command line (main.py:15-41, same flag names and defaults) in front of
+PDGNTrainer.fit (--phase train) and evaluation.generate_and_evaluate (--phase test).
+
+train: ShapeNetCore(choice, 'train', 'shape_unit') -> stack(device) -> data.BatchFeeder -> fit; checkpoints and the log go
+where the reference puts them (<checkpoint_dir>/<model_dir>/<network>/<epoch>_<category>_{G,D}.pth,
+<checkpoint_dir>/<model_dir>/<log_info>).  test: load --pretrain_model_G/_D from that directory, generate as many clouds as
+the test split has, write nonormal_out.npy / out.npy and log.txt under <save_dir>/GEN_Ours_<choice>_<time>/
+(models/PDGNet_v2.py:271-326).  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+Under torch.distributed.run every rank trains on its own slice of each global batch."""
+import argparse
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m pdgn_amd.train", description="PDGN training / test phase on an AMD Instinct GPU")
+    p.add_argument("--phase", type=str, default="train", help="train or test")
+    p.add_argument("--workers", type=int, default=4, help="accepted and ignored: the data set lives on the device")
+    p.add_argument("--gpu", type=int, default=0, help="accepted and ignored, as in the reference")
+    p.add_argument("--batch_size", type=int, default=50, help="batch size (per rank)")
+    p.add_argument("--num_point", type=int, default=2048, help="points of the finest resolution")
+    p.add_argument("--num_k", type=int, default=20, help="neighbours of the knn graph")
+    p.add_argument("--learning_rate", type=float, default=0.0001)
+    p.add_argument("--max_epoch", type=int, default=300)
+    p.add_argument("--noise_dim", type=int, default=128)
+    p.add_argument("--optimizer", default="adam", help="accepted and ignored, as in the reference")
+    p.add_argument("--debug", type=bool, default=True, help="accepted and ignored, as in the reference")
+    p.add_argument("--data_root", default="/opt/data/private/shapenet/shapenet.hdf5", help="shapenet.hdf5, or an .npz with '<synsetid>/<split>' keys")
+    p.add_argument("--log_info", default="log_info.txt")
+    p.add_argument("--model_dir", help="model dir (required)")
+    p.add_argument("--checkpoint_dir", default="checkpoint")
+    p.add_argument("--snapshot", type=int, default=20, help="epochs between checkpoints")
+    p.add_argument("--choice", default=None, help="category")
+    p.add_argument("--network", default="PDGNet_v2", help="names the checkpoint sub-directory; PDGNet_v2 is the one network")
+    p.add_argument("--savename", default=None, help="accepted and ignored, as in the reference")
+    p.add_argument("--pretrain_model_G", default=None)
+    p.add_argument("--pretrain_model_D", default=None)
+    p.add_argument("--softmax", default="True", help="softmax for the bilateral interpolation")
+    p.add_argument("--dataset", default="shapenet15k")
+    p.add_argument("--normalize", type=lambda s: None if s == "None" else s, default="shape_bbox", choices=[None, "shape_unit", "shape_bbox"])
+    p.add_argument("--seed", type=int, default=9999)
+    p.add_argument("--save_dir", type=str, default="./results")
+    p.add_argument("--device", type=str, default="cuda")
+    return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.model_dir is None:
+        p.error("please create model dir (--model_dir)")                                       # main.py:56-58
+    if args.dataset != "shapenet15k":
+        p.error("--dataset %s: only shapenet15k is supported (the ModelNet / Part loaders are not part of pdgn_amd)" % args.dataset)
+    if args.phase not in ("train", "test"):
+        p.error("--phase %s: train or test" % args.phase)
+    if args.noise_dim != 128:
+        p.error("--noise_dim %d: the generator takes 128" % args.noise_dim)
+    if args.num_point < 16 or args.num_point % 16:
+        p.error("--num_point %d: a multiple of 16 (the generator doubles base_points four times)" % args.num_point)
+    if args.max_epoch < 1 or args.batch_size < 1:
+        p.error("--max_epoch and --batch_size must be at least one")
+    return args
+
+
+def open_data_root(path):
+    """What ShapeNetCore takes as `path`: the HDF5 path itself, or -- for an .npz with '<synsetid>/<split>' keys -- the
+    {synsetid: {split: array}} mapping."""
+    if str(path).endswith(".npz"):
+        out = {}
+        with np.load(path) as f:
+            for key in f.files:
+                sid, split = key.split("/")
+                out.setdefault(sid, {})[split] = f[key]
+        return out
+    return path
+
+
+def load_split(args, split, scale_mode):
+    from .data import ShapeNetCore, synsetid_to_cate
+    src = open_data_root(args.data_root)
+    cates = args.choice
+    if cates is None:                                            # the reference's category 'full'
+        cates = [synsetid_to_cate[s] for s in sorted(src)] if isinstance(src, dict) else "all"
+    return ShapeNetCore(cates, split, scale_mode, src)
+
+
+def init_dist(device):
+    """(rank, world): from the process group under torch.distributed.run, else (0, 1)."""
+    import torch.distributed as dist
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        return dist.get_rank(), dist.get_world_size(), torch.device("cuda", local)
+    return 0, 1, torch.device(device)
+
+
+def make_trainer(args, device):
+    from .generator import PointGenerator
+    from .trainer import PDGNTrainer
+    base = args.num_point // 16
+    gen = PointGenerator(args.num_point, args.num_k, softmax=args.softmax == "True", base_points=base)
+    return PDGNTrainer(device=device, lr=args.learning_rate, num_k=args.num_k, base_points=base, generator=gen)
+
+
+def _resume(args, trainer, ckpt):
+    if args.pretrain_model_G is None and args.pretrain_model_D is None:
+        return None                                              # a new training (:334-336)
+    if args.pretrain_model_G is None or args.pretrain_model_D is None:
+        raise SystemExit("--pretrain_model_G and --pretrain_model_D go together")                 # (:354-356, :377-379)
+    return trainer.load(os.path.join(ckpt, args.pretrain_model_G), os.path.join(ckpt, args.pretrain_model_D))
+
+
+def train(args):
+    from .data import BatchFeeder
+    rank, world, device = init_dist(args.device)
+    run_dir = os.path.join(args.checkpoint_dir, args.model_dir)
+    ckpt = os.path.join(run_dir, args.network)
+    os.makedirs(ckpt, exist_ok=True)
+    torch.manual_seed(args.seed)                                 # the networks' initial weights
+    dset = load_split(args, "train", "shape_unit")
+    n = args.num_point
+    feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world)
+    if feeder.N != n:
+        raise SystemExit("--num_point %d but the clouds of %s have %d points" % (n, args.data_root, feeder.N))
+    trainer = make_trainer(args, device)
+    trainer.train()
+    start = _resume(args, trainer, ckpt) or 1
+    log = None
+    if rank == 0:
+        path = os.path.join(run_dir, args.log_info)
+        with open(path, "a") as f:
+            f.write(str(args) + "\n")
+
+        def log(line, _f=path):
+            print(line)
+            with open(_f, "a") as f:
+                f.write(line + "\n")
+    last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
+                       category=args.choice or "full", log=log)
+    torch.cuda.synchronize(device)
+    if world > 1:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
+    print(" [*] Training finished! (epoch %d)" % last)
+    return last
+
+
+def test(args):
+    from . import evaluation
+    device = torch.device(args.device)
+    ckpt = os.path.join(args.checkpoint_dir, args.model_dir, args.network)
+    trainer = make_trainer(args, device)
+    if _resume(args, trainer, ckpt) is None:
+        print(" [!] Load failed...")                             # (:275-276: the reference goes on with the initial weights too)
+    save_dir = os.path.join(args.save_dir, "GEN_Ours_%s_%d" % (args.choice or "full", int(time.time())))
+    os.makedirs(save_dir, exist_ok=True)
+    torch.manual_seed(args.seed)                                 # seed_all (:282)
+    np.random.seed(args.seed)
+    random.seed(args.seed)
+    ref = load_split(args, "test", args.normalize).stack(device).float().contiguous()
+    trainer.G.eval()
+    gen, results, raw = evaluation.generate_and_evaluate(trainer.G, ref, args.batch_size, normalize=args.normalize, return_raw=True)
+    np.save(os.path.join(save_dir, "nonormal_out.npy"), raw.cpu().numpy())
+    np.save(os.path.join(save_dir, "out.npy"), gen.cpu().numpy())
+    with open(os.path.join(save_dir, "log.txt"), "a") as f:
+        for k, v in results.items():
+            line = "%s: %.12f" % (k, float(v))                   # (:324-325)
+            print(line)
+            f.write(line + "\n")
+    print(" [*] Test finished!")
+    return save_dir
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    return train(args) if args.phase == "train" else test(args)
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

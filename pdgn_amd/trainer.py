@@ -884,6 +884,80 @@ class PDGNTrainer:
         self._list.launch(lo)
         return st["out"]
 
+    # ---------------------------------------------------------------- the training loop (models/PDGNet_v2.py:157-269)
+    LOG_FORMAT = ("Epoch: [%2d] [%4d/%4d] time: %2dm %2ds d_loss1: %.8f d_loss2: %.8f d_loss3: %.8f d_loss4: %.8f, "
+                  "g_loss: %.8f, similar_loss: %.8f")         # :259
+    LOSS_KEYS = ("d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss")
+
+    def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
+            on_epoch=None):
+        """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
+        `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
+        them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
+        `load` returned as start_epoch -- the reference starts AT the stored epoch (:158-160), and the feed of an epoch is a
+        pure function of (seed, epoch, batch), so the resumed epoch sees the batches an uninterrupted run saw.
+
+        issue="list": the feeder writes into the static buffers of `capture_list` and `step_list()` runs without arguments --
+        one launch and no torch op in front of the list.  The list is captured on first use from the first batch (its
+        warm-up iterations are real optimizer updates on that batch).  issue="eager": trainer-owned buffers and `step`.
+        The losses stay on the device: every iteration stacks them and copies them, non-blocking, into one of two pinned host
+        rows; the line of iteration n is written after iteration n + 1 has been issued, when that copy is long complete.
+        log: a callable taking the line, or a path (appended to); on_epoch: called with the epoch number after each epoch."""
+        import time
+        if issue not in ("list", "eager"):
+            raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
+        sink, opened = log, None
+        if isinstance(log, (str, bytes, os.PathLike)):
+            opened = open(log, "a")
+            sink = lambda line: (opened.write(line + "\n"), opened.flush())
+        nb = feeder.batches_per_epoch
+        cuda = self.device.type == "cuda"
+        host = torch.empty(2, len(self.LOSS_KEYS), dtype=torch.float32, pin_memory=cuda)
+        done = [torch.cuda.Event() for _ in range(2)] if cuda else None
+        pending, n, start = None, 0, time.time()
+
+        def flush():
+            slot, ep, idx = pending
+            if cuda:
+                done[slot].synchronize()
+            dt = time.time() - start
+            sink(self.LOG_FORMAT % ((ep, idx + 1, nb, dt / 60, dt % 60) + tuple(host[slot].tolist())))
+
+        try:
+            if issue == "eager" or getattr(self, "_list", None) is None:
+                reals, z1, z2 = feeder.buffers()
+            if issue == "list" and getattr(self, "_list", None) is None and start_epoch <= epochs:
+                feeder.fill(start_epoch, 0, reals, z1, z2)
+                self.capture_list(reals, z1, z2)
+            if issue == "list":
+                st = self._static
+                reals, z1, z2 = st["reals"], st["z1"], st["z2"]
+            for epoch in range(start_epoch, epochs + 1):
+                for i in range(nb):
+                    feeder.fill(epoch, i, reals, z1, z2)
+                    out = self.step_list() if issue == "list" else self.step(reals, z1, z2)
+                    if sink is not None:
+                        slot = n & 1
+                        host[slot].copy_(torch.stack([out[k] for k in self.LOSS_KEYS]), non_blocking=True)
+                        if cuda:
+                            done[slot].record(torch.cuda.current_stream(self.device))
+                        if pending is not None:
+                            flush()
+                        pending = (slot, epoch, i)
+                        n += 1
+                if checkpoint_dir is not None and epoch % snapshot == 0 and getattr(feeder, "rank", 0) == 0:
+                    self.save(checkpoint_dir, epoch, category)
+                if on_epoch is not None:
+                    on_epoch(epoch)
+            if pending is not None:
+                flush()
+            if checkpoint_dir is not None and getattr(feeder, "rank", 0) == 0:
+                self.save(checkpoint_dir, epochs, category)           # (:268: always, whatever the snapshot period)
+        finally:
+            if opened is not None:
+                opened.close()
+        return epochs
+
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()
 
