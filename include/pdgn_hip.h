@@ -704,6 +704,27 @@ int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *da
                     unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2, float *p3,
                     float *p4, float *z1, float *z2, pdgn_stream_t stream);
 
+/* ------------------------------------------------------------------ preview sheets
+ * A contact sheet of point clouds as ONE 8-bit grey image (what pdgn_amd/report.py writes at a snapshot): `rows` samples down,
+ * `cols` <= 8 cloud lists across, every cell `cell` x `cell` pixels; image (rows * cell, cols * cell) uint8, row-major.
+ * clouds: HOST array of `cols` device pointers, npoints: HOST array of their point counts; cloud c is (rows, npoints[c], 3)
+ * fp32, or (rows, 3, npoints[c]) where bit c of channel_major is set.  view: HOST, 3 x 4 row-major; for a point (x, y, z)
+ *   u = fma(m02, z, fma(m01, y, fma(m00, x, m03)))   column inside the cell, pixel floor(u)
+ *   v = fma(m12, z, fma(m11, y, fma(m10, x, m13)))   row inside the cell, pixel floor(v)
+ *   d = fma(m22, z, fma(m21, y, fma(m20, x, m23)))   depth, clamped to [0, 1], 0 = nearest
+ * in exactly this order.  q = min((uint32)(d * 2^24), 2^24 - 1); key = q << 8 | shade, shade = 255 - (q >> 17) (255 nearest ..
+ * 128 farthest).  Every pixel of the disc dx^2 + dy^2 <= radius^2 around (floor(u), floor(v)) that lies INSIDE the point's own
+ * cell takes the minimum of its key and this one (integer atomic minimum on a uint32: the result does not depend on the
+ * order of arrival, so the image is bitwise repeatable); pixels outside the cell are dropped, never written to a
+ * neighbour.  A pixel no point reached is 0, any other one the low byte of its smallest key.  Points with a NaN coordinate
+ * are skipped.  workspace: pdgn_render_workspace_bytes(rows, cols, cell) bytes of the caller's (one uint32 key per pixel),
+ * 16-byte aligned; image 4-byte aligned.  Three launches on `stream` (clear, splat, resolve): 46 us for 35 x 5 cells of 128 pixels.
+ * PDGN_ERR_INVALID: rows outside [1, 65535], cols outside [1, 8], cell outside [1, 4096], more than 2^30 pixels, radius
+ * outside [0, 16], a point count outside [1, 2^24], a null or misaligned pointer; all checked before anything is launched. */
+long long pdgn_render_workspace_bytes(int rows, int cols, int cell);
+int pdgn_render_sheet(int rows, int cols, const float *const *clouds, const int *npoints, int channel_major, const float *view,
+                      int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

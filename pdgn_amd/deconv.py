@@ -399,6 +399,22 @@ class PointDeconv(nn.Module):
     def drop_preassembled(self):
         self._pre = None
 
+    # -- what a forward leaves behind on the host besides its result: the row count that picks the arithmetic of the NEXT
+    # pre-assembly (_rows_hint) and the operands pre-assembled for the current parameters (_pre).  A caller that runs forwards
+    # which must not influence training (the snapshot reports, pdgn_amd/report.py) takes them before and puts them back after;
+    # host-side forward state added to this class later belongs in _FORWARD_HINTS.
+    _FORWARD_HINTS = ("_rows_hint", "_pre")
+
+    def forward_hints(self):
+        return {k: self.__dict__[k] for k in self._FORWARD_HINTS if k in self.__dict__}
+
+    def restore_forward_hints(self, hints):
+        for k in self._FORWARD_HINTS:
+            if k in hints:
+                self.__dict__[k] = hints[k]
+            else:
+                self.__dict__.pop(k, None)
+
     def assembled(self, Fc):
         pre = getattr(self, "_pre", None)
         if pre is not None and pre[0] == self._weights_key(Fc) and (pre[1] or not torch.is_grad_enabled()):

@@ -51,6 +51,16 @@ def pairwise_emd_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False
     CD = mean_i min_j P + mean_j min_i P with the Gram-form P of distChamfer (:35-45);
     EMD = match_cost / N (:26-31).  `batch_size` is accepted for signature parity and ignored.
     shard_over_ranks: every rank of `group` holds the same two sets and computes 1/world of the pairs (`shard_pairs`)."""
+    return _pairwise(sample_pcs, ref_pcs, True, shard_over_ranks, group)
+
+
+def pairwise_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False, group=None):
+    """The Chamfer half of `pairwise_emd_cd` alone: all_cd (N_sample, N_ref), the same launches in the same order and therefore
+    the same bits; the EMD kernel is not launched (the cheap metrics of a training run's snapshot reports, pdgn_amd/report.py)."""
+    return _pairwise(sample_pcs, ref_pcs, False, shard_over_ranks, group)[0]
+
+
+def _pairwise(sample_pcs, ref_pcs, with_emd, shard_over_ranks, group):
     require(sample_pcs, "sample_pcs", F32, 3)
     require(ref_pcs, "ref_pcs", F32, 3)
     S, N, _ = sample_pcs.shape
@@ -60,7 +70,7 @@ def pairwise_emd_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False
 
     def fill(lo, hi):
         cd = torch.empty(hi - lo, dtype=F32, device=dev)
-        emd = torch.empty(hi - lo, dtype=F32, device=dev)
+        emd = torch.empty(hi - lo if with_emd else 0, dtype=F32, device=dev)
         for start in range(lo, hi, _MAX_PAIRS):
             stop = min(hi, start + _MAX_PAIRS)
             npairs = stop - start
@@ -74,16 +84,18 @@ def pairwise_emd_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False
                   "pdgn_chamfer_gram_indexed")
             # distChamfer returns (P.min(1), P.min(2)) = (per ref point, per sample point); :108 adds their means
             cd[start - lo:stop - lo] = miny.mean(dim=1) + minx.mean(dim=1)
+            if not with_emd:
+                continue
             L.pdgn_emd_cost_temp_floats.restype = ctypes.c_longlong
             temp = torch.empty(L.pdgn_emd_cost_temp_floats(ctypes.c_longlong(npairs), N, M), dtype=F32, device=dev)
             out = torch.empty((npairs,), dtype=F32, device=dev)
             check(L.pdgn_emd_cost_indexed(npairs, N, M, ptr(sample_pcs), ptr(ia), ptr(ref_pcs), ptr(ib), ptr(temp),
                                           ptr(out), stream_of(sample_pcs)), "pdgn_emd_cost_indexed")
             emd[start - lo:stop - lo] = out / float(N)
-        return cd, emd
+        return (cd, emd) if with_emd else (cd,)
 
-    cd, emd = shard_pairs(S * R, fill, group) if shard_over_ranks else fill(0, S * R)
-    return cd.view(S, R), emd.view(S, R)
+    out = shard_pairs(S * R, fill, group) if shard_over_ranks else fill(0, S * R)
+    return tuple(t.view(S, R) for t in out)
 
 
 def emd_cd(sample_pcs, ref_pcs, batch_size=None, reduced=True):
@@ -128,6 +140,15 @@ def knn(Mxx, Mxy, Myy, k, sqrt=False):
               "acc_t": s["tp"] / (s["tp"] + s["fn"] + 1e-10), "acc_f": s["tn"] / (s["tn"] + s["fp"] + 1e-10),
               "acc": torch.eq(label, pred).float().mean()})
     return s
+
+
+def reduce_metrics(all_dist, Mxx, Mxy, Myy, tag="CD"):
+    """The reduction stage of compute_all_metrics (:179-199) for ONE distance: MMD / COV from `all_dist` (the transposed
+    sample-vs-reference matrix) and the 1-NN accuracies from the three matrices, under compute_all_metrics' keys
+    ("lgan_mmd-<tag>", ..., "1-NN-<tag>-acc").  Small torch reductions on whatever device the matrices live on: no library call."""
+    results = {"%s-%s" % (k, tag): v for k, v in lgan_mmd_cov(all_dist).items()}
+    results.update({"1-NN-%s-%s" % (tag, k): v for k, v in knn(Mxx, Mxy, Myy, 1).items() if "acc" in k})
+    return results
 
 
 def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=False, shard_over_ranks=False, group=None):
@@ -210,21 +231,27 @@ def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
 
 # ---------------------------------------------------------------------------- the test phase (models/PDGNet_v2.py:296-331)
 @torch.no_grad()
+def generate_clouds(generator, n, batch_size, normalize=None, rng=None, device=None):
+    """The generation of PDGNet_v2.test (:300-312): ceil(n / batch_size) batches of z ~ N(0, 1) from `rng`, the finest cloud of
+    each, truncated to n -> (clouds normalised with `normalize`, clouds as generated), both (n, N, 3)."""
+    from .data import normalize_point_clouds
+    dev = device if device is not None else next(generator.parameters()).device
+    gen = []
+    for _ in range((n + batch_size - 1) // batch_size):
+        z = torch.randn(batch_size, 128, generator=rng, device=dev if rng is None or rng.device.type != "cpu" else "cpu").to(dev)
+        gen.append(generator(z)[3].transpose(2, 1).contiguous())
+    raw = torch.cat(gen, dim=0)[:n].contiguous()
+    return normalize_point_clouds(raw, normalize), raw
+
+
+@torch.no_grad()
 def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=None, with_jsd=True, return_raw=False):
     """PDGNet_v2.test: draw ceil(N_ref / batch_size) batches of z ~ N(0, 1) (:304 -- sigma 1, unlike training's
     0.2), keep the finest cloud of each, truncate to N_ref, normalise like the reference set (`normalize` =
     the data set's scale mode: shape_unit / shape_bbox / None), then compute_all_metrics (+ 'jsd').
     Returns (generated clouds (N_ref, N, 3), results dict of floats-on-device); with return_raw also, third, the clouds as
     generated, before the normalisation (the reference's `nonormal_out.npy`, :309)."""
-    from .data import normalize_point_clouds
-    dev = ref_pcs.device
-    n_ref = ref_pcs.shape[0]
-    gen = []
-    for _ in range((n_ref + batch_size - 1) // batch_size):
-        z = torch.randn(batch_size, 128, generator=rng, device=dev if rng is None or rng.device.type != "cpu" else "cpu").to(dev)
-        gen.append(generator(z)[3].transpose(2, 1).contiguous())
-    raw = torch.cat(gen, dim=0)[:n_ref].contiguous()
-    gen_pcs = normalize_point_clouds(raw, normalize)
+    gen_pcs, raw = generate_clouds(generator, ref_pcs.shape[0], batch_size, normalize, rng, ref_pcs.device)
     results = compute_all_metrics(gen_pcs, ref_pcs, batch_size)
     if with_jsd:
         results["jsd"] = jsd_between_point_cloud_sets(gen_pcs, ref_pcs)

@@ -208,6 +208,15 @@ class PointGenerator(nn.Module):
         for dec in self._deconvs():
             dec.drop_preassembled()
 
+    def forward_hints(self):
+        """The host-side state the four transposed convolutions keep from their last forward (PointDeconv.forward_hints), for
+        `restore_forward_hints`: forwards in between (a snapshot report's) then leave the next training step's choices alone."""
+        return [dec.forward_hints() for dec in self._deconvs()]
+
+    def restore_forward_hints(self, hints):
+        for dec, h in zip(self._deconvs(), hints):
+            dec.restore_forward_hints(h)
+
 
 class PointDiscriminator(nn.Module):
     """PointDiscriminator_1..4 :882-1023.  (B,3,N) -> (B,1)."""

@@ -1,0 +1,256 @@
+"""Snapshot reports of a training run, written by the training process itself: a preview sheet of what the generator makes at
+all four resolutions (csrc/render.hip, pdgn_render_sheet -> an 8-bit grey PNG) and one line of cheap held-out metrics
+(CD-only MMD / COV / 1-NNA and JSD: the all-pairs Chamfer pair-list kernel, never the EMD kernel).
+
+    reporter = SnapshotReporter(trainer, val_clouds, out_dir, every=20, batch_size=35, normalize="shape_bbox", seed=9999)
+    trainer.fit(feeder, epochs, on_epoch=reporter)
+    python -m pdgn_amd.train ... --report_every 20
+    python -m pdgn_amd.report results/GEN_Ours_chair_<time>/out.npy -o sheet.png
+
+A report does not touch training: it runs under no_grad in eval mode after a device synchronise, draws from generators of its
+own (torch's global RNG state is left alone), and leaves every parameter, buffer and optimizer state as it found them
+(DESIGN.md section 7c).
+"""
+import argparse
+import ctypes
+import math
+import os
+import struct
+import sys
+import time
+import zlib
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_COLUMNS = 8
+QUICK_KEYS = ("lgan_mmd-CD", "lgan_cov-CD", "lgan_mmd_smp-CD", "1-NN-CD-acc_t", "1-NN-CD-acc_f", "1-NN-CD-acc", "jsd")
+FULL_KEYS = QUICK_KEYS[:3] + ("lgan_mmd-EMD", "lgan_cov-EMD", "lgan_mmd_smp-EMD") + QUICK_KEYS[3:6] + (
+    "1-NN-EMD-acc_t", "1-NN-EMD-acc_f", "1-NN-EMD-acc", "jsd")
+
+
+# ---------------------------------------------------------------------------- the sheet
+def default_view(cell=128, yaw=-35.0, pitch=25.0, fill=0.48):
+    """The fixed three-quarter view: a 3 x 4 fp32 matrix (rows: pixel column u, pixel row v, depth d in [0, 1] with 0 nearest;
+    include/pdgn_hip.h, pdgn_render_sheet) that maps a cloud inside the unit sphere into a cell of `cell` pixels.  The cloud's
+    y axis points up (ShapeNetCore.GRAVITATIONAL_AXIS); the camera turns `yaw` degrees about it, then tilts `pitch` degrees
+    down; orthographic, the unit sphere spans `fill` * cell pixels either side of the cell's centre.  Built in fp32."""
+    f = np.float32
+    cy, sy = f(math.cos(math.radians(yaw))), f(math.sin(math.radians(yaw)))
+    cp, sp = f(math.cos(math.radians(pitch))), f(math.sin(math.radians(pitch)))
+    ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=f)
+    rx = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]], dtype=f)
+    cam = rx @ ry                                                # camera axes: x right, y up, z towards the viewer
+    s, half = f(fill) * f(cell), f(cell) * f(0.5)
+    view = np.zeros((3, 4), dtype=f)
+    view[0, :3], view[0, 3] = s * cam[0], half
+    view[1, :3], view[1, 3] = -s * cam[1], half                  # image rows grow downwards
+    view[2, :3], view[2, 3] = f(-0.5) * cam[2], f(0.5)
+    return view
+
+
+def fit_unit_sphere(pcs):
+    """(B, N, 3) -> each cloud centred on its bounding box and scaled to touch the unit sphere (what `default_view` frames)."""
+    lo, hi = pcs.min(dim=1, keepdim=True)[0], pcs.max(dim=1, keepdim=True)[0]
+    centred = pcs - (lo + hi) / 2
+    return (centred / centred.norm(dim=2).max(dim=1)[0].clamp_min(1e-12).view(-1, 1, 1)).contiguous()
+
+
+def _column(t, name, fit):
+    """One cloud list as the kernel takes it: (tensor whose memory is (B,N,3) or (B,3,N) contiguous, N, channel_major)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if not t.is_cuda:
+        raise _lib.PdgnHipError("%s must live on a ROCm device (pdgn_amd has no CPU path)" % name)
+    if t.dtype != torch.float32 or t.dim() != 3 or 3 not in t.shape[1:]:
+        raise ValueError("%s must be fp32 (B,3,N) or (B,N,3), got %s %s" % (name, t.dtype, tuple(t.shape)))
+    point_major = t.shape[2] == 3                                # (B,3,3) reads as point-major
+    if fit:
+        return fit_unit_sphere(t if point_major else t.transpose(1, 2)), (t.shape[1] if point_major else t.shape[2]), False
+    n = t.shape[1] if point_major else t.shape[2]
+    if t.is_contiguous():
+        return t, n, not point_major
+    if t.transpose(1, 2).is_contiguous():                        # the generator's outputs: (B,3,N) views of (B,N,3) memory
+        return t, n, point_major
+    return t.contiguous(), n, not point_major
+
+
+def render_sheet(clouds, view=None, cell=128, radius=1, fit=False):
+    """A contact sheet of clouds: one row per sample, one column per entry of `clouds` (a tensor, or a list of up to 8; each
+    (B,3,N) -- the reference's layout, the generator's outputs as they are -- or point-major (B,N,3), fp32 on the device, the
+    same B) -> (B * cell, len(clouds) * cell) uint8 device tensor.  view: 3 x 4 fp32 (default `default_view(cell)`); radius: the
+    splat's radius in pixels; fit: centre and scale every cloud into the unit sphere first.  One launch sequence on the current
+    stream; bitwise repeatable."""
+    cols = [clouds] if isinstance(clouds, torch.Tensor) else list(clouds)
+    if not 1 <= len(cols) <= MAX_COLUMNS:
+        raise ValueError("render_sheet takes 1 to %d cloud lists, got %d" % (MAX_COLUMNS, len(cols)))
+    view = np.ascontiguousarray(np.asarray(default_view(cell) if view is None else view, dtype=np.float32))
+    if view.shape != (3, 4):
+        raise ValueError("view must be 3 x 4, got %s" % (view.shape,))
+    held = [_column(t, "clouds[%d]" % i, fit) for i, t in enumerate(cols)]
+    B, dev = cols[0].shape[0], cols[0].device
+    if any(t.shape[0] != B or t.device != dev for t in cols):
+        raise ValueError("every cloud list must hold the same number of clouds on the same device")
+    L = _lib.lib()
+    L.pdgn_render_workspace_bytes.restype = ctypes.c_longlong
+    nbytes = L.pdgn_render_workspace_bytes(B, len(cols), int(cell))
+    if nbytes < 0:
+        raise _lib.PdgnHipError("pdgn_render_workspace_bytes: argument outside the supported range")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        image = torch.empty((B * int(cell), len(cols) * int(cell)), dtype=torch.uint8, device=dev)
+        ptrs = (ctypes.c_void_p * len(cols))(*[t.data_ptr() for t, _, _ in held])
+        counts = (ctypes.c_int * len(cols))(*[n for _, n, _ in held])
+        mask = sum(1 << i for i, (_, _, cm) in enumerate(held) if cm)
+        _lib.check(L.pdgn_render_sheet(B, len(cols), ptrs, counts, mask, view.ctypes.data_as(ctypes.c_void_p), int(cell), int(radius),
+                                       _lib.ptr(ws), _lib.ptr(image), _lib.stream_of(image)), "pdgn_render_sheet")
+    return image
+
+
+# ---------------------------------------------------------------------------- PNG (8-bit grey, filter type 0)
+def _chunk(tag, data):
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+
+def write_png(path, image):
+    """A (H, W) uint8 array (numpy, or a tensor on any device) as an 8-bit greyscale PNG; zlib and struct only."""
+    if isinstance(image, torch.Tensor):
+        image = image.detach().cpu().numpy()
+    image = np.ascontiguousarray(image)
+    if image.dtype != np.uint8 or image.ndim != 2 or 0 in image.shape:
+        raise ValueError("write_png takes a non-empty (H, W) uint8 image, got %s %s" % (image.dtype, image.shape))
+    h, w = image.shape
+    raw = np.zeros((h, w + 1), dtype=np.uint8)                   # every scanline starts with its filter type: 0, none
+    raw[:, 1:] = image
+    data = (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0))
+            + _chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(data)
+    return path
+
+
+# ---------------------------------------------------------------------------- cheap held-out metrics
+@torch.no_grad()
+def quick_metrics(generator, ref_pcs, batch_size, normalize=None, rng=None, cache=None):
+    """The CD entries and the JSD of evaluation.generate_and_evaluate without its EMD passes: generation as there (sigma-1 noise
+    from `rng`, the finest cloud, truncated to the reference set's size, normalised with `normalize`) with the generator in
+    eval mode (its mode is put back), all-pairs Chamfer from the pair-list kernel (evaluation.pairwise_cd), the reductions of
+    evaluation.reduce_metrics, under compute_all_metrics' keys (`QUICK_KEYS`).  cache: a dict that keeps what depends on the
+    reference set alone -- its ref-vs-ref matrix and its occupancy counters -- between calls."""
+    from . import evaluation as ev
+    cache = {} if cache is None else cache
+    ident = (ref_pcs.data_ptr(), tuple(ref_pcs.shape), ref_pcs._version)
+    if cache.get("ref") != ident:
+        cache.clear()
+        cache["ref"] = ident
+        cache["M_rr"] = ev.pairwise_cd(ref_pcs, ref_pcs)
+        cache["ref_counters"] = ev.entropy_of_occupancy_grid(ref_pcs, 28, True)[1]
+    was_training = generator.training
+    generator.eval()
+    try:
+        gen_pcs, _ = ev.generate_clouds(generator, ref_pcs.shape[0], batch_size, normalize, rng, ref_pcs.device)
+    finally:
+        generator.train(was_training)
+    M_rs = ev.pairwise_cd(gen_pcs, ref_pcs)
+    M_ss = ev.pairwise_cd(gen_pcs, gen_pcs)
+    results = ev.reduce_metrics(M_rs.t(), cache["M_rr"], M_rs, M_ss, "CD")
+    results["jsd"] = ev.jensen_shannon_divergence(ev.entropy_of_occupancy_grid(gen_pcs, 28, True)[1], cache["ref_counters"])
+    return results
+
+
+# ---------------------------------------------------------------------------- the fit hook
+class SnapshotReporter:
+    """`fit(on_epoch=SnapshotReporter(...))`: at every epoch that is a multiple of `every`, on rank 0, write
+    `<out_dir>/preview_<epoch>.png` (`rows` samples down; the generator's four resolutions and a column of reference clouds
+    across) and append a row to `<out_dir>/metrics.csv` (epoch, `QUICK_KEYS` -- with full=True `FULL_KEYS`, through
+    compute_all_metrics and its EMD passes -- and the seconds the report took).  The preview's noise and the metrics' noise
+    come from generators seeded the same way at every report, so sheets and rows are comparable across epochs.  Training
+    state is left as found; the generator's train / eval flag is put back."""
+
+    def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1):
+        _lib.require(ref_pcs, "ref_pcs", torch.float32, 3)
+        self.trainer, self.ref, self.out_dir = trainer, ref_pcs, str(out_dir)
+        self.every, self.batch_size, self.normalize, self.seed = int(every), int(batch_size), normalize, int(seed)
+        self.rows, self.full, self.rank, self.cell, self.radius = min(int(rows), ref_pcs.shape[0]), bool(full), int(rank), int(cell), int(radius)
+        if self.rows < 1:
+            raise ValueError("a report needs at least one row and one reference cloud")
+        self.cache = {}
+        self.keys = FULL_KEYS if self.full else QUICK_KEYS
+        self.last = None                                         # (epoch, {key: float}, seconds) of the latest report
+
+    def _generator(self, offset):
+        return torch.Generator(device=self.ref.device).manual_seed(self.seed + offset)
+
+    @torch.no_grad()
+    def __call__(self, epoch):
+        if self.every <= 0 or epoch % self.every or self.rank != 0:
+            return None
+        from . import evaluation as ev
+        t0 = time.perf_counter()
+        dev = self.ref.device
+        torch.cuda.synchronize(dev)
+        G = self.trainer.G
+        was_training = G.training
+        hints = G.forward_hints()                                # (what the eager step's next pre-assembly would read: generator.py)
+        G.eval()
+        try:
+            z = torch.randn(self.rows, 128, generator=self._generator(0), device=dev)
+            sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True)
+            if self.full:
+                _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1))
+            else:
+                results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
+            results = {k: float(results[k]) for k in self.keys}
+            image = sheet.cpu().numpy()
+        finally:
+            G.train(was_training)
+            G.restore_forward_hints(hints)
+        os.makedirs(self.out_dir, exist_ok=True)
+        write_png(os.path.join(self.out_dir, "preview_%d.png" % epoch), image)
+        seconds = time.perf_counter() - t0
+        path = os.path.join(self.out_dir, "metrics.csv")
+        fresh = not os.path.exists(path) or os.path.getsize(path) == 0
+        with open(path, "a") as f:
+            if fresh:
+                f.write(",".join(("epoch",) + self.keys + ("seconds",)) + "\n")
+            f.write(",".join([str(epoch)] + ["%.9g" % results[k] for k in self.keys] + ["%.3f" % seconds]) + "\n")
+        self.last = (epoch, results, seconds)
+        return self.last
+
+
+# ---------------------------------------------------------------------------- python -m pdgn_amd.report
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m pdgn_amd.report", description="render a saved (S, N, 3) array of clouds (the test "
+                                "phase's out.npy) as a preview sheet")
+    p.add_argument("clouds", help=".npy file holding (S, N, 3) or (S, 3, N) clouds")
+    p.add_argument("-o", "--output", default="sheet.png")
+    p.add_argument("--rows", type=int, default=8, help="clouds per column")
+    p.add_argument("--cols", type=int, default=MAX_COLUMNS, help="columns (at most %d)" % MAX_COLUMNS)
+    p.add_argument("--cell", type=int, default=128, help="pixels per cell side")
+    p.add_argument("--radius", type=int, default=1, help="splat radius in pixels")
+    p.add_argument("--device", default="cuda")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    pcs = np.load(args.clouds)
+    if pcs.ndim != 3 or 3 not in pcs.shape[1:]:
+        raise SystemExit("%s: expected (S, N, 3) or (S, 3, N), got %s" % (args.clouds, pcs.shape))
+    if pcs.shape[2] != 3:
+        pcs = pcs.transpose(0, 2, 1)
+    rows = max(1, min(args.rows, pcs.shape[0]))
+    cols = max(1, min(args.cols, MAX_COLUMNS, pcs.shape[0] // rows))
+    dev = torch.device(args.device)
+    pcs = torch.from_numpy(np.ascontiguousarray(pcs[:rows * cols], dtype=np.float32)).to(dev)
+    sheet = render_sheet([pcs[j * rows:(j + 1) * rows] for j in range(cols)], cell=args.cell, radius=args.radius, fit=True)
+    write_png(args.output, sheet)
+    print("%s: %d clouds, %d x %d pixels" % (args.output, rows * cols, sheet.shape[1], sheet.shape[0]))
+    return args.output
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

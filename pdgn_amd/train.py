@@ -5,7 +5,8 @@ train: ShapeNetCore(choice, 'train', 'shape_unit') -> stack(device) -> data.Batc
 where the reference puts them (<checkpoint_dir>/<model_dir>/<network>/<epoch>_<category>_{G,D}.pth,
 <checkpoint_dir>/<model_dir>/<log_info>).  test: load --pretrain_model_G/_D from that directory, generate as many clouds as
 the test split has, write nonormal_out.npy / out.npy and log.txt under <save_dir>/GEN_Ours_<choice>_<time>/
-(models/PDGNet_v2.py:271-326).  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+(models/PDGNet_v2.py:271-326).  --report_every N (train): every N epochs a preview sheet and a row of held-out metrics on the val
+split, under <checkpoint_dir>/<model_dir>/report (pdgn_amd/report.py).  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -46,6 +47,10 @@ def build_parser():
     p.add_argument("--seed", type=int, default=9999)
     p.add_argument("--save_dir", type=str, default="./results")
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--report_every", type=int, default=0, help="epochs between snapshot reports (pdgn_amd.report: a preview sheet and "
+                   "a row of held-out metrics on the val split, under <checkpoint_dir>/<model_dir>/report); 0: none")
+    p.add_argument("--report_rows", type=int, default=8, help="samples per preview sheet")
+    p.add_argument("--report_full", action="store_true", help="reports run the full evaluation (EMD included) instead of the CD-only one")
     return p
 
 
@@ -64,7 +69,17 @@ def parse_args(argv=None):
         p.error("--num_point %d: a multiple of 16 (the generator doubles base_points four times)" % args.num_point)
     if args.max_epoch < 1 or args.batch_size < 1:
         p.error("--max_epoch and --batch_size must be at least one")
+    if args.report_every < 0 or args.report_rows < 1:
+        p.error("--report_every must not be negative and --report_rows at least one")
     return args
+
+
+def logged_args(args):
+    """What the first line of <log_info> shows: with reports off (--report_every 0) the namespace without the report flags, so
+    that the file is what it was before they existed."""
+    if args.report_every:
+        return args
+    return argparse.Namespace(**{k: v for k, v in vars(args).items() if not k.startswith("report_")})
 
 
 def open_data_root(path):
@@ -137,14 +152,20 @@ def train(args):
     if rank == 0:
         path = os.path.join(run_dir, args.log_info)
         with open(path, "a") as f:
-            f.write(str(args) + "\n")
+            f.write(str(logged_args(args)) + "\n")
 
         def log(line, _f=path):
             print(line)
             with open(_f, "a") as f:
                 f.write(line + "\n")
+    reporter = None
+    if args.report_every > 0 and rank == 0:
+        from .report import SnapshotReporter
+        val = load_split(args, "val", args.normalize).stack(device).float().contiguous()
+        reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
+                                    args.seed, rows=args.report_rows, full=args.report_full, rank=rank)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
-                       category=args.choice or "full", log=log)
+                       category=args.choice or "full", log=log, on_epoch=reporter)
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()
