@@ -652,6 +652,24 @@ int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *co
  * gradients into the flat buffer of its one all-reduce (the gradient reduction of nn.DataParallel, models/PDGNet_v2.py:101-105);
  * replaces torch._foreach_copy_. */
 int pdgn_copy_multi(int ntensors, void *const *dst, const void *const *src, const long long *n, pdgn_stream_t stream);
+/* The averaged generator: an exponential moving average e of the parameters, kept by the optimizer's own launch.  No reference
+ * counterpart (the reference evaluates the generator of the last iteration).  pdgn_adam_ema_multi is pdgn_adam_multi with one more
+ * HOST array of device pointers, e (4-byte aligned; a tensor whose five pointers are 16-byte aligned takes the vector path, the
+ * results are the same): p, m, v come out bit for bit as pdgn_adam_multi writes them, and in the same launch, on the same walk
+ * (64 tensors per launch here: five pointer arrays in 3.4 KB of kernel arguments), with t = step[0], the count of THIS update,
+ *   d_t = min(ema_decay, (1 + t) / (10 + t))    in fp64, evaluated on the device;    omd = (float)(1.0 - d_t)
+ *   e   = fadd(e, fmul(omd, fsub(p_new, e)))     three separately rounded fp32 operations, never contracted into an FMA.
+ * State touched: p, m, v, e; read: g, step.  Keeps none of its own, allocates nothing.
+ * PDGN_ERR_INVALID: pdgn_adam_multi's cases, a null or misaligned e[i], ema_decay outside [0, 1); checked before any launch. */
+int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                        const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay, const float *step,
+                        pdgn_stream_t stream);
+/* The average alone, by the same expressions (the same bits as the fused launch gives for the same p and e): for an optimizer
+ * step that did not go through pdgn_adam_ema_multi.  e, p: HOST arrays of ntensors device pointers (128 tensors per launch), n:
+ * element counts, step (device): the count t of the update that produced p.  State touched: e; read: p, step.  Allocates nothing.
+ * No reference counterpart.  PDGN_ERR_INVALID: ntensors < 1, a null or misaligned pointer, n[i] < 1, ema_decay outside [0, 1). */
+int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
+                   pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ deterministic mode
  * pdgn_set_deterministic: process-wide switch, like pdgn_gemm_set_mode.  -1 queries the current value; any other value

@@ -15,6 +15,9 @@
 #define ADAM_CHUNK 4096            // elements per workgroup: four float4 per thread
 #define ADAM_MAXT 72               // tensors per launch: their pointers travel in the kernel arguments (3.5 KB of the 4 KB there are)
 
+#define ADAM_EMA_MAXT 64           // ... with the averages' pointers beside them: 52 bytes per tensor, 3.4 KB of arguments (72 would be 3.8 KB,
+                                   // which leaves the runtime's hidden arguments less room than they take)
+
 struct AdamArgs {                  // by value: a recorded iteration (csrc/replay.hip) re-issues the launch with the same pointers
     float *p[ADAM_MAXT];
     const float *g[ADAM_MAXT];
@@ -25,9 +28,36 @@ struct AdamArgs {                  // by value: a recorded iteration (csrc/repla
     int ntensors;
 };
 
-__global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
-                                                                  const float *__restrict__ step) {
-    __shared__ float sc[2];
+struct AdamEmaArgs {               // the same table with the list of averages (pdgn_adam_ema_multi)
+    float *p[ADAM_EMA_MAXT];
+    const float *g[ADAM_EMA_MAXT];
+    float *m[ADAM_EMA_MAXT];
+    float *v[ADAM_EMA_MAXT];
+    float *e[ADAM_EMA_MAXT];
+    long long n[ADAM_EMA_MAXT];
+    int chunk0[ADAM_EMA_MAXT];
+    int ntensors;
+};
+static_assert(sizeof(AdamArgs) + 40 <= 3584 && sizeof(AdamEmaArgs) + 48 <= 3584, "pointer tables: 3.5 KB of the 4 KB of kernel arguments");
+
+// ---- the generator's averaged copy (an exponential moving average of the parameters, Yazici et al. 2019), one expression for the
+// fused launch, the stand-alone launch and the host mirror of the tests: with t the step count of THIS update,
+//     d_t = min(ema_decay, (1 + t) / (10 + t))   in fp64 (the usual warm-up, from the device-side counter: a replayed launch needs
+//                                                 no host value);      omd = (float)(1 - d_t)
+//     e <- e + omd * (p_new - e)                  three separately rounded fp32 operations, never an FMA
+__device__ __forceinline__ float ema_one_minus_decay(double ema_decay, const float *step) {
+    const double t = (double)step[0];
+    const double warm = (1.0 + t) / (10.0 + t);
+    return (float)(1.0 - (ema_decay < warm ? ema_decay : warm));
+}
+__device__ __forceinline__ void ema_one(float &e, float p, float omd) { e = __fadd_rn(e, __fmul_rn(omd, __fsub_rn(p, e))); }
+
+// One chunk of one tensor.  EMA = false is pdgn_adam_multi's kernel; EMA = true adds the average E to the same walk (one more load
+// in front of the stores, one more store behind them): the Adam arithmetic is this one text for both.
+template <bool EMA, class Args>
+__device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta1d, double beta2d, double eps, double ema_decay,
+                                           const float *__restrict__ step) {
+    __shared__ float sc[EMA ? 3 : 2];
     // the chunk's tensor: the last one whose first chunk is <= this chunk
     int lo = 0, hi = a.ntensors - 1;
     const int c = blockIdx.x;
@@ -37,6 +67,8 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs
     }
     float *const P = a.p[lo], *const M = a.m[lo], *const V = a.v[lo];
     const float *const G = a.g[lo];
+    float *E = nullptr;
+    if constexpr (EMA) E = a.e[lo];
     const long long n = a.n[lo];
     if (threadIdx.x == 0) {
         // torch: the two bias corrections in fp64, handed to the arithmetic as floats; step_size = lr (double) / that float
@@ -44,12 +76,15 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs
         const float bc1 = (float)(1.0 - pow(beta1d, t));
         sc[0] = (float)(lr / (double)bc1);
         sc[1] = (float)sqrt(1.0 - pow(beta2d, t));
+        if constexpr (EMA) sc[2] = ema_one_minus_decay(ema_decay, step);
     }
     __syncthreads();
     const float step_size = sc[0], bc2s = sc[1];
+    float omd = 0.f;
+    if constexpr (EMA) omd = sc[2];
     const double epsd = (double)eps, w1 = 1.0 - beta1d, w2 = 1.0 - beta2d;
     const long long i0 = (long long)(c - a.chunk0[lo]) * ADAM_CHUNK;
-    const bool vec = ((((uintptr_t)P | (uintptr_t)G | (uintptr_t)M | (uintptr_t)V) & 15) == 0);
+    const bool vec = ((((uintptr_t)P | (uintptr_t)G | (uintptr_t)M | (uintptr_t)V | (uintptr_t)E) & 15) == 0);
     // torch's expressions with torch's types (lr, betas, eps are doubles there: the moment updates are evaluated in fp64 and rounded
     // once, 1 - beta is 1 - the DOUBLE beta): the results are torch's bits, not merely close to them
     auto one = [&](float &p, float g, float &m, float &v) {
@@ -62,7 +97,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs
         // all loads of the chunk first (the stores below may alias them as far as the compiler knows: interleaved, every float4
         // group waited for the one before), then the arithmetic, then the stores
         constexpr int NU = ADAM_CHUNK / (4 * ADAM_THREADS);
-        float4 p4[NU], g4[NU], m4[NU], v4[NU];
+        float4 p4[NU], g4[NU], m4[NU], v4[NU], e4[EMA ? NU : 1];
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
@@ -71,6 +106,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs
                 g4[u] = *reinterpret_cast<const float4 *>(G + i);
                 m4[u] = *reinterpret_cast<const float4 *>(M + i);
                 v4[u] = *reinterpret_cast<const float4 *>(V + i);
+                if constexpr (EMA) e4[u] = *reinterpret_cast<const float4 *>(E + i);
             }
         }
 #pragma unroll
@@ -82,13 +118,34 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs
                 *reinterpret_cast<float4 *>(P + i) = p4[u];
                 *reinterpret_cast<float4 *>(M + i) = m4[u];
                 *reinterpret_cast<float4 *>(V + i) = v4[u];
+                if constexpr (EMA) {
+                    ema_one(e4[u].x, p4[u].x, omd); ema_one(e4[u].y, p4[u].y, omd);
+                    ema_one(e4[u].z, p4[u].z, omd); ema_one(e4[u].w, p4[u].w, omd);
+                    *reinterpret_cast<float4 *>(E + i) = e4[u];
+                }
             } else {
-                for (long long j = i; j < n && j < i + 4; ++j) one(P[j], G[j], M[j], V[j]);
+                for (long long j = i; j < n && j < i + 4; ++j) {
+                    one(P[j], G[j], M[j], V[j]);
+                    if constexpr (EMA) ema_one(E[j], P[j], omd);
+                }
             }
         }
     } else {
-        for (long long i = i0 + threadIdx.x; i < n && i < i0 + ADAM_CHUNK; i += ADAM_THREADS) one(P[i], G[i], M[i], V[i]);
+        for (long long i = i0 + threadIdx.x; i < n && i < i0 + ADAM_CHUNK; i += ADAM_THREADS) {
+            one(P[i], G[i], M[i], V[i]);
+            if constexpr (EMA) ema_one(E[i], P[i], omd);
+        }
     }
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
+                                                                  const float *__restrict__ step) {
+    adam_chunk<false>(a, lr, beta1d, beta2d, eps, 0.0, step);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_multi_kernel(const AdamEmaArgs a, double lr, double beta1d, double beta2d, double eps,
+                                                                      double ema_decay, const float *__restrict__ step) {
+    adam_chunk<true>(a, lr, beta1d, beta2d, eps, ema_decay, step);
 }
 
 // One Adam step of `ntensors` fp32 tensors (p, g, m, v: HOST arrays of device pointers; n: their element counts), in
@@ -116,6 +173,42 @@ extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *
         }
         for (int i = a.ntensors; i < ADAM_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
         hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps, step);
+    }
+    return pdgn_launch_status();
+}
+
+// pdgn_adam_multi with the averages e (HOST array of device pointers) updated in the same launches, ceil(ntensors / 64) of them:
+// p, m, v are pdgn_adam_multi's bits; e <- e + (1 - d_t) (p_new - e) as written at ema_one_minus_decay above.  No reference
+// counterpart (the reference keeps no averaged generator).
+extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                                   const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
+                                   const float *step, pdgn_stream_t stream) {
+    if (ntensors < 1 || !p || !g || !m || !v || !e || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
+        !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || !(ema_decay >= 0. && ema_decay < 1.))
+        return PDGN_ERR_INVALID;
+    for (int i = 0; i < ntensors; ++i)
+        if (!p[i] || !g[i] || !m[i] || !v[i] || !e[i] || n[i] < 1 ||
+            (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (uintptr_t)e[i]) & 3))
+            return PDGN_ERR_INVALID;
+    for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {                  // every launch's chunk count is checked before the first launch
+        long long chunks = 0;
+        for (int i = t0; i < ntensors && i < t0 + ADAM_EMA_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
+    }
+    for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {
+        AdamEmaArgs a;
+        a.ntensors = ntensors - t0 < ADAM_EMA_MAXT ? ntensors - t0 : ADAM_EMA_MAXT;
+        long long chunks = 0;
+        for (int i = 0; i < a.ntensors; ++i) {
+            a.p[i] = (float *)p[t0 + i]; a.g[i] = (const float *)g[t0 + i]; a.m[i] = (float *)m[t0 + i]; a.v[i] = (float *)v[t0 + i];
+            a.e[i] = (float *)e[t0 + i];
+            a.n[i] = n[t0 + i];
+            a.chunk0[i] = (int)chunks;
+            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        }
+        for (int i = a.ntensors; i < ADAM_EMA_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = a.e[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
+        hipLaunchKernelGGL(adam_ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps,
+                           ema_decay, step);
     }
     return pdgn_launch_status();
 }
@@ -179,6 +272,83 @@ extern "C" int pdgn_copy_multi(int ntensors, void *const *dst, const void *const
         }
         for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.d[i] = nullptr; a.s[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
         hipLaunchKernelGGL(copy_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a);
+    }
+    return pdgn_launch_status();
+}
+
+// ---- the same walk for the average alone: e[i] <- e[i] + (1 - d_t) (p[i] - e[i]), where the optimizer step in front of it was not
+// pdgn_adam_ema_multi (the optimizer's first, ordinary step; torch's fused kernel).  ema_one_minus_decay / ema_one are the fused
+// launch's: the same bits.
+struct EmaArgs {
+    float *e[COPY_MAXT];
+    const float *p[COPY_MAXT];
+    long long n[COPY_MAXT];
+    int chunk0[COPY_MAXT];
+    int ntensors;
+};
+
+__global__ __launch_bounds__(ADAM_THREADS) void ema_multi_kernel(const EmaArgs a, double ema_decay, const float *__restrict__ step) {
+    int lo = 0, hi = a.ntensors - 1;
+    const int c = blockIdx.x;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.chunk0[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    float *const E = a.e[lo];
+    const float *const P = a.p[lo];
+    const long long n = a.n[lo], i0 = (long long)(c - a.chunk0[lo]) * ADAM_CHUNK;
+    const float omd = ema_one_minus_decay(ema_decay, step);
+    if (((((uintptr_t)E | (uintptr_t)P) & 15) == 0)) {
+        constexpr int NU = ADAM_CHUNK / (4 * ADAM_THREADS);
+        float4 e4[NU], p4[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
+            if (i + 3 < n) {
+                e4[u] = *reinterpret_cast<const float4 *>(E + i);
+                p4[u] = *reinterpret_cast<const float4 *>(P + i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
+            if (i + 3 < n) {
+                ema_one(e4[u].x, p4[u].x, omd); ema_one(e4[u].y, p4[u].y, omd);
+                ema_one(e4[u].z, p4[u].z, omd); ema_one(e4[u].w, p4[u].w, omd);
+                *reinterpret_cast<float4 *>(E + i) = e4[u];
+            } else {
+                for (long long j = i; j < n && j < i + 4; ++j) ema_one(E[j], P[j], omd);
+            }
+        }
+    } else {
+        for (long long i = i0 + threadIdx.x; i < n && i < i0 + ADAM_CHUNK; i += ADAM_THREADS) ema_one(E[i], P[i], omd);
+    }
+}
+
+// e[i] (n[i] floats) <- e[i] + (1 - d_t) (p[i] - e[i]) for ntensors fp32 tensors (HOST arrays of device pointers, 4-byte aligned;
+// 16-byte aligned pairs take the vector path), d_t = min(ema_decay, (1 + t) / (10 + t)) from step[0] (device), in
+// ceil(ntensors / 128) launches.  No reference counterpart.
+extern "C" int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
+                              pdgn_stream_t stream) {
+    if (ntensors < 1 || !e || !p || !n || !step || !(ema_decay >= 0. && ema_decay < 1.)) return PDGN_ERR_INVALID;
+    for (int i = 0; i < ntensors; ++i)
+        if (!e[i] || !p[i] || n[i] < 1 || (((uintptr_t)e[i] | (uintptr_t)p[i]) & 3)) return PDGN_ERR_INVALID;
+    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
+        long long chunks = 0;
+        for (int i = t0; i < ntensors && i < t0 + COPY_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
+    }
+    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
+        EmaArgs a;
+        a.ntensors = ntensors - t0 < COPY_MAXT ? ntensors - t0 : COPY_MAXT;
+        long long chunks = 0;
+        for (int i = 0; i < a.ntensors; ++i) {
+            a.e[i] = (float *)e[t0 + i]; a.p[i] = (const float *)p[t0 + i]; a.n[i] = n[t0 + i];
+            a.chunk0[i] = (int)chunks;
+            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        }
+        for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.e[i] = nullptr; a.p[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
+        hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step);
     }
     return pdgn_launch_status();
 }

@@ -9,9 +9,11 @@ all four resolutions (csrc/render.hip, pdgn_render_sheet -> an 8-bit grey PNG) a
 
 A report does not touch training: it runs under no_grad in eval mode after a device synchronise, draws from generators of its
 own (torch's global RNG state is left alone), and leaves every parameter, buffer and optimizer state as it found them
-(DESIGN.md section 7c).
+(DESIGN.md section 7c).  Where the trainer keeps an averaged generator (`PDGNTrainer(ema_decay=...)`, section 7d) the sheet and the
+metrics are the averaged generator's: the report runs inside `trainer.averaged_generator()`, and the averages are left as found too.
 """
 import argparse
+import contextlib
 import ctypes
 import math
 import os
@@ -195,15 +197,19 @@ class SnapshotReporter:
         was_training = G.training
         hints = G.forward_hints()                                # (what the eager step's next pre-assembly would read: generator.py)
         G.eval()
+        # with an averaged generator the report shows THAT one (what one would evaluate or ship): its parameters by value for
+        # the duration of the report, the live BatchNorm buffers
+        averaged = self.trainer.averaged_generator() if getattr(self.trainer, "ema", None) is not None else contextlib.nullcontext()
         try:
-            z = torch.randn(self.rows, 128, generator=self._generator(0), device=dev)
-            sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True)
-            if self.full:
-                _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1))
-            else:
-                results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
-            results = {k: float(results[k]) for k in self.keys}
-            image = sheet.cpu().numpy()
+            with averaged:
+                z = torch.randn(self.rows, 128, generator=self._generator(0), device=dev)
+                sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True)
+                if self.full:
+                    _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1))
+                else:
+                    results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
+                results = {k: float(results[k]) for k in self.keys}
+                image = sheet.cpu().numpy()
         finally:
             G.train(was_training)
             G.restore_forward_hints(hints)

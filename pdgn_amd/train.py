@@ -6,7 +6,9 @@ where the reference puts them (<checkpoint_dir>/<model_dir>/<network>/<epoch>_<c
 <checkpoint_dir>/<model_dir>/<log_info>).  test: load --pretrain_model_G/_D from that directory, generate as many clouds as
 the test split has, write nonormal_out.npy / out.npy and log.txt under <save_dir>/GEN_Ours_<choice>_<time>/
 (models/PDGNet_v2.py:271-326).  --report_every N (train): every N epochs a preview sheet and a row of held-out metrics on the val
-split, under <checkpoint_dir>/<model_dir>/report (pdgn_amd/report.py).  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+split, under <checkpoint_dir>/<model_dir>/report (pdgn_amd/report.py).  --ema_decay D (train): keep an exponential moving average of
+the generator's parameters (decay D, e.g. 0.999), write it as <epoch>_<category>_G_ema.pth beside every checkpoint pair and report
+on it; --phase test --pretrain_model_G <epoch>_<category>_G_ema.pth evaluates it.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -51,12 +53,20 @@ def build_parser():
                    "a row of held-out metrics on the val split, under <checkpoint_dir>/<model_dir>/report); 0: none")
     p.add_argument("--report_rows", type=int, default=8, help="samples per preview sheet")
     p.add_argument("--report_full", action="store_true", help="reports run the full evaluation (EMD included) instead of the CD-only one")
+    p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS, help="decay of the averaged generator (an exponential moving average of the "
+                   "generator's parameters, e.g. 0.999: written as <epoch>_<category>_G_ema.pth, shown by the reports); 0: none")
     return p
+
+
+class Args(argparse.Namespace):
+    """The parsed command line.  --ema_decay is listed (vars(), the log's first line) only where it was given: a run without it
+    has the namespace, and writes the log line, of the time before the flag existed; reading it gives 0 then."""
+    ema_decay = 0.0
 
 
 def parse_args(argv=None):
     p = build_parser()
-    args = p.parse_args(argv)
+    args = p.parse_args(argv, namespace=Args())
     if args.model_dir is None:
         p.error("please create model dir (--model_dir)")                                       # main.py:56-58
     if args.dataset != "shapenet15k":
@@ -71,15 +81,15 @@ def parse_args(argv=None):
         p.error("--max_epoch and --batch_size must be at least one")
     if args.report_every < 0 or args.report_rows < 1:
         p.error("--report_every must not be negative and --report_rows at least one")
+    if not 0.0 <= args.ema_decay < 1.0:
+        p.error("--ema_decay %r: at least 0 and below 1" % args.ema_decay)
     return args
 
 
 def logged_args(args):
     """What the first line of <log_info> shows: with reports off (--report_every 0) the namespace without the report flags, so
     that the file is what it was before they existed."""
-    if args.report_every:
-        return args
-    return argparse.Namespace(**{k: v for k, v in vars(args).items() if not k.startswith("report_")})
+    return argparse.Namespace(**{k: v for k, v in vars(args).items() if args.report_every or not k.startswith("report_")})
 
 
 def open_data_root(path):
@@ -122,7 +132,9 @@ def make_trainer(args, device):
     from .trainer import PDGNTrainer
     base = args.num_point // 16
     gen = PointGenerator(args.num_point, args.num_k, softmax=args.softmax == "True", base_points=base)
-    return PDGNTrainer(device=device, lr=args.learning_rate, num_k=args.num_k, base_points=base, generator=gen)
+    # (--phase test loads whichever file it is given -- G.pth or G_ema.pth -- into the generator itself: no average to keep)
+    return PDGNTrainer(device=device, lr=args.learning_rate, num_k=args.num_k, base_points=base, generator=gen,
+                       ema_decay=args.ema_decay if args.phase == "train" else 0.0)
 
 
 def _resume(args, trainer, ckpt):

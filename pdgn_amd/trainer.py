@@ -6,6 +6,7 @@ BatchNorm statistics stay local (same semantics), and gradients are all-reduced 
 as ONE flat fp32 buffer per network (G: 50.8 MB, D1-4: 6.8 MB) -- parameters' ``.grad`` tensors
 are views into that buffer, so there is no bucket copy in or out.
 """
+import contextlib
 import os
 import warnings
 
@@ -223,15 +224,51 @@ class LeanAdamStep:
     `state_dict()` are untouched); anything unusual (a parameter without gradient, several groups, amsgrad, weight decay, a
     non-fused optimizer, step hooks, replaced state tensors) keeps calling `optimizer.step()`; the invariants are re-checked on
     every call.  `torch._fused_adam_` / `torch._foreach_add_` are private torch entry points (written against torch 2.10): a
-    changed signature falls back to `optimizer.step()` for good."""
+    changed signature falls back to `optimizer.step()` for good.
 
-    def __init__(self, opt):
+    ema / ema_decay (the generator's optimizer under `PDGNTrainer(ema_decay=...)`): one fp32 tensor per parameter, in the order of
+    the optimizer's group, holding the exponential moving average of that parameter.  Every route out of `step` updates it on the
+    same stream, right behind the parameters: the own Adam kernel in its own launch (pdgn_adam_ema_multi), every other route with
+    pdgn_ema_multi behind the optimizer step (csrc/adam.hip: the same expressions, the same bits)."""
+
+    def __init__(self, opt, ema=None, ema_decay=0.0):
         self.opt, self.lists, self._table = opt, None, None
+        self.ema, self.ema_decay, self._ema_table = (list(ema) if ema else None), float(ema_decay), None
 
     def reset(self):
         """The optimizer's state tensors were replaced (load_state_dict): rebuild the lists after the next ordinary step."""
         self.lists = None
         self._table = None
+        self._ema_table = None
+
+    def _plain_step(self):
+        """`optimizer.step()` itself, with the average behind it."""
+        self.opt.step()
+        self._ema_alone()
+
+    def _ema_alone(self):
+        """e <- e + (1 - d_t)(p - e) behind an optimizer step that was not pdgn_adam_ema_multi: one launch per 128 tensors on the
+        current stream; t is the optimizer's own device-side step count (already incremented by that step).  There is no torch
+        form of it: anything but fp32 CUDA tensors and a device-side fp32 counter raises."""
+        if self.ema is None:
+            return
+        import ctypes
+        ps = self.opt.param_groups[0]["params"]
+        step = self.opt.state[ps[0]]["step"]
+        n = len(ps)
+        tab = self._ema_table
+        if tab is None or tab[0] != n or tab[2][0] != ps[0].data_ptr() or tab[2][n - 1] != ps[n - 1].data_ptr():
+            if len(self.ema) != n or any(t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or e.numel() != t.numel()
+                                          or e.dtype != torch.float32 or not e.is_contiguous() or e.device != t.device
+                                          for t, e in zip(ps, self.ema)):
+                raise _lib.PdgnHipError("the averaged generator needs contiguous fp32 parameters on a ROCm device (pdgn_amd has no CPU path)")
+            vp = ctypes.c_void_p * n
+            tab = self._ema_table = (n, vp(*[e.data_ptr() for e in self.ema]), vp(*[t.data_ptr() for t in ps]),
+                                     (ctypes.c_longlong * n)(*[t.numel() for t in ps]))
+        if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.float32):
+            raise _lib.PdgnHipError("the averaged generator reads Adam's step count on the device: a capturable optimizer is required")
+        _lib.check(_lib.lib().pdgn_ema_multi(n, tab[1], tab[2], tab[3], ctypes.c_double(self.ema_decay), _lib.ptr(step),
+                                             _lib.stream_of(ps[0])), "pdgn_ema_multi")
 
     _OWN = os.environ.get("PDGN_OWN_ADAM", "1") == "1"           # A/B switch: 0 = torch._fused_adam_
 
@@ -255,6 +292,16 @@ class LeanAdamStep:
                                  vp(*[t.data_ptr() for t in exp_avg_sqs]), (ctypes.c_longlong * n)(*[t.numel() for t in ps]), vp)
         if any(t.dtype != torch.float32 or not t.is_contiguous() for t in grads):
             return False
+        if self.ema is not None:                                 # the average rides in the same launches
+            et = self._ema_table
+            if et is None or et[0] != n or et[2][0] != tab[1][0] or et[2][n - 1] != tab[1][n - 1]:
+                return False                                     # (not validated yet, or other parameters: _ema_alone checks and raises)
+            _lib.check(_lib.lib().pdgn_adam_ema_multi(n, tab[1], tab[5](*[t.data_ptr() for t in grads]), tab[2], tab[3], et[1], tab[4],
+                                                      ctypes.c_double(g["lr"]), ctypes.c_double(g["betas"][0]),
+                                                      ctypes.c_double(g["betas"][1]), ctypes.c_double(g["eps"]),
+                                                      ctypes.c_double(self.ema_decay), _lib.ptr(steps[0]), _lib.stream_of(ps[0])),
+                       "pdgn_adam_ema_multi")
+            return True
         _lib.check(_lib.lib().pdgn_adam_multi(n, tab[1], tab[5](*[t.data_ptr() for t in grads]), tab[2], tab[3], tab[4],
                                               ctypes.c_double(g["lr"]), ctypes.c_double(g["betas"][0]), ctypes.c_double(g["betas"][1]),
                                               ctypes.c_double(g["eps"]), _lib.ptr(steps[0]), _lib.stream_of(ps[0])), "pdgn_adam_multi")
@@ -263,7 +310,7 @@ class LeanAdamStep:
     def step(self):
         opt = self.opt
         if self.lists is None:
-            opt.step()
+            self._plain_step()
             g = opt.param_groups[0]
             ok = (len(opt.param_groups) == 1 and g.get("fused") and g.get("capturable") and not g.get("amsgrad")
                   and not g.get("maximize") and not g.get("differentiable") and g.get("weight_decay", 0) == 0
@@ -276,7 +323,7 @@ class LeanAdamStep:
                 self.lists = False
             return
         if self.lists is False:
-            opt.step()
+            self._plain_step()
             return
         ps, exp_avgs, exp_avg_sqs, steps = self.lists
         grads = [p.grad for p in ps]
@@ -288,7 +335,7 @@ class LeanAdamStep:
                 or g.get("maximize") or isinstance(g["lr"], torch.Tensor) or st0 is None or st0.get("exp_avg") is not exp_avgs[0]
                 or opt._optimizer_step_pre_hooks or opt._optimizer_step_post_hooks or any(gr is None for gr in grads)):
             self.lists = None                                    # re-validated after the next ordinary step
-            opt.step()
+            self._plain_step()
             return
         try:
             with torch.no_grad():
@@ -298,19 +345,27 @@ class LeanAdamStep:
                 torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=g["lr"], beta1=g["betas"][0],
                                    beta2=g["betas"][1], weight_decay=0.0, eps=g["eps"], maximize=False, grad_scale=None,
                                    found_inf=None)
+                self._ema_alone()
         except TypeError:                                        # the private op's signature changed (another torch version):
             torch._foreach_sub_(steps, 1)                        # undo the counter and take the public path from now on
             self.lists = False
-            opt.step()
+            self._plain_step()
 
 
 class PDGNTrainer:
     """Generator + D1..D4 + their Adam optimisers (lr 1e-4, betas (0.5, 0.999), :121-125) and the
     op sequence of one iteration.  ``step`` returns the six logged losses (:259-261) as 0-dim
-    device tensors (no host sync inside the step)."""
+    device tensors (no host sync inside the step).
+
+    ema_decay > 0 keeps an exponential moving average of the generator's parameters (`ema`: one view per parameter of the flat
+    `ema_buf`), updated by the generator's optimizer step itself (LeanAdamStep); `averaged_generator()`
+    puts it into the generator for a while, `save` writes it as `<epoch>_<category>_G_ema.pth`.  0: nothing of this exists."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
-                 discriminators=None, distributed=None):
+                 discriminators=None, distributed=None, ema_decay=0.0):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
+        self.ema_decay = float(ema_decay)
         self.device = torch.device(device)
         self.G = (generator or PointGenerator(num_k=num_k, base_points=base_points)).to(self.device)
         self.D = [d.to(self.device) for d in
@@ -328,7 +383,11 @@ class PDGNTrainer:
         cap = self.device.type == "cuda"                     # device-side step counter: graph-capturable
         adam = lambda m: torch.optim.Adam(m.parameters(), lr=lr, betas=(0.5, 0.999), capturable=cap, fused=cap and os.environ.get("PDGN_FUSED_ADAM", "1") == "1")
         self.optG, self.optD = adam(self.G), [adam(d) for d in self.D]
-        self._stepG, self._stepD = LeanAdamStep(self.optG), [LeanAdamStep(o) for o in self.optD]
+        self.ema_buf = self.ema = self._ema_spare = None
+        if self.ema_decay > 0:
+            # one flat buffer, every average on a 16-byte boundary of it (the kernels' float4 path), in the optimizer's order
+            self.ema_buf, self.ema = self._flat_like(self.optG.param_groups[0]["params"])
+        self._stepG, self._stepD = LeanAdamStep(self.optG, self.ema, self.ema_decay), [LeanAdamStep(o) for o in self.optD]
         # stream-overlapped schedule of the eager step (see _step_overlapped); PDGN_OVERLAP=0 turns it off
         self.overlap = cap and os.environ.get("PDGN_OVERLAP", "1") == "1"
         self._side = None
@@ -338,7 +397,57 @@ class PDGNTrainer:
         self._early_tail = os.environ.get("PDGN_EARLY_TAIL", "1") == "1"
         self._split_d = os.environ.get("PDGN_SPLIT_D", "1") == "1"
         self._defer_d = os.environ.get("PDGN_DEFER_D", "1") == "1"
+        self._ema_from_parameters()
         self.sync_replicas()
+
+    @staticmethod
+    def _flat_like(params):
+        slot = lambda p: (p.numel() + 3) // 4 * 4
+        buf = torch.zeros(sum(slot(p) for p in params), dtype=torch.float32, device=params[0].device)
+        views, off = [], 0
+        for p in params:
+            views.append(buf[off:off + p.numel()].view_as(p))
+            off += slot(p)
+        return buf, views
+
+    def _ema_from_parameters(self):
+        """The averages start from the parameters as they are now (construction; a checkpoint without averages)."""
+        if self.ema is not None:
+            with torch.no_grad():
+                torch._foreach_copy_(self.ema, [p.detach() for p in self.optG.param_groups[0]["params"]])
+
+    @contextlib.contextmanager
+    def averaged_generator(self):
+        """`with trainer.averaged_generator():` -- inside, `trainer.G` computes with the averaged parameters (and its live
+        BatchNorm buffers); afterwards the trained ones are back, bit for bit.  The swap is BY VALUE: the launch list has the
+        parameters' addresses baked in, so the tensors stay where they are.  On entry the device is synchronised, the
+        parameters are saved to a spare buffer and overwritten with the averages; on exit the saved values are copied back.
+        The copies are torch's in-place ones, which bump the parameters' version counters: PointDeconv recognises stale
+        pre-assembled operands by (data_ptr, _version), and a raw pdgn_copy_multi would leave operands of the OTHER weights
+        looking current.  The pre-assembled operands are dropped on both sides anyway, and the forward hints are put back as
+        the snapshot reports do.  Not for use between `capture` graphs' replays or inside a step."""
+        if self.ema is None:
+            raise RuntimeError("averaged_generator(): this trainer keeps no averaged generator (ema_decay=0)")
+        params = self.optG.param_groups[0]["params"]
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        if self._ema_spare is None:
+            self._ema_spare = self._flat_like(params)
+        own = hasattr(self.G, "forward_hints")                   # (a caller's own generator module may keep no such state)
+        hints = self.G.forward_hints() if own else None
+        with torch.no_grad():
+            torch._foreach_copy_(self._ema_spare[1], [p.detach() for p in params])
+            torch._foreach_copy_(list(params), self.ema)
+        if own:
+            self.G.drop_preassembled()
+        try:
+            yield self.G
+        finally:
+            with torch.no_grad():
+                torch._foreach_copy_(list(params), self._ema_spare[1])
+            if own:
+                self.G.drop_preassembled()
+                self.G.restore_forward_hints(hints)
 
     def sync_replicas(self, src=0):
         """nn.DataParallel replicates module 0's parameters and buffers onto every device each forward
@@ -364,6 +473,8 @@ class PDGNTrainer:
                     for v in st.values():
                         if torch.is_tensor(v):
                             dist.broadcast(v, src)
+            if self.ema_buf is not None:
+                dist.broadcast(self.ema_buf, src)
 
     def train(self):
         self.G.train()
@@ -390,7 +501,9 @@ class PDGNTrainer:
 
     def save(self, checkpoint_dir, index_epoch, category="chair"):
         """Writes `<epoch>_<category>_G.pth` / `_D.pth` with the reference's keys (:391-407) so that either code
-        base can resume from the other's files."""
+        base can resume from the other's files.  With an averaged generator also `<epoch>_<category>_G_ema.pth`: G.pth's layout
+        with the AVERAGED parameters under `G_model` (buffers: the live ones) plus `ema_decay`, so that either code base's
+        `--phase test --pretrain_model_G <epoch>_<category>_G_ema.pth` evaluates the averaged generator; returned third."""
         os.makedirs(checkpoint_dir, exist_ok=True)
         stem = os.path.join(checkpoint_dir, "%s_%s" % (index_epoch, category))
         held = hold_bn_counters(False)
@@ -403,7 +516,20 @@ class PDGNTrainer:
             dfile["D_model%d" % i] = self._ref_model_state(d)
             dfile["D_optimizer%d" % i] = self._ref_optim_state(o)
         torch.save(dfile, stem + "_D.pth")
+        if self.ema is not None:
+            model = self._ref_model_state(self.G)
+            for (name, p), e in zip(self.G.named_parameters(), self._ema_in_module_order()):
+                assert model["module." + name].shape == e.shape, name
+                model["module." + name] = e.detach().cpu().clone()
+            torch.save({"G_model": model, "G_optimizer": self._ref_optim_state(self.optG), "G_epoch": index_epoch,
+                        "ema_decay": self.ema_decay}, stem + "_G_ema.pth")
+            return stem + "_G.pth", stem + "_D.pth", stem + "_G_ema.pth"
         return stem + "_G.pth", stem + "_D.pth"
+
+    def _ema_in_module_order(self):
+        """The averages in `G.named_parameters()` order (they are kept in the optimizer's, which is the same list today)."""
+        by_id = {id(p): e for p, e in zip(self.optG.param_groups[0]["params"], self.ema)}
+        return [by_id[id(p)] for p in self.G.parameters()]
 
     @staticmethod
     def _load_optim(opt, sd):
@@ -416,7 +542,9 @@ class PDGNTrainer:
 
     def load(self, path_G, path_D):
         """Resume from a reference (or own) checkpoint pair; returns the stored epoch (:352, :374).
-        A missing file raises FileNotFoundError (the reference calls exit(), :345-347)."""
+        A missing file raises FileNotFoundError (the reference calls exit(), :345-347).  With an averaged generator: the
+        averages come from the sibling `..._G_ema.pth` of `..._G.pth` where it exists, else they start from the loaded
+        parameters; the warm-up of the decay needs no state of its own (it reads Adam's restored step count)."""
         from .generator import load_reference_state_dict
         g = torch.load(path_G, map_location="cpu")
         d = torch.load(path_D, map_location="cpu")
@@ -427,6 +555,16 @@ class PDGNTrainer:
             self._load_optim(o, d["D_optimizer%d" % i])
         for st in [self._stepG] + self._stepD:                   # the optimizers' state tensors are new objects now
             st.reset()
+        if self.ema is not None:
+            sibling = str(path_G)[:-len("_G.pth")] + "_G_ema.pth" if str(path_G).endswith("_G.pth") else None
+            if sibling is not None and os.path.exists(sibling):
+                avg = torch.load(sibling, map_location="cpu")["G_model"]
+                avg = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in avg.items()}
+                with torch.no_grad():
+                    for (name, _), e in zip(self.G.named_parameters(), self._ema_in_module_order()):
+                        e.copy_(avg[name])
+            else:
+                self._ema_from_parameters()
         self.sync_replicas()
         return g["G_epoch"]
 
