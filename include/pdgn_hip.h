@@ -32,7 +32,11 @@ extern "C" {
 
 typedef void *pdgn_stream_t; /* hipStream_t */
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header: bump it on any signature change, here and nowhere else.  The library returns it
+ * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
+ * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
+ * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
+#define PDGN_ABI_VERSION 30
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops

@@ -5,12 +5,13 @@ call raises.  Building is explicit (`python -m pdgn_amd.build` / `__graft_entry_
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libpdgn_hip.so")
-ABI_VERSION = 30
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "pdgn_hip.h")
 _lib = None
 
 
@@ -18,8 +19,50 @@ class PdgnHipError(RuntimeError):
     pass
 
 
+# The header is the ABI: the vocabulary of its prototypes, and nothing else, is understood here.
+_RETURNS = {"int": ctypes.c_int, "long long": ctypes.c_longlong}
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint,
+            "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float, "double": ctypes.c_double,
+            "pdgn_stream_t": ctypes.c_void_p}
+
+
+def parse_header(text):
+    """(PDGN_ABI_VERSION, {name: (restype, argtypes)}) of every prototype `RET pdgn_name(ARGS);` in the text of a header.  A
+    parameter with a `*` is a pointer (c_void_p), every other one is `TYPE name` with TYPE in _SCALARS; a prototype with anything
+    else in it raises PdgnHipError -- a wrong guess here is a wrong argument on the device."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+PDGN_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    if version is None:
+        raise PdgnHipError("no `#define PDGN_ABI_VERSION <number>` in the header")
+    signatures = {}
+    for stmt in re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).split(";"):
+        if not re.search(r"\bpdgn_\w+\s*\(", stmt):
+            continue
+        proto = " ".join(stmt.split())
+        m = re.fullmatch(r"(.*?) ?\b(pdgn_\w+) ?\((.*)\)", proto)
+        if m is None or m.group(1) not in _RETURNS or m.group(2) in signatures:
+            raise PdgnHipError("include/pdgn_hip.h: cannot read the prototype `%s;`" % proto)
+        argtypes = []
+        for arg in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            words = [w for w in arg.split() if w != "const"]
+            if "*" in arg and "(" not in arg and "[" not in arg:
+                ctype = ctypes.c_void_p
+            else:
+                ctype = _SCALARS.get(" ".join(words[:-1])) if words and words[-1].isidentifier() else None
+            if ctype is None:
+                raise PdgnHipError("include/pdgn_hip.h: cannot read the parameter `%s` of `%s;`" % (arg.strip(), proto))
+            argtypes.append(ctype)
+        signatures[m.group(2)] = (_RETURNS[m.group(1)], tuple(argtypes))
+    return int(version.group(1)), signatures
+
+
+with open(HEADER) as _f:
+    ABI_VERSION, SIGNATURES = parse_header(_f.read())
+
+
 def lib():
-    """Load (once) and return the ctypes handle of libpdgn_hip.so."""
+    """Load (once) and return the ctypes handle of libpdgn_hip.so, every entry point with the restype / argtypes of its prototype in
+    include/pdgn_hip.h: call sites pass plain Python ints and floats, ptr() / stream_of() handles, None or ctypes arrays."""
     global _lib
     if _lib is None:
         if not os.path.exists(SO_PATH):
@@ -27,11 +70,15 @@ def lib():
                 "libpdgn_hip.so is not built (%s missing): run `python -m pdgn_amd.build`; "
                 "pdgn_amd has no CPU fallback" % SO_PATH)
         handle = ctypes.CDLL(SO_PATH)
-        handle.pdgn_abi_version.restype = ctypes.c_int
         got = handle.pdgn_abi_version()
         if got != ABI_VERSION:
             raise PdgnHipError("libpdgn_hip.so ABI %d != expected %d: rebuild" % (got, ABI_VERSION))
-        handle.pdgn_det_workspace_ints.restype = ctypes.c_longlong
+        for name, (restype, argtypes) in SIGNATURES.items():
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:
+                raise PdgnHipError("libpdgn_hip.so does not export %s, which include/pdgn_hip.h declares: rebuild" % name) from None
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = handle
         if handle.pdgn_gemm_set_mode(-1) == 2:                     # the default mode: a ring on the current device now (raw ctypes callers);
             ensure_scale_slots(handle=handle)                      # the wrappers move it if the contractions run on another one
@@ -55,8 +102,7 @@ def ensure_scale_slots(device=None, handle=None):
     if idx not in _SCALE_SLOTS:
         _SCALE_SLOTS[idx] = torch.zeros(1 << 24, dtype=torch.int32, device=torch.device("cuda", idx))
     t = _SCALE_SLOTS[idx]
-    check((handle or lib()).pdgn_gemm_set_scale_slots(ctypes.c_void_p(t.data_ptr()), ctypes.c_longlong(t.numel() * 4)),
-          "pdgn_gemm_set_scale_slots")
+    check((handle or lib()).pdgn_gemm_set_scale_slots(ptr(t), t.numel() * 4), "pdgn_gemm_set_scale_slots")
     _SCALE_SLOTS["attached"] = idx
 
 
@@ -169,5 +215,5 @@ def set_deterministic(on):
 def det_workspace(device, *transposes):
     """Integer workspace of a fixed-order scatter adjoint: pdgn_det_workspace_ints per (b, targets, edges) transpose it makes."""
     L = lib()
-    ints = sum(L.pdgn_det_workspace_ints(int(b), int(t), ctypes.c_longlong(e)) for b, t, e in transposes)
+    ints = sum(L.pdgn_det_workspace_ints(int(b), int(t), int(e)) for b, t, e in transposes)
     return torch.empty(ints, dtype=torch.int32, device=device)

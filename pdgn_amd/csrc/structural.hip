@@ -713,5 +713,3 @@ extern "C" int pdgn_matchcost_grad(int b, int n, int m, const float *xyz1, const
                        s, n, m, xyz1, xyz2, match, grad2);
     return pdgn_launch_status();
 }
-
-extern "C" int pdgn_abi_version(void) { return 30; }

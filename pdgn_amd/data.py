@@ -10,7 +10,6 @@ shape (which is also how the tests drive it: this image has no h5py).
 pdgn_feed_batch) writes a batch -- shuffled clouds, the three sub-samplings, the transposes and both noise draws --
 into the buffers the training step reads.
 """
-import ctypes
 import os
 import random
 
@@ -261,9 +260,8 @@ class BatchFeeder:
             raise IndexError("batch %d of epoch %d: an epoch has %d batches, epochs count from 1" % (i, epoch, self.batches_per_epoch))
         if epoch != self._order_epoch:
             self._upload_order(epoch)
-        ll, ull = ctypes.c_longlong, ctypes.c_ulonglong
         _lib.check(self._fn(self.B, self.S, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(self.clouds),
-                            _lib.ptr(self._order), ll((i * self.world + self.rank) * self.B), ull(self.seed & 0xFFFFFFFFFFFFFFFF),
-                            ull((epoch - 1) * self.batches_per_epoch + i), ll(self.rank * self.B), ctypes.c_float(self.sigma),
+                            _lib.ptr(self._order), (i * self.world + self.rank) * self.B, self.seed & 0xFFFFFFFFFFFFFFFF,
+                            (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B, self.sigma,
                             _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
                             _lib.stream_of(self.clouds)), "pdgn_feed_batch")

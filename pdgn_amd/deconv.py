@@ -132,8 +132,7 @@ class EdgeGatherSum(Function):
                 bstride = C if (bias is not None and bias.dim() == 2) else 0
             if len(spec) > 5 and spec[5]:
                 # the consumer is a training-mode BatchNorm over (b*n*P, C): emit its partial statistics here
-                L.pdgn_bn_scratch_floats.restype = ctypes.c_longlong
-                scr = torch.empty(L.pdgn_bn_scratch_floats(ctypes.c_longlong(b * n * P), C), dtype=F32, device=Y.device)
+                scr = torch.empty(L.pdgn_bn_scratch_floats(b * n * P, C), dtype=F32, device=Y.device)
                 check(L.pdgn_window_gather_sum_stats(b, n, k, ldy, T, P, C, off, offc, ptr(Y), ptr(idx), ptr(bias_c),
                                                      bstride, ptr(out), ptr(scr), stream_of(Y)),
                       "pdgn_window_gather_sum_stats")

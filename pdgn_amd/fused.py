@@ -1,5 +1,4 @@
 """Autograd wrappers of the fused channels-last kernels of libpdgn_hip.so (bnact.hip)."""
-import ctypes
 import os
 import weakref
 
@@ -14,8 +13,7 @@ ACT = {"none": 0, "relu": 1, "leaky_relu": 2}
 
 
 def _scratch_floats(L, rows, C):
-    L.pdgn_bn_scratch_floats.restype = ctypes.c_longlong
-    n = L.pdgn_bn_scratch_floats(ctypes.c_longlong(rows), C)
+    n = L.pdgn_bn_scratch_floats(rows, C)
     if n < 0:
         raise _lib.PdgnHipError("pdgn_bn_scratch_floats: argument outside the supported range")
     return n
@@ -172,8 +170,7 @@ def group_colsum(x2d, group_rows=None):
             and rows // gr <= 65535):
         return x2d.sum(dim=0, keepdim=True) if gr == rows else x2d.reshape(rows // gr, gr, C).sum(dim=1)
     out = _zeros((rows // gr, C), x2d.device)
-    check(_lib.lib().pdgn_group_colsum(ctypes.c_longlong(rows // gr), ctypes.c_longlong(gr), C, ptr(x2d), ctypes.c_longlong(x2d.stride(0)),
-                                       ptr(out), stream_of(x2d)), "pdgn_group_colsum")
+    check(_lib.lib().pdgn_group_colsum(rows // gr, gr, C, ptr(x2d), x2d.stride(0), ptr(out), stream_of(x2d)), "pdgn_group_colsum")
     return out
 
 
@@ -187,25 +184,20 @@ def _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training
         partials, block = partials                              # block-shifted rows, with the block size linear_cl attached
     if training and block is not None:
         nparts = partials.shape[0]
-        L.pdgn_bn_blocks_scratch_doubles.restype = ctypes.c_longlong
-        nd = L.pdgn_bn_blocks_scratch_doubles(C, ctypes.c_longlong(nparts))
+        nd = L.pdgn_bn_blocks_scratch_doubles(C, nparts)
         scr = torch.empty(nd, dtype=torch.float64, device=x.device) if nd > 0 else None
-        check(L.pdgn_bn_stats_from_gemm_partials(ctypes.c_longlong(rows), C, ctypes.c_longlong(nparts), block,
-                                                 ctypes.c_float(eps), ctypes.c_float(momentum), ptr(g), ptr(b), ptr(pb),
-                                                 ptr(running_mean), ptr(running_var), ptr(partials), ptr(stats), ptr(scr),
-                                                 stream_of(x)),
+        check(L.pdgn_bn_stats_from_gemm_partials(rows, C, nparts, block, eps, momentum, ptr(g), ptr(b), ptr(pb),
+                                                 ptr(running_mean), ptr(running_var), ptr(partials), ptr(stats), ptr(scr), stream_of(x)),
               "pdgn_bn_stats_from_gemm_partials")
     elif training and partials is not None:                     # first stage done by x's producer (its epilogue)
-        check(L.pdgn_bn_stats_from_partials(ctypes.c_longlong(rows), C, ctypes.c_float(eps), ctypes.c_float(momentum),
-                                            ptr(g), ptr(b), ptr(pb), ptr(running_mean), ptr(running_var), ptr(partials),
+        check(L.pdgn_bn_stats_from_partials(rows, C, eps, momentum, ptr(g), ptr(b), ptr(pb), ptr(running_mean), ptr(running_var), ptr(partials),
                                             ptr(stats), stream_of(x)), "pdgn_bn_stats_from_partials")
     elif training:
         scratch = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
-        check(L.pdgn_bn_stats(ctypes.c_longlong(rows), C, ctypes.c_float(eps), ctypes.c_float(momentum), ptr(x),
-                              ptr(g), ptr(b), ptr(pb), ptr(running_mean), ptr(running_var), ptr(scratch), ptr(stats),
+        check(L.pdgn_bn_stats(rows, C, eps, momentum, ptr(x), ptr(g), ptr(b), ptr(pb), ptr(running_mean), ptr(running_var), ptr(scratch), ptr(stats),
                               stream_of(x)), "pdgn_bn_stats")
     else:
-        check(L.pdgn_bn_eval_stats(C, ctypes.c_float(eps), ptr(g), ptr(b), ptr(pb), ptr(running_mean),
+        check(L.pdgn_bn_eval_stats(C, eps, ptr(g), ptr(b), ptr(pb), ptr(running_mean),
                                    ptr(running_var), ptr(stats), stream_of(x)), "pdgn_bn_eval_stats")
     return stats
 
@@ -243,8 +235,7 @@ class BNActCL(Function):
         mul_c = mul.contiguous() if mul is not None else None
         # interleave_n = N: y is (rows * 2, C / 2), x row b*N + n / channel 2c + j at y row b*2N + j*N + n / channel c
         y = torch.empty((rows * 2, C // 2), dtype=F32, device=x.device) if interleave_n else torch.empty_like(x)
-        check(L.pdgn_bn_act_forward(ctypes.c_longlong(rows), C, act, ptr(x), ptr(stats), ptr(mul_c), ptr(y), int(interleave_n),
-                                    stream_of(x)), "pdgn_bn_act_forward")
+        check(L.pdgn_bn_act_forward(rows, C, act, ptr(x), ptr(stats), ptr(mul_c), ptr(y), int(interleave_n), stream_of(x)), "pdgn_bn_act_forward")
         ctx.save_for_backward(x, stats, mul_c)
         ctx.cfg = (rows, C, act, bool(training), mul is not None and mul.requires_grad, int(interleave_n))
         return y
@@ -259,9 +250,8 @@ class BNActCL(Function):
         bs = torch.empty(2 * C, dtype=F32, device=x.device)
         dx = torch.empty_like(x)
         dmul = torch.empty_like(x) if need_dmul else None
-        check(L.pdgn_bn_act_backward(ctypes.c_longlong(rows), C, act, int(training), ptr(x), ptr(dy), ptr(mul),
-                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(dmul), inter, stream_of(x)),
-              "pdgn_bn_act_backward")
+        check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dy), ptr(mul),
+                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(dmul), inter, stream_of(x)), "pdgn_bn_act_backward")
         if training:
             mark_zero_colsum(dx)
         return (dx, bs[C:], bs[:C], None, None, None, None, None, None, dmul, _pre_bias_grad(ctx.has_pre_bias, C, x.device),
@@ -368,13 +358,13 @@ class Planes:
 def two_part(m, n, k, scan_bytes):
     """Whether the contraction (m, n, k) runs on two scaled fp16 parts when scan_bytes of its operands still have to be scanned
     for their maxima (mode "x2" and a launch whose time is its matrix-core work: csrc/gemm_x3.hip x2_pays)."""
-    return _lib.gemm_mode() == "x2" and bool(_lib.lib().pdgn_gemm_two_part(ctypes.c_longlong(m), n, k, ctypes.c_longlong(scan_bytes)))
+    return _lib.gemm_mode() == "x2" and bool(_lib.lib().pdgn_gemm_two_part(m, n, k, scan_bytes))
 
 
 def two_part_planes(m, n, k, scan_bytes):
     """Whether the product (m, n, k) against PRE-SPLIT planes should use two-part ones when scan_bytes of the activations still have
     to be scanned (csrc/gemm_x3.hip pdgn_gemm_two_part_planes: from ~2 GFLOP on, the 256 x 128 eight-wave tile)."""
-    return _lib.gemm_mode() == "x2" and bool(_lib.lib().pdgn_gemm_two_part_planes(ctypes.c_longlong(m), n, k, ctypes.c_longlong(scan_bytes)))
+    return _lib.gemm_mode() == "x2" and bool(_lib.lib().pdgn_gemm_two_part_planes(m, n, k, scan_bytes))
 
 
 def _slots(t):
@@ -408,11 +398,10 @@ def split_planes(w, want_t, rows=None, dy_maxima_free=False, x_maxima_free=False
     st = stream_of(w)
     if parts_p == parts_t or not want_t:
         fn = L.pdgn_split_bf16x3 if parts_p == 3 else L.pdgn_split_f16x2
-        check(fn(n, k, ptr(w), w.stride(0), ptr(P), ldp, ctypes.c_longlong(n * ldp), ptr(PT), ldt,
-                 ctypes.c_longlong(k * ldt if want_t else 0), st), "pdgn_split")
+        check(fn(n, k, ptr(w), w.stride(0), ptr(P), ldp, n * ldp, ptr(PT), ldt, k * ldt if want_t else 0, st), "pdgn_split")
     else:                                                          # one form each: two launches
-        for parts, args in ((parts_p, (ptr(P), ldp, ctypes.c_longlong(n * ldp), None, 0, ctypes.c_longlong(0))),
-                            (parts_t, (None, 0, ctypes.c_longlong(0), ptr(PT), ldt, ctypes.c_longlong(k * ldt)))):
+        for parts, args in ((parts_p, (ptr(P), ldp, n * ldp, None, 0, 0)),
+                            (parts_t, (None, 0, 0, ptr(PT), ldt, k * ldt))):
             fn = L.pdgn_split_bf16x3 if parts == 3 else L.pdgn_split_f16x2
             check(fn(n, k, ptr(w), w.stride(0), *args, st), "pdgn_split")
     return Planes(P, PT, (n, k), parts_p, parts_t)
@@ -435,8 +424,7 @@ def operand_maxima(t, rows=True, cols=False):
         return (None, None) if (rows and cols) else None
     rm = torch.empty((t.shape[0],), dtype=torch.int32, device=t.device) if rows else None
     cm = torch.empty((t.shape[1],), dtype=torch.int32, device=t.device) if cols else None
-    check(_lib.lib().pdgn_absmax_rows_cols(ctypes.c_longlong(t.shape[0]), t.shape[1], ptr(t), t.stride(0), ptr(rm), ptr(cm),
-                                            stream_of(t)), "pdgn_absmax_rows_cols")
+    check(_lib.lib().pdgn_absmax_rows_cols(t.shape[0], t.shape[1], ptr(t), t.stride(0), ptr(rm), ptr(cm), stream_of(t)), "pdgn_absmax_rows_cols")
     return (rm, cm) if (rows and cols) else (rm if rows else cm)
 
 
@@ -456,22 +444,20 @@ def _tail_workspace(L, m, n, k, with_stats, device, parts=None):
     by the caching allocator is safe: the next user runs behind this call on the same stream).  parts: of the pre-split planes the
     call multiplies (two-part planes run on the 256 x 128 tile whatever the launch model picks)."""
     if parts is not None:
-        L.pdgn_gemm_nt_ps_workspace_floats.restype = ctypes.c_longlong
-        need = L.pdgn_gemm_nt_ps_workspace_floats(ctypes.c_longlong(m), n, k, parts, 1 if with_stats else 0)
+        need = L.pdgn_gemm_nt_ps_workspace_floats(m, n, k, parts, 1 if with_stats else 0)
     else:
-        L.pdgn_gemm_tail_workspace_floats.restype = ctypes.c_longlong
-        need = L.pdgn_gemm_tail_workspace_floats(ctypes.c_longlong(m), n, k, 1 if with_stats else 0)
+        need = L.pdgn_gemm_tail_workspace_floats(m, n, k, 1 if with_stats else 0)
     if need <= 0:
         return None
     ws = torch.empty(need, dtype=F32, device=device)
-    check(L.pdgn_gemm_set_tail_workspace(ptr(ws), ctypes.c_longlong(need)), "pdgn_gemm_set_tail_workspace")
+    check(L.pdgn_gemm_set_tail_workspace(ptr(ws), need), "pdgn_gemm_set_tail_workspace")
     return ws
 
 
 def _rp_takes(m, n, k, parts, plain):
     """Whether pdgn_gemm_nt_ps(m, n, k) on `parts`-part planes runs on the row-panel kernel (csrc/gemm_rp.hip: short reductions on
     two-part planes, no bias / addend): its BatchNorm partials cover a 256-row panel each."""
-    return parts == 2 and plain and _lib.lib().pdgn_gemm_nt_ps_row_panel(ctypes.c_longlong(m), n, k, 2, 1) == 1
+    return parts == 2 and plain and _lib.lib().pdgn_gemm_nt_ps_row_panel(m, n, k, 2, 1) == 1
 
 
 def planes_fit(P, m, n, k, with_stats=False, plain=False):
@@ -479,8 +465,7 @@ def planes_fit(P, m, n, k, with_stats=False, plain=False):
     whatever the launch model picks, or -- short reductions without bias / addend: plain -- on the row-panel kernel) unless the
     launch emits BatchNorm partials and neither the row-panel kernel takes it nor the model's pick -- whose geometry the partials'
     consumers were told -- is the 256 x 128 tile."""
-    return (P.shape[0] == 3 or not with_stats or _rp_takes(m, n, k, P.shape[0], plain)
-            or (_lib.lib().pdgn_gemm_nt_config(ctypes.c_longlong(m), n, k, 1) & 15) == 0)
+    return (P.shape[0] == 3 or not with_stats or _rp_takes(m, n, k, P.shape[0], plain) or (_lib.lib().pdgn_gemm_nt_config(m, n, k, 1) & 15) == 0)
 
 
 def gemm_nt_planes(a, P, n, k, bias=None, addend=None, want_stats=False, max_a=None):
@@ -495,15 +480,14 @@ def gemm_nt_planes(a, P, n, k, bias=None, addend=None, want_stats=False, max_a=N
     out = torch.empty((m, n), dtype=F32, device=a.device)
     part = None
     if want_stats:
-        L.pdgn_gemm_nt_ps_stat_rows.restype = ctypes.c_longlong
-        part = torch.empty((L.pdgn_gemm_nt_ps_stat_rows(ctypes.c_longlong(m), n, k, P.shape[0], 1 if (bias is None and addend is None) else 0),
+        part = torch.empty((L.pdgn_gemm_nt_ps_stat_rows(m, n, k, P.shape[0], 1 if (bias is None and addend is None) else 0),
                             3 * n), dtype=F32, device=a.device)
     b = bias.detach().contiguous() if bias is not None else None
     if addend is not None:
         addend = _pad_cols(addend)
     ws = _tail_workspace(L, m, n, k, want_stats, a.device, parts=P.shape[0])
     _hand_maxima(L, max_a)
-    check(L.pdgn_gemm_nt_ps(ctypes.c_longlong(m), n, k, ptr(ap), ap.stride(0), ptr(P), P.shape[2], ctypes.c_longlong(P.shape[1] * P.shape[2]), P.shape[0],
+    check(L.pdgn_gemm_nt_ps(m, n, k, ptr(ap), ap.stride(0), ptr(P), P.shape[2], P.shape[1] * P.shape[2], P.shape[0],
                             ptr(b), ptr(addend), addend.stride(0) if addend is not None else 0, ptr(out), n, ptr(part), None, 0, 1, 0,
                             None, 0, stream_of(a)), "pdgn_gemm_nt_ps")
     return (out, part) if want_stats else out
@@ -540,13 +524,12 @@ def gemm_nt(a, w, bias=None, addend=None, want_stats=False, w_transposed=False, 
     out = torch.empty((m, np_), dtype=F32, device=a.device)
     part = None
     if want_stats:
-        L.pdgn_gemm_nt_stat_rows.restype = ctypes.c_longlong
-        part = torch.empty((L.pdgn_gemm_nt_stat_rows(ctypes.c_longlong(m), np_, kp), 3 * np_), dtype=F32, device=a.device)
+        part = torch.empty((L.pdgn_gemm_nt_stat_rows(m, np_, kp), 3 * np_), dtype=F32, device=a.device)
     b = bias.detach().contiguous() if bias is not None else None
     fn = L.pdgn_gemm_nn if w_transposed else L.pdgn_gemm_nt
     ws = _tail_workspace(L, m, np_, kp, want_stats, a.device)       # (kept alive to the end of this function: the launch is issued by then)
     _hand_maxima(L, max_a)
-    check(fn(ctypes.c_longlong(m), np_, kp, ptr(ap), ap.stride(0), ptr(wp), wp.stride(0), ptr(b), ptr(addend),
+    check(fn(m, np_, kp, ptr(ap), ap.stride(0), ptr(wp), wp.stride(0), ptr(b), ptr(addend),
              addend.stride(0) if addend is not None else 0, ptr(out), np_, ptr(part), stream_of(a)),
           "pdgn_gemm_nn" if w_transposed else "pdgn_gemm_nt")
     if np_ != n:
@@ -571,16 +554,15 @@ def gemm_tn(dy, x, max_dy=None, max_x=None):
         # smaller outputs (and, on the fp32 kernels, the two largest ones: conv2's dense half, the per-point GEMM) stay on
         # pdgn_gemm_tn
         L = _lib.lib()
-        L.pdgn_gemm_tn_big_workspace_floats.restype = ctypes.c_longlong
-        need = L.pdgn_gemm_tn_big_workspace_floats(ctypes.c_longlong(m), dyp.shape[1], xp.shape[1])
+        need = L.pdgn_gemm_tn_big_workspace_floats(m, dyp.shape[1], xp.shape[1])
         if need > 0:                                               # the k slices' partial tiles: summed in a fixed order, no atomics
             ws = torch.empty(need, dtype=F32, device=dy.device)
-            check(L.pdgn_gemm_set_tail_workspace(ptr(ws), ctypes.c_longlong(need)), "pdgn_gemm_set_tail_workspace")
+            check(L.pdgn_gemm_set_tail_workspace(ptr(ws), need), "pdgn_gemm_set_tail_workspace")
             dwp = torch.empty((dyp.shape[1], xp.shape[1]), dtype=F32, device=dy.device)
         else:
             dwp = _zeros((dyp.shape[1], xp.shape[1]), dy.device)   # a slice of the backward pass's zero arena: no fill launch here
         _hand_maxima(L, max_dy, max_x)
-        check(_lib.lib().pdgn_gemm_tn_big(ctypes.c_longlong(m), dyp.shape[1], xp.shape[1], ptr(dyp), dyp.stride(0), ptr(xp),
+        check(_lib.lib().pdgn_gemm_tn_big(m, dyp.shape[1], xp.shape[1], ptr(dyp), dyp.stride(0), ptr(xp),
                                           xp.stride(0), ptr(dwp), 0 if need > 0 else 1, stream_of(dy)), "pdgn_gemm_tn_big")      # (not zero-filled when the workspace form is expected: the atomic form, should the library take it after all, fills it itself)
         return dwp if (dyp.shape[1] == n and xp.shape[1] == k) else dwp[:n, :k]
     if dyp.stride(0) != dyp.shape[1]:
@@ -588,8 +570,7 @@ def gemm_tn(dy, x, max_dy=None, max_x=None):
     if xp.stride(0) != xp.shape[1]:
         xp = xp.contiguous()
     dwp = _zeros((dyp.shape[1], xp.shape[1]), dy.device)
-    check(_lib.lib().pdgn_gemm_tn(ctypes.c_longlong(m), dyp.shape[1], xp.shape[1], ptr(dyp), ptr(xp), ptr(dwp),
-                                  stream_of(dy)), "pdgn_gemm_tn")
+    check(_lib.lib().pdgn_gemm_tn(m, dyp.shape[1], xp.shape[1], ptr(dyp), ptr(xp), ptr(dwp), stream_of(dy)), "pdgn_gemm_tn")
     return dwp if (dyp.shape[1] == n and xp.shape[1] == k) else dwp[:n, :k]
 
 
@@ -608,11 +589,9 @@ def thin_nt(x, w, wrs, wcs, n, bias=None, want_stats=False):
     out = torch.empty((m, n), dtype=F32, device=x.device)
     part = None
     if want_stats and k <= 4:
-        L.pdgn_thin_stat_rows.restype = ctypes.c_longlong
-        part = torch.empty((L.pdgn_thin_stat_rows(ctypes.c_longlong(m)), 3 * n), dtype=F32, device=x.device)
+        part = torch.empty((L.pdgn_thin_stat_rows(m), 3 * n), dtype=F32, device=x.device)
     b = bias.detach().contiguous() if bias is not None else None
-    check(L.pdgn_thin_nt(ctypes.c_longlong(m), n, k, ptr(x), x.stride(0), ptr(w), wrs, wcs, ptr(b), ptr(out), n, ptr(part),
-                         stream_of(x)), "pdgn_thin_nt")
+    check(L.pdgn_thin_nt(m, n, k, ptr(x), x.stride(0), ptr(w), wrs, wcs, ptr(b), ptr(out), n, ptr(part), stream_of(x)), "pdgn_thin_nt")
     return (out, part) if want_stats else out
 
 
@@ -626,11 +605,9 @@ def thin_tn(dy, x, want_db):
     db = _zeros((n,), dy.device) if want_db else None
     L = _lib.lib()
     if k <= 4:                      # A = x (thin), B = dy (wide): O[i = kk, j = n] -> dw[j, i]
-        check(L.pdgn_thin_tn(ctypes.c_longlong(m), k, n, ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(dw), 1, k, ptr(None),
-                             ptr(db), stream_of(dy)), "pdgn_thin_tn")
+        check(L.pdgn_thin_tn(m, k, n, ptr(x), x.stride(0), ptr(dy), dy.stride(0), ptr(dw), 1, k, ptr(None), ptr(db), stream_of(dy)), "pdgn_thin_tn")
     else:                           # A = dy (thin), B = x (wide): O[i = n, j = kk] -> dw[i, j]
-        check(L.pdgn_thin_tn(ctypes.c_longlong(m), n, k, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), k, 1, ptr(db),
-                             ptr(None), stream_of(dy)), "pdgn_thin_tn")
+        check(L.pdgn_thin_tn(m, n, k, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), k, 1, ptr(db), ptr(None), stream_of(dy)), "pdgn_thin_tn")
     return dw, db
 
 
@@ -853,10 +830,9 @@ def gemm_nt_ex(a, w, ldw, n, bias=None, row_bias=None, rows_per_group=1, act=0, 
         GEMM_LOG.append(("nn" if w_transposed else "nt", m, n, k))
     out = torch.empty((m, n), dtype=F32, device=a.device)
     b = bias.detach().contiguous() if bias is not None else None
-    check(_lib.lib().pdgn_gemm_nt_ex(ctypes.c_longlong(m), n, k, ptr(a), a.stride(0), ptr(w), ldw, ptr(b), None, 0, ptr(out), n, None,
+    check(_lib.lib().pdgn_gemm_nt_ex(m, n, k, ptr(a), a.stride(0), ptr(w), ldw, ptr(b), None, 0, ptr(out), n, None,
                                      ptr(row_bias), row_bias.stride(0) if row_bias is not None else 0, rows_per_group, act,
-                                     ptr(gate), gate.stride(0) if gate is not None else 0, int(w_transposed), stream_of(a)),
-          "pdgn_gemm_nt_ex")
+                                     ptr(gate), gate.stride(0) if gate is not None else 0, int(w_transposed), stream_of(a)), "pdgn_gemm_nt_ex")
     return out
 
 
@@ -895,7 +871,7 @@ class HeadMLP(Function):
         if GEMM_LOG is not None:
             GEMM_LOG.append(("thin", rows, k3, n3))
         dpre2 = torch.empty((rows, k3), dtype=F32, device=x.device)               # (dp W3) * lrelu'(y2)
-        check(L.pdgn_thin_nt_ex(ctypes.c_longlong(rows), k3, n3, ptr(dp), dp.stride(0), ptr(W3), 1, k3, None, ptr(dpre2), k3, None,
+        check(L.pdgn_thin_nt_ex(rows, k3, n3, ptr(dp), dp.stride(0), ptr(W3), 1, k3, None, ptr(dpre2), k3, None,
                                 ptr(y2), y2.stride(0), stream_of(x)), "pdgn_thin_nt_ex")
         dW2 = gemm_tn(dpre2, y1)
         db2 = group_colsum(dpre2)[0]
@@ -934,10 +910,10 @@ def stat_block_rows(x2d, weight, addend=None, planes=None, bias=None):
     n, k = weight.shape
     plain = bias is None and addend is None
     if _planes_taken(x2d, weight, planes, True, plain):
-        return int(L.pdgn_gemm_nt_ps_stat_block_rows(ctypes.c_longlong(x2d.shape[0]), n, k, planes.p.shape[0], 1 if plain else 0))
+        return int(L.pdgn_gemm_nt_ps_stat_block_rows(x2d.shape[0], n, k, planes.p.shape[0], 1 if plain else 0))
     if addend is None and weight.is_contiguous() and _thin_ok(x2d, n, k):
         return int(L.pdgn_thin_stat_block_rows())
-    return int(L.pdgn_gemm_nt_stat_block_rows(ctypes.c_longlong(x2d.shape[0]), (n + 3) // 4 * 4, (k + 3) // 4 * 4))
+    return int(L.pdgn_gemm_nt_stat_block_rows(x2d.shape[0], (n + 3) // 4 * 4, (k + 3) // 4 * 4))
 
 
 class SoftmaxSlotsPermute(Function):
@@ -949,8 +925,7 @@ class SoftmaxSlotsPermute(Function):
         h = h.contiguous()
         m, k, c = h.shape
         w = torch.empty((m, k // 2, 2 * c), dtype=F32, device=h.device)
-        check(_lib.lib().pdgn_softmax_slots_permute(ctypes.c_longlong(m), k, c, ptr(h), ptr(w), stream_of(h)),
-              "pdgn_softmax_slots_permute")
+        check(_lib.lib().pdgn_softmax_slots_permute(m, k, c, ptr(h), ptr(w), stream_of(h)), "pdgn_softmax_slots_permute")
         ctx.save_for_backward(w)
         ctx.shape = (m, k, c)
         return w
@@ -961,8 +936,7 @@ class SoftmaxSlotsPermute(Function):
         m, k, c = ctx.shape
         dw = dw.contiguous()
         dh = torch.empty((m, k, c), dtype=F32, device=w.device)
-        check(_lib.lib().pdgn_softmax_slots_permute_backward(ctypes.c_longlong(m), k, c, ptr(w), ptr(dw), ptr(dh),
-                                                             stream_of(w)), "pdgn_softmax_slots_permute_backward")
+        check(_lib.lib().pdgn_softmax_slots_permute_backward(m, k, c, ptr(w), ptr(dw), ptr(dh), stream_of(w)), "pdgn_softmax_slots_permute_backward")
         return dh
 
 
@@ -985,8 +959,7 @@ class BNSoftmaxSlotsPermute(Function):
         stats = _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps)
         ctx.has_pre_bias = pre_bias is not None
         w = torch.empty((m, k // 2, 2 * C), dtype=F32, device=x.device)
-        check(L.pdgn_bn_softmax_slots_permute(ctypes.c_longlong(m), k, C, act, ptr(x), ptr(stats), ptr(w),
-                                              stream_of(x)), "pdgn_bn_softmax_slots_permute")
+        check(L.pdgn_bn_softmax_slots_permute(m, k, C, act, ptr(x), ptr(stats), ptr(w), stream_of(x)), "pdgn_bn_softmax_slots_permute")
         ctx.save_for_backward(x, stats, w)
         ctx.cfg = (rows, C, act, bool(training), k)
         return w
@@ -998,14 +971,12 @@ class BNSoftmaxSlotsPermute(Function):
         L = _lib.lib()
         dw = dw.contiguous()
         dh = torch.empty((rows, C), dtype=F32, device=x.device)
-        check(L.pdgn_softmax_slots_permute_backward(ctypes.c_longlong(rows // k), k, C, ptr(w), ptr(dw), ptr(dh),
-                                                    stream_of(w)), "pdgn_softmax_slots_permute_backward")
+        check(L.pdgn_softmax_slots_permute_backward(rows // k, k, C, ptr(w), ptr(dw), ptr(dh), stream_of(w)), "pdgn_softmax_slots_permute_backward")
         scratch = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
         bs = torch.empty(2 * C, dtype=F32, device=x.device)
         dx = torch.empty_like(x)
-        check(L.pdgn_bn_act_backward(ctypes.c_longlong(rows), C, act, int(training), ptr(x), ptr(dh), ptr(None),
-                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(None), 0, stream_of(x)),
-              "pdgn_bn_act_backward")
+        check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dh), ptr(None),
+                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(None), 0, stream_of(x)), "pdgn_bn_act_backward")
         if training:
             mark_zero_colsum(dx)
         return dx, bs[C:], bs[:C], None, None, None, None, None, None, None, _pre_bias_grad(ctx.has_pre_bias, C, x.device)
@@ -1059,9 +1030,8 @@ class BilateralWeighting(Function):
             ycmax = torch.empty((k // 2 * 2 * C,), dtype=torch.int32, device=x.device)
             g_u, b_u = gu.detach().contiguous(), bu.detach().contiguous()
             bound = max(float(u.shape[0]) - 1.0, 1.0) ** 0.5
-        check(L.pdgn_bn_softmax_slots_permute_mul(ctypes.c_longlong(m), k, C, act, ptr(x), ptr(stats_x), act, ptr(u),
-                                                  ptr(stats_u), ptr(w), ptr(y), ptr(ymax), ptr(g_u), ptr(b_u), ctypes.c_float(bound),
-                                                  ptr(ycmax), stream_of(x)),
+        check(L.pdgn_bn_softmax_slots_permute_mul(m, k, C, act, ptr(x), ptr(stats_x), act, ptr(u),
+                                                  ptr(stats_u), ptr(w), ptr(y), ptr(ymax), ptr(g_u), ptr(b_u), bound, ptr(ycmax), stream_of(x)),
               "pdgn_bn_softmax_slots_permute_mul")
         ctx.save_for_backward(x, u, w, stats_x, stats_u)
         ctx.cfg = (rows, C, act, bool(training), k, pbx is not None, pbu is not None)
@@ -1082,33 +1052,29 @@ class BilateralWeighting(Function):
         rows_u, Cu = u.shape
         if k in (4, 10):
             # both BatchNorm adjoints and the softmax adjoint in two passes over (x, u, w, dy): dW and dh stay in registers
-            L.pdgn_bilateral_scratch_floats.restype = ctypes.c_longlong
-            scr = torch.empty(L.pdgn_bilateral_scratch_floats(ctypes.c_longlong(rows // k), k, C), dtype=F32, device=x.device)
+            scr = torch.empty(L.pdgn_bilateral_scratch_floats(rows // k, k, C), dtype=F32, device=x.device)
             bsx = torch.empty(2 * C, dtype=F32, device=x.device)
             bsu = torch.empty(2 * Cu, dtype=F32, device=x.device)
             dx, du = torch.empty_like(x), torch.empty_like(u)
-            check(L.pdgn_bilateral_weighting_backward(ctypes.c_longlong(rows // k), k, C, act, int(training), ptr(x),
+            check(L.pdgn_bilateral_weighting_backward(rows // k, k, C, act, int(training), ptr(x),
                                                       ptr(stats_x), ptr(u), ptr(stats_u), ptr(w), ptr(dy), ptr(scr), ptr(bsx),
-                                                      ptr(bsu), ptr(dx), ptr(du), stream_of(x)),
-                  "pdgn_bilateral_weighting_backward")
+                                                      ptr(bsu), ptr(dx), ptr(du), stream_of(x)), "pdgn_bilateral_weighting_backward")
         else:
             # y = act(BN(u)) * w: adjoint wrt u, the BatchNorm parameters and w
             scr = torch.empty(_scratch_floats(L, rows_u, Cu), dtype=F32, device=x.device)
             bsu = torch.empty(2 * Cu, dtype=F32, device=x.device)
             du, dw = torch.empty_like(u), torch.empty_like(u)
-            check(L.pdgn_bn_act_backward(ctypes.c_longlong(rows_u), Cu, act, int(training), ptr(u), ptr(dy), ptr(w),
-                                         ptr(stats_u), ptr(scr), ptr(bsu), ptr(du), ptr(dw), 0, stream_of(x)),
-                  "pdgn_bn_act_backward")
+            check(L.pdgn_bn_act_backward(rows_u, Cu, act, int(training), ptr(u), ptr(dy), ptr(w),
+                                         ptr(stats_u), ptr(scr), ptr(bsu), ptr(du), ptr(dw), 0, stream_of(x)), "pdgn_bn_act_backward")
             # w = softmax_slots_permute(act(BN(x)))
             dh = torch.empty((rows, C), dtype=F32, device=x.device)
-            check(L.pdgn_softmax_slots_permute_backward(ctypes.c_longlong(rows // k), k, C, ptr(w), ptr(dw), ptr(dh),
+            check(L.pdgn_softmax_slots_permute_backward(rows // k, k, C, ptr(w), ptr(dw), ptr(dh),
                                                         stream_of(x)), "pdgn_softmax_slots_permute_backward")
             scr = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
             bsx = torch.empty(2 * C, dtype=F32, device=x.device)
             dx = torch.empty_like(x)
-            check(L.pdgn_bn_act_backward(ctypes.c_longlong(rows), C, act, int(training), ptr(x), ptr(dh), ptr(None),
-                                         ptr(stats_x), ptr(scr), ptr(bsx), ptr(dx), ptr(None), 0, stream_of(x)),
-                  "pdgn_bn_act_backward")
+            check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dh), ptr(None),
+                                         ptr(stats_x), ptr(scr), ptr(bsx), ptr(dx), ptr(None), 0, stream_of(x)), "pdgn_bn_act_backward")
         if training:
             mark_zero_colsum(du)
             mark_zero_colsum(dx)
@@ -1154,7 +1120,7 @@ class SmallLinearBNAct(Function):
         g = gamma.detach().contiguous() if gamma is not None else None
         b = beta.detach().contiguous() if beta is not None else None
         bi = bias.detach().contiguous() if bias is not None else None
-        check(_lib.lib().pdgn_small_mlp_forward(R, K, N, act, bn_mode, ctypes.c_float(eps), ctypes.c_float(momentum), ptr(x),
+        check(_lib.lib().pdgn_small_mlp_forward(R, K, N, act, bn_mode, eps, momentum, ptr(x),
                                                 ptr(weight), ptr(bi), ptr(g), ptr(b), ptr(running_mean), ptr(running_var),
                                                 ptr(y), ptr(pre), ptr(stat), stream_of(x)), "pdgn_small_mlp_forward")
         ctx.save_for_backward(x, weight, pre, stat, g, b)
@@ -1290,14 +1256,12 @@ class BNActMaxPool(Function):
             # no statistics from the producer: ONE pass over x for the statistics and the extremes (the sign of the scale picks later)
             stats = torch.empty(4 * C, dtype=F32, device=dev)
             pb = pre_bias.detach().contiguous() if pre_bias is not None else None
-            L.pdgn_bn_stats_maxpool_scratch_floats.restype = ctypes.c_longlong
             scr = torch.empty(L.pdgn_bn_stats_maxpool_scratch_floats(B, C), dtype=F32, device=dev)
-            check(L.pdgn_bn_stats_act_maxpool(B, N, C, act, ctypes.c_float(eps), ctypes.c_float(momentum), ptr(x), ptr(g), ptr(b), ptr(pb),
+            check(L.pdgn_bn_stats_act_maxpool(B, N, C, act, eps, momentum, ptr(x), ptr(g), ptr(b), ptr(pb),
                                               ptr(running_mean), ptr(running_var), ptr(scr), ptr(stats), ptr(ymax), ptr(yarg),
                                               stream_of(x)), "pdgn_bn_stats_act_maxpool")
         else:
             stats = _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps, partials)
-            L.pdgn_bn_maxpool_scratch_floats.restype = ctypes.c_longlong
             scr = torch.empty(L.pdgn_bn_maxpool_scratch_floats(B, C), dtype=F32, device=dev)
             check(L.pdgn_bn_act_maxpool(B, N, C, act, ptr(x), ptr(stats), ptr(scr), ptr(ymax), ptr(yarg), stream_of(x)),
                   "pdgn_bn_act_maxpool")
@@ -1319,7 +1283,6 @@ class BNActMaxPool(Function):
             K = w.shape[1]
             L = _lib.lib()
             want_w, want_bn = w.requires_grad, any(ctx.needs_input_grad[1:3])
-            L.pdgn_dense_bn_maxpool_backward_scratch.restype = ctypes.c_longlong
             scr = torch.empty(L.pdgn_dense_bn_maxpool_backward_scratch(B, C, K), dtype=F32, device=x.device)
             dh = torch.empty((B * N, K), dtype=F32, device=x.device) if h.requires_grad else None
             dw = torch.empty((C, K), dtype=F32, device=x.device) if want_w else None
@@ -1387,7 +1350,6 @@ class PointMax(Function):
         require(x, "x", F32, 3)
         b, n, c = x.shape
         L = _lib.lib()
-        L.pdgn_point_max_scratch.restype = ctypes.c_longlong
         ns = int(L.pdgn_point_max_scratch(b, n, c))
         sval = torch.empty(ns, dtype=F32, device=x.device)
         sarg = torch.empty(ns, dtype=torch.int32, device=x.device)

@@ -1,7 +1,6 @@
 """Losses of the PDGN training step: Chamfer (utils/chamfer_loss.py:13-38) and the
 shape-preserving local-statistics loss (models/PDGNet_v2.py:127-155), on fused HIP kernels
 (csrc/localpair.hip): no (B,M,N) distance matrix, no (B,3,M,20) grouped tensor, no bmm."""
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -72,8 +71,7 @@ class ChamferSum(Function):
         ctx.save_for_backward(x, y, args)
         ctx.scale = float(scale)
         out = torch.empty((), dtype=F32, device=x.device)
-        check(_lib.lib().pdgn_scaled_sum(ctypes.c_longlong(b * (m + n)), ptr(mins), ctypes.c_float(ctx.scale), ptr(out),
-                                         stream_of(x)), "pdgn_scaled_sum")
+        check(_lib.lib().pdgn_scaled_sum(b * (m + n), ptr(mins), ctx.scale, ptr(out), stream_of(x)), "pdgn_scaled_sum")
         return out
 
     @staticmethod
@@ -84,7 +82,7 @@ class ChamferSum(Function):
         gbuf = torch.empty((b * (m + n) * d,), dtype=F32, device=x.device)      # gx | gy: one zero-fill inside the call
         gx, gy = gbuf[:b * m * d].view(b, m, d), gbuf[b * m * d:].view(b, n, d)
         g = g.contiguous()
-        check(_lib.lib().pdgn_chamfer_gram_grad_uniform(b, m, n, d, ptr(x), ptr(y), ptr(g), ctypes.c_float(ctx.scale),
+        check(_lib.lib().pdgn_chamfer_gram_grad_uniform(b, m, n, d, ptr(x), ptr(y), ptr(g), ctx.scale,
                                                         ptr(args[:b * m]), ptr(args[b * m:]), ptr(gx), ptr(gy), stream_of(x)),
               "pdgn_chamfer_gram_grad_uniform")
         return gx, gy, None
@@ -99,8 +97,7 @@ class MseConst(Function):
         x = x.contiguous()
         require(x, "x", F32)
         out = torch.empty((), dtype=F32, device=x.device)
-        check(_lib.lib().pdgn_mse_const(ctypes.c_longlong(x.numel()), ptr(x), ctypes.c_float(target), ctypes.c_float(scale),
-                                        ptr(out), stream_of(x)), "pdgn_mse_const")
+        check(_lib.lib().pdgn_mse_const(x.numel(), ptr(x), target, scale, ptr(out), stream_of(x)), "pdgn_mse_const")
         ctx.save_for_backward(x)
         ctx.cfg = (float(target), float(scale))
         return out
@@ -111,9 +108,7 @@ class MseConst(Function):
         target, scale = ctx.cfg
         dx = torch.empty_like(x)
         g = g.contiguous()
-        check(_lib.lib().pdgn_mse_const_backward(ctypes.c_longlong(x.numel()), ptr(x), ctypes.c_float(target),
-                                                 ctypes.c_float(scale), ptr(g), ptr(dx), stream_of(x)),
-              "pdgn_mse_const_backward")
+        check(_lib.lib().pdgn_mse_const_backward(x.numel(), ptr(x), target, scale, ptr(g), ptr(dx), stream_of(x)), "pdgn_mse_const_backward")
         return dx, None, None
 
 

@@ -10,7 +10,6 @@ instead of the ``pointops_cuda`` pybind module.  Differences, all deliberate:
   * launch failures raise ``PdgnHipError`` (the reference calls ``exit(-1)``).
 There is no CPU path: CPU tensors raise.
 """
-import ctypes
 from typing import Tuple
 
 import numpy as np
@@ -248,8 +247,7 @@ def ballquery(radius, nsample, xyz, new_xyz):
     b, n, _ = xyz.shape
     m = new_xyz.shape[1]
     idx = torch.zeros((b, m, nsample), dtype=I32, device=xyz.device)
-    check(_lib.lib().pdgn_ballquery(b, n, m, ctypes.c_float(radius), int(nsample), ptr(new_xyz), ptr(xyz), ptr(idx),
-                                    stream_of(xyz)), "pdgn_ballquery")
+    check(_lib.lib().pdgn_ballquery(b, n, m, radius, int(nsample), ptr(new_xyz), ptr(xyz), ptr(idx), stream_of(xyz)), "pdgn_ballquery")
     return idx
 
 
@@ -296,7 +294,7 @@ def labelstat_ballrange(radius, xyz, new_xyz, label_stat):
     b, n, nclass = label_stat.shape
     m = new_xyz.shape[1]
     out = torch.empty((b, m, nclass), dtype=I32, device=xyz.device)
-    check(_lib.lib().pdgn_labelstat_ballrange(b, n, m, ctypes.c_float(radius), nclass, ptr(new_xyz), ptr(xyz),
+    check(_lib.lib().pdgn_labelstat_ballrange(b, n, m, radius, nclass, ptr(new_xyz), ptr(xyz),
                                               ptr(label_stat), ptr(out), stream_of(xyz)), "pdgn_labelstat_ballrange")
     return out
 
@@ -311,9 +309,8 @@ def labelstat_and_ballquery(radius, nsample, xyz, new_xyz, label_stat):
     m = new_xyz.shape[1]
     out = torch.empty((b, m, nclass), dtype=I32, device=xyz.device)
     idx = torch.zeros((b, m, nsample), dtype=I32, device=xyz.device)
-    check(_lib.lib().pdgn_labelstat_and_ballquery(b, n, m, ctypes.c_float(radius), int(nsample), nclass, ptr(new_xyz),
-                                                  ptr(xyz), ptr(label_stat), ptr(idx), ptr(out), stream_of(xyz)),
-          "pdgn_labelstat_and_ballquery")
+    check(_lib.lib().pdgn_labelstat_and_ballquery(b, n, m, radius, int(nsample), nclass, ptr(new_xyz),
+                                                  ptr(xyz), ptr(label_stat), ptr(idx), ptr(out), stream_of(xyz)), "pdgn_labelstat_and_ballquery")
     return out, idx
 
 

@@ -71,7 +71,6 @@ class LaunchList:
         check(L.pdgn_replay_chains(self._plan, labels, sizes), "pdgn_replay_chains")
         self.labels, self.sizes = list(labels), list(sizes)
         self._bound = None
-        L.pdgn_replay_points.restype = ctypes.c_int
         n = L.pdgn_replay_points(self._plan, None, None, None, 0)
         if n < 0:
             raise _lib.PdgnHipError("pdgn_replay_points failed with %d" % n)
@@ -116,11 +115,10 @@ class LaunchList:
 
     def neighbor(self, pos, direction):
         """(list position, kind, kernel symbol) of the next / previous node of `pos`'s chain; position -1 when there is none."""
-        kind, sym = ctypes.c_int(-1), ctypes.c_void_p()
+        kind, sym = (ctypes.c_int * 1)(-1), ctypes.c_void_p()
         L = _lib.lib()
-        L.pdgn_replay_chain_neighbor.restype = ctypes.c_int
-        p = L.pdgn_replay_chain_neighbor(self._plan, int(pos), int(direction), ctypes.byref(kind), ctypes.byref(sym))
-        return p, kind.value, sym.value
+        p = L.pdgn_replay_chain_neighbor(self._plan, int(pos), int(direction), kind, ctypes.byref(sym))
+        return p, kind[0], sym.value
 
     def time_spans(self, spans, slots):
         """Bracket spans [(first, last), ...] of the list (each inside one chain) with timing events on that chain's stream for the

@@ -96,7 +96,6 @@ def render_sheet(clouds, view=None, cell=128, radius=1, fit=False):
     if any(t.shape[0] != B or t.device != dev for t in cols):
         raise ValueError("every cloud list must hold the same number of clouds on the same device")
     L = _lib.lib()
-    L.pdgn_render_workspace_bytes.restype = ctypes.c_longlong
     nbytes = L.pdgn_render_workspace_bytes(B, len(cols), int(cell))
     if nbytes < 0:
         raise _lib.PdgnHipError("pdgn_render_workspace_bytes: argument outside the supported range")

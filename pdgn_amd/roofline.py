@@ -102,11 +102,9 @@ def gemm_accuracy(device, M=20000, N=512, K=2560):
     try:
         for mode in ("x3", "x2", "fp32"):
             _lib.set_gemm_mode(mode)
-            check(L.pdgn_gemm_nt(ctypes.c_longlong(M), N, K, ptr(a), K, ptr(w), K, None, None, 0, ptr(c), N, None, stream_of(a)),
-                  "pdgn_gemm_nt")
+            check(L.pdgn_gemm_nt(M, N, K, ptr(a), K, ptr(w), K, None, None, 0, ptr(c), N, None, stream_of(a)), "pdgn_gemm_nt")
             out["max_error_vs_fp64_" + mode] = ((c.double() - ref).abs() / mag).max().item()
-            check(L.pdgn_gemm_nt(ctypes.c_longlong(M), N, K, ptr(a2), K, ptr(w2), K, None, None, 0, ptr(c), N, None, stream_of(a)),
-                  "pdgn_gemm_nt")
+            check(L.pdgn_gemm_nt(M, N, K, ptr(a2), K, ptr(w2), K, None, None, 0, ptr(c), N, None, stream_of(a)), "pdgn_gemm_nt")
             rows["max_error_vs_fp64_" + mode] = ((c.double() - ref2).abs() / mag2).max().item()
     finally:
         _lib.set_gemm_mode(saved)
@@ -132,11 +130,10 @@ def _nt_entry(label, M, N, K, device):
         ws = _tail_workspace(L, M, N, K, False, device, parts=planes.p.shape[0] if planes is not None else None)      # the stream-K tail without atomics, as the step's calls run it
         if planes is not None:
             P = planes.p
-            check(L.pdgn_gemm_nt_ps(ctypes.c_longlong(M), N, K, ptr(a), K, ptr(P), P.shape[2], ctypes.c_longlong(P.shape[1] * P.shape[2]),
+            check(L.pdgn_gemm_nt_ps(M, N, K, ptr(a), K, ptr(P), P.shape[2], P.shape[1] * P.shape[2],
                                     P.shape[0], None, None, 0, ptr(c), N, None, None, 0, 1, 0, None, 0, stream_of(a)), "pdgn_gemm_nt_ps")
         else:
-            check(L.pdgn_gemm_nt(ctypes.c_longlong(M), N, K, ptr(a), K, ptr(w), K, None, None, 0, ptr(c), N, None, stream_of(a)),
-                  "pdgn_gemm_nt")
+            check(L.pdgn_gemm_nt(M, N, K, ptr(a), K, ptr(w), K, None, None, 0, ptr(c), N, None, stream_of(a)), "pdgn_gemm_nt")
     us = _time_us(run)
     e = _entry("%s (%s, M=%d N=%d K=%d%s)" % ("gemm_x3_kernel" if x3 else "gemm_nt_kernel", label, M, N, K,
                                                "; PW instance = pdgn_gemm_nt_ps, the weight pre-split once per iteration" if planes is not None else ""),
@@ -176,8 +173,7 @@ def conv2_dense_dx_stage4(B, base_points, device):
     L = _lib.lib()
 
     def run():
-        check(L.pdgn_gemm_nn(ctypes.c_longlong(M), N, K, ptr(dy), K, ptr(wb), N, None, None, 0, ptr(dx), N, None, stream_of(dy)),
-              "pdgn_gemm_nn")
+        check(L.pdgn_gemm_nn(M, N, K, ptr(dy), K, ptr(wb), N, None, None, 0, ptr(dx), N, None, stream_of(dy)), "pdgn_gemm_nn")
     us = _time_us(run)
     x3 = gemm_mode() != "fp32"
     e = _entry("%s<WT> = pdgn_gemm_nn (conv2 dense half input gradient, stage 4, M=%d N=%d K=%d)"
@@ -198,7 +194,7 @@ def weight_grad_stage4(B, base_points, device):
     L = _lib.lib()
     if gemm_mode() != "fp32":
         def run():
-            check(L.pdgn_gemm_tn_big(ctypes.c_longlong(M), N, K, ptr(dy), N, ptr(x), K, ptr(dw), 0, stream_of(dy)), "pdgn_gemm_tn_big")
+            check(L.pdgn_gemm_tn_big(M, N, K, ptr(dy), N, ptr(x), K, ptr(dw), 0, stream_of(dy)), "pdgn_gemm_tn_big")
         us = _time_us(run)
         e = _entry("gemm_x3_kernel<AT,WT> = pdgn_gemm_tn_big (dW of conv2's dense half, stage 4, M=%d N=%d K=%d)" % (M, N, K), "mfma",
                    2.0 * M * N * K, us, x3=True, two=_two_part(N, K, M, (M * N + M * K) * 4), shape=[M, N, K])
@@ -207,7 +203,7 @@ def weight_grad_stage4(B, base_points, device):
 
     def run():
         dw.zero_()
-        check(L.pdgn_gemm_tn(ctypes.c_longlong(M), N, K, ptr(dy), ptr(x), ptr(dw), stream_of(dy)), "pdgn_gemm_tn")
+        check(L.pdgn_gemm_tn(M, N, K, ptr(dy), ptr(x), ptr(dw), stream_of(dy)), "pdgn_gemm_tn")
     # the zero-fill of dW is part of the price (pdgn_gemm_tn accumulates split partial sums with atomics): it is timed
     # WITH the kernel; `kernel_only_us` (the fill timed alone subtracted) is what rocprofv3's kernel trace reports
     us = _time_us(run)
@@ -228,13 +224,12 @@ def bn_act_backward_stage4(B, base_points, device):
     mul = torch.rand(rows, C, device=device)
     stats = torch.cat([torch.ones(C), torch.zeros(C), torch.zeros(C), torch.ones(C)]).to(device)
     L = _lib.lib()
-    L.pdgn_bn_scratch_floats.restype = ctypes.c_longlong
-    scratch = torch.empty(L.pdgn_bn_scratch_floats(ctypes.c_longlong(rows), C), device=device)
+    scratch = torch.empty(L.pdgn_bn_scratch_floats(rows, C), device=device)
     bs = torch.empty(2 * C, device=device)
     dx, dmul = torch.empty_like(x), torch.empty_like(x)
 
     def run():
-        check(L.pdgn_bn_act_backward(ctypes.c_longlong(rows), C, 2, 1, ptr(x), ptr(dy), ptr(mul), ptr(stats),
+        check(L.pdgn_bn_act_backward(rows, C, 2, 1, ptr(x), ptr(dy), ptr(mul), ptr(stats),
                                      ptr(scratch), ptr(bs), ptr(dx), ptr(dmul), 0, stream_of(x)), "pdgn_bn_act_backward")
     us = _time_us(run)
     return _entry("cl_bwd_reduce + cl_bwd_apply (BN+LeakyReLU*w backward, rows=%d C=%d)" % (rows, C), "hbm",
@@ -324,13 +319,13 @@ def conv2_in_step_spans(launch_list, B, base_points):
     M = B * 8 * base_points
     from .fused import two_part_planes
     parts = 2 if two_part_planes(M, 512, 5120, 0) else 3          # (the step's planes: inte arrives with its maxima)
-    sym, grid, red, scan = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_void_p(), ctypes.c_void_p()
-    if L.pdgn_gemm_nt_ps_launch_info(ctypes.c_longlong(M), 512, 5120, parts, ctypes.byref(sym), ctypes.byref(grid)) != 0 or not sym.value:
+    sym, grid, red, scan = ctypes.c_void_p(), (ctypes.c_int * 1)(), ctypes.c_void_p(), ctypes.c_void_p()
+    if L.pdgn_gemm_nt_ps_launch_info(M, 512, 5120, parts, ctypes.byref(sym), grid) != 0 or not sym.value:
         return []
     L.pdgn_gemm_aux_symbols(ctypes.byref(red), ctypes.byref(scan))
-    cfg = L.pdgn_gemm_nt_config(ctypes.c_longlong(M), 512, 5120, 0)
+    cfg = L.pdgn_gemm_nt_config(M, 512, 5120, 0)
     spans = []
-    for pos in launch_list.kernel_nodes(sym.value, grid.value):
+    for pos in launch_list.kernel_nodes(sym.value, grid[0]):
         first = last = pos
         p, kind, ksym = launch_list.neighbor(pos, -1)             # in front: the zero-fill of an atomic tail, or the scan of the activations (two parts)
         if p >= 0 and ((cfg >= 16 and kind == 1) or (kind == 0 and ksym == scan.value)):

@@ -33,7 +33,7 @@ _PLANS = {}
 
 
 def _spin(stream, us=SPIN_US):
-    _lib.check(_lib.lib().pdgn_spin(ctypes.c_uint(us), ctypes.c_void_p(stream.cuda_stream)), "pdgn_spin")
+    _lib.check(_lib.lib().pdgn_spin(us, ctypes.c_void_p(stream.cuda_stream)), "pdgn_spin")
 
 
 def shares_queue(a, b, device, us=SPIN_US):

@@ -1,7 +1,6 @@
 """Approximate EMD.  Mirrors evaluation/pytorch_structural_losses/match_cost.py:6-44
 (MatchCostFunction) and the pybind entry points ApproxMatch / MatchCost / MatchCostGrad
 (src/structural_loss.cpp:22-78): the callee allocates outputs."""
-import ctypes
 
 import torch
 from .._fn import Function
@@ -78,8 +77,7 @@ def emd_cost(seta, setb):
     b, n, _ = seta.shape
     m = setb.shape[1]
     L = _lib.lib()
-    L.pdgn_emd_cost_temp_floats.restype = ctypes.c_longlong
-    temp = torch.empty(L.pdgn_emd_cost_temp_floats(ctypes.c_longlong(b), n, m), dtype=F32, device=seta.device)
+    temp = torch.empty(L.pdgn_emd_cost_temp_floats(b, n, m), dtype=F32, device=seta.device)
     out = torch.empty((b,), dtype=F32, device=seta.device)
     check(_lib.lib().pdgn_emd_cost(b, n, m, ptr(seta), ptr(setb), ptr(temp), ptr(out), stream_of(seta)),
           "pdgn_emd_cost")

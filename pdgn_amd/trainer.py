@@ -7,6 +7,7 @@ as ONE flat fp32 buffer per network (G: 50.8 MB, D1-4: 6.8 MB) -- parameters' ``
 are views into that buffer, so there is no bucket copy in or out.
 """
 import contextlib
+import ctypes
 import os
 import warnings
 
@@ -22,6 +23,24 @@ from . import losses
 from .losses import LocalPairLoss
 
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # get_local_pair calls :232-237
+
+
+def _fp32_lists(*lists):
+    """What the multi-tensor launches of csrc/adam.hip take: lists of contiguous fp32 tensors on one ROCm device, every list as
+    long as the first and its i-th tensor as large as the first's."""
+    first = lists[0]
+    return bool(first) and first[0].is_cuda and all(
+        len(lst) == len(first) and all(t.dtype == torch.float32 and t.is_contiguous() and t.device == f.device and t.numel() == f.numel()
+                                       for t, f in zip(lst, first)) for lst in lists)
+
+
+def _pointer_table(tensors):
+    """The HOST array of device pointers those launches read a list from."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _count_table(tensors):
+    return (ctypes.c_longlong * len(tensors))(*[t.numel() for t in tensors])
 
 
 class FlatGrads:
@@ -94,22 +113,15 @@ class FlatGrads:
     def _copy(self, dsts, srcs, full=None):
         """views <- fresh gradients: one launch of csrc/adam.hip's multi-tensor copy per 128 tensors (torch._foreach_copy_: 82 us for
         the generator's 160 gradients); anything but contiguous fp32 CUDA tensors of equal sizes goes torch's way."""
-        if (os.environ.get("PDGN_OWN_ADAM", "1") == "1" and dsts[0].is_cuda and all(
-                d.dtype == torch.float32 and s.dtype == torch.float32 and d.is_contiguous() and s.is_contiguous() and d.numel() == s.numel()
-                and s.is_cuda for d, s in zip(dsts, srcs))):
-            import ctypes
-            from . import _lib
-            n = len(dsts)
+        if os.environ.get("PDGN_OWN_ADAM", "1") == "1" and _fp32_lists(dsts, srcs):
             # (full = (lo, hi): every view of that range takes part -- the views are static, their pointer and size arrays are built once)
             cache = self.__dict__.setdefault("_copy_cache", {})
             hit = cache.get(full) if full is not None else None
             if hit is None:
-                vp = ctypes.c_void_p * n
-                hit = (vp, vp(*[d.data_ptr() for d in dsts]), (ctypes.c_longlong * n)(*[d.numel() for d in dsts]))
+                hit = (_pointer_table(dsts), _count_table(dsts))
                 if full is not None:
                     cache[full] = hit
-            _lib.check(_lib.lib().pdgn_copy_multi(n, hit[1], hit[0](*[s.data_ptr() for s in srcs]), hit[2], _lib.stream_of(dsts[0])),
-                       "pdgn_copy_multi")
+            _lib.check(_lib.lib().pdgn_copy_multi(len(dsts), hit[0], _pointer_table(srcs), hit[1], _lib.stream_of(dsts[0])), "pdgn_copy_multi")
             return
         torch._foreach_copy_(dsts, srcs)
 
@@ -252,23 +264,17 @@ class LeanAdamStep:
         form of it: anything but fp32 CUDA tensors and a device-side fp32 counter raises."""
         if self.ema is None:
             return
-        import ctypes
         ps = self.opt.param_groups[0]["params"]
         step = self.opt.state[ps[0]]["step"]
         n = len(ps)
         tab = self._ema_table
         if tab is None or tab[0] != n or tab[2][0] != ps[0].data_ptr() or tab[2][n - 1] != ps[n - 1].data_ptr():
-            if len(self.ema) != n or any(t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or e.numel() != t.numel()
-                                          or e.dtype != torch.float32 or not e.is_contiguous() or e.device != t.device
-                                          for t, e in zip(ps, self.ema)):
+            if not _fp32_lists(ps, self.ema):
                 raise _lib.PdgnHipError("the averaged generator needs contiguous fp32 parameters on a ROCm device (pdgn_amd has no CPU path)")
-            vp = ctypes.c_void_p * n
-            tab = self._ema_table = (n, vp(*[e.data_ptr() for e in self.ema]), vp(*[t.data_ptr() for t in ps]),
-                                     (ctypes.c_longlong * n)(*[t.numel() for t in ps]))
+            tab = self._ema_table = (n, _pointer_table(self.ema), _pointer_table(ps), _count_table(ps))
         if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.float32):
             raise _lib.PdgnHipError("the averaged generator reads Adam's step count on the device: a capturable optimizer is required")
-        _lib.check(_lib.lib().pdgn_ema_multi(n, tab[1], tab[2], tab[3], ctypes.c_double(self.ema_decay), _lib.ptr(step),
-                                             _lib.stream_of(ps[0])), "pdgn_ema_multi")
+        _lib.check(_lib.lib().pdgn_ema_multi(n, tab[1], tab[2], tab[3], self.ema_decay, _lib.ptr(step), _lib.stream_of(ps[0])), "pdgn_ema_multi")
 
     _OWN = os.environ.get("PDGN_OWN_ADAM", "1") == "1"           # A/B switch: 0 = torch._fused_adam_
 
@@ -279,32 +285,24 @@ class LeanAdamStep:
         for anything but contiguous fp32 CUDA tensors."""
         if not self._OWN or not ps or not ps[0].is_cuda:
             return False
-        from . import _lib
-        import ctypes
         n = len(ps)
         tab = self._table
         if tab is None or tab[0] != n or tab[1][0] != ps[0].data_ptr() or tab[2][n - 1] != exp_avgs[n - 1].data_ptr():
-            if any(t.dtype != torch.float32 or not t.is_contiguous() for lst in (ps, exp_avgs, exp_avg_sqs) for t in lst) \
-                    or steps[0].dtype != torch.float32:
+            if not _fp32_lists(ps, exp_avgs, exp_avg_sqs) or steps[0].dtype != torch.float32:
                 return False
-            vp = ctypes.c_void_p * n
-            tab = self._table = (n, vp(*[t.data_ptr() for t in ps]), vp(*[t.data_ptr() for t in exp_avgs]),
-                                 vp(*[t.data_ptr() for t in exp_avg_sqs]), (ctypes.c_longlong * n)(*[t.numel() for t in ps]), vp)
+            tab = self._table = (n, _pointer_table(ps), _pointer_table(exp_avgs), _pointer_table(exp_avg_sqs), _count_table(ps))
         if any(t.dtype != torch.float32 or not t.is_contiguous() for t in grads):
             return False
         if self.ema is not None:                                 # the average rides in the same launches
             et = self._ema_table
             if et is None or et[0] != n or et[2][0] != tab[1][0] or et[2][n - 1] != tab[1][n - 1]:
                 return False                                     # (not validated yet, or other parameters: _ema_alone checks and raises)
-            _lib.check(_lib.lib().pdgn_adam_ema_multi(n, tab[1], tab[5](*[t.data_ptr() for t in grads]), tab[2], tab[3], et[1], tab[4],
-                                                      ctypes.c_double(g["lr"]), ctypes.c_double(g["betas"][0]),
-                                                      ctypes.c_double(g["betas"][1]), ctypes.c_double(g["eps"]),
-                                                      ctypes.c_double(self.ema_decay), _lib.ptr(steps[0]), _lib.stream_of(ps[0])),
+            _lib.check(_lib.lib().pdgn_adam_ema_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], et[1], tab[4], g["lr"], g["betas"][0],
+                                                      g["betas"][1], g["eps"], self.ema_decay, _lib.ptr(steps[0]), _lib.stream_of(ps[0])),
                        "pdgn_adam_ema_multi")
             return True
-        _lib.check(_lib.lib().pdgn_adam_multi(n, tab[1], tab[5](*[t.data_ptr() for t in grads]), tab[2], tab[3], tab[4],
-                                              ctypes.c_double(g["lr"]), ctypes.c_double(g["betas"][0]), ctypes.c_double(g["betas"][1]),
-                                              ctypes.c_double(g["eps"]), _lib.ptr(steps[0]), _lib.stream_of(ps[0])), "pdgn_adam_multi")
+        _lib.check(_lib.lib().pdgn_adam_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], tab[4], g["lr"], g["betas"][0], g["betas"][1],
+                                              g["eps"], _lib.ptr(steps[0]), _lib.stream_of(ps[0])), "pdgn_adam_multi")
         return True
 
     def step(self):

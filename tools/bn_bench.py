@@ -6,7 +6,6 @@ import torch
 from pdgn_amd import _lib
 from pdgn_amd._lib import ptr, stream_of
 L = _lib.lib()
-L.pdgn_bn_scratch_floats.restype = ctypes.c_longlong
 def t(fn, it=20):
     for _ in range(3): fn()
     torch.cuda.synchronize()

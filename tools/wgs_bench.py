@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from pdgn_amd import _lib
 from pdgn_amd._lib import ptr, stream_of
-L = _lib.lib(); L.pdgn_bn_scratch_floats.restype = ctypes.c_longlong
+L = _lib.lib()
 def t(fn, it=20):
     for _ in range(3): fn()
     torch.cuda.synchronize()
