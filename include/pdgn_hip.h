@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 30
+#define PDGN_ABI_VERSION 31
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -674,6 +674,52 @@ int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void
  * No reference counterpart.  PDGN_ERR_INVALID: ntensors < 1, a null or misaligned pointer, n[i] < 1, ema_decay outside [0, 1). */
 int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
                    pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ gradient guard
+ * The 2-norm of a network's whole gradient list, known on the device before the optimizer's launch reads it: global-norm
+ * clipping, a view of the gradient magnitudes, and an update that does not happen when a gradient is not finite -- also where no
+ * host is in the loop (a replayed launch list).  No reference counterpart: the reference's five optimizer.step() calls
+ * (models/PDGNet_v2.py:186-226, 256) apply whatever gradient they are given.
+ *
+ * The guard record, one per network, in device memory (32 bytes, 4-byte aligned; the caller zero-fills it once): */
+typedef struct pdgn_guard_record {
+    float norm;          /* (float) sqrt(total): the fp64 root of the fp64 sum of squares, rounded once (Inf / NaN when the total is) */
+    float coef;          /* the clip factor: (float) min(1.0, max_norm / (sqrt(total) + 1e-6)) in fp64 for a finite total and a finite
+                            max_norm > 0; exactly 1.0f for max_norm <= 0 or infinite ("no clipping") and for a non-finite total */
+    float applied;       /* 1.0f: the total is finite; 0.0f: some element is NaN or +-Inf (fp64 squares of fp32 values cannot overflow) */
+    float found_inf;     /* 1.0f - applied: the flag in the form torch's fused optimizer kernel takes as `found_inf` */
+    unsigned n_applied;  /* calls so far with applied == 1 ...                                                                    */
+    unsigned n_skipped;  /* ... and with applied == 0: written by the finalising workgroup alone, with ordinary vector stores      */
+    unsigned reserved[2];
+} pdgn_guard_record;
+/* Doubles of workspace pdgn_gradnorm_multi needs for a list: one per 4096-element chunk of every tensor (sum of ceil(n[i] / 4096));
+ * -1 for ntensors < 1, a null n, an n[i] < 1 or more than 2^30 - 1 chunks in one launch's 128 tensors. */
+long long pdgn_gradnorm_workspace_doubles(int ntensors, const long long *n);
+/* record <- the guard record of the list g (HOST array of ntensors device pointers to fp32 tensors, 4-byte aligned, n: element
+ * counts), max_norm as above.  ceil(ntensors / 128) launches of one workgroup per 4096-element chunk -- every element squared and
+ * added IN FP64 (per thread in element order, the wave by a shuffle tree, the waves from LDS in order), one partial per chunk
+ * into workspace -- then ONE workgroup that adds the partials in index order and writes the record.  No float atomics, no
+ * counter of finished workgroups: the same bytes at the same addresses give the same bits.  State touched: workspace (8-byte
+ * aligned, workspace_doubles >= pdgn_gradnorm_workspace_doubles(ntensors, n) doubles), record (norm, coef, applied, found_inf
+ * overwritten; n_applied or n_skipped incremented); read: g.  Allocates nothing.  PDGN_ERR_INVALID, checked before any launch:
+ * an invalid list (the -1 cases above), a null or misaligned g[i], workspace or record, a workspace too small, max_norm NaN. */
+int pdgn_gradnorm_multi(int ntensors, const void *const *g, const long long *n, double max_norm, double *workspace,
+                        long long workspace_doubles, pdgn_guard_record *record, pdgn_stream_t stream);
+/* pdgn_adam_multi / pdgn_adam_ema_multi / pdgn_ema_multi behind a guard: the same kernel text with one more switch.  Every
+ * workgroup reads `coef` and `applied` from the record (complete before the launch: same stream, behind pdgn_gradnorm_multi).
+ * applied == 0: it returns before touching p, m, v or e -- the caller advances `step` by the device value `applied`, so a skipped
+ * update leaves every byte of the optimizer's state as it was.  Otherwise the gradient in the arithmetic is fmul(g, coef),
+ * rounded on its own, never contracted into what follows; g itself is not written.  coef == 1 and applied == 1: the bits of the
+ * unguarded entry points.  They replace those entry points where a guard is on; state touched: p, m, v (e); read: g, step, guard.
+ * PDGN_ERR_INVALID: the unguarded entry point's cases, a null or misaligned guard; checked before any launch. */
+int pdgn_adam_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
+                          double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
+                          pdgn_stream_t stream);
+int pdgn_adam_ema_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                              const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay, const float *step,
+                              const pdgn_guard_record *guard, pdgn_stream_t stream);
+int pdgn_ema_guard_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
+                         const pdgn_guard_record *guard, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ deterministic mode
  * pdgn_set_deterministic: process-wide switch, like pdgn_gemm_set_mode.  -1 queries the current value; any other value

@@ -38,7 +38,7 @@ struct AdamEmaArgs {               // the same table with the list of averages (
     int chunk0[ADAM_EMA_MAXT];
     int ntensors;
 };
-static_assert(sizeof(AdamArgs) + 40 <= 3584 && sizeof(AdamEmaArgs) + 48 <= 3584, "pointer tables: 3.5 KB of the 4 KB of kernel arguments");
+static_assert(sizeof(AdamArgs) + 48 <= 3584 && sizeof(AdamEmaArgs) + 56 <= 3584, "pointer tables: 3.5 KB of the 4 KB of kernel arguments");
 
 // ---- the generator's averaged copy (an exponential moving average of the parameters, Yazici et al. 2019), one expression for the
 // fused launch, the stand-alone launch and the host mirror of the tests: with t the step count of THIS update,
@@ -53,11 +53,18 @@ __device__ __forceinline__ float ema_one_minus_decay(double ema_decay, const flo
 __device__ __forceinline__ void ema_one(float &e, float p, float omd) { e = __fadd_rn(e, __fmul_rn(omd, __fsub_rn(p, e))); }
 
 // One chunk of one tensor.  EMA = false is pdgn_adam_multi's kernel; EMA = true adds the average E to the same walk (one more load
-// in front of the stores, one more store behind them): the Adam arithmetic is this one text for both.
-template <bool EMA, class Args>
+// in front of the stores, one more store behind them): the Adam arithmetic is this one text for both.  GUARD = true reads the
+// network's guard record first (written by pdgn_gradnorm_multi on the same stream): applied == 0 leaves before anything is touched,
+// otherwise the gradient that enters the arithmetic is fmul(g, coef), rounded on its own; g itself is never written.
+template <bool EMA, bool GUARD, class Args>
 __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta1d, double beta2d, double eps, double ema_decay,
-                                           const float *__restrict__ step) {
+                                           const float *__restrict__ step, const pdgn_guard_record *__restrict__ guard = nullptr) {
     __shared__ float sc[EMA ? 3 : 2];
+    float coef = 1.f;
+    if constexpr (GUARD) {
+        if (guard->applied == 0.f) return;                       // the whole grid takes the same way: the record is complete before the launch
+        coef = guard->coef;
+    }
     // the chunk's tensor: the last one whose first chunk is <= this chunk
     int lo = 0, hi = a.ntensors - 1;
     const int c = blockIdx.x;
@@ -88,6 +95,7 @@ __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta
     // torch's expressions with torch's types (lr, betas, eps are doubles there: the moment updates are evaluated in fp64 and rounded
     // once, 1 - beta is 1 - the DOUBLE beta): the results are torch's bits, not merely close to them
     auto one = [&](float &p, float g, float &m, float &v) {
+        if constexpr (GUARD) g = __fmul_rn(g, coef);
         m = (float)(beta1d * (double)m + w1 * (double)g);
         v = (float)(beta2d * (double)v + (w2 * (double)g) * (double)g);
         const float denom = (float)((double)(sqrtf(v) / bc2s) + epsd);
@@ -140,26 +148,48 @@ __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta
 
 __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
                                                                   const float *__restrict__ step) {
-    adam_chunk<false>(a, lr, beta1d, beta2d, eps, 0.0, step);
+    adam_chunk<false, false>(a, lr, beta1d, beta2d, eps, 0.0, step);
 }
 
 __global__ __launch_bounds__(ADAM_THREADS) void adam_ema_multi_kernel(const AdamEmaArgs a, double lr, double beta1d, double beta2d, double eps,
                                                                       double ema_decay, const float *__restrict__ step) {
-    adam_chunk<true>(a, lr, beta1d, beta2d, eps, ema_decay, step);
+    adam_chunk<true, false>(a, lr, beta1d, beta2d, eps, ema_decay, step);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_guard_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
+                                                                        const float *__restrict__ step,
+                                                                        const pdgn_guard_record *__restrict__ guard) {
+    adam_chunk<false, true>(a, lr, beta1d, beta2d, eps, 0.0, step, guard);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_guard_multi_kernel(const AdamEmaArgs a, double lr, double beta1d, double beta2d,
+                                                                            double eps, double ema_decay, const float *__restrict__ step,
+                                                                            const pdgn_guard_record *__restrict__ guard) {
+    adam_chunk<true, true>(a, lr, beta1d, beta2d, eps, ema_decay, step, guard);
 }
 
 // One Adam step of `ntensors` fp32 tensors (p, g, m, v: HOST arrays of device pointers; n: their element counts), in
 // ceil(ntensors / 72) launches of one workgroup per 4096 elements.  step (device): the step count t >= 1 of THIS update as one
 // float (torch's `state["step"]` after its increment).  Replaces torch._fused_adam_ / optimizer.step() of the reference's five Adam
 // optimisers (models/PDGNet_v2.py:121-125) for lists without weight decay, amsgrad or maximize.
-extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
-                               double lr, double beta1, double beta2, double eps, const float *step, pdgn_stream_t stream) {
+// (a guard record is read with dword loads: the address the guarded entry points refuse.  `guard` null = the unguarded kernel.)
+static bool guard_misplaced(const pdgn_guard_record *guard) { return ((uintptr_t)guard & 3) != 0; }
+
+static int adam_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
+                             double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
+                             pdgn_stream_t stream) {
     if (ntensors < 1 || !p || !g || !m || !v || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
         !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.))
         return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
         if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 1 || (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3))
             return PDGN_ERR_INVALID;
+    if (guard_misplaced(guard)) return PDGN_ERR_INVALID;
+    for (int t0 = 0; t0 < ntensors; t0 += ADAM_MAXT) {                      // every launch's chunk count is checked before the first launch
+        long long chunks = 0;
+        for (int i = t0; i < ntensors && i < t0 + ADAM_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
+    }
     for (int t0 = 0; t0 < ntensors; t0 += ADAM_MAXT) {
         AdamArgs a;
         a.ntensors = ntensors - t0 < ADAM_MAXT ? ntensors - t0 : ADAM_MAXT;
@@ -169,20 +199,28 @@ extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *
             a.n[i] = n[t0 + i];
             a.chunk0[i] = (int)chunks;
             chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-            if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
         }
         for (int i = a.ntensors; i < ADAM_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps, step);
+        if (guard)
+            hipLaunchKernelGGL(adam_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2,
+                               eps, step, guard);
+        else
+            hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps, step);
     }
     return pdgn_launch_status();
+}
+
+extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
+                               double lr, double beta1, double beta2, double eps, const float *step, pdgn_stream_t stream) {
+    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, nullptr, stream);
 }
 
 // pdgn_adam_multi with the averages e (HOST array of device pointers) updated in the same launches, ceil(ntensors / 64) of them:
 // p, m, v are pdgn_adam_multi's bits; e <- e + (1 - d_t) (p_new - e) as written at ema_one_minus_decay above.  No reference
 // counterpart (the reference keeps no averaged generator).
-extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
-                                   const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
-                                   const float *step, pdgn_stream_t stream) {
+static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                                 const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
+                                 const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
     if (ntensors < 1 || !p || !g || !m || !v || !e || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
         !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || !(ema_decay >= 0. && ema_decay < 1.))
         return PDGN_ERR_INVALID;
@@ -190,6 +228,7 @@ extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *con
         if (!p[i] || !g[i] || !m[i] || !v[i] || !e[i] || n[i] < 1 ||
             (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (uintptr_t)e[i]) & 3))
             return PDGN_ERR_INVALID;
+    if (guard_misplaced(guard)) return PDGN_ERR_INVALID;
     for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {                  // every launch's chunk count is checked before the first launch
         long long chunks = 0;
         for (int i = t0; i < ntensors && i < t0 + ADAM_EMA_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
@@ -207,10 +246,37 @@ extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *con
             chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
         }
         for (int i = a.ntensors; i < ADAM_EMA_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = a.e[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        hipLaunchKernelGGL(adam_ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps,
-                           ema_decay, step);
+        if (guard)
+            hipLaunchKernelGGL(adam_ema_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
+                               beta2, eps, ema_decay, step, guard);
+        else
+            hipLaunchKernelGGL(adam_ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps,
+                               ema_decay, step);
     }
     return pdgn_launch_status();
+}
+
+extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                                   const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
+                                   const float *step, pdgn_stream_t stream) {
+    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, nullptr, stream);
+}
+
+// The two launches above behind a gradient guard (pdgn_gradnorm_multi below, on the same stream in front of them): every workgroup
+// reads the network's record; applied == 0 leaves p, m, v, e as they are, otherwise the gradient in the arithmetic is fmul(g, coef).
+// With coef == 1 the bits are the unguarded launches'.  guard: the record (device), never null here.
+extern "C" int pdgn_adam_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
+                                     double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
+                                     pdgn_stream_t stream) {
+    if (!guard) return PDGN_ERR_INVALID;
+    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, stream);
+}
+
+extern "C" int pdgn_adam_ema_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                                         const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
+                                         const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
+    if (!guard) return PDGN_ERR_INVALID;
+    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, stream);
 }
 
 // ---- the same walk for a plain copy: dst[i] <- src[i] for a list of fp32 tensors (the pack of a network's fresh gradients into the
@@ -287,6 +353,140 @@ struct EmaArgs {
     int ntensors;
 };
 
+// ---- the gradient guard: the 2-norm of a whole list of fp32 tensors, on the device, in two launches and a fixed order of additions
+// (no float atomics, no last-block-done counter: the same bytes give the same bits).
+//   launch 1 (one workgroup per 4096-element chunk, the walk of the kernels above): every thread squares its 16 elements IN FP64 and
+//     adds them in element order, the wave adds its 64 lanes by a shuffle tree, thread 0 adds the four waves' sums from LDS in wave
+//     order; one fp64 partial per chunk goes to the caller's workspace.  A thread's elements are the same 16 on the vector and the
+//     scalar path, so the bits do not depend on the tensors' alignment either.
+//   launch 2 (one workgroup): the partials through LDS, added by thread 0 in index order; the record is written there.
+// fp64 squares of fp32 values neither overflow nor vanish (|g| <= 3.4e38: g^2 <= 1.2e77; the smallest denormal squared is 2e-90),
+// so the total is non-finite exactly when an element is NaN or +-Inf.
+struct GradArgs {
+    const float *g[COPY_MAXT];
+    long long n[COPY_MAXT];
+    int chunk0[COPY_MAXT];
+    int ntensors;
+};
+#define GUARD_TILE 2048             // partials per pass of the finalising workgroup through LDS (16 KB)
+
+__global__ __launch_bounds__(ADAM_THREADS) void gradnorm_partial_kernel(const GradArgs a, double *__restrict__ partial) {
+    __shared__ double sw[ADAM_THREADS / 64];
+    int lo = 0, hi = a.ntensors - 1;
+    const int c = blockIdx.x;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.chunk0[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    const float *const G = a.g[lo];
+    const long long n = a.n[lo], i0 = (long long)(c - a.chunk0[lo]) * ADAM_CHUNK;
+    constexpr int NU = ADAM_CHUNK / (4 * ADAM_THREADS);
+    const bool vec = (((uintptr_t)G & 15) == 0);
+    float4 g4[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
+        g4[u] = make_float4(0.f, 0.f, 0.f, 0.f);                 // past the end: zeros, whose squares change no sum
+        if (vec && i + 3 < n) {
+            g4[u] = *reinterpret_cast<const float4 *>(G + i);
+        } else {
+            if (i < n) g4[u].x = G[i];
+            if (i + 1 < n) g4[u].y = G[i + 1];
+            if (i + 2 < n) g4[u].z = G[i + 2];
+            if (i + 3 < n) g4[u].w = G[i + 3];
+        }
+    }
+    double s = 0.0;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        s += (double)g4[u].x * (double)g4[u].x; s += (double)g4[u].y * (double)g4[u].y;
+        s += (double)g4[u].z * (double)g4[u].z; s += (double)g4[u].w * (double)g4[u].w;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = sw[0];
+#pragma unroll
+        for (int w = 1; w < ADAM_THREADS / 64; ++w) t += sw[w];
+        partial[c] = t;
+    }
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void gradnorm_final_kernel(const double *__restrict__ partial, long long nparts, double max_norm,
+                                                                      pdgn_guard_record *__restrict__ rec) {
+    __shared__ double tile[GUARD_TILE];
+    double total = 0.0;
+    for (long long base = 0; base < nparts; base += GUARD_TILE) {
+        const int m = (int)(nparts - base < GUARD_TILE ? nparts - base : GUARD_TILE);
+        for (int i = threadIdx.x; i < m; i += ADAM_THREADS) tile[i] = partial[base + i];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < m; ++i) total += tile[i];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const bool finite = isfinite(total);
+        const double norm64 = sqrt(total);
+        float coef = 1.f;                                        // no clipping: max_norm <= 0 or infinite; nothing to clip: a skipped update
+        if (finite && max_norm > 0. && isfinite(max_norm)) {
+            const double r = max_norm / (norm64 + 1e-6);
+            coef = (float)(r < 1.0 ? r : 1.0);
+        }
+        rec->norm = (float)norm64;
+        rec->coef = coef;
+        rec->applied = finite ? 1.f : 0.f;
+        rec->found_inf = finite ? 0.f : 1.f;
+        rec->n_applied += finite ? 1u : 0u;
+        rec->n_skipped += finite ? 0u : 1u;
+    }
+}
+
+// ema_multi_kernel (below) behind a guard record: applied == 0 (the update in front of this launch was skipped) leaves e as it is.
+// Its own copy of the text, not a switch in that kernel, and placed -- like the guard's other kernels -- in front of it: the unguarded
+// kernel's machine code is pinned (tools/isa_diff.py compares it with its padding, which depends on what follows it in the object,
+// and the compiler numbers the registers of an inlined shared body differently).
+__global__ __launch_bounds__(ADAM_THREADS) void ema_guard_multi_kernel(const EmaArgs a, double ema_decay, const float *__restrict__ step,
+                                                                       const pdgn_guard_record *__restrict__ guard) {
+    if (guard->applied == 0.f) return;
+    int lo = 0, hi = a.ntensors - 1;
+    const int c = blockIdx.x;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.chunk0[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    float *const E = a.e[lo];
+    const float *const P = a.p[lo];
+    const long long n = a.n[lo], i0 = (long long)(c - a.chunk0[lo]) * ADAM_CHUNK;
+    const float omd = ema_one_minus_decay(ema_decay, step);
+    if (((((uintptr_t)E | (uintptr_t)P) & 15) == 0)) {
+        constexpr int NU = ADAM_CHUNK / (4 * ADAM_THREADS);
+        float4 e4[NU], p4[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
+            if (i + 3 < n) {
+                e4[u] = *reinterpret_cast<const float4 *>(E + i);
+                p4[u] = *reinterpret_cast<const float4 *>(P + i);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const long long i = i0 + 4LL * (threadIdx.x + u * ADAM_THREADS);
+            if (i + 3 < n) {
+                ema_one(e4[u].x, p4[u].x, omd); ema_one(e4[u].y, p4[u].y, omd);
+                ema_one(e4[u].z, p4[u].z, omd); ema_one(e4[u].w, p4[u].w, omd);
+                *reinterpret_cast<float4 *>(E + i) = e4[u];
+            } else {
+                for (long long j = i; j < n && j < i + 4; ++j) ema_one(E[j], P[j], omd);
+            }
+        }
+    } else {
+        for (long long i = i0 + threadIdx.x; i < n && i < i0 + ADAM_CHUNK; i += ADAM_THREADS) ema_one(E[i], P[i], omd);
+    }
+}
+
 __global__ __launch_bounds__(ADAM_THREADS) void ema_multi_kernel(const EmaArgs a, double ema_decay, const float *__restrict__ step) {
     int lo = 0, hi = a.ntensors - 1;
     const int c = blockIdx.x;
@@ -328,8 +528,9 @@ __global__ __launch_bounds__(ADAM_THREADS) void ema_multi_kernel(const EmaArgs a
 // e[i] (n[i] floats) <- e[i] + (1 - d_t) (p[i] - e[i]) for ntensors fp32 tensors (HOST arrays of device pointers, 4-byte aligned;
 // 16-byte aligned pairs take the vector path), d_t = min(ema_decay, (1 + t) / (10 + t)) from step[0] (device), in
 // ceil(ntensors / 128) launches.  No reference counterpart.
-extern "C" int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
-                              pdgn_stream_t stream) {
+static int ema_multi_launch(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
+                            const pdgn_guard_record *guard, pdgn_stream_t stream) {
+    if (guard_misplaced(guard)) return PDGN_ERR_INVALID;
     if (ntensors < 1 || !e || !p || !n || !step || !(ema_decay >= 0. && ema_decay < 1.)) return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
         if (!e[i] || !p[i] || n[i] < 1 || (((uintptr_t)e[i] | (uintptr_t)p[i]) & 3)) return PDGN_ERR_INVALID;
@@ -348,7 +549,69 @@ extern "C" int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p
             chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
         }
         for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.e[i] = nullptr; a.p[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step);
+        if (guard)
+            hipLaunchKernelGGL(ema_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step, guard);
+        else
+            hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step);
     }
+    return pdgn_launch_status();
+}
+
+extern "C" int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
+                              pdgn_stream_t stream) {
+    return ema_multi_launch(ntensors, e, p, n, ema_decay, step, nullptr, stream);
+}
+
+// pdgn_ema_multi behind a guarded optimizer step that was not pdgn_adam_ema_guard_multi: applied == 0 in the record leaves e as it is.
+extern "C" int pdgn_ema_guard_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay,
+                                    const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
+    if (!guard) return PDGN_ERR_INVALID;
+    return ema_multi_launch(ntensors, e, p, n, ema_decay, step, guard, stream);
+}
+
+static long long gradnorm_chunks(int ntensors, const long long *n) {
+    if (ntensors < 1 || !n) return -1;
+    long long total = 0;
+    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
+        long long chunks = 0;
+        for (int i = t0; i < ntensors && i < t0 + COPY_MAXT; ++i) {
+            if (n[i] < 1) return -1;
+            chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        }
+        if (chunks > 0x3fffffffLL) return -1;
+        total += chunks;
+    }
+    return total;
+}
+
+// Doubles of workspace pdgn_gradnorm_multi takes for this list: one per 4096-element chunk of every tensor; -1 for an invalid list.
+extern "C" long long pdgn_gradnorm_workspace_doubles(int ntensors, const long long *n) { return gradnorm_chunks(ntensors, n); }
+
+// The guard record of one network from its gradient list g (HOST array of device pointers, n: element counts): ceil(ntensors / 128)
+// partial launches and one finalising launch on `stream`.  No reference counterpart (the reference applies every gradient unseen).
+extern "C" int pdgn_gradnorm_multi(int ntensors, const void *const *g, const long long *n, double max_norm, double *workspace,
+                                   long long workspace_doubles, pdgn_guard_record *record, pdgn_stream_t stream) {
+    const long long total = gradnorm_chunks(ntensors, n);
+    if (total < 1 || !g || !workspace || ((uintptr_t)workspace & 7) || workspace_doubles < total || !record || ((uintptr_t)record & 3) ||
+        max_norm != max_norm)
+        return PDGN_ERR_INVALID;
+    for (int i = 0; i < ntensors; ++i)
+        if (!g[i] || ((uintptr_t)g[i] & 3)) return PDGN_ERR_INVALID;
+    long long done = 0;
+    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
+        GradArgs a;
+        a.ntensors = ntensors - t0 < COPY_MAXT ? ntensors - t0 : COPY_MAXT;
+        long long chunks = 0;
+        for (int i = 0; i < a.ntensors; ++i) {
+            a.g[i] = (const float *)g[t0 + i]; a.n[i] = n[t0 + i];
+            a.chunk0[i] = (int)chunks;
+            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        }
+        for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
+        hipLaunchKernelGGL(gradnorm_partial_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, workspace + done);
+        done += chunks;
+    }
+    hipLaunchKernelGGL(gradnorm_final_kernel, dim3(1), dim3(ADAM_THREADS), 0, (hipStream_t)stream, (const double *)workspace, total, max_norm,
+                       record);
     return pdgn_launch_status();
 }

@@ -55,13 +55,23 @@ def build_parser():
     p.add_argument("--report_full", action="store_true", help="reports run the full evaluation (EMD included) instead of the CD-only one")
     p.add_argument("--ema_decay", type=float, default=argparse.SUPPRESS, help="decay of the averaged generator (an exponential moving average of the "
                    "generator's parameters, e.g. 0.999: written as <epoch>_<category>_G_ema.pth, shown by the reports); 0: none")
+    p.add_argument("--grad_guard", action="store_true", default=argparse.SUPPRESS, help="gradient guard: each network's global gradient "
+                   "norm on the device before its Adam launch, an update with a non-finite gradient is skipped, grad_norms.csv beside the log")
+    p.add_argument("--clip_grad_norm", type=float, default=argparse.SUPPRESS, help="clip each network's global gradient norm to this "
+                   "value (implies --grad_guard)")
+    p.add_argument("--guard_max_skips", type=int, default=argparse.SUPPRESS, help="stop, with a checkpoint, after this many consecutive "
+                   "skipped updates of a network (default 50)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay is listed (vars(), the log's first line) only where it was given: a run without it
-    has the namespace, and writes the log line, of the time before the flag existed; reading it gives 0 then."""
+    """The parsed command line.  --ema_decay and the gradient guard's flags are listed (vars(), the log's first line) only where
+    they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
+    them gives the defaults below then."""
     ema_decay = 0.0
+    grad_guard = False
+    clip_grad_norm = None
+    guard_max_skips = 50
 
 
 def parse_args(argv=None):
@@ -83,6 +93,12 @@ def parse_args(argv=None):
         p.error("--report_every must not be negative and --report_rows at least one")
     if not 0.0 <= args.ema_decay < 1.0:
         p.error("--ema_decay %r: at least 0 and below 1" % args.ema_decay)
+    if args.clip_grad_norm is not None:
+        if not args.clip_grad_norm > 0.0:
+            p.error("--clip_grad_norm %r: a positive number" % args.clip_grad_norm)
+        args.grad_guard = True
+    if args.guard_max_skips < 1:
+        p.error("--guard_max_skips must be at least one")
     return args
 
 
@@ -134,7 +150,9 @@ def make_trainer(args, device):
     gen = PointGenerator(args.num_point, args.num_k, softmax=args.softmax == "True", base_points=base)
     # (--phase test loads whichever file it is given -- G.pth or G_ema.pth -- into the generator itself: no average to keep)
     return PDGNTrainer(device=device, lr=args.learning_rate, num_k=args.num_k, base_points=base, generator=gen,
-                       ema_decay=args.ema_decay if args.phase == "train" else 0.0)
+                       ema_decay=args.ema_decay if args.phase == "train" else 0.0,
+                       grad_guard=args.grad_guard and args.phase == "train",
+                       clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None)
 
 
 def _resume(args, trainer, ckpt):
@@ -177,7 +195,8 @@ def train(args):
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
-                       category=args.choice or "full", log=log, on_epoch=reporter)
+                       category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
+                       grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None)
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()

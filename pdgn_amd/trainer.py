@@ -228,6 +228,61 @@ def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+GUARD_RECORD_FLOATS = 8             # sizeof(pdgn_guard_record) / 4 (include/pdgn_hip.h): norm, coef, applied, found_inf, two counters, two spare
+
+
+class GradGuardError(RuntimeError):
+    """`fit` saw `guard_max_skips` consecutive skipped updates of a network: its gradients have stopped being finite."""
+
+
+class GradGuard:
+    """One network's gradient guard: the device-side record that pdgn_gradnorm_multi writes from the network's
+    whole gradient list and the guarded optimizer launches read, the fp64 workspace of the reduction, and the clipping bound.
+
+    record: 8 fp32 words of device memory laid out as pdgn_guard_record (a row of the trainer's `guard_buf`), zero at the start;
+    `applied`, `found_inf` and `coef` are 0-dim views of it -- the device values LeanAdamStep hands to torch (`_foreach_add_` on the
+    step counters, `found_inf` of torch's fused kernel, `_foreach_mul_` on the gradients): the host never reads them inside a step.
+    max_norm: None / 0 / inf = no clipping (coef is exactly 1)."""
+
+    def __init__(self, params, max_norm=None, record=None):
+        params = list(params)
+        dev = params[0].device
+        self.max_norm = 0.0 if max_norm is None else float(max_norm)
+        if self.max_norm != self.max_norm or self.max_norm < 0:
+            raise ValueError("clip_grad_norm must be a positive number (or None), got %r" % (max_norm,))
+        self.record = record if record is not None else torch.zeros(GUARD_RECORD_FLOATS, dtype=torch.float32, device=dev)
+        if (self.record.dtype != torch.float32 or self.record.numel() != GUARD_RECORD_FLOATS or not self.record.is_contiguous()
+                or self.record.device != dev):
+            raise ValueError("guard record: %d contiguous fp32 words on the parameters' device" % GUARD_RECORD_FLOATS)
+        self.coef, self.applied, self.found_inf = self.record[1], self.record[2], self.record[3]
+        self.counters = self.record.view(torch.int32)[4:6]
+        counts = _count_table(params)
+        # pdgn_gradnorm_workspace_doubles(): one partial per 4096-element chunk (the library checks the size it is given; on the CPU
+        # device the trainer can be built and inspected, the launches themselves raise)
+        self.workspace = torch.zeros(sum((p.numel() + 4095) // 4096 for p in params), dtype=torch.float64, device=dev)
+        self._n, self._counts = len(params), counts
+
+    def measure(self, grads):
+        """record <- norm, coef, applied of this gradient list: the partial launches and the finalising one, on the current stream."""
+        if len(grads) != self._n or not _fp32_lists(grads) or any(g.numel() != c for g, c in zip(grads, self._counts)):
+            raise _lib.PdgnHipError("the gradient guard reads one contiguous fp32 gradient per parameter on a ROCm device; this list "
+                                    "cannot be guarded")
+        _lib.check(_lib.lib().pdgn_gradnorm_multi(self._n, _pointer_table(grads), self._counts, self.max_norm, _lib.ptr(self.workspace),
+                                                  self.workspace.numel(), _lib.ptr(self.record), _lib.stream_of(grads[0])),
+                   "pdgn_gradnorm_multi")
+
+    @staticmethod
+    def decode(words):
+        """{norm, coef, applied, skipped} from the 8 words of a record read back as fp32 (a host tensor): the two counters are
+        the running numbers of applied and skipped updates."""
+        ints = words.contiguous().view(torch.int32)
+        return {"norm": float(words[0]), "coef": float(words[1]), "applied": int(ints[4]) & 0xffffffff, "skipped": int(ints[5]) & 0xffffffff}
+
+    def state(self):
+        """The record as a dict (synchronises: a device-to-host copy on the current stream)."""
+        return self.decode(self.record.cpu())
+
+
 class LeanAdamStep:
     """`optimizer.step()` of a fused, capturable `torch.optim.Adam` without its per-call Python (profile hooks, `_init_group`,
     grouping by device and dtype: ~0.3 ms of host time per call, five calls per training step -- tools/host_prof.py): after the
@@ -241,11 +296,21 @@ class LeanAdamStep:
     ema / ema_decay (the generator's optimizer under `PDGNTrainer(ema_decay=...)`): one fp32 tensor per parameter, in the order of
     the optimizer's group, holding the exponential moving average of that parameter.  Every route out of `step` updates it on the
     same stream, right behind the parameters: the own Adam kernel in its own launch (pdgn_adam_ema_multi), every other route with
-    pdgn_ema_multi behind the optimizer step (csrc/adam.hip: the same expressions, the same bits)."""
+    pdgn_ema_multi behind the optimizer step (csrc/adam.hip: the same expressions, the same bits).
 
-    def __init__(self, opt, ema=None, ema_decay=0.0):
+    guard (a GradGuard; None: nothing below exists): `step` first runs the norm launches on the gradients as they are at that moment
+    -- behind the all-reduce under data parallelism, so every rank decides from the same bytes -- then advances the step counters by
+    the DEVICE value `applied` and runs the guarded launch (pdgn_adam_guard_multi / pdgn_adam_ema_guard_multi).  A skipped update
+    leaves parameters, moments, counters and the average byte-identical.  The routes through torch (`optimizer.step()`,
+    `torch._fused_adam_`) scale the gradients in place by `coef` beforehand -- the one case where the guard writes g -- and hand the
+    flag to torch's kernel as `found_inf`, which makes it return early (and `optimizer.step()` take its increment back); the average
+    behind them is pdgn_ema_guard_multi.  An optimizer that cannot take `found_inf` (not fused, not capturable) raises: no route
+    applies an unguarded update while the guard is on."""
+
+    def __init__(self, opt, ema=None, ema_decay=0.0, guard=None):
         self.opt, self.lists, self._table = opt, None, None
         self.ema, self.ema_decay, self._ema_table = (list(ema) if ema else None), float(ema_decay), None
+        self.guard = guard
 
     def reset(self):
         """The optimizer's state tensors were replaced (load_state_dict): rebuild the lists after the next ordinary step."""
@@ -253,9 +318,33 @@ class LeanAdamStep:
         self._table = None
         self._ema_table = None
 
-    def _plain_step(self):
-        """`optimizer.step()` itself, with the average behind it."""
+    def _plain_step(self, measured=False):
+        """`optimizer.step()` itself, with the average behind it.  Guarded: the gradients are measured and scaled by coef first
+        (measured: that has happened already), and the optimizer takes the skip flag as `found_inf`, as it does from a GradScaler."""
+        if self.guard is not None:
+            self._guarded_plain_step(measured)
+            return
         self.opt.step()
+        self._ema_alone()
+
+    def _guarded_plain_step(self, measured):
+        opt, guard = self.opt, self.guard
+        if len(opt.param_groups) != 1 or not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
+            raise _lib.PdgnHipError("the gradient guard hands its skip flag to torch's fused, capturable Adam as `found_inf`; this "
+                                    "optimizer cannot take it, and an unguarded update is not an option")
+        params = opt.param_groups[0]["params"]
+        if any(p.grad is None for p in params):
+            raise _lib.PdgnHipError("the gradient guard needs a gradient for every parameter of the optimizer")
+        if not measured:
+            grads = [p.grad for p in params]
+            guard.measure(grads)
+            with torch.no_grad():
+                torch._foreach_mul_(grads, guard.coef)
+        opt.grad_scale, opt.found_inf = None, guard.found_inf
+        try:
+            opt.step()
+        finally:
+            opt.grad_scale = opt.found_inf = None
         self._ema_alone()
 
     def _ema_alone(self):
@@ -274,6 +363,10 @@ class LeanAdamStep:
             tab = self._ema_table = (n, _pointer_table(self.ema), _pointer_table(ps), _count_table(ps))
         if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.float32):
             raise _lib.PdgnHipError("the averaged generator reads Adam's step count on the device: a capturable optimizer is required")
+        if self.guard is not None:                               # skipped on the device with the update in front of it
+            _lib.check(_lib.lib().pdgn_ema_guard_multi(n, tab[1], tab[2], tab[3], self.ema_decay, _lib.ptr(step), _lib.ptr(self.guard.record),
+                                                       _lib.stream_of(ps[0])), "pdgn_ema_guard_multi")
+            return
         _lib.check(_lib.lib().pdgn_ema_multi(n, tab[1], tab[2], tab[3], self.ema_decay, _lib.ptr(step), _lib.stream_of(ps[0])), "pdgn_ema_multi")
 
     _OWN = os.environ.get("PDGN_OWN_ADAM", "1") == "1"           # A/B switch: 0 = torch._fused_adam_
@@ -297,9 +390,19 @@ class LeanAdamStep:
             et = self._ema_table
             if et is None or et[0] != n or et[2][0] != tab[1][0] or et[2][n - 1] != tab[1][n - 1]:
                 return False                                     # (not validated yet, or other parameters: _ema_alone checks and raises)
+            if self.guard is not None:
+                _lib.check(_lib.lib().pdgn_adam_ema_guard_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], et[1], tab[4], g["lr"],
+                                                                g["betas"][0], g["betas"][1], g["eps"], self.ema_decay, _lib.ptr(steps[0]),
+                                                                _lib.ptr(self.guard.record), _lib.stream_of(ps[0])), "pdgn_adam_ema_guard_multi")
+                return True
             _lib.check(_lib.lib().pdgn_adam_ema_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], et[1], tab[4], g["lr"], g["betas"][0],
                                                       g["betas"][1], g["eps"], self.ema_decay, _lib.ptr(steps[0]), _lib.stream_of(ps[0])),
                        "pdgn_adam_ema_multi")
+            return True
+        if self.guard is not None:
+            _lib.check(_lib.lib().pdgn_adam_guard_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], tab[4], g["lr"], g["betas"][0],
+                                                        g["betas"][1], g["eps"], _lib.ptr(steps[0]), _lib.ptr(self.guard.record),
+                                                        _lib.stream_of(ps[0])), "pdgn_adam_guard_multi")
             return True
         _lib.check(_lib.lib().pdgn_adam_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], tab[4], g["lr"], g["betas"][0], g["betas"][1],
                                               g["eps"], _lib.ptr(steps[0]), _lib.stream_of(ps[0])), "pdgn_adam_multi")
@@ -335,6 +438,9 @@ class LeanAdamStep:
             self.lists = None                                    # re-validated after the next ordinary step
             self._plain_step()
             return
+        if self.guard is not None:
+            self._guarded_lean_step(ps, grads, exp_avgs, exp_avg_sqs, steps, g)
+            return
         try:
             with torch.no_grad():
                 torch._foreach_add_(steps, 1)
@@ -349,6 +455,30 @@ class LeanAdamStep:
             self.lists = False
             self._plain_step()
 
+    def _guarded_lean_step(self, ps, grads, exp_avgs, exp_avg_sqs, steps, g):
+        """The lean step behind the guard: norm launches, counters += applied (a device value), the guarded launch; where the own
+        kernel declines, torch's fused kernel on gradients scaled in place by coef, with the flag as its `found_inf`."""
+        guard = self.guard
+        guard.measure(grads)
+        scaled = False
+        try:
+            with torch.no_grad():
+                # (the list form, as torch's own capturable optimizers take `found_inf` back: `_foreach_add_(list, Tensor)` reads its
+                #  tensor on the host, which a capturing stream refuses)
+                torch._foreach_add_(steps, [guard.applied] * len(steps))
+                if self._own_adam(ps, grads, exp_avgs, exp_avg_sqs, steps, g):
+                    return
+                torch._foreach_mul_(grads, guard.coef)
+                scaled = True
+                torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=g["lr"], beta1=g["betas"][0],
+                                   beta2=g["betas"][1], weight_decay=0.0, eps=g["eps"], maximize=False, grad_scale=None,
+                                   found_inf=guard.found_inf)
+                self._ema_alone()
+        except TypeError:                                        # (as above; the gradients may be scaled already: not twice)
+            torch._foreach_sub_(steps, [guard.applied] * len(steps))
+            self.lists = False
+            self._plain_step(measured=scaled)
+
 
 class PDGNTrainer:
     """Generator + D1..D4 + their Adam optimisers (lr 1e-4, betas (0.5, 0.999), :121-125) and the
@@ -360,10 +490,14 @@ class PDGNTrainer:
     puts it into the generator for a while, `save` writes it as `<epoch>_<category>_G_ema.pth`.  0: nothing of this exists."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
-                 discriminators=None, distributed=None, ema_decay=0.0):
+                 discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None):
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
+        if clip_grad_norm is not None and not float(clip_grad_norm) > 0.0:
+            raise ValueError("clip_grad_norm must be positive (or None), got %r" % (clip_grad_norm,))
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self.grad_guard = bool(grad_guard) or self.clip_grad_norm is not None
         self.device = torch.device(device)
         self.G = (generator or PointGenerator(num_k=num_k, base_points=base_points)).to(self.device)
         self.D = [d.to(self.device) for d in
@@ -385,7 +519,16 @@ class PDGNTrainer:
         if self.ema_decay > 0:
             # one flat buffer, every average on a 16-byte boundary of it (the kernels' float4 path), in the optimizer's order
             self.ema_buf, self.ema = self._flat_like(self.optG.param_groups[0]["params"])
-        self._stepG, self._stepD = LeanAdamStep(self.optG, self.ema, self.ema_decay), [LeanAdamStep(o) for o in self.optD]
+        self.guard_buf = self.guards = None
+        if self.grad_guard:
+            # one record per network (G, D1..D4: the rows of guard_buf), each with its own workspace -- the five updates run on
+            # five streams; the bound applies to each network separately, as torch.nn.utils.clip_grad_norm_ per module would
+            self.guard_buf = torch.zeros(len(self.GUARD_KEYS), GUARD_RECORD_FLOATS, dtype=torch.float32, device=self.device)
+            self.guards = [GradGuard(o.param_groups[0]["params"], self.clip_grad_norm, self.guard_buf[i])
+                           for i, o in enumerate([self.optG] + self.optD)]
+        guard_of = lambda i: self.guards[i] if self.guards is not None else None
+        self._stepG = LeanAdamStep(self.optG, self.ema, self.ema_decay, guard_of(0))
+        self._stepD = [LeanAdamStep(o, guard=guard_of(1 + i)) for i, o in enumerate(self.optD)]
         # stream-overlapped schedule of the eager step (see _step_overlapped); PDGN_OVERLAP=0 turns it off
         self.overlap = cap and os.environ.get("PDGN_OVERLAP", "1") == "1"
         self._side = None
@@ -397,6 +540,18 @@ class PDGNTrainer:
         self._defer_d = os.environ.get("PDGN_DEFER_D", "1") == "1"
         self._ema_from_parameters()
         self.sync_replicas()
+
+    GUARD_KEYS = ("G", "D1", "D2", "D3", "D4")
+
+    def guard_state(self):
+        """{network: {norm, coef, applied, skipped}} for G, D1..D4: norm and clip factor of each network's LAST gradient list, and
+        the running numbers of applied and skipped updates.  Synchronises the device.  Guard on only."""
+        if self.guards is None:
+            raise RuntimeError("guard_state(): this trainer has no gradient guard (grad_guard=False, clip_grad_norm=None)")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        host = self.guard_buf.cpu()
+        return {k: GradGuard.decode(host[i]) for i, k in enumerate(self.GUARD_KEYS)}
 
     @staticmethod
     def _flat_like(params):
@@ -1026,7 +1181,7 @@ class PDGNTrainer:
     LOSS_KEYS = ("d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss")
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-            on_epoch=None):
+            on_epoch=None, guard_max_skips=50, grad_norms=None):
         """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
         `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
         them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
@@ -1038,26 +1193,75 @@ class PDGNTrainer:
         warm-up iterations are real optimizer updates on that batch).  issue="eager": trainer-owned buffers and `step`.
         The losses stay on the device: every iteration stacks them and copies them, non-blocking, into one of two pinned host
         rows; the line of iteration n is written after iteration n + 1 has been issued, when that copy is long complete.
-        log: a callable taking the line, or a path (appended to); on_epoch: called with the epoch number after each epoch."""
+        log: a callable taking the line, or a path (appended to); on_epoch: called with the epoch number after each epoch.
+
+        With a gradient guard the five records travel with the losses, in the same pinned rows behind the
+        same events, every iteration (also without a log).  The log line stays the reference's; `grad_norms` (a path; default:
+        grad_norms.csv beside a log given as a path, else none) gets one row per iteration: epoch, iter, norm and coef of G, D1..D4,
+        and the total number of skipped updates so far.  After `guard_max_skips` consecutive iterations in which some one network
+        skipped its update, a checkpoint of the current epoch is written (checkpoint_dir given, rank 0) and GradGuardError raised:
+        the parameters are the last finite ones (the guard's counters are not part of a checkpoint).  Once a network is one skip
+        short of that, the line of an iteration is awaited right behind it instead of one iteration later, so that no further
+        iteration is issued."""
         import time
         if issue not in ("list", "eager"):
             raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
+        guarded = getattr(self, "guards", None) is not None
+        if guarded and int(guard_max_skips) < 1:
+            raise ValueError("guard_max_skips must be at least one, got %r" % (guard_max_skips,))
         sink, opened = log, None
         if isinstance(log, (str, bytes, os.PathLike)):
             opened = open(log, "a")
             sink = lambda line: (opened.write(line + "\n"), opened.flush())
         nb = feeder.batches_per_epoch
         cuda = self.device.type == "cuda"
-        host = torch.empty(2, len(self.LOSS_KEYS), dtype=torch.float32, pin_memory=cuda)
+        nl, nk = len(self.LOSS_KEYS), len(PDGNTrainer.GUARD_KEYS)
+        host = torch.empty(2, nl + (nk * GUARD_RECORD_FLOATS if guarded else 0), dtype=torch.float32, pin_memory=cuda)
         done = [torch.cuda.Event() for _ in range(2)] if cuda else None
         pending, n, start = None, 0, time.time()
+        norms_file = None
+        if guarded:
+            if grad_norms is None and isinstance(log, (str, bytes, os.PathLike)):
+                grad_norms = os.path.join(os.path.dirname(os.fspath(log)) or ".", "grad_norms.csv")
+            if grad_norms is not None and getattr(feeder, "rank", 0) == 0:
+                fresh = not os.path.exists(grad_norms) or os.path.getsize(grad_norms) == 0
+                norms_file = open(grad_norms, "a")
+                if fresh:
+                    norms_file.write(",".join(["epoch", "iter"] + ["%s_%s" % (k, f) for k in PDGNTrainer.GUARD_KEYS for f in ("norm", "coef")]
+                                              + ["skipped_total"]) + "\n")
+            skipped_before, run_of_skips = None, [0] * nk
 
         def flush():
             slot, ep, idx = pending
             if cuda:
                 done[slot].synchronize()
             dt = time.time() - start
-            sink(self.LOG_FORMAT % ((ep, idx + 1, nb, dt / 60, dt % 60) + tuple(host[slot].tolist())))
+            if sink is not None:
+                sink(self.LOG_FORMAT % ((ep, idx + 1, nb, dt / 60, dt % 60) + tuple(host[slot, :nl].tolist())))
+            if guarded:
+                guard_line(ep, idx, [GradGuard.decode(host[slot, nl + i * GUARD_RECORD_FLOATS:nl + (i + 1) * GUARD_RECORD_FLOATS]) for i in range(nk)])
+
+        def guard_line(ep, idx, recs):
+            nonlocal skipped_before
+            if norms_file is not None:
+                norms_file.write(",".join(["%d" % ep, "%d" % (idx + 1)] + ["%.9g" % r[f] for r in recs for f in ("norm", "coef")]
+                                          + ["%d" % sum(r["skipped"] for r in recs)]) + "\n")
+                norms_file.flush()
+            now = [r["skipped"] for r in recs]
+            if skipped_before is not None:                       # (the first line has nothing to compare with: capture_list's warm-up
+                for i in range(nk):                              #  iterations, an earlier fit, have counted too)
+                    run_of_skips[i] = run_of_skips[i] + 1 if now[i] != skipped_before[i] else 0
+            else:
+                for i in range(nk):
+                    run_of_skips[i] = 1 if recs[i]["applied"] + recs[i]["skipped"] > 0 and PDGNTrainer._last_skipped(recs[i]) else 0
+            skipped_before = now
+            worst = max(range(nk), key=lambda i: run_of_skips[i])
+            if run_of_skips[worst] >= int(guard_max_skips):
+                where = ""
+                if checkpoint_dir is not None and getattr(feeder, "rank", 0) == 0:
+                    where = "; checkpoint of the last finite parameters: " + self.save(checkpoint_dir, ep, category)[0]
+                raise GradGuardError("gradient guard: %s skipped %d consecutive updates (epoch %d, iteration %d): its gradients are "
+                                     "not finite%s" % (PDGNTrainer.GUARD_KEYS[worst], run_of_skips[worst], ep, idx + 1, where))
 
         try:
             if issue == "eager" or getattr(self, "_list", None) is None:
@@ -1072,15 +1276,19 @@ class PDGNTrainer:
                 for i in range(nb):
                     feeder.fill(epoch, i, reals, z1, z2)
                     out = self.step_list() if issue == "list" else self.step(reals, z1, z2)
-                    if sink is not None:
+                    if sink is not None or guarded:
                         slot = n & 1
-                        host[slot].copy_(torch.stack([out[k] for k in self.LOSS_KEYS]), non_blocking=True)
+                        row = torch.stack([out[k] for k in self.LOSS_KEYS])
+                        host[slot].copy_(torch.cat([row, self.guard_buf.view(-1)]) if guarded else row, non_blocking=True)
                         if cuda:
                             done[slot].record(torch.cuda.current_stream(self.device))
                         if pending is not None:
                             flush()
                         pending = (slot, epoch, i)
                         n += 1
+                        if guarded and max(run_of_skips) >= int(guard_max_skips) - 1:
+                            flush()                              # one skip short of the end: this iteration's line now, not behind the next
+                            pending = None
                 if checkpoint_dir is not None and epoch % snapshot == 0 and getattr(feeder, "rank", 0) == 0:
                     self.save(checkpoint_dir, epoch, category)
                 if on_epoch is not None:
@@ -1092,7 +1300,14 @@ class PDGNTrainer:
         finally:
             if opened is not None:
                 opened.close()
+            if norms_file is not None:
+                norms_file.close()
         return epochs
+
+    @staticmethod
+    def _last_skipped(rec):
+        """Whether the record's LAST gradient list was not finite (norm is Inf or NaN exactly then)."""
+        return not (rec["norm"] == rec["norm"] and abs(rec["norm"]) != float("inf"))
 
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()
