@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 31
+#define PDGN_ABI_VERSION 32
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -720,6 +720,44 @@ int pdgn_adam_ema_guard_multi(int ntensors, void *const *p, const void *const *g
                               const pdgn_guard_record *guard, pdgn_stream_t stream);
 int pdgn_ema_guard_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
                          const pdgn_guard_record *guard, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ learning-rate schedule
+ * The rate of an Adam launch as a function of Adam's own device-side step count: warm-up, decay and drops also where no host is in
+ * the loop (a replayed launch list re-issues `lr` as the double it was captured with), and with no state of its own -- a resumed
+ * run continues from the restored counter.  No reference counterpart: the reference's five optimizers keep lr 1e-4 throughout
+ * (models/PDGNet_v2.py:121-125).
+ *
+ * A schedule is a table of PDGN_LR_TABLE_DOUBLES fp64 words in device memory (8-byte aligned), a piecewise-linear factor f(t):
+ *   tab[0]                      n, the number of knots, 1 <= n <= PDGN_LR_MAX_KNOTS
+ *   tab[1 + 2i], tab[2 + 2i]    t_i, f_i for i < n: t_i finite, >= 0, strictly increasing; f_i finite, >= 0; the rest is not read
+ * With t the step count of THIS update (step[0] as the Adam kernels read it, after the increment; the t of the average's warm-up):
+ *   f(t) = f_0                  for t <= t_0
+ *   f(t) = f_{n-1}              for t >= t_{n-1}
+ *   f(t) = dadd(f_i, dmul(dsub(f_{i+1}, f_i), ddiv(dsub(t, t_i), dsub(t_{i+1}, t_i))))   otherwise, for the i with t_i <= t < t_{i+1},
+ *                               found by a scan from i = 0
+ *   lr_eff = dmul(lr, f(t))     and step_size = (float)(lr_eff / (double)bc1), the expression lr was in
+ * Every fp64 operation is rounded on its own (__dadd_rn and its kin), none contracted into an FMA, and there is no transcendental
+ * function: a numpy fp64 restatement gives the same bits; at t = t_i the factor is exactly f_i.  A malformed table on the device
+ * (n no integer in 1 .. 16; some t_{i+1} > t_i false for i + 1 < n, NaN included) gives f = f_0 = tab[2]; nothing past tab[2n] is
+ * read, and nothing past tab[2] when n is out of range.  The values are the host's to validate before it uploads them. */
+#define PDGN_LR_MAX_KNOTS 16
+#define PDGN_LR_TABLE_DOUBLES 33
+/* pdgn_adam_multi / _ema_multi / _guard_multi / _ema_guard_multi with a schedule: the same kernel text with one more switch, the
+ * table read with uniform loads and evaluated once per workgroup where step_size is formed.  e null: no average (ema_decay is
+ * not read); guard null: no guard -- the four combinations are four kernels, and with f == 1 their results are the bits of the
+ * entry point without a schedule.  A skipped update (guard, applied == 0) returns before anything is touched; t advances by
+ * `applied` only, so it does not advance the schedule either.  State touched: p, m, v (e); read: g, step, guard, sched.  Allocates
+ * nothing.  PDGN_ERR_INVALID: that entry point's cases, a null or misaligned (8 bytes) sched; checked before any launch. */
+int pdgn_adam_sched_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                          const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay, const float *step,
+                          const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream);
+/* The schedule for the update that is ABOUT to happen, by one thread of one launch on `stream`: t = fadd(step[0], guard ?
+ * guard->applied : 1.0f) -- the fp32 sum the counter update in front of the Adam launch forms -- out2[0] = f(t), out2[1] = lr_eff
+ * (fp64, 8-byte aligned), out_lr32[0] = (float)lr_eff, written with ordinary vector stores.  For the optimizer routes that go
+ * through torch's fused kernel (it takes the fp32 word as a tensor lr) and for tests.  State touched: out2, out_lr32; read: sched,
+ * step, guard (nullable).  PDGN_ERR_INVALID: a null or misaligned pointer (guard excepted), lr negative or NaN. */
+int pdgn_lr_eval(const double *sched, double lr, const float *step, const pdgn_guard_record *guard, double *out2, float *out_lr32,
+                 pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ deterministic mode
  * pdgn_set_deterministic: process-wide switch, like pdgn_gemm_set_mode.  -1 queries the current value; any other value

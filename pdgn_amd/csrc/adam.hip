@@ -39,6 +39,7 @@ struct AdamEmaArgs {               // the same table with the list of averages (
     int ntensors;
 };
 static_assert(sizeof(AdamArgs) + 48 <= 3584 && sizeof(AdamEmaArgs) + 56 <= 3584, "pointer tables: 3.5 KB of the 4 KB of kernel arguments");
+static_assert(sizeof(AdamArgs) + 56 <= 3584 && sizeof(AdamEmaArgs) + 64 <= 3584, "... with the schedule's pointer behind them");
 
 // ---- the generator's averaged copy (an exponential moving average of the parameters, Yazici et al. 2019), one expression for the
 // fused launch, the stand-alone launch and the host mirror of the tests: with t the step count of THIS update,
@@ -52,13 +53,38 @@ __device__ __forceinline__ float ema_one_minus_decay(double ema_decay, const flo
 }
 __device__ __forceinline__ void ema_one(float &e, float p, float omd) { e = __fadd_rn(e, __fmul_rn(omd, __fsub_rn(p, e))); }
 
+// ---- the learning-rate schedule: a piecewise-linear factor f(t) of the step count t of THIS update, from a table of
+// PDGN_LR_TABLE_DOUBLES fp64 words in device memory (include/pdgn_hip.h states the layout and these expressions; tests/lr_mirror.py
+// restates them in numpy and demands equal bits): tab[0] = n knots, tab[1 + 2i] = t_i, tab[2 + 2i] = f_i.
+//     f = f_0 for t <= t_0;  f = f_{n-1} for t >= t_{n-1};  else, with the first i (scanned from 0) for which t < t_{i+1}:
+//     f = dadd(f_i, dmul(dsub(f_{i+1}, f_i), ddiv(dsub(t, t_i), dsub(t_{i+1}, t_i))))      every operation rounded on its own
+// A malformed table (n no integer in 1 .. 16, some t_{i+1} <= t_i or NaN) gives f_0; no word past tab[2n] is ever read, and none
+// past tab[2] for an n out of range.  The index is uniform and the table read-only: the loads are scalar ones.
+__device__ __forceinline__ double lr_factor(const double *__restrict__ tab, double t) {
+    const double nd = tab[0], f0 = tab[2];
+    if (!(nd >= 1.0 && nd <= (double)PDGN_LR_MAX_KNOTS)) return f0;
+    const int n = (int)nd;
+    if ((double)n != nd) return f0;
+    int seg = -1;
+    for (int i = 0; i + 1 < n; ++i) {
+        if (!(tab[3 + 2 * i] > tab[1 + 2 * i])) return f0;
+        if (seg < 0 && t < tab[3 + 2 * i]) seg = i;
+    }
+    if (t <= tab[1]) return f0;
+    if (seg < 0) return tab[2 * n];                              // t >= t_{n-1}
+    const double ti = tab[1 + 2 * seg], fi = tab[2 + 2 * seg], tj = tab[3 + 2 * seg], fj = tab[4 + 2 * seg];
+    return __dadd_rn(fi, __dmul_rn(__dsub_rn(fj, fi), __ddiv_rn(__dsub_rn(t, ti), __dsub_rn(tj, ti))));
+}
+
 // One chunk of one tensor.  EMA = false is pdgn_adam_multi's kernel; EMA = true adds the average E to the same walk (one more load
 // in front of the stores, one more store behind them): the Adam arithmetic is this one text for both.  GUARD = true reads the
 // network's guard record first (written by pdgn_gradnorm_multi on the same stream): applied == 0 leaves before anything is touched,
-// otherwise the gradient that enters the arithmetic is fmul(g, coef), rounded on its own; g itself is never written.
-template <bool EMA, bool GUARD, class Args>
+// otherwise the gradient that enters the arithmetic is fmul(g, coef), rounded on its own; g itself is never written.  SCHED = true
+// multiplies lr by the schedule's factor at this update's t (lr_factor above), once per workgroup where step_size is formed.
+template <bool EMA, bool GUARD, bool SCHED = false, class Args>
 __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta1d, double beta2d, double eps, double ema_decay,
-                                           const float *__restrict__ step, const pdgn_guard_record *__restrict__ guard = nullptr) {
+                                           const float *__restrict__ step, const pdgn_guard_record *__restrict__ guard = nullptr,
+                                           const double *__restrict__ sched = nullptr) {
     __shared__ float sc[EMA ? 3 : 2];
     float coef = 1.f;
     if constexpr (GUARD) {
@@ -81,6 +107,7 @@ __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta
         // torch: the two bias corrections in fp64, handed to the arithmetic as floats; step_size = lr (double) / that float
         const double t = (double)step[0];
         const float bc1 = (float)(1.0 - pow(beta1d, t));
+        if constexpr (SCHED) lr = __dmul_rn(lr, lr_factor(sched, t));
         sc[0] = (float)(lr / (double)bc1);
         sc[1] = (float)sqrt(1.0 - pow(beta2d, t));
         if constexpr (EMA) sc[2] = ema_one_minus_decay(ema_decay, step);
@@ -146,6 +173,46 @@ __device__ __forceinline__ void adam_chunk(const Args &a, double lr, double beta
     }
 }
 
+// The four launches with a schedule (pdgn_adam_sched_multi).  Defined in front of the kernels they are variants of, as the guard's
+// are in front of ema_multi_kernel: tools/isa_diff.py compares a kernel with its trailing padding, which depends on what follows it.
+__global__ __launch_bounds__(ADAM_THREADS) void adam_sched_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
+                                                                        const float *__restrict__ step, const double *__restrict__ sched) {
+    adam_chunk<false, false, true>(a, lr, beta1d, beta2d, eps, 0.0, step, nullptr, sched);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_sched_multi_kernel(const AdamEmaArgs a, double lr, double beta1d, double beta2d,
+                                                                            double eps, double ema_decay, const float *__restrict__ step,
+                                                                            const double *__restrict__ sched) {
+    adam_chunk<true, false, true>(a, lr, beta1d, beta2d, eps, ema_decay, step, nullptr, sched);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_guard_sched_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d,
+                                                                              double eps, const float *__restrict__ step,
+                                                                              const pdgn_guard_record *__restrict__ guard,
+                                                                              const double *__restrict__ sched) {
+    adam_chunk<false, true, true>(a, lr, beta1d, beta2d, eps, 0.0, step, guard, sched);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_guard_sched_multi_kernel(const AdamEmaArgs a, double lr, double beta1d, double beta2d,
+                                                                                  double eps, double ema_decay, const float *__restrict__ step,
+                                                                                  const pdgn_guard_record *__restrict__ guard,
+                                                                                  const double *__restrict__ sched) {
+    adam_chunk<true, true, true>(a, lr, beta1d, beta2d, eps, ema_decay, step, guard, sched);
+}
+
+// f and lr_eff of the update that is ABOUT to happen, by one thread: t = fadd(step[0], guard ? guard->applied : 1) -- the fp32 sum the
+// caller's counter update forms -- out2 = {f, dmul(lr, f)} and out_lr32 = (float)out2[1]: what the routes through torch hand its
+// kernel as a tensor lr.
+__global__ void lr_eval_kernel(const double *__restrict__ sched, double lr, const float *__restrict__ step,
+                               const pdgn_guard_record *__restrict__ guard, double *__restrict__ out2, float *__restrict__ out_lr32) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double t = (double)__fadd_rn(step[0], guard ? guard->applied : 1.f);
+    const double f = lr_factor(sched, t), lr_eff = __dmul_rn(lr, f);
+    out2[0] = f;
+    out2[1] = lr_eff;
+    out_lr32[0] = (float)lr_eff;
+}
+
 __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const AdamArgs a, double lr, double beta1d, double beta2d, double eps,
                                                                   const float *__restrict__ step) {
     adam_chunk<false, false>(a, lr, beta1d, beta2d, eps, 0.0, step);
@@ -174,17 +241,19 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_ema_guard_multi_kernel(cons
 // optimisers (models/PDGNet_v2.py:121-125) for lists without weight decay, amsgrad or maximize.
 // (a guard record is read with dword loads: the address the guarded entry points refuse.  `guard` null = the unguarded kernel.)
 static bool guard_misplaced(const pdgn_guard_record *guard) { return ((uintptr_t)guard & 3) != 0; }
+// (a schedule is read with 8-byte loads.  `sched` null = the kernel without one.)
+static bool sched_misplaced(const double *sched) { return ((uintptr_t)sched & 7) != 0; }
 
 static int adam_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
                              double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
-                             pdgn_stream_t stream) {
+                             const double *sched, pdgn_stream_t stream) {
     if (ntensors < 1 || !p || !g || !m || !v || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
         !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.))
         return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
         if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 1 || (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3))
             return PDGN_ERR_INVALID;
-    if (guard_misplaced(guard)) return PDGN_ERR_INVALID;
+    if (guard_misplaced(guard) || sched_misplaced(sched)) return PDGN_ERR_INVALID;
     for (int t0 = 0; t0 < ntensors; t0 += ADAM_MAXT) {                      // every launch's chunk count is checked before the first launch
         long long chunks = 0;
         for (int i = t0; i < ntensors && i < t0 + ADAM_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
@@ -201,7 +270,13 @@ static int adam_multi_launch(int ntensors, void *const *p, const void *const *g,
             chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
         }
         for (int i = a.ntensors; i < ADAM_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        if (guard)
+        if (sched && guard)
+            hipLaunchKernelGGL(adam_guard_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
+                               beta2, eps, step, guard, sched);
+        else if (sched)
+            hipLaunchKernelGGL(adam_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2,
+                               eps, step, sched);
+        else if (guard)
             hipLaunchKernelGGL(adam_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2,
                                eps, step, guard);
         else
@@ -212,7 +287,7 @@ static int adam_multi_launch(int ntensors, void *const *p, const void *const *g,
 
 extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
                                double lr, double beta1, double beta2, double eps, const float *step, pdgn_stream_t stream) {
-    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, nullptr, stream);
+    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, nullptr, nullptr, stream);
 }
 
 // pdgn_adam_multi with the averages e (HOST array of device pointers) updated in the same launches, ceil(ntensors / 64) of them:
@@ -220,7 +295,7 @@ extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *
 // counterpart (the reference keeps no averaged generator).
 static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
                                  const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
-                                 const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
+                                 const float *step, const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream) {
     if (ntensors < 1 || !p || !g || !m || !v || !e || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
         !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || !(ema_decay >= 0. && ema_decay < 1.))
         return PDGN_ERR_INVALID;
@@ -228,7 +303,7 @@ static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const
         if (!p[i] || !g[i] || !m[i] || !v[i] || !e[i] || n[i] < 1 ||
             (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (uintptr_t)e[i]) & 3))
             return PDGN_ERR_INVALID;
-    if (guard_misplaced(guard)) return PDGN_ERR_INVALID;
+    if (guard_misplaced(guard) || sched_misplaced(sched)) return PDGN_ERR_INVALID;
     for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {                  // every launch's chunk count is checked before the first launch
         long long chunks = 0;
         for (int i = t0; i < ntensors && i < t0 + ADAM_EMA_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
@@ -246,7 +321,13 @@ static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const
             chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
         }
         for (int i = a.ntensors; i < ADAM_EMA_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = a.e[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        if (guard)
+        if (sched && guard)
+            hipLaunchKernelGGL(adam_ema_guard_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr,
+                               beta1, beta2, eps, ema_decay, step, guard, sched);
+        else if (sched)
+            hipLaunchKernelGGL(adam_ema_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
+                               beta2, eps, ema_decay, step, sched);
+        else if (guard)
             hipLaunchKernelGGL(adam_ema_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
                                beta2, eps, ema_decay, step, guard);
         else
@@ -259,7 +340,7 @@ static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const
 extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
                                    const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
                                    const float *step, pdgn_stream_t stream) {
-    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, nullptr, stream);
+    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, nullptr, nullptr, stream);
 }
 
 // The two launches above behind a gradient guard (pdgn_gradnorm_multi below, on the same stream in front of them): every workgroup
@@ -269,14 +350,36 @@ extern "C" int pdgn_adam_guard_multi(int ntensors, void *const *p, const void *c
                                      double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
                                      pdgn_stream_t stream) {
     if (!guard) return PDGN_ERR_INVALID;
-    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, stream);
+    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, nullptr, stream);
 }
 
 extern "C" int pdgn_adam_ema_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
                                          const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
                                          const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
     if (!guard) return PDGN_ERR_INVALID;
-    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, stream);
+    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, nullptr, stream);
+}
+
+// The four launches above with a learning-rate schedule (lr_factor at the top of this file): the rate in the arithmetic is
+// dmul(lr, f(t)) with t = step[0], everything else is the entry point that e and guard select -- e null: pdgn_adam_multi /
+// pdgn_adam_guard_multi (ema_decay is not read), else pdgn_adam_ema_multi / pdgn_adam_ema_guard_multi; guard null: unguarded.
+// sched (device, 8-byte aligned, PDGN_LR_TABLE_DOUBLES doubles): never null here.  No reference counterpart.
+extern "C" int pdgn_adam_sched_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                                     const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
+                                     const float *step, const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream) {
+    if (!sched) return PDGN_ERR_INVALID;
+    if (!e) return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, sched, stream);
+    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, sched, stream);
+}
+
+// out2[0..1] <- {f, lr_eff}, out_lr32[0] <- (float)lr_eff of the update about to happen (lr_eval_kernel above): one thread, on `stream`.
+extern "C" int pdgn_lr_eval(const double *sched, double lr, const float *step, const pdgn_guard_record *guard, double *out2,
+                            float *out_lr32, pdgn_stream_t stream) {
+    if (!sched || sched_misplaced(sched) || !(lr >= 0.) || !step || ((uintptr_t)step & 3) || guard_misplaced(guard) || !out2 ||
+        ((uintptr_t)out2 & 7) || !out_lr32 || ((uintptr_t)out_lr32 & 3))
+        return PDGN_ERR_INVALID;
+    hipLaunchKernelGGL(lr_eval_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sched, lr, step, guard, out2, out_lr32);
+    return pdgn_launch_status();
 }
 
 // ---- the same walk for a plain copy: dst[i] <- src[i] for a list of fp32 tensors (the pack of a network's fresh gradients into the

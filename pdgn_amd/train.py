@@ -8,7 +8,10 @@ the test split has, write nonormal_out.npy / out.npy and log.txt under <save_dir
 (models/PDGNet_v2.py:271-326).  --report_every N (train): every N epochs a preview sheet and a row of held-out metrics on the val
 split, under <checkpoint_dir>/<model_dir>/report (pdgn_amd/report.py).  --ema_decay D (train): keep an exponential moving average of
 the generator's parameters (decay D, e.g. 0.999), write it as <epoch>_<category>_G_ema.pth beside every checkpoint pair and report
-on it; --phase test --pretrain_model_G <epoch>_<category>_G_ema.pth evaluates it.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+on it; --phase test --pretrain_model_G <epoch>_<category>_G_ema.pth evaluates it.  --lr_g / --lr_d (train): base rates of the
+generator / the four discriminators instead of --learning_rate; --lr_schedule constant|linear|cosine|step with --lr_warmup_iters,
+--lr_final_factor, --lr_step_epochs, --lr_gamma: the rate as a function of Adam's step count over max_epoch x batches-per-epoch
+updates, evaluated on the device (pdgn_amd/schedule.py); lr.csv beside the log.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -61,17 +64,32 @@ def build_parser():
                    "value (implies --grad_guard)")
     p.add_argument("--guard_max_skips", type=int, default=argparse.SUPPRESS, help="stop, with a checkpoint, after this many consecutive "
                    "skipped updates of a network (default 50)")
+    p.add_argument("--lr_g", type=float, default=argparse.SUPPRESS, help="base learning rate of the generator (default: --learning_rate)")
+    p.add_argument("--lr_d", type=float, default=argparse.SUPPRESS, help="base learning rate of the four discriminators (default: --learning_rate)")
+    p.add_argument("--lr_schedule", choices=["constant", "linear", "cosine", "step"], default=argparse.SUPPRESS,
+                   help="learning-rate schedule over max_epoch x batches-per-epoch updates, evaluated on the device from Adam's step count")
+    p.add_argument("--lr_warmup_iters", type=int, default=argparse.SUPPRESS, help="updates of linear warm-up from 0 (default 0)")
+    p.add_argument("--lr_final_factor", type=float, default=argparse.SUPPRESS, help="linear / cosine: the factor reached at the last update (default 0)")
+    p.add_argument("--lr_step_epochs", type=int, default=argparse.SUPPRESS, help="step: epochs between drops")
+    p.add_argument("--lr_gamma", type=float, default=argparse.SUPPRESS, help="step: the factor of a drop (default 0.1)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay and the gradient guard's flags are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's and the learning-rate flags are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
     grad_guard = False
     clip_grad_norm = None
     guard_max_skips = 50
+    lr_g = None
+    lr_d = None
+    lr_schedule = None
+    lr_warmup_iters = 0
+    lr_final_factor = 0.0
+    lr_step_epochs = None
+    lr_gamma = 0.1
 
 
 def parse_args(argv=None):
@@ -99,7 +117,45 @@ def parse_args(argv=None):
         args.grad_guard = True
     if args.guard_max_skips < 1:
         p.error("--guard_max_skips must be at least one")
+    given = vars(args)
+    for flag in ("lr_g", "lr_d"):
+        rate = getattr(args, flag)
+        if rate is not None and not (rate >= 0.0 and rate != float("inf")):
+            p.error("--%s %r: a finite rate, not negative" % (flag, rate))
+    kind = args.lr_schedule
+    if kind is None:
+        for flag in ("lr_warmup_iters", "lr_final_factor", "lr_step_epochs", "lr_gamma"):
+            if flag in given:
+                p.error("--%s needs --lr_schedule" % flag)
+    else:
+        if args.lr_warmup_iters < 0:
+            p.error("--lr_warmup_iters must not be negative")
+        if kind not in ("linear", "cosine") and "lr_final_factor" in given:
+            p.error("--lr_final_factor goes with --lr_schedule linear or cosine, not %s" % kind)
+        if not (args.lr_final_factor >= 0.0 and args.lr_final_factor != float("inf")):
+            p.error("--lr_final_factor %r: finite and not negative" % args.lr_final_factor)
+        if kind != "step" and ("lr_step_epochs" in given or "lr_gamma" in given):
+            p.error("--lr_step_epochs and --lr_gamma go with --lr_schedule step, not %s" % kind)
+        if kind == "step":
+            if args.lr_step_epochs is None or args.lr_step_epochs < 1:
+                p.error("--lr_schedule step needs --lr_step_epochs of at least one")
+            if not (args.lr_gamma > 0.0 and args.lr_gamma != float("inf")):
+                p.error("--lr_gamma %r: a positive number" % args.lr_gamma)
+            drops = (args.max_epoch - 1) // args.lr_step_epochs  # (a drop every lr_step_epochs epochs, none at the end: whatever the batches per epoch)
+            if 1 + (args.lr_warmup_iters > 0) + 2 * drops > 16:
+                p.error("--lr_schedule step: %d drops in %d epochs do not fit into the schedule's 16 knots" % (drops, args.max_epoch))
     return args
+
+
+def schedule_knots(args, batches_per_epoch):
+    """The knot list of the command line's schedule over max_epoch x batches_per_epoch updates (None without --lr_schedule);
+    --lr_step_epochs is converted by the same factor, --lr_warmup_iters is in updates already."""
+    if args.lr_schedule is None:
+        return None
+    from .schedule import knots
+    nb = int(batches_per_epoch)
+    return knots(args.lr_schedule, args.max_epoch * nb, args.lr_warmup_iters, args.lr_final_factor,
+                 None if args.lr_step_epochs is None else args.lr_step_epochs * nb, args.lr_gamma)
 
 
 def logged_args(args):
@@ -143,7 +199,7 @@ def init_dist(device):
     return 0, 1, torch.device(device)
 
 
-def make_trainer(args, device):
+def make_trainer(args, device, batches_per_epoch=None):
     from .generator import PointGenerator
     from .trainer import PDGNTrainer
     base = args.num_point // 16
@@ -152,7 +208,9 @@ def make_trainer(args, device):
     return PDGNTrainer(device=device, lr=args.learning_rate, num_k=args.num_k, base_points=base, generator=gen,
                        ema_decay=args.ema_decay if args.phase == "train" else 0.0,
                        grad_guard=args.grad_guard and args.phase == "train",
-                       clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None)
+                       clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None,
+                       lr_g=args.lr_g if args.phase == "train" else None, lr_d=args.lr_d if args.phase == "train" else None,
+                       lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None)
 
 
 def _resume(args, trainer, ckpt):
@@ -175,7 +233,10 @@ def train(args):
     feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world)
     if feeder.N != n:
         raise SystemExit("--num_point %d but the clouds of %s have %d points" % (n, args.data_root, feeder.N))
-    trainer = make_trainer(args, device)
+    try:
+        trainer = make_trainer(args, device, feeder.batches_per_epoch)
+    except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
+        raise SystemExit(str(e))
     trainer.train()
     start = _resume(args, trainer, ckpt) or 1
     log = None
@@ -196,7 +257,8 @@ def train(args):
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
-                       grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None)
+                       grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
+                       lr_log=os.path.join(run_dir, "lr.csv"))
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()

@@ -16,6 +16,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib
+from . import schedule as _schedule
 from . import streams as _streams
 from .fused import clear_zero_colsum, flush_bn_counters, hold_bn_counters, release_zero_arena, reset_zero_arena
 from .generator import PointDiscriminator, PointGenerator
@@ -305,12 +306,28 @@ class LeanAdamStep:
     `torch._fused_adam_`) scale the gradients in place by `coef` beforehand -- the one case where the guard writes g -- and hand the
     flag to torch's kernel as `found_inf`, which makes it return early (and `optimizer.step()` take its increment back); the average
     behind them is pdgn_ema_guard_multi.  An optimizer that cannot take `found_inf` (not fused, not capturable) raises: no route
-    applies an unguarded update while the guard is on."""
+    applies an unguarded update while the guard is on.
 
-    def __init__(self, opt, ema=None, ema_decay=0.0, guard=None):
+    sched (a learning-rate table, schedule.table(): 33 fp64 words on the parameters' device; None: nothing below exists): the rate
+    of every update is lr * f(t), with lr the Python float of the group -- it stays the BASE rate -- and t the count of that update
+    (DESIGN.md section 7f).  The own kernel evaluates the table itself (pdgn_adam_sched_multi: no launch more).  The routes through
+    torch -- the first, ordinary `optimizer.step()`, the fall-backs, `PDGN_OWN_ADAM=0` / `torch._fused_adam_` -- run pdgn_lr_eval on the
+    same stream first and hand torch's fused, capturable kernel the resulting fp32 device scalar as a tensor `lr` (for
+    `optimizer.step()` it sits in the group for the duration of the call): on those routes the rate is lr * f(t) ROUNDED TO FP32.  An
+    optimizer that cannot take a tensor rate (not fused, not capturable, several groups) raises: no route applies the unscheduled
+    rate while a schedule is set.  The table is read, never replaced: overwrite it in place to change the schedule."""
+
+    def __init__(self, opt, ema=None, ema_decay=0.0, guard=None, sched=None):
         self.opt, self.lists, self._table = opt, None, None
         self.ema, self.ema_decay, self._ema_table = (list(ema) if ema else None), float(ema_decay), None
         self.guard = guard
+        self.sched = sched
+        if sched is not None:
+            if not (torch.is_tensor(sched) and sched.dtype == torch.float64 and sched.numel() == _schedule.TABLE_DOUBLES
+                    and sched.is_contiguous()):
+                raise ValueError("lr schedule: a contiguous torch.float64 tensor of %d words (schedule.table)" % _schedule.TABLE_DOUBLES)
+            self.lr_out = torch.zeros(2, dtype=torch.float64, device=sched.device)      # {f, lr_eff} of the last pdgn_lr_eval
+            self.lr32 = torch.zeros((), dtype=torch.float32, device=sched.device)       # lr_eff as torch's kernel takes it
 
     def reset(self):
         """The optimizer's state tensors were replaced (load_state_dict): rebuild the lists after the next ordinary step."""
@@ -324,8 +341,45 @@ class LeanAdamStep:
         if self.guard is not None:
             self._guarded_plain_step(measured)
             return
-        self.opt.step()
+        if self.sched is not None:
+            self._scheduled_opt_step()
+        else:
+            self.opt.step()
         self._ema_alone()
+
+    def _eval_lr(self, step=None):
+        """lr32 <- (float)(lr * f(t)) for the update about to happen, t = step + 1 (step + applied behind a guard, whose record is
+        complete by now): one one-thread launch on the current stream.  step: the optimizer's device-side counter (default: the
+        first parameter's; zero before the optimizer's first step has made one)."""
+        opt = self.opt
+        if len(opt.param_groups) != 1 or not all(g.get("fused") and g.get("capturable") for g in opt.param_groups):
+            raise _lib.PdgnHipError("a learning-rate schedule reaches torch's Adam as a tensor `lr`, which takes a fused, capturable "
+                                    "optimizer with one parameter group; the unscheduled rate is not an option")
+        g = opt.param_groups[0]
+        if isinstance(g["lr"], torch.Tensor):
+            raise _lib.PdgnHipError("a learning-rate schedule multiplies a Python float base rate; this group's lr is a tensor")
+        if step is None:
+            st = opt.state.get(g["params"][0])
+            step = st["step"] if st and "step" in st else torch.zeros(1, dtype=torch.float32, device=self.sched.device)
+        if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.float32 and step.device == self.sched.device):
+            raise _lib.PdgnHipError("a learning-rate schedule reads Adam's step count on the device: a capturable optimizer on the "
+                                    "table's device is required")
+        _lib.check(_lib.lib().pdgn_lr_eval(_lib.ptr(self.sched), float(g["lr"]), _lib.ptr(step),
+                                           _lib.ptr(self.guard.record) if self.guard is not None else None, _lib.ptr(self.lr_out),
+                                           _lib.ptr(self.lr32), _lib.stream_of(self.sched)), "pdgn_lr_eval")
+        return self.lr32
+
+    def _scheduled_opt_step(self):
+        """`optimizer.step()` at the scheduled rate: the fp32 device scalar sits in the group while torch runs, the float is back
+        afterwards (checkpoints and the lean step's invariants see the base rate)."""
+        g = self.opt.param_groups[0] if self.opt.param_groups else None
+        lr32 = self._eval_lr()
+        base = g["lr"]
+        g["lr"] = lr32
+        try:
+            self.opt.step()
+        finally:
+            g["lr"] = base
 
     def _guarded_plain_step(self, measured):
         opt, guard = self.opt, self.guard
@@ -342,7 +396,10 @@ class LeanAdamStep:
                 torch._foreach_mul_(grads, guard.coef)
         opt.grad_scale, opt.found_inf = None, guard.found_inf
         try:
-            opt.step()
+            if self.sched is not None:
+                self._scheduled_opt_step()
+            else:
+                opt.step()
         finally:
             opt.grad_scale = opt.found_inf = None
         self._ema_alone()
@@ -371,11 +428,12 @@ class LeanAdamStep:
 
     _OWN = os.environ.get("PDGN_OWN_ADAM", "1") == "1"           # A/B switch: 0 = torch._fused_adam_
 
-    def _own_adam(self, ps, grads, exp_avgs, exp_avg_sqs, steps, g):
+    def _own_adam(self, ps, grads, exp_avgs, exp_avg_sqs, steps, g, launch=True):
         """The whole list in ceil(n / 72) launches of csrc/adam.hip, one workgroup per 4096 elements (torch's fused kernel: 64 K-element
         chunks, five launches and 230 us for the generator's 12.7 M parameters at the end of every iteration).  The pointers travel in
         the kernel arguments: nothing to upload, and a recorded iteration re-issues them as they were.  False (torch's kernel runs)
-        for anything but contiguous fp32 CUDA tensors."""
+        for anything but contiguous fp32 CUDA tensors.  launch=False: the answer alone (a scheduled step has to know the route
+        before it advances the counters)."""
         if not self._OWN or not ps or not ps[0].is_cuda:
             return False
         n = len(ps)
@@ -386,10 +444,20 @@ class LeanAdamStep:
             tab = self._table = (n, _pointer_table(ps), _pointer_table(exp_avgs), _pointer_table(exp_avg_sqs), _count_table(ps))
         if any(t.dtype != torch.float32 or not t.is_contiguous() for t in grads):
             return False
+        et = None
         if self.ema is not None:                                 # the average rides in the same launches
             et = self._ema_table
             if et is None or et[0] != n or et[2][0] != tab[1][0] or et[2][n - 1] != tab[1][n - 1]:
                 return False                                     # (not validated yet, or other parameters: _ema_alone checks and raises)
+        if not launch:
+            return True
+        if self.sched is not None:                               # one entry point for the four scheduled kernels
+            _lib.check(_lib.lib().pdgn_adam_sched_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], et[1] if et is not None else None,
+                                                        tab[4], g["lr"], g["betas"][0], g["betas"][1], g["eps"], self.ema_decay,
+                                                        _lib.ptr(steps[0]), _lib.ptr(self.guard.record) if self.guard is not None else None,
+                                                        _lib.ptr(self.sched), _lib.stream_of(ps[0])), "pdgn_adam_sched_multi")
+            return True
+        if self.ema is not None:
             if self.guard is not None:
                 _lib.check(_lib.lib().pdgn_adam_ema_guard_multi(n, tab[1], _pointer_table(grads), tab[2], tab[3], et[1], tab[4], g["lr"],
                                                                 g["betas"][0], g["betas"][1], g["eps"], self.ema_decay, _lib.ptr(steps[0]),
@@ -441,12 +509,15 @@ class LeanAdamStep:
         if self.guard is not None:
             self._guarded_lean_step(ps, grads, exp_avgs, exp_avg_sqs, steps, g)
             return
+        lr = g["lr"]
+        if self.sched is not None and not self._own_adam(ps, grads, exp_avgs, exp_avg_sqs, steps, g, launch=False):
+            lr = self._eval_lr(steps[0])                         # torch's kernel: the rate as a device scalar, from the counter BEFORE its increment
         try:
             with torch.no_grad():
                 torch._foreach_add_(steps, 1)
                 if self._own_adam(ps, grads, exp_avgs, exp_avg_sqs, steps, g):
                     return
-                torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=g["lr"], beta1=g["betas"][0],
+                torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=lr, beta1=g["betas"][0],
                                    beta2=g["betas"][1], weight_decay=0.0, eps=g["eps"], maximize=False, grad_scale=None,
                                    found_inf=None)
                 self._ema_alone()
@@ -461,6 +532,9 @@ class LeanAdamStep:
         guard = self.guard
         guard.measure(grads)
         scaled = False
+        lr = g["lr"]
+        if self.sched is not None and not self._own_adam(ps, grads, exp_avgs, exp_avg_sqs, steps, g, launch=False):
+            lr = self._eval_lr(steps[0])                         # (behind the norm launches: t = step + applied)
         try:
             with torch.no_grad():
                 # (the list form, as torch's own capturable optimizers take `found_inf` back: `_foreach_add_(list, Tensor)` reads its
@@ -470,7 +544,7 @@ class LeanAdamStep:
                     return
                 torch._foreach_mul_(grads, guard.coef)
                 scaled = True
-                torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=g["lr"], beta1=g["betas"][0],
+                torch._fused_adam_(ps, grads, exp_avgs, exp_avg_sqs, [], steps, amsgrad=False, lr=lr, beta1=g["betas"][0],
                                    beta2=g["betas"][1], weight_decay=0.0, eps=g["eps"], maximize=False, grad_scale=None,
                                    found_inf=guard.found_inf)
                 self._ema_alone()
@@ -487,10 +561,18 @@ class PDGNTrainer:
 
     ema_decay > 0 keeps an exponential moving average of the generator's parameters (`ema`: one view per parameter of the flat
     `ema_buf`), updated by the generator's optimizer step itself (LeanAdamStep); `averaged_generator()`
-    puts it into the generator for a while, `save` writes it as `<epoch>_<category>_G_ema.pth`.  0: nothing of this exists."""
+    puts it into the generator for a while, `save` writes it as `<epoch>_<category>_G_ema.pth`.  0: nothing of this exists.
+
+    lr_g / lr_d: the base rate of the generator's optimizer / of the four discriminators' (None: `lr`).  lr_schedule: a knot list
+    [(t, factor), ...] (schedule.knots / schedule.validate) or None.  With one, the trainer owns ONE device table (`lr_table`, 33
+    fp64 words) that all five optimizers' launches evaluate at their own step count: rate = base * f(t) (DESIGN.md section 7f);
+    `param_groups[..]["lr"]` stays the Python float base rate, so checkpoints are what they were.  `set_lr_schedule` overwrites the
+    table in place (a captured launch list follows it with no recapture), `lr_state` reads the current rates.  With none of the
+    three nothing of this exists: no buffer, no launch, the same kernels and the same list."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
-                 discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None):
+                 discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
+                 lr_g=None, lr_d=None, lr_schedule=None):
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
@@ -498,6 +580,12 @@ class PDGNTrainer:
             raise ValueError("clip_grad_norm must be positive (or None), got %r" % (clip_grad_norm,))
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
         self.grad_guard = bool(grad_guard) or self.clip_grad_norm is not None
+        for name, rate in (("lr", lr), ("lr_g", lr_g), ("lr_d", lr_d)):
+            if rate is not None and not float(rate) >= 0.0:
+                raise ValueError("%s must not be negative, got %r" % (name, rate))
+        self.per_network_lr = lr_g is not None or lr_d is not None
+        lr_g, lr_d = float(lr if lr_g is None else lr_g), float(lr if lr_d is None else lr_d)
+        knots = None if lr_schedule is None else _schedule.validate(lr_schedule)     # (raises before anything is allocated)
         self.device = torch.device(device)
         self.G = (generator or PointGenerator(num_k=num_k, base_points=base_points)).to(self.device)
         self.D = [d.to(self.device) for d in
@@ -513,8 +601,10 @@ class PDGNTrainer:
             self.gradG.arm_early()
         self.gradD = [FlatGrads(d.parameters()) for d in self.D]
         cap = self.device.type == "cuda"                     # device-side step counter: graph-capturable
-        adam = lambda m: torch.optim.Adam(m.parameters(), lr=lr, betas=(0.5, 0.999), capturable=cap, fused=cap and os.environ.get("PDGN_FUSED_ADAM", "1") == "1")
-        self.optG, self.optD = adam(self.G), [adam(d) for d in self.D]
+        adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr, betas=(0.5, 0.999), capturable=cap, fused=cap and os.environ.get("PDGN_FUSED_ADAM", "1") == "1")
+        self.optG, self.optD = adam(self.G, lr_g if self.per_network_lr else lr), [adam(d, lr_d if self.per_network_lr else lr) for d in self.D]
+        # one table for the five optimizers: its address is in every scheduled launch, its contents are set_lr_schedule's to change
+        self.lr_table = None if knots is None else _schedule.table(knots, self.device)
         self.ema_buf = self.ema = self._ema_spare = None
         if self.ema_decay > 0:
             # one flat buffer, every average on a 16-byte boundary of it (the kernels' float4 path), in the optimizer's order
@@ -527,8 +617,8 @@ class PDGNTrainer:
             self.guards = [GradGuard(o.param_groups[0]["params"], self.clip_grad_norm, self.guard_buf[i])
                            for i, o in enumerate([self.optG] + self.optD)]
         guard_of = lambda i: self.guards[i] if self.guards is not None else None
-        self._stepG = LeanAdamStep(self.optG, self.ema, self.ema_decay, guard_of(0))
-        self._stepD = [LeanAdamStep(o, guard=guard_of(1 + i)) for i, o in enumerate(self.optD)]
+        self._stepG = LeanAdamStep(self.optG, self.ema, self.ema_decay, guard_of(0), self.lr_table)
+        self._stepD = [LeanAdamStep(o, guard=guard_of(1 + i), sched=self.lr_table) for i, o in enumerate(self.optD)]
         # stream-overlapped schedule of the eager step (see _step_overlapped); PDGN_OVERLAP=0 turns it off
         self.overlap = cap and os.environ.get("PDGN_OVERLAP", "1") == "1"
         self._side = None
@@ -552,6 +642,33 @@ class PDGNTrainer:
             torch.cuda.synchronize(self.device)
         host = self.guard_buf.cpu()
         return {k: GradGuard.decode(host[i]) for i, k in enumerate(self.GUARD_KEYS)}
+
+    def set_lr_schedule(self, knots):
+        """Replace the schedule: the knots are validated and written INTO the trainer's table -- the same tensor at the same
+        address, which the launch list has baked in: the next `step_list()` (or eager step) runs on the new schedule, with no
+        recapture.  Raises on a trainer built without `lr_schedule` (it has no table, and its launches read none)."""
+        if self.lr_table is None:
+            raise RuntimeError("set_lr_schedule(): this trainer was built without an lr_schedule; build it with one (e.g. [(0, 1.0)])")
+        fresh = _schedule.table(knots, "cpu")                    # validates; raises before the table is touched
+        with torch.no_grad():
+            self.lr_table.copy_(fresh)
+
+    def lr_state(self):
+        """{network: {step, factor, lr}} for G, D1..D4: the count of the network's last applied update, the schedule's factor at
+        that count (1.0 without a schedule) and the rate that update ran at, base * factor in fp64 -- the host evaluation
+        (schedule.factor) of the table as it is on the device.  Before a network's first update: step 0 and the schedule at 0.
+        Synchronises the device."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        tab = None if self.lr_table is None else self.lr_table.cpu()
+        out = {}
+        for key, opt in zip(self.GUARD_KEYS, [self.optG] + self.optD):
+            g = opt.param_groups[0]
+            st = opt.state.get(g["params"][0])
+            step = float(st["step"]) if st and "step" in st else 0.0
+            f = 1.0 if tab is None else _schedule.factor(tab, step)
+            out[key] = {"step": int(step), "factor": f, "lr": float(g["lr"]) * f}
+        return out
 
     @staticmethod
     def _flat_like(params):
@@ -628,6 +745,8 @@ class PDGNTrainer:
                             dist.broadcast(v, src)
             if self.ema_buf is not None:
                 dist.broadcast(self.ema_buf, src)
+            if self.lr_table is not None:
+                dist.broadcast(self.lr_table, src)
 
     def train(self):
         self.G.train()
@@ -1181,7 +1300,7 @@ class PDGNTrainer:
     LOSS_KEYS = ("d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss")
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-            on_epoch=None, guard_max_skips=50, grad_norms=None):
+            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None):
         """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
         `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
         them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
@@ -1202,7 +1321,11 @@ class PDGNTrainer:
         skipped its update, a checkpoint of the current epoch is written (checkpoint_dir given, rank 0) and GradGuardError raised:
         the parameters are the last finite ones (the guard's counters are not part of a checkpoint).  Once a network is one skip
         short of that, the line of an iteration is awaited right behind it instead of one iteration later, so that no further
-        iteration is issued."""
+        iteration is issued.
+
+        With a learning-rate schedule or per-network rates, `lr_log` (a path; default: lr.csv beside a log
+        given as a path, else none) gets one row -- epoch, step_G, lr_G, lr_D1 .. lr_D4, from `lr_state()` -- wherever a checkpoint is
+        written or `on_epoch` is called: points at which the host waits for the device anyway.  Rank 0 only; without either, no file."""
         import time
         if issue not in ("list", "eager"):
             raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
@@ -1230,6 +1353,24 @@ class PDGNTrainer:
                     norms_file.write(",".join(["epoch", "iter"] + ["%s_%s" % (k, f) for k in PDGNTrainer.GUARD_KEYS for f in ("norm", "coef")]
                                               + ["skipped_total"]) + "\n")
             skipped_before, run_of_skips = None, [0] * nk
+        rates_file, rates_epoch = None, None
+        if getattr(self, "lr_table", None) is not None or getattr(self, "per_network_lr", False):
+            if lr_log is None and isinstance(log, (str, bytes, os.PathLike)):
+                lr_log = os.path.join(os.path.dirname(os.fspath(log)) or ".", "lr.csv")
+            if lr_log is not None and getattr(feeder, "rank", 0) == 0:
+                fresh = not os.path.exists(lr_log) or os.path.getsize(lr_log) == 0
+                rates_file = open(lr_log, "a")
+                if fresh:
+                    rates_file.write(",".join(["epoch", "step_G"] + ["lr_%s" % k for k in PDGNTrainer.GUARD_KEYS]) + "\n")
+
+        def rates_line(ep):
+            nonlocal rates_epoch
+            if rates_file is None or rates_epoch == ep:          # (the last epoch's checkpoint may be written twice: one row)
+                return
+            rates_epoch = ep
+            state = self.lr_state()
+            rates_file.write(",".join(["%d" % ep, "%d" % state["G"]["step"]] + ["%.17g" % state[k]["lr"] for k in PDGNTrainer.GUARD_KEYS]) + "\n")
+            rates_file.flush()
 
         def flush():
             slot, ep, idx = pending
@@ -1291,17 +1432,22 @@ class PDGNTrainer:
                             pending = None
                 if checkpoint_dir is not None and epoch % snapshot == 0 and getattr(feeder, "rank", 0) == 0:
                     self.save(checkpoint_dir, epoch, category)
+                    rates_line(epoch)
                 if on_epoch is not None:
                     on_epoch(epoch)
+                    rates_line(epoch)
             if pending is not None:
                 flush()
             if checkpoint_dir is not None and getattr(feeder, "rank", 0) == 0:
                 self.save(checkpoint_dir, epochs, category)           # (:268: always, whatever the snapshot period)
+                rates_line(epochs)
         finally:
             if opened is not None:
                 opened.close()
             if norms_file is not None:
                 norms_file.close()
+            if rates_file is not None:
+                rates_file.close()
         return epochs
 
     @staticmethod
