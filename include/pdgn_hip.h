@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 32
+#define PDGN_ABI_VERSION 33
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -809,6 +809,76 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
 int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
                     unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2, float *p3,
                     float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ discriminator augmentation
+ * A fresh random similarity transform plus jitter for every cloud in front of every discriminator call (DiffAugment, Zhao et al.
+ * 2020 / ADA, Karras et al. 2020, for point clouds), differentiable, drawn on the device.  No reference counterpart
+ * (utils/provider.py's augmentation is host code of another training loop and is not ported).
+ *
+ *   rows[b*N + n] = A_b x[b, :, n] + t_b + jitter,      A_b = s R F
+ *   F       negates coordinate flip_axis;
+ *   R       rotates about up_axis by theta = rot_max * v:  with (ia, ib) = (up + 1, up + 2) mod 3,
+ *           R[ia][ia] = R[ib][ib] = cos, R[ia][ib] = -sin, R[ib][ia] = sin, R[up][up] = 1;
+ *   s       = exp(log_scale_max * v): log-uniform in [1 / scale_max, scale_max);
+ *   t_i     = trans_max * v_i;
+ *   jitter  ~ N(0, sigma^2) per point and coordinate;
+ *   v       = ((word >> 8) - 2^23) * 2^-23 in [-1, 1), exact in fp32.
+ * Each of the five components is enabled per sample iff (its word >> 8) < its threshold, an integer in [0, 2^24]: 0 is never,
+ * 2^24 always, round(p 2^24) probability p.  A disabled component is exactly the identity (cos = 1, sin = 0, s = 1, t = 0, no
+ * jitter added).  Arithmetic, every operation rounded on its own:
+ *   A[i][j]    = fmul(s, j == flip_axis && flipped ? -R[i][j] : R[i][j])
+ *   rows[.][i] = fadd(fadd(fadd(fmul(A[i][0], x0), fmul(A[i][1], x1)), fmul(A[i][2], x2)), t_i)   (+ jitter_i by one more fadd when enabled)
+ *   dx[b,j,n]  = fadd(fadd(fmul(A[0][j], d0), fmul(A[1][j], d1)), fmul(A[2][j], d2)),   d = d_rows[b*N + n]
+ * so that an fp32 host evaluation from affine_out reproduces rows (sigma = 0) and dx bit for bit.
+ *
+ * The parameters are a table in device memory (64 bytes, 4-byte aligned) that the launches read: its address is what a captured
+ * launch bakes in, its contents are the host's to overwrite in place (and to validate: the kernels take what they find). */
+typedef struct pdgn_aug_table {
+    unsigned thr_flip, thr_rot, thr_scale, thr_trans, thr_jitter; /* enable thresholds, each in [0, 2^24] */
+    int flip_axis, up_axis;                                       /* 0 .. 2 */
+    float rot_max;                                                /* radians */
+    float log_scale_max;                                          /* ln(scale_max) >= 0 */
+    float trans_max;
+    float sigma;
+    unsigned reserved[5];
+} pdgn_aug_table;
+/* Randomness: Philox4x32-10 with the feeder's layout (pdgn_feed_batch above: the same routine, csrc/philox.h):
+ *   key     = (seed low 32, seed high 32)
+ *   counter = (group, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8),    t = clock[0] - 1
+ *   tag     = PDGN_AUG_TAG_BASE + 3 * network + role: network 0 .. 3 = D1 .. D4; role 0 = real, 1 = fake (the generated cloud of the
+ *             discriminator's update), 2 = gen (the generator's own pass through the discriminator): 16 .. 27, disjoint from the
+ *             feeder's tags 0 .. 5 -- under one seed all twelve call sites of an iteration draw independently of each other and of the feed
+ *   group 0      words 0 .. 3: flip, rotation, scale, translation enabled?
+ *   group 1      word 0: jitter enabled?  word 1: v of theta, word 2: v of s
+ *   group 2      words 0 .. 2: v of t_x, t_y, t_z
+ *   group 4 + n  point n's jitter: Box-Muller pairs (words 0, 1) -> x, y and (words 2, 3) -> z, unused; pdgn_feed_batch's formula
+ * The CLOCK is a 64-bit word in device memory (8-byte aligned) that the kernels read themselves -- it is not a launch argument, so
+ * a replayed launch list draws afresh every time.  It counts the iterations BEGUN: pdgn_augment_tick opens an iteration, and every
+ * launch of that iteration draws at t = clock - 1 (the first iteration after clock = c draws at t = c).  With the GLOBAL row
+ * (row0 = rank * B), W ranks at batch B draw what one rank draws at batch B * W.
+ *
+ * pdgn_augment_rows_fwd: x (B,3,N) -> rows (B*N,3); replaces the copy kernel of PointDiscriminator.forward's
+ * `x.transpose(1, 2).reshape(B * N, 3)` (torch; the reference's Conv1d reads (B,3,N) directly, models/PDGNet_v2.py:886-1014).
+ * x_point_major != 0: x is stored (B,N,3) -- a (B,3,N) view of point-major rows, which is what the generator hands out
+ * (torch's reshape is a view then, and this launch replaces nothing: it is one the feature adds).  dx_point_major likewise for dx.
+ * affine_out (may be NULL): (B,12), per sample A row-major then t, exactly the values used.  One thread writes four points'
+ * rows (16-byte loads and stores where N % 4 == 0 and both bases are 16-byte aligned, element-wise otherwise).
+ * pdgn_augment_rows_bwd: d_rows (B*N,3) -> dx (B,3,N) = A^T d_rows; replaces that copy's adjoint (torch's copy kernel in the
+ * backward pass).  It re-derives A from the same counter words: nothing but the clock word itself links the two launches, which
+ * must therefore run in the same iteration (no tick between them).  Translation and jitter have zero / identity adjoints.
+ * pdgn_augment_tick: clock[0] += 1 by one thread of one launch on `stream` (an ordinary vector store); replaces nothing -- the
+ * one launch per iteration the feature adds.
+ * State touched: rows / dx / affine_out / clock; read: x / d_rows, table, clock.  Allocates nothing.
+ * PDGN_ERR_INVALID: B outside [1, 65535], N < 1 or 3 N >= 2^31, a null x / rows / table / clock, a pointer not 4-byte (clock:
+ * 8-byte) aligned, row0 < 0 or row0 + B > 2^32, a tag outside [PDGN_AUG_TAG_BASE, PDGN_AUG_TAG_BASE + PDGN_AUG_SITES); all
+ * checked on the host before anything is launched. */
+#define PDGN_AUG_TAG_BASE 16
+#define PDGN_AUG_SITES 12
+int pdgn_augment_rows_fwd(int B, int N, const float *x, int x_point_major, float *rows, float *affine_out, const pdgn_aug_table *table,
+                          const unsigned long long *clock, unsigned long long seed, long long row0, int tag, pdgn_stream_t stream);
+int pdgn_augment_rows_bwd(int B, int N, const float *d_rows, float *dx, int dx_point_major, const pdgn_aug_table *table,
+                          const unsigned long long *clock, unsigned long long seed, long long row0, int tag, pdgn_stream_t stream);
+int pdgn_augment_tick(unsigned long long *clock, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ preview sheets
  * A contact sheet of point clouds as ONE 8-bit grey image (what pdgn_amd/report.py writes at a snapshot): `rows` samples down,

@@ -240,9 +240,11 @@ class PointDiscriminator(nn.Module):
         mlp.append(nn.Linear(cin, 1))
         self.mlp = nn.Sequential(*mlp)
 
-    def forward(self, x):
+    def forward(self, x, aug=None):
+        """aug: None, or a call site of the discriminator augmentation (augment.Augment.at(network, role)): the rows are then the
+        randomly transformed cloud, written by the kernel that takes the place of the transpose copy (csrc/augment.hip)."""
         B, _, N = x.shape
-        h = x.transpose(1, 2).reshape(B * N, 3)
+        h = x.transpose(1, 2).reshape(B * N, 3) if aug is None else aug.rows(x)
         last = len(self.fc1) - 3
         for i in range(0, last, 3):                             # Conv1d(k=1) + BatchNorm1d + LeakyReLU
             # the conv bias is folded into the BatchNorm (pre_bias): the GEMM runs without a bias epilogue

@@ -11,7 +11,10 @@ the generator's parameters (decay D, e.g. 0.999), write it as <epoch>_<category>
 on it; --phase test --pretrain_model_G <epoch>_<category>_G_ema.pth evaluates it.  --lr_g / --lr_d (train): base rates of the
 generator / the four discriminators instead of --learning_rate; --lr_schedule constant|linear|cosine|step with --lr_warmup_iters,
 --lr_final_factor, --lr_step_epochs, --lr_gamma: the rate as a function of Adam's step count over max_epoch x batches-per-epoch
-updates, evaluated on the device (pdgn_amd/schedule.py); lr.csv beside the log.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+updates, evaluated on the device (pdgn_amd/schedule.py); lr.csv beside the log.  --d_augment P (train): every cloud a discriminator
+sees goes through a random similarity transform drawn on the device, each component enabled per sample with probability P
+(pdgn_amd/augment.py); --aug_rotate DEG (default 180, about the y axis), --aug_scale S (1.25: log-uniform in [1/S, S]), --aug_flip [0|1]
+(1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -72,11 +75,18 @@ def build_parser():
     p.add_argument("--lr_final_factor", type=float, default=argparse.SUPPRESS, help="linear / cosine: the factor reached at the last update (default 0)")
     p.add_argument("--lr_step_epochs", type=int, default=argparse.SUPPRESS, help="step: epochs between drops")
     p.add_argument("--lr_gamma", type=float, default=argparse.SUPPRESS, help="step: the factor of a drop (default 0.1)")
+    p.add_argument("--d_augment", type=float, default=argparse.SUPPRESS, metavar="P", help="discriminator augmentation: a random flip / rotation / "
+                   "scale / translation (/ jitter) of every cloud in front of every discriminator call, each enabled per sample with probability P")
+    p.add_argument("--aug_rotate", type=float, default=argparse.SUPPRESS, metavar="DEG", help="largest rotation about the up (y) axis, degrees (default 180)")
+    p.add_argument("--aug_scale", type=float, default=argparse.SUPPRESS, metavar="S", help="isotropic scale, log-uniform in [1/S, S] (default 1.25)")
+    p.add_argument("--aug_flip", type=int, choices=[0, 1], nargs="?", const=1, default=argparse.SUPPRESS, help="mirror the x coordinate (default 1; 0: off)")
+    p.add_argument("--aug_translate", type=float, default=argparse.SUPPRESS, metavar="T", help="translation, uniform in [-T, T] per coordinate (default 0.1)")
+    p.add_argument("--aug_jitter", type=float, default=argparse.SUPPRESS, metavar="SIGMA", help="per-point Gaussian jitter (default 0: none)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's and the learning-rate flags are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate and the augmentation flags are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -90,6 +100,12 @@ class Args(argparse.Namespace):
     lr_final_factor = 0.0
     lr_step_epochs = None
     lr_gamma = 0.1
+    d_augment = None                                             # (the ranges' defaults are augment.DEFAULTS: one place)
+    aug_rotate = None
+    aug_scale = None
+    aug_flip = None
+    aug_translate = None
+    aug_jitter = None
 
 
 def parse_args(argv=None):
@@ -144,7 +160,30 @@ def parse_args(argv=None):
             drops = (args.max_epoch - 1) // args.lr_step_epochs  # (a drop every lr_step_epochs epochs, none at the end: whatever the batches per epoch)
             if 1 + (args.lr_warmup_iters > 0) + 2 * drops > 16:
                 p.error("--lr_schedule step: %d drops in %d epochs do not fit into the schedule's 16 knots" % (drops, args.max_epoch))
+    if args.d_augment is None:
+        for flag in ("aug_rotate", "aug_scale", "aug_flip", "aug_translate", "aug_jitter"):
+            if flag in given:
+                p.error("--%s needs --d_augment" % flag)
+    else:
+        from .augment import validate
+        try:
+            validate(**augment_kwargs(args))
+        except ValueError as e:
+            p.error("--d_augment: %s" % e)
     return args
+
+
+def augment_kwargs(args):
+    """augment.Augment's parameters from the command line (None without --d_augment): augment.DEFAULTS where a flag was not given."""
+    if args.d_augment is None:
+        return None
+    from .augment import DEFAULTS
+    kw = dict(DEFAULTS, p=args.d_augment)
+    for flag, name in (("aug_rotate", "rot_max_deg"), ("aug_scale", "scale_max"), ("aug_flip", "flip"), ("aug_translate", "trans_max"),
+                       ("aug_jitter", "jitter_sigma")):
+        if getattr(args, flag) is not None:
+            kw[name] = bool(getattr(args, flag)) if name == "flip" else getattr(args, flag)
+    return kw
 
 
 def schedule_knots(args, batches_per_epoch):
@@ -210,7 +249,13 @@ def make_trainer(args, device, batches_per_epoch=None):
                        grad_guard=args.grad_guard and args.phase == "train",
                        clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None,
                        lr_g=args.lr_g if args.phase == "train" else None, lr_d=args.lr_d if args.phase == "train" else None,
-                       lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None)
+                       lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None,
+                       augment=_augment_arg(args) if args.phase == "train" else None)
+
+
+def _augment_arg(args):
+    kw = augment_kwargs(args)
+    return None if kw is None else dict(kw, seed=args.seed)
 
 
 def _resume(args, trainer, ckpt):

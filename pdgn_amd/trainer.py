@@ -568,11 +568,17 @@ class PDGNTrainer:
     fp64 words) that all five optimizers' launches evaluate at their own step count: rate = base * f(t) (DESIGN.md section 7f);
     `param_groups[..]["lr"]` stays the Python float base rate, so checkpoints are what they were.  `set_lr_schedule` overwrites the
     table in place (a captured launch list follows it with no recapture), `lr_state` reads the current rates.  With none of the
-    three nothing of this exists: no buffer, no launch, the same kernels and the same list."""
+    three nothing of this exists: no buffer, no launch, the same kernels and the same list.
+
+    augment: None, an augment.Augment, or a dict of its arguments.  With one, every cloud a discriminator sees -- all twelve calls of
+    an iteration -- goes through a random similarity transform drawn on the device: `aug` owns the parameter
+    table, the clock and the optional record buffer; the iteration opens with ONE extra launch, the clock's tick; `set_augment`
+    overwrites the table in place, `aug_state` reads it back.  The shape-preserving loss sees the un-augmented clouds.  None: `aug`
+    is None, no buffer, no launch, and the discriminators' forward is the code it was."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
                  discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
-                 lr_g=None, lr_d=None, lr_schedule=None):
+                 lr_g=None, lr_d=None, lr_schedule=None, augment=None):
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
@@ -587,6 +593,16 @@ class PDGNTrainer:
         lr_g, lr_d = float(lr if lr_g is None else lr_g), float(lr if lr_d is None else lr_d)
         knots = None if lr_schedule is None else _schedule.validate(lr_schedule)     # (raises before anything is allocated)
         self.device = torch.device(device)
+        self.aug = None
+        if augment is not None:
+            from . import augment as _augment
+            if isinstance(augment, dict):
+                # (under data parallelism every rank draws for its own global rows: rank * B + b)
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                augment = _augment.Augment(**dict({"rank": rank, "device": self.device}, **augment))      # (validates; raises before allocating)
+            elif not isinstance(augment, _augment.Augment):
+                raise TypeError("augment: None, an augment.Augment or a dict of its arguments, got %r" % (type(augment),))
+            self.aug = augment
         self.G = (generator or PointGenerator(num_k=num_k, base_points=base_points)).to(self.device)
         self.D = [d.to(self.device) for d in
                   (discriminators or [PointDiscriminator(i, (2 * base_points) << (i - 1)) for i in (1, 2, 3, 4)])]
@@ -652,6 +668,23 @@ class PDGNTrainer:
         fresh = _schedule.table(knots, "cpu")                    # validates; raises before the table is touched
         with torch.no_grad():
             self.lr_table.copy_(fresh)
+
+    def set_augment(self, **changes):
+        """Change augmentation parameters (augment.Augment's: p, rot_max_deg, scale_max, flip, trans_max, jitter_sigma, up_axis,
+        flip_axis): validated, then written INTO the trainer's table -- the same tensor at the same address, which the launch list
+        has baked in: the next `step_list()` (or eager step) draws with the new values, with no recapture.  Raises on a trainer
+        built without `augment` (it has no table, and its launches read none)."""
+        if self.aug is None:
+            raise RuntimeError("set_augment(): this trainer was built without augment; build it with one (e.g. augment={'p': 0.0})")
+        self.aug.set(**changes)
+
+    def aug_state(self):
+        """{clock, params, records}: the number of iterations begun, the table as it is on the device (thresholds of 2^24, axes,
+        ranges in radians / log-scale) and, with record=True, the (12, B, 12) affine maps of the last iteration (row 3 * network +
+        role, role = real | fake | gen; per sample the 3 x 3 matrix row-major, then the translation).  Synchronises the device."""
+        if self.aug is None:
+            raise RuntimeError("aug_state(): this trainer was built without augment")
+        return self.aug.state()
 
     def lr_state(self):
         """{network: {step, factor, lr}} for G, D1..D4: the count of the network's last applied update, the schedule's factor at
@@ -883,7 +916,11 @@ class PDGNTrainer:
     def _seg_d(self, st, i):
         D = self.D[i]
         self.gradD[i].begin()
-        lossD = losses.mse_const(D(st["reals"][i]), 1.0, 0.5) + losses.mse_const(D(st["fakes"][i]), 0.0, 0.5)
+        if self.aug is None:
+            lossD = losses.mse_const(D(st["reals"][i]), 1.0, 0.5) + losses.mse_const(D(st["fakes"][i]), 0.0, 0.5)
+        else:
+            lossD = (losses.mse_const(D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5)
+                     + losses.mse_const(D(st["fakes"][i], self.aug.at(i, "fake")), 0.0, 0.5))
         lossD.backward()
         st["out"]["d_loss%d" % (i + 1)] = lossD.detach()
 
@@ -897,14 +934,14 @@ class PDGNTrainer:
         D = self.D[i]
         self.gradD[i].begin()
         params = self.gradD[i].params
-        loss_r = losses.mse_const(D(st["reals"][i]), 1.0, 0.5)
+        loss_r = losses.mse_const(D(st["reals"][i]) if self.aug is None else D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5)
         st["d_half"][i] = (loss_r.detach(), torch.autograd.grad(loss_r, params))
 
     def _seg_d_fake(self, st, i):
         D = self.D[i]
         fg = self.gradD[i]
         fg.resume()
-        loss_f = losses.mse_const(D(st["fakes"][i]), 0.0, 0.5)
+        loss_f = losses.mse_const(D(st["fakes"][i]) if self.aug is None else D(st["fakes"][i], self.aug.at(i, "fake")), 0.0, 0.5)
         loss_r, g_real = st["d_half"][i]
         st.setdefault("keep", []).append(loss_r)            # (it may have been computed on another stream than this half runs on: it must
                                                             #  not return to that stream's pool before the sum below has RUN)
@@ -917,6 +954,8 @@ class PDGNTrainer:
 
     def _segment(self, st, k):
         if k == 0:
+            if self.aug is not None:
+                self.aug.tick()                                  # the iteration's draws: every discriminator call below reads this clock
             # generator pass #1 (:179): only its detached outputs are ever used => no graph needed;
             # BatchNorm running statistics update exactly as in the reference.
             with torch.no_grad():
@@ -933,7 +972,7 @@ class PDGNTrainer:
             self._freeze_D(True)
             gen = self.G(self._z(st, "z2"))
             similar = self.similar_loss(gen)
-            g_loss = [losses.mse_const(self.D[i](gen[i]), 1.0) for i in range(4)]
+            g_loss = [losses.mse_const(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), 1.0) for i in range(4)]
             adv = 1.2 * g_loss[0] + 1.2 * g_loss[1] + 1.2 * g_loss[2] + g_loss[3]
             lossG = adv + 0.1 * similar
             # MSE is a batch MEAN, the shape loss a batch SUM (chamfer_loss.py:16-20): to reproduce
@@ -1008,6 +1047,12 @@ class PDGNTrainer:
             # on, so every stream of the schedule opens with a marker node carrying its id (csrc/replay.hip)
             from . import replay as _replay
             _replay.mark(_replay.MAIN, main)
+        if self.aug is not None:
+            # The augmentation clock ticks once, HERE: on the issuing stream, before any side stream forks from it (each of them waits
+            # for `main` before its first launch of the iteration), and behind the previous iteration, whose chains were all joined
+            # into this stream at its end -- so every discriminator launch of this iteration, on whichever stream, reads this value.
+            self.aug.tick()
+        if st.get("tag_streams"):
             for sid, s in enumerate(list(pl.d) + [pl.lp, pl.knn], 1):
                 s.wait_stream(main)
                 _replay.mark(sid, s)
@@ -1090,7 +1135,7 @@ class PDGNTrainer:
             side = self._side[level]
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                g_loss[level] = losses.mse_const(self.D[level](cloud), 1.0)
+                g_loss[level] = losses.mse_const(self.D[level](cloud) if self.aug is None else self.D[level](cloud, self.aug.at(level, "gen")), 1.0)
 
         def tail(level, cloud):
             gen_so_far.append(cloud)
@@ -1109,7 +1154,7 @@ class PDGNTrainer:
             for i, side in enumerate(self._side):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    g_loss[i] = losses.mse_const(self.D[i](gen[i]), 1.0)
+                    g_loss[i] = losses.mse_const(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), 1.0)
         for side in self._side:
             main.wait_stream(side)
         main.wait_stream(self._side_lp)
@@ -1325,7 +1370,11 @@ class PDGNTrainer:
 
         With a learning-rate schedule or per-network rates, `lr_log` (a path; default: lr.csv beside a log
         given as a path, else none) gets one row -- epoch, step_G, lr_G, lr_D1 .. lr_D4, from `lr_state()` -- wherever a checkpoint is
-        written or `on_epoch` is called: points at which the host waits for the device anyway.  Rank 0 only; without either, no file."""
+        written or `on_epoch` is called: points at which the host waits for the device anyway.  Rank 0 only; without either, no file.
+
+        With augmentation the clock is set to (start_epoch - 1) * batches_per_epoch behind any capture_list
+        warm-up: iteration i of epoch e draws at (e - 1) * nb + i, whether the run was interrupted or not.  The clock is derived,
+        not stored: checkpoints are what they were."""
         import time
         if issue not in ("list", "eager"):
             raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
@@ -1413,6 +1462,10 @@ class PDGNTrainer:
             if issue == "list":
                 st = self._static
                 reals, z1, z2 = st["reals"], st["z1"], st["z2"]
+            if getattr(self, "aug", None) is not None:
+                # iteration i of epoch e always draws at (e - 1) * nb + i, the feeder's global iteration: set behind capture_list's
+                # warm-up iterations (they tick too), so that a resumed epoch draws what the uninterrupted run drew
+                self.aug.set_clock((start_epoch - 1) * nb)
             for epoch in range(start_epoch, epochs + 1):
                 for i in range(nb):
                     feeder.fill(epoch, i, reals, z1, z2)
