@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 33
+#define PDGN_ABI_VERSION 34
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -796,7 +796,8 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
  * no dependence on grid shape or launch order:
  *   key     = (seed low 32, seed high 32)
  *   counter = (group j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8)
- *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order)
+ *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order;
+ *             6: the round keys of pdgn_feed_batch_resample, below)
  * A group is the four output words of one counter.  Index streams: word e of group j is column 4j + e, i = (word * N) >> 32
  * (bias of a point's probability at most N / 2^32 relative: 4.8e-7 at N = 2048).  Noise: group j gives columns 4j .. 4j+3 as
  * two Box-Muller pairs (words 0,1 and 2,3): u1 = ((w >> 8) + 1) * 2^-24 in (0, 1], u2 = (w' >> 8) * 2^-24 in [0, 1),
@@ -809,6 +810,34 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
 int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
                     unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2, float *p3,
                     float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
+/* The same launch for clouds stored DENSER than they are trained on: data (S,M,3), of which the leading P points of a cloud (the
+ * pool) may be drawn and N points make the finest output, N <= P <= M.  A fresh N-point subset per row and iteration (the training
+ * protocol of the 15 000-point ShapeNetCore.v2.PC15k sets; no reference counterpart: the reference trains on a pre-cut file).
+ * With c = order[first + b]:
+ *   p4[b,:,j]       = data[c, pi(j), :],  j < N, pi a bijection of [0, P) chosen by (seed, t, global row): N DISTINCT points, drawn
+ *                     without replacement;
+ *   pk[b,:,j]       = data[c, i, :],  i = (word * P) >> 32: pdgn_feed_batch's counters and tags 0 1 2, WITH replacement from the pool,
+ *                     independently of p4 (datasets_4point.py:374-379 draws them from the whole stored cloud);
+ *   z1, z2          exactly what pdgn_feed_batch writes for the same (seed, t, row0, sigma) (tags 3 4).
+ * pi is a keyed balanced Feistel network extended to [0, P) by cycle-walking, evaluated per output point (no sort, no state):
+ *   bits = max(2, bit length of P - 1),  h = (bits + 1) / 2 (integer division),  the network permutes [0, 2^(2h)) >= [0, P);
+ *   keys k0 .. k5 = words 0 1 2 3 of the counter (0, global row, t low 32, 6 | (t >> 32 & 0xffffff) << 8) and words 0 1 of the counter
+ *                   (1, ...) with the key (seed low 32, seed high 32): one key set per row and iteration;
+ *   E(x):  L = x >> h, R = x & (2^h - 1);  for i = 0 .. 5: (L, R) <- (R, L ^ F(R, k_i));  E = L << h | R
+ *   F(r, k) = (((r ^ k) * 0x9E3779B1) mod 2^32) >> (32 - h)            (the top h bits of a multiplicative hash)
+ *   pi(j):  x = E(j);  while x >= P: x = E(x).
+ * Every Feistel round is invertible whatever F is, so E is a bijection of [0, 2^(2h)); following E from j < P until it is
+ * back below P visits j's own cycle, so the walk ends (at j itself at the latest) and pi is a bijection of [0, P).  2^(2h) <= 4 P,
+ * so a pass lands below P with probability >= 1/4.  Uniformity is a claim for pools of thousands of points only (chi^2
+ * of the inclusion counts at P = 15000, N = 2048: tests/test_resample_host.py); at h <= 3 bits the round function is visibly
+ * non-uniform and only bijectivity holds.  One thread owns four consecutive columns: four 12-byte gathers, a 16-byte store per
+ * channel where aligned.  No LDS, no atomics.
+ * PDGN_ERR_INVALID: pdgn_feed_batch's cases (with P or M <= 0 as well), N > P, P > M, 3 M beyond the int range; checked on the
+ * host before anything is launched. */
+int pdgn_feed_batch_resample(int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
+                             long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1,
+                             float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ discriminator augmentation
  * A fresh random similarity transform plus jitter for every cloud in front of every discriminator call (DiffAugment, Zhao et al.

@@ -9,6 +9,11 @@
 // in, one 16-byte store per channel), four points of the transposed full cloud (48 contiguous bytes in, one 16-byte
 // store per channel) or four normals (one 16-byte store).  A wave therefore writes 1 KiB contiguous per channel.
 // No LDS, no atomics.
+//
+// pdgn_feed_batch_resample: the same launch for clouds stored with M >= N points each.  p4 is a fresh N-point subset of the
+// cloud's leading P points per row and iteration -- column j takes point pi(j), pi a keyed Feistel permutation of [0, P)
+// (construction in include/pdgn_hip.h; mirror: tests/resample_mirror.py) -- four 12-byte gathers per thread instead of 48
+// contiguous bytes; the sub-resolutions draw from the pool, the noise is pdgn_feed_batch's.
 #include "common.h"
 #include "philox.h"                                             // philox4x32_10, box_muller (shared with augment.hip)
 
@@ -16,9 +21,13 @@
 #define FEED_NOISE_DIM 128                                      // (B,128): models/PDGNet_v2.py:178 with main.py:23's default
 #define FEED_TAG_Z1 3u
 #define FEED_TAG_Z2 4u
+#define FEED_TAG_PERM 6u                                        // the round keys of the resampling permutation
+#define FEED_PERM_ROUNDS 6
 
 struct FeedArgs {
     int S, N, r[3];
+    int M, P;                                                    // points stored per cloud (the row stride) and the pool drawn from; pdgn_feed_batch: M = P = N
+    int h;                                                       // resample: bits of one Feistel half
     int g[6];                                                    // exclusive prefix of the groups of one row: p1 p2 p3 p4 z1 z2 (g[5] + 32 = all)
     int groups;
     int vec;                                                     // bit k: output k (p1 p2 p3 p4) takes 16-byte stores; bit 4: the cloud rows take 16-byte loads
@@ -43,6 +52,20 @@ __device__ __forceinline__ void store4(float *dst, int cols, bool vec, float a, 
     }
 }
 
+// one pass of the Feistel network over [0, 2^(2h)): a bijection for any round function
+__device__ __forceinline__ unsigned feistel_pass(unsigned x, int h, const unsigned key[FEED_PERM_ROUNDS]) {
+    unsigned L = x >> h, R = x & ((1u << h) - 1u);
+#pragma unroll
+    for (int i = 0; i < FEED_PERM_ROUNDS; ++i) {
+        const unsigned f = ((R ^ key[i]) * 0x9E3779B1u) >> (32 - h);
+        const unsigned nr = L ^ f;
+        L = R, R = nr;
+    }
+    return (L << h) | R;
+}
+
+// RESAMPLE = false is pdgn_feed_batch (M = P = N, p4 the transposed cloud), true pdgn_feed_batch_resample
+template <bool RESAMPLE>
 __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
     const int q = blockIdx.x * FEED_THREADS + threadIdx.x;       // the group of row b this thread owns
     const int b = blockIdx.y;
@@ -60,7 +83,27 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
         return;
     }
     const int c = min(max(a.order[a.first + b], 0), a.S - 1);    // (a permutation of [0, S) by contract; clamped so that a bad one cannot read outside data)
-    const float *cloud = a.data + (size_t)c * a.N * 3;
+    const float *cloud = a.data + (size_t)c * a.M * 3;
+    if (RESAMPLE && q >= a.g[3]) {                               // ---- N distinct points of the pool: columns 4j .. 4j+3 take the points pi(4j) .. pi(4j+3)
+        const int j = q - a.g[3];
+        const int cols = min(4, a.N - 4 * j);
+        unsigned key[8];
+        philox4x32_10(0u, row, a.t_lo, FEED_TAG_PERM | (a.t_hi24 << 8), a.k0, a.k1, key);
+        philox4x32_10(1u, row, a.t_lo, FEED_TAG_PERM | (a.t_hi24 << 8), a.k0, a.k1, key + 4);
+        float v[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            unsigned x = i < cols ? (unsigned)(4 * j + i) : 0u;  // (< N <= P: inside the domain, and on a cycle that comes back below P)
+            do x = feistel_pass(x, a.h, key); while (x >= (unsigned)a.P);
+            const float *pt = cloud + (size_t)x * 3;             // x < P <= M
+            v[3 * i] = pt[0], v[3 * i + 1] = pt[1], v[3 * i + 2] = pt[2];
+        }
+        float *dst = a.p[3] + (size_t)b * 3 * a.N + 4 * j;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            store4(dst + (size_t)ch * a.N, cols, a.vec & 8, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
+        return;
+    }
     if (q >= a.g[3]) {                                           // ---- the full cloud, transposed: points 4j .. 4j+3
         const int j = q - a.g[3];
         const int cols = min(4, a.N - 4 * j);
@@ -81,7 +124,7 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
             store4(dst + (size_t)ch * a.N, cols, a.vec & 8, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
         return;
     }
-    // ---- a sub-resolution: columns 4j .. 4j+3 of p_k[b] are the points i = umulhi(word, N), drawn with replacement
+    // ---- a sub-resolution: columns 4j .. 4j+3 of p_k[b] are the points i = umulhi(word, P), drawn with replacement
     const int k = (q >= a.g[1]) + (q >= a.g[2]);
     const int j = q - a.g[k];
     const int r = a.r[k];
@@ -90,7 +133,7 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
     float v[12];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float *pt = cloud + (size_t)__umulhi(w[i], (unsigned)a.N) * 3;
+        const float *pt = cloud + (size_t)__umulhi(w[i], (unsigned)a.P) * 3;
         v[3 * i] = pt[0], v[3 * i + 1] = pt[1], v[3 * i + 2] = pt[2];
     }
     float *dst = a.p[k] + (size_t)b * 3 * r + 4 * j;
@@ -99,19 +142,24 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
         store4(dst + (size_t)ch * r, cols, (a.vec >> k) & 1, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
 }
 
-extern "C" int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
-                               unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
-                               float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
+static int feed_launch(bool resample, int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
+                       long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
+                       float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
     // host-side checks only: nothing here touches the device
     if (B <= 0 || B > 65535 || S <= 0 || N <= 0 || r1 <= 0 || r2 <= 0 || r3 <= 0) return PDGN_ERR_INVALID;
+    if (N > P || P > M) return PDGN_ERR_INVALID;
     if (first < 0 || first > (long long)S - B) return PDGN_ERR_INVALID;                       // first + B > S
     if (row0 < 0 || row0 + B > 0x100000000LL) return PDGN_ERR_INVALID;                        // the global row is one 32-bit counter word
     if (!data || !order || !p1 || !p2 || !p3 || !p4 || !z1 || !z2) return PDGN_ERR_INVALID;
     if ((((uintptr_t)z1 | (uintptr_t)z2) & 15) || (((uintptr_t)data | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)p4) & 3))
         return PDGN_ERR_INVALID;
-    if ((long long)N > 0x7fffffffLL / 3 || (long long)r1 + r2 + r3 + N > 0x7fffff00LL) return PDGN_ERR_INVALID;
+    if ((long long)M > 0x7fffffffLL / 3 || (long long)r1 + r2 + r3 + N > 0x7fffff00LL) return PDGN_ERR_INVALID;
     FeedArgs a;
     a.S = S, a.N = N, a.r[0] = r1, a.r[1] = r2, a.r[2] = r3;
+    a.M = M, a.P = P;
+    int bits = 2;                                                // the Feistel network permutes [0, 2^(2h)) >= [0, P)
+    while (bits < 31 && (1LL << bits) < (long long)P) ++bits;
+    a.h = (bits + 1) / 2;
     const int len[4] = {r1, r2, r3, N};
     float *const out[4] = {p1, p2, p3, p4};
     int at = 0;
@@ -122,7 +170,7 @@ extern "C" int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, cons
         a.p[k] = out[k];
         if (len[k] % 4 == 0 && !((uintptr_t)out[k] & 15)) a.vec |= 1 << k;
     }
-    if (N % 4 == 0 && !((uintptr_t)data & 15)) a.vec |= 16;
+    if (!resample && N % 4 == 0 && !((uintptr_t)data & 15)) a.vec |= 16;
     a.g[4] = at, a.g[5] = at + FEED_NOISE_DIM / 4;
     a.groups = at + 2 * (FEED_NOISE_DIM / 4);
     a.data = data, a.order = order, a.first = first;
@@ -132,6 +180,21 @@ extern "C" int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, cons
     a.sigma = sigma;
     a.z[0] = z1, a.z[1] = z2;
     dim3 grid(cdiv(a.groups, FEED_THREADS), B);
-    hipLaunchKernelGGL(feed_batch_kernel, grid, dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    if (resample)
+        hipLaunchKernelGGL(feed_batch_kernel<true>, grid, dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(feed_batch_kernel<false>, grid, dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
     return pdgn_launch_status();
+}
+
+extern "C" int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *data, const int32_t *order, long long first,
+                               unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
+                               float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
+    return feed_launch(false, B, S, N, N, N, r1, r2, r3, data, order, first, seed, t, row0, sigma, p1, p2, p3, p4, z1, z2, stream);
+}
+
+extern "C" int pdgn_feed_batch_resample(int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
+                                        long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma,
+                                        float *p1, float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
+    return feed_launch(true, B, S, M, P, N, r1, r2, r3, data, order, first, seed, t, row0, sigma, p1, p2, p3, p4, z1, z2, stream);
 }

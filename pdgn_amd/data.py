@@ -8,7 +8,8 @@ shape (which is also how the tests drive it: this image has no h5py).
 
 `BatchFeeder` is the training-side feed: the whole split stays on the device and ONE launch (csrc/feed.hip,
 pdgn_feed_batch) writes a batch -- shuffled clouds, the three sub-samplings, the transposes and both noise draws --
-into the buffers the training step reads.
+into the buffers the training step reads.  Clouds stored denser than they are trained on (the 15 000 points per shape of
+ShapeNetCore.v2.PC15k) go through pdgn_feed_batch_resample: a fresh `num_point` subset of every cloud each time it is visited.
 """
 import os
 import random
@@ -101,7 +102,9 @@ class ShapeNetCore(torch.utils.data.Dataset):
 
     GRAVITATIONAL_AXIS = 1
 
-    def __init__(self, cates_list, split, scale_mode, path, transform=None):
+    def __init__(self, cates_list, split, scale_mode, path, transform=None, tail=None):
+        """tail = N: keep the LAST N points of every stored cloud, all three splits alike, cut before any statistic or
+        normalisation (the held-out points of clouds a BatchFeeder trains on the head of); None: the clouds as stored."""
         super().__init__()
         cates = [cates_list] if isinstance(cates_list, str) else list(cates_list)
         assert split in ("train", "val", "test")
@@ -112,11 +115,15 @@ class ShapeNetCore(torch.utils.data.Dataset):
         self.split, self.scale_mode, self.transform, self.path = split, scale_mode, transform, path
         f, closer = _open(path)
         try:
-            every = [torch.as_tensor(np.asarray(f[sid][sp])) for sid in self.cate_synsetids for sp in ("train", "val", "test")]
+            def read(sid, sp):
+                pcs = torch.as_tensor(np.asarray(f[sid][sp]))
+                return pcs if tail is None else pcs[:, max(pcs.shape[1] - int(tail), 0):]
+
+            every = [read(sid, sp) for sid in self.cate_synsetids for sp in ("train", "val", "test")]
             self.stats = dataset_statistics(torch.cat(every, dim=0))
             self.pointclouds = []
             for sid in self.cate_synsetids:
-                pcs = torch.as_tensor(np.asarray(f[sid][split]))
+                pcs = read(sid, split)
                 norm, shift, scale = normalize_clouds(pcs, scale_mode, self.stats["std"])
                 for j in range(pcs.shape[0]):
                     self.pointclouds.append({"pointcloud": norm[j], "cate": synsetid_to_cate[sid], "id": j,
@@ -179,15 +186,18 @@ def batches_per_epoch(S, B, world=1):
 class BatchFeeder:
     """A device-resident split and the launch that turns it into training batches.
 
-    clouds: (S, N, 3) fp32 device tensor (`ShapeNetCore.stack(device)`; `from_dataset` does that and refuses a data set with a
+    clouds: (S, M, 3) fp32 device tensor (`ShapeNetCore.stack(device)`; `from_dataset` does that and refuses a data set with a
     per-item `transform`, for which the device path has no hook).  sizes: the three sub-resolutions (a fourth entry must
-    equal N).  Batch i of `epoch` on `rank` of `world` takes the clouds order[(i * world + rank) * B ...] of
+    equal N).  num_point: N, the points of the finest output (default M: the stored clouds themselves); pool: P, the leading
+    points of a cloud that may be drawn (default M).  With N < M or a pool every row of the finest output is a fresh draw of N
+    distinct points of its cloud's pool per iteration and the sub-resolutions draw from the pool (pdgn_feed_batch_resample);
+    with neither, the launch is pdgn_feed_batch.  Batch i of `epoch` on `rank` of `world` takes the clouds order[(i * world + rank) * B ...] of
     `epoch_order(seed, epoch, S)`; global rows rank * B + b and the global iteration (epoch - 1) * batches_per_epoch + i index
     the random streams, so that `world` ranks at batch B draw what one rank draws at batch B * world."""
 
     NOISE_DIM = 128
 
-    def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2):
+    def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=None, pool=None):
         from . import _lib
         if not isinstance(clouds, torch.Tensor):
             if getattr(clouds, "transform", None) is not None:
@@ -197,13 +207,21 @@ class BatchFeeder:
         _lib.require(clouds, "clouds", torch.float32, 3)
         if clouds.shape[2] != 3:
             raise ValueError("clouds must be (S,N,3), got %s" % (tuple(clouds.shape),))
+        self.M = int(clouds.shape[1])
+        self.N = self.M if num_point is None else int(num_point)
+        self.P = self.M if pool is None else int(pool)
+        if not 1 <= self.N <= self.M:
+            raise ValueError("num_point %d: the clouds have %d points" % (self.N, self.M))
+        if not self.N <= self.P <= self.M:
+            raise ValueError("pool %d: at least num_point = %d and at most the %d stored points" % (self.P, self.N, self.M))
+        self._resample = self.N != self.M or pool is not None
         sizes = tuple(int(r) for r in sizes)
-        if len(sizes) == 4 and sizes[3] == clouds.shape[1]:
+        if len(sizes) == 4 and sizes[3] == self.N:
             sizes = sizes[:3]
         if len(sizes) != 3 or min(sizes) < 1:
             raise ValueError("sizes: the three sub-resolutions (optionally followed by N), got %r" % (sizes,))
         self.clouds, self.sizes = clouds, sizes
-        self.S, self.N = int(clouds.shape[0]), int(clouds.shape[1])
+        self.S = int(clouds.shape[0])
         self.B, self.seed, self.rank, self.world, self.sigma = int(batch_size), int(seed), int(rank), int(world), float(sigma)
         if self.B < 1 or self.world < 1 or not 0 <= self.rank < self.world:
             raise ValueError("batch_size >= 1 and 0 <= rank < world, got %d, %d, %d" % (self.B, self.rank, self.world))
@@ -213,7 +231,7 @@ class BatchFeeder:
         self._order = torch.empty(self.S, dtype=torch.int32, device=clouds.device)
         self._order_host = torch.empty(self.S, dtype=torch.int32).pin_memory()
         self._order_epoch = None
-        self._fn = _lib.lib().pdgn_feed_batch
+        self._fn = _lib.lib().pdgn_feed_batch_resample if self._resample else _lib.lib().pdgn_feed_batch
         self._check = None
 
     @classmethod
@@ -260,8 +278,9 @@ class BatchFeeder:
             raise IndexError("batch %d of epoch %d: an epoch has %d batches, epochs count from 1" % (i, epoch, self.batches_per_epoch))
         if epoch != self._order_epoch:
             self._upload_order(epoch)
-        _lib.check(self._fn(self.B, self.S, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(self.clouds),
+        dims = (self.B, self.S, self.M, self.P, self.N) if self._resample else (self.B, self.S, self.N)
+        _lib.check(self._fn(*dims, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(self.clouds),
                             _lib.ptr(self._order), (i * self.world + self.rank) * self.B, self.seed & 0xFFFFFFFFFFFFFFFF,
                             (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B, self.sigma,
                             _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
-                            _lib.stream_of(self.clouds)), "pdgn_feed_batch")
+                            _lib.stream_of(self.clouds)), "pdgn_feed_batch_resample" if self._resample else "pdgn_feed_batch")

@@ -14,7 +14,11 @@ generator / the four discriminators instead of --learning_rate; --lr_schedule co
 updates, evaluated on the device (pdgn_amd/schedule.py); lr.csv beside the log.  --d_augment P (train): every cloud a discriminator
 sees goes through a random similarity transform drawn on the device, each component enabled per sample with probability P
 (pdgn_amd/augment.py); --aug_rotate DEG (default 180, about the y axis), --aug_scale S (1.25: log-uniform in [1/S, S]), --aug_flip [0|1]
-(1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.  --data_root: the HDF5 file (needs h5py) or an .npz whose keys are "<synsetid>/<split>".
+(1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.  --data_root: the HDF5 file (needs h5py), an .npz whose keys are "<synsetid>/<split>",
+or a directory in the layout of ShapeNetCore.v2.PC15k (<synsetid>/<split>/*.npy, each (M,3)).  Clouds stored with M > --num_point points (PC15k: 15 000)
+are trained on a fresh draw of --num_point distinct points per cloud and visit, made inside the feed launch (data.BatchFeeder, pdgn_feed_batch_resample),
+from the leading --resample_pool P points (default: all M); --phase test and the reports take the LAST --num_point points of every stored cloud as
+their reference clouds (disjoint from the pool whenever P <= M - num_point).
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -39,7 +43,8 @@ def build_parser():
     p.add_argument("--noise_dim", type=int, default=128)
     p.add_argument("--optimizer", default="adam", help="accepted and ignored, as in the reference")
     p.add_argument("--debug", type=bool, default=True, help="accepted and ignored, as in the reference")
-    p.add_argument("--data_root", default="/opt/data/private/shapenet/shapenet.hdf5", help="shapenet.hdf5, or an .npz with '<synsetid>/<split>' keys")
+    p.add_argument("--data_root", default="/opt/data/private/shapenet/shapenet.hdf5", help="shapenet.hdf5, an .npz with '<synsetid>/<split>' keys, or a "
+                   "directory <synsetid>/<split>/*.npy (ShapeNetCore.v2.PC15k)")
     p.add_argument("--log_info", default="log_info.txt")
     p.add_argument("--model_dir", help="model dir (required)")
     p.add_argument("--checkpoint_dir", default="checkpoint")
@@ -82,11 +87,13 @@ def build_parser():
     p.add_argument("--aug_flip", type=int, choices=[0, 1], nargs="?", const=1, default=argparse.SUPPRESS, help="mirror the x coordinate (default 1; 0: off)")
     p.add_argument("--aug_translate", type=float, default=argparse.SUPPRESS, metavar="T", help="translation, uniform in [-T, T] per coordinate (default 0.1)")
     p.add_argument("--aug_jitter", type=float, default=argparse.SUPPRESS, metavar="SIGMA", help="per-point Gaussian jitter (default 0: none)")
+    p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
+                   "each visit's points from the leading P points of a cloud (default: all stored points)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate and the augmentation flags are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags and --resample_pool are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -106,6 +113,7 @@ class Args(argparse.Namespace):
     aug_flip = None
     aug_translate = None
     aug_jitter = None
+    resample_pool = None
 
 
 def parse_args(argv=None):
@@ -133,6 +141,8 @@ def parse_args(argv=None):
         args.grad_guard = True
     if args.guard_max_skips < 1:
         p.error("--guard_max_skips must be at least one")
+    if args.resample_pool is not None and args.resample_pool < args.num_point:
+        p.error("--resample_pool %d: at least --num_point %d" % (args.resample_pool, args.num_point))
     given = vars(args)
     for flag in ("lr_g", "lr_d"):
         rate = getattr(args, flag)
@@ -203,9 +213,40 @@ def logged_args(args):
     return argparse.Namespace(**{k: v for k, v in vars(args).items() if args.report_every or not k.startswith("report_")})
 
 
-def open_data_root(path):
-    """What ShapeNetCore takes as `path`: the HDF5 path itself, or -- for an .npz with '<synsetid>/<split>' keys -- the
-    {synsetid: {split: array}} mapping."""
+def _open_pc15k(root, synsetids=None):
+    """A directory <synsetid>/<split>/*.npy, each file one (M,3) cloud (ShapeNetCore.v2.PC15k) -> {synsetid: {split: (S,M,3) fp32}},
+    the files of a split in sorted name order; synsetids: load these categories only."""
+    out, points = {}, None
+    for sid in sorted(os.listdir(root)):
+        if not os.path.isdir(os.path.join(root, sid)) or (synsetids is not None and sid not in synsetids):
+            continue
+        for split in ("train", "val", "test"):
+            folder = os.path.join(root, sid, split)
+            if not os.path.isdir(folder):
+                continue
+            clouds = []
+            for name in sorted(n for n in os.listdir(folder) if n.endswith(".npy")):
+                pc = np.load(os.path.join(folder, name))
+                if pc.ndim != 2 or pc.shape[1] != 3:
+                    raise ValueError("%s: a cloud is (M,3), got %s" % (os.path.join(folder, name), pc.shape))
+                if points is None:
+                    points = pc.shape[0]
+                if pc.shape[0] != points:
+                    raise ValueError("%s has %d points, the clouds read before it %d: every cloud of a data set must store the same "
+                                     "number of points" % (os.path.join(folder, name), pc.shape[0], points))
+                clouds.append(pc.astype(np.float32, copy=False))
+            if clouds:
+                out.setdefault(sid, {})[split] = np.stack(clouds, 0)
+    if not out:
+        raise ValueError("%s: no <synsetid>/<split>/*.npy clouds found" % (root,))
+    return out
+
+
+def open_data_root(path, synsetids=None):
+    """What ShapeNetCore takes as `path`: the HDF5 path itself, or -- for an .npz with '<synsetid>/<split>' keys or a directory
+    <synsetid>/<split>/*.npy -- the {synsetid: {split: array}} mapping (a directory: of `synsetids` only, where given)."""
+    if os.path.isdir(path):
+        return _open_pc15k(str(path), synsetids)
     if str(path).endswith(".npz"):
         out = {}
         with np.load(path) as f:
@@ -216,13 +257,14 @@ def open_data_root(path):
     return path
 
 
-def load_split(args, split, scale_mode):
-    from .data import ShapeNetCore, synsetid_to_cate
-    src = open_data_root(args.data_root)
+def load_split(args, split, scale_mode, tail=None):
+    """tail = N: the last N points of every stored cloud (ShapeNetCore's `tail`): the reference clouds of the test phase and the reports."""
+    from .data import ShapeNetCore, cate_to_synsetid, synsetid_to_cate
     cates = args.choice
+    src = open_data_root(args.data_root, None if cates is None or cates not in cate_to_synsetid else {cate_to_synsetid[cates]})
     if cates is None:                                            # the reference's category 'full'
         cates = [synsetid_to_cate[s] for s in sorted(src)] if isinstance(src, dict) else "all"
-    return ShapeNetCore(cates, split, scale_mode, src)
+    return ShapeNetCore(cates, split, scale_mode, src, tail=tail)
 
 
 def init_dist(device):
@@ -275,9 +317,15 @@ def train(args):
     torch.manual_seed(args.seed)                                 # the networks' initial weights
     dset = load_split(args, "train", "shape_unit")
     n = args.num_point
-    feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world)
-    if feeder.N != n:
-        raise SystemExit("--num_point %d but the clouds of %s have %d points" % (n, args.data_root, feeder.N))
+    stored = int(dset.pointclouds[0]["pointcloud"].shape[0])
+    if stored < n:
+        raise SystemExit("--num_point %d but the clouds of %s have %d points" % (n, args.data_root, stored))
+    if args.resample_pool is not None and stored == n:
+        raise SystemExit("--resample_pool: the clouds of %s have exactly --num_point %d points, there is nothing to draw" % (args.data_root, n))
+    if args.resample_pool is not None and args.resample_pool > stored:
+        raise SystemExit("--resample_pool %d but the clouds of %s have %d points" % (args.resample_pool, args.data_root, stored))
+    feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world,
+                                      num_point=n, pool=args.resample_pool)
     try:
         trainer = make_trainer(args, device, feeder.batches_per_epoch)
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
@@ -297,7 +345,7 @@ def train(args):
     reporter = None
     if args.report_every > 0 and rank == 0:
         from .report import SnapshotReporter
-        val = load_split(args, "val", args.normalize).stack(device).float().contiguous()
+        val = load_split(args, "val", args.normalize, tail=n).stack(device).float().contiguous()
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
@@ -324,7 +372,7 @@ def test(args):
     torch.manual_seed(args.seed)                                 # seed_all (:282)
     np.random.seed(args.seed)
     random.seed(args.seed)
-    ref = load_split(args, "test", args.normalize).stack(device).float().contiguous()
+    ref = load_split(args, "test", args.normalize, tail=args.num_point).stack(device).float().contiguous()
     trainer.G.eval()
     gen, results, raw = evaluation.generate_and_evaluate(trainer.G, ref, args.batch_size, normalize=args.normalize, return_raw=True)
     np.save(os.path.join(save_dir, "nonormal_out.npy"), raw.cpu().numpy())
