@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 34
+#define PDGN_ABI_VERSION 35
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -513,6 +513,16 @@ int pdgn_chamfer_gram_grad_uniform(int b, int m, int n, int d, const float *x, c
  * pdgn_mse_const_backward: dx[i] = g[0] * scale * 2 (x[i] - target) / n. */
 int pdgn_scaled_sum(long long n, const float *x, float scale, float *out, pdgn_stream_t stream);
 int pdgn_mse_const(long long n, const float *x, float target, float scale, float *out, pdgn_stream_t stream);
+/* pdgn_mse_const_count: pdgn_mse_const plus, in the same pass of the same single workgroup, three integer counts of x against a
+ * decision boundary (the adaptive discriminator augmentation's statistic, below: pdgn_augment_tick_ada):
+ *   count[0] = #{x[i] > boundary}, count[1] = #{x[i] < boundary}, count[2] = n
+ * (a value equal to the boundary and a NaN count to neither).  The counts are STORED, not added: `count` is the caller's slot of
+ * four 32-bit words (16 bytes, 4-byte aligned; word 3 is not touched), one slot per discriminator.  out[0] is bit for bit
+ * pdgn_mse_const's: the float sum runs in the same order; the integer sums are block reductions (wave shuffles, then shared
+ * memory), no atomics.  The backward is pdgn_mse_const_backward.  Replaces nothing in the reference.
+ * PDGN_ERR_INVALID: n < 1 or n >= 2^31 (the counts are 32-bit), a null or misaligned x / out / count. */
+int pdgn_mse_const_count(long long n, const float *x, float target, float scale, float boundary, float *out, int32_t *count,
+                         pdgn_stream_t stream);
 int pdgn_mse_const_backward(long long n, const float *x, float target, float scale, const float *g, float *dx,
                             pdgn_stream_t stream);
 
@@ -908,6 +918,56 @@ int pdgn_augment_rows_fwd(int B, int N, const float *x, int x_point_major, float
 int pdgn_augment_rows_bwd(int B, int N, const float *d_rows, float *dx, int dx_point_major, const pdgn_aug_table *table,
                           const unsigned long long *clock, unsigned long long seed, long long row0, int tag, pdgn_stream_t stream);
 int pdgn_augment_tick(unsigned long long *clock, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ adaptive discriminator augmentation (ADA, Karras et al. 2020)
+ * The probability p behind the table's thresholds, steered on the device from the discriminators' own outputs on the real batch.
+ * The discriminators are least-squares (real -> 1, fake -> 0; decision boundary 0.5); per iteration and discriminator i the
+ * real-batch loss term (pdgn_mse_const_count) stores pos_i = #{x > 0.5}, neg_i = #{x < 0.5}, n_i = n into slot i of
+ * `slots`, a contiguous int32[16] of its own (4 words per discriminator, word 3 unused; separate from the state so that it can be
+ * all-reduced (SUM) across ranks).  pdgn_augment_tick_ada, which opens every iteration in place of pdgn_augment_tick:
+ *   clock[0] += 1
+ *   fold: (P, G, N) = the sum of the four slots; the slots are zeroed.  If N > 0: pos += P, neg += G, n += N, the per-network
+ *         accumulators net[3 i ..] += slot i, iters += 1  (an iteration that contributed nothing does not count)
+ *   if iters >= interval, ONE update:
+ *         r    = (double)(pos - neg) / (double)n                        IEEE fp64, the operands exact
+ *         step = max(1, (n * 2^24) / (4 * span))                        unsigned 64-bit integer division; span: the number of real
+ *                                                                       clouds over which p travels 0 -> 1 (4: four discriminators count each)
+ *         r > target: thr += step;  r < target: thr -= step;  r == target: thr unchanged;  thr clamped to [thr_min, thr_max]
+ *         table->thr_<component k> = thr for every k with bit k of `mask` set (flip, rot, scale, trans, jitter = bits 0 .. 4); a
+ *         component outside the mask (its range is zero) keeps what it has, 0
+ *         last_r = r, last_pos / last_neg / last_n = pos, neg, n, last_net = net; pos = neg = n = iters = 0, net = 0, updates += 1
+ * thr = round(p 2^24) as in the table.  Integers throughout, and the step derived from n: W ranks at batch B whose slots are
+ * summed take exactly the step one rank takes at B W.
+ * No fence and no atomic: every writer of a slot (one pdgn_mse_const_count per discriminator and iteration, on that discriminator's
+ * stream) is stream-ordered BEFORE the next tick, which runs on the issuing stream after all chains of the previous iteration
+ * have joined it, and before any side stream of its own iteration forks; each slot has a single writer per iteration, the state
+ * and the thresholds only the tick (and the host, between iterations, in stream order).  The argument of the clock, above.
+ * The state is the host's to write (and to validate: the kernel takes what it finds); 8-byte aligned, 40 64-bit words. */
+typedef struct pdgn_ada_state {
+    double target;                                /* word 0: in (-1, 1) */
+    unsigned long long interval;                  /* 1: contributing iterations per update, >= 1 */
+    unsigned long long span;                      /* 2: real clouds for p to travel from 0 to 1, in [1, 2^40] */
+    unsigned long long thr_min, thr_max;          /* 3, 4: thr_min <= thr_max <= 2^24 */
+    unsigned long long mask;                      /* 5: bit k: the tick writes thr into component k's threshold */
+    unsigned long long thr;                       /* 6: the current threshold, round(p 2^24) */
+    unsigned long long pos, neg, n;               /* 7 .. 9: accumulators since the last update */
+    unsigned long long iters;                     /* 10: contributing iterations since the last update */
+    unsigned long long updates;                   /* 11: updates made */
+    double last_r;                                /* 12: r of the last update */
+    unsigned long long last_pos, last_neg, last_n; /* 13 .. 15: its totals */
+    unsigned long long last_net[12];              /* 16 .. 27: its per-network (pos, neg, n), D1 .. D4 */
+    unsigned long long net[12];                   /* 28 .. 39: per-network accumulators since the last update */
+} pdgn_ada_state;
+#define PDGN_ADA_STATE_WORDS 40
+#define PDGN_ADA_SLOT_WORDS 16
+/* pdgn_augment_tick_ada: one launch of a single wave on `stream`, plain loads and ordinary vector stores; replaces
+ * pdgn_augment_tick in adaptive mode, so an adaptive iteration has exactly the launches of a fixed-p one.
+ * State touched: clock, state, slots, table's five thresholds.  Allocates nothing.
+ * PDGN_ERR_INVALID (host-side, from a copy the caller passes of the parameters it wrote -- the device record is not read on the
+ * host): a null clock / state / slots / table, clock or state not 8-byte aligned, slots or table not 4-byte aligned,
+ * interval < 1, span < 1 or > 2^40, thr_min > thr_max, thr_max > 2^24. */
+int pdgn_augment_tick_ada(unsigned long long *clock, pdgn_ada_state *state, int32_t *slots, pdgn_aug_table *table, long long interval,
+                          long long span, long long thr_min, long long thr_max, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ preview sheets
  * A contact sheet of point clouds as ONE 8-bit grey image (what pdgn_amd/report.py writes at a snapshot): `rows` samples down,

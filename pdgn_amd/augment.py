@@ -11,7 +11,12 @@ with record=True a (12, B, 12) buffer into which every call site writes the affi
 of (seed, clock, global row, call site): include/pdgn_hip.h has the layout, tests/augment_mirror.py the numpy restatement.
 
 The clock counts the iterations BEGUN; the launches of the iteration in flight draw at t = clock - 1.  `set_clock(c)` therefore
-means "the next iteration draws at t = c", and after it the clock reads c + 1."""
+means "the next iteration draws at t = c", and after it the clock reads c + 1.
+
+adaptive={...} (ADA, Karras et al. 2020): p is steered on the device.  The real-batch loss terms count D_i's
+scores above and below the decision boundary 0.5 into `slots` (int32[16], `counter(i)`), and `tick()` -- pdgn_augment_tick_ada in
+place of pdgn_augment_tick -- folds them into `ada` (pdgn_ada_state, 40 64-bit words) and every `interval` iterations moves the
+thresholds one integer step towards r = (POS - NEG) / N = target.  tests/ada_mirror.py is the numpy restatement."""
 import math
 
 import numpy as np
@@ -65,6 +70,71 @@ def validate(p, rot_max_deg, scale_max, flip, trans_max, jitter_sigma, up_axis, 
     if out["flip"] and out["flip_axis"] == out["up_axis"]:
         raise ValueError("flip_axis must differ from up_axis (%d): the mirror goes through a horizontal axis" % out["up_axis"])
     return out
+
+
+ADA_DEFAULTS = dict(target=0.6, interval=4, span=500_000, p_min=0.0, p_max=0.8)     # (Karras et al. 2020: r_t target 0.6, every 4 minibatches, 500 k images)
+ADA_WORDS, ADA_SLOT_WORDS = 40, 16                               # PDGN_ADA_STATE_WORDS, PDGN_ADA_SLOT_WORDS
+ADA_BOUNDARY = 0.5                                               # least-squares discriminators: real -> 1, fake -> 0
+# word indices of pdgn_ada_state (include/pdgn_hip.h)
+(W_TARGET, W_INTERVAL, W_SPAN, W_THR_MIN, W_THR_MAX, W_MASK, W_THR, W_POS, W_NEG, W_N, W_ITERS, W_UPDATES, W_LAST_R, W_LAST_POS,
+ W_LAST_NEG, W_LAST_N, W_LAST_NET, W_NET) = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 28)
+
+
+def validate_adaptive(adaptive, p):
+    """The adaptive parameters as a dict of plain Python values (ADA_DEFAULTS where a name is missing), or ValueError: target strictly
+    inside (-1, 1); interval an integer in [1, 2^20], span an integer in [1, 2^40]; 0 <= p_min <= p <= p_max <= 1."""
+    if not isinstance(adaptive, dict):
+        raise ValueError("adaptive: None or a dict of %s, got %r" % (sorted(ADA_DEFAULTS), adaptive))
+    unknown = set(adaptive) - set(ADA_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown adaptive parameters: %s" % sorted(unknown))
+    a = dict(ADA_DEFAULTS, **adaptive)
+    out = {}
+    for name in ("target", "p_min", "p_max"):
+        try:
+            out[name] = float(a[name])
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (name, a[name])) from None
+    if not -1.0 < out["target"] < 1.0:                           # (NaN fails both)
+        raise ValueError("target must lie strictly inside (-1, 1), got %r" % (a["target"],))
+    for name, hi in (("interval", 1 << 20), ("span", 1 << 40)):
+        v = a[name]
+        if not (isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= v <= hi):
+            raise ValueError("%s must be an integer in [1, 2^%d], got %r" % (name, hi.bit_length() - 1, v))
+        out[name] = int(v)
+    if not 0.0 <= out["p_min"] <= out["p_max"] <= 1.0:
+        raise ValueError("0 <= p_min <= p_max <= 1 required, got p_min %r, p_max %r" % (a["p_min"], a["p_max"]))
+    if not out["p_min"] <= float(p) <= out["p_max"]:
+        raise ValueError("p = %r lies outside [p_min, p_max] = [%r, %r]" % (p, out["p_min"], out["p_max"]))
+    return out
+
+
+def component_mask(params):
+    """Five bits, flip .. jitter: the components whose threshold follows p (a component whose range is zero keeps threshold 0)."""
+    on = (params["flip"], params["rot_max_deg"] > 0, params["scale_max"] > 1, params["trans_max"] > 0, params["jitter_sigma"] > 0)
+    return sum(1 << k for k, e in enumerate(on) if e)
+
+
+def ada_words(params, adaptive):
+    """The 40 words of a FRESH pdgn_ada_state (accumulators and counters zero) as a uint64 array."""
+    w = np.zeros(ADA_WORDS, dtype=np.uint64)
+    w.view(np.float64)[W_TARGET] = adaptive["target"]
+    w[W_INTERVAL], w[W_SPAN] = adaptive["interval"], adaptive["span"]
+    w[W_THR_MIN], w[W_THR_MAX] = threshold(adaptive["p_min"]), threshold(adaptive["p_max"])
+    w[W_MASK], w[W_THR] = component_mask(params), threshold(params["p"])
+    return w
+
+
+def decode_ada(words):
+    """pdgn_ada_state as it is on the device -> the "ada" dict of `Augment.state()`."""
+    w = np.ascontiguousarray(words).view(np.uint64)
+    f = w.view(np.float64)
+    triples = lambda at: [tuple(int(v) for v in w[at + 3 * i:at + 3 * i + 3]) for i in range(NETWORKS)]
+    return {"p": int(w[W_THR]) / float(1 << 24), "thr": int(w[W_THR]), "target": float(f[W_TARGET]), "interval": int(w[W_INTERVAL]),
+            "span": int(w[W_SPAN]), "thr_min": int(w[W_THR_MIN]), "thr_max": int(w[W_THR_MAX]), "p_min": int(w[W_THR_MIN]) / float(1 << 24),
+            "p_max": int(w[W_THR_MAX]) / float(1 << 24), "mask": int(w[W_MASK]), "pos": int(w[W_POS]), "neg": int(w[W_NEG]), "n": int(w[W_N]),
+            "iters": int(w[W_ITERS]), "net": triples(W_NET), "updates": int(w[W_UPDATES]), "last_r": float(f[W_LAST_R]),
+            "last": (int(w[W_LAST_POS]), int(w[W_LAST_NEG]), int(w[W_LAST_N])), "last_net": triples(W_LAST_NET)}
 
 
 def threshold(p):
@@ -132,8 +202,9 @@ class AugmentSite:
 class Augment:
     def __init__(self, p=DEFAULTS["p"], rot_max_deg=DEFAULTS["rot_max_deg"], scale_max=DEFAULTS["scale_max"], flip=DEFAULTS["flip"],
                  trans_max=DEFAULTS["trans_max"], jitter_sigma=DEFAULTS["jitter_sigma"], up_axis=DEFAULTS["up_axis"],
-                 flip_axis=DEFAULTS["flip_axis"], seed=9999, record=False, rank=0, device="cuda"):
+                 flip_axis=DEFAULTS["flip_axis"], seed=9999, record=False, rank=0, device="cuda", adaptive=None):
         self.params = validate(p, rot_max_deg, scale_max, flip, trans_max, jitter_sigma, up_axis, flip_axis)    # raises before anything is allocated
+        self.adaptive = None if adaptive is None else validate_adaptive(adaptive, self.params["p"])
         if not (isinstance(seed, (int, np.integer)) and 0 <= seed < 1 << 64):
             raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
         if not (isinstance(rank, (int, np.integer)) and rank >= 0):
@@ -146,24 +217,62 @@ class Augment:
         self._sites = [[AugmentSite(self, n, r) for r in ROLES] for n in range(NETWORKS)]
         lib = _lib.lib()
         self._fwd, self._bwd, self._tick = lib.pdgn_augment_rows_fwd, lib.pdgn_augment_rows_bwd, lib.pdgn_augment_tick
+        self.ada = self.slots = None                             # adaptive only: pdgn_ada_state (40 x int64) and the four count slots (16 x int32)
+        if self.adaptive is not None:
+            self.ada = torch.from_numpy(ada_words(self.params, self.adaptive).view(np.int64).copy()).to(self.device)
+            self.slots = torch.zeros(ADA_SLOT_WORDS, dtype=torch.int32, device=self.device)
+            self._counters = [self.slots[4 * i:4 * i + 4] for i in range(NETWORKS)]
+            self._tick_ada = lib.pdgn_augment_tick_ada
 
     # ------------------------------------------------------------------ the parameters
     def set(self, **changes):
         """Overwrite parameters IN PLACE (same tensor, same address: launches that have the table's address baked in read the new
-        values from their next run on).  Validates the merged set first; raises without touching the table."""
-        unknown = set(changes) - set(self.params)
+        values from their next run on).  Validates the merged set first; raises without touching the table.
+        Adaptive: the five adaptive parameters are accepted too and written into the state record in place; `p` sets the CURRENT
+        threshold (it must lie inside [p_min, p_max]); without `p` the thresholds keep the device's current value (read back:
+        synchronises), so changing a component's range only recomputes the mask."""
+        known = set(self.params) | (set(ADA_DEFAULTS) if self.adaptive is not None else set())
+        unknown = set(changes) - known
         if unknown:
             raise ValueError("unknown augmentation parameters: %s" % sorted(unknown))
-        merged = validate(**dict(self.params, **changes))
-        fresh = torch.from_numpy(table_words(merged).view(np.int32).copy())
+        if self.adaptive is None:
+            merged = validate(**dict(self.params, **changes))
+            fresh = torch.from_numpy(table_words(merged).view(np.int32).copy())
+            with torch.no_grad():
+                self.table.copy_(fresh)
+            self.params = merged
+            return
+        ada_changes = {k: v for k, v in changes.items() if k in ADA_DEFAULTS}
+        own = {k: v for k, v in changes.items() if k not in ADA_DEFAULTS}
+        if "p" not in own:                                       # the device's p, exactly: thr 2^-24 rounds back to thr
+            own["p"] = int(self.ada[W_THR].item()) / float(1 << 24)
+        merged = validate(**dict(self.params, **own))
+        adaptive = validate_adaptive(dict(self.adaptive, **ada_changes), merged["p"])
+        head = ada_words(merged, adaptive)[:W_THR + 1]           # the parameters, the mask and thr: words 0 .. 6, one contiguous copy
         with torch.no_grad():
-            self.table.copy_(fresh)
-        self.params = merged
+            self.table.copy_(torch.from_numpy(table_words(merged).view(np.int32).copy()))
+            self.ada[:W_THR + 1].copy_(torch.from_numpy(head.view(np.int64).copy()))
+        self.params, self.adaptive = merged, adaptive
 
     # ------------------------------------------------------------------ the clock
     def tick(self):
-        """Open an iteration: clock += 1 by one launch on the current stream (capturable)."""
+        """Open an iteration: clock += 1 by one launch on the current stream (capturable); adaptive: the same single launch also
+        folds the previous iteration's counts and, when due, moves the thresholds."""
+        if self.adaptive is not None:
+            a = self.adaptive                                    # (the parameters travel for the entry point's checks only: the kernel reads the record)
+            _lib.check(self._tick_ada(_lib.ptr(self.clock), _lib.ptr(self.ada), _lib.ptr(self.slots), _lib.ptr(self.table), a["interval"], a["span"],
+                                      threshold(a["p_min"]), threshold(a["p_max"]), _lib.stream_of(self.clock)), "pdgn_augment_tick_ada")
+            return
         _lib.check(self._tick(_lib.ptr(self.clock), _lib.stream_of(self.clock)), "pdgn_augment_tick")
+
+    def counter(self, network):
+        """The 16-byte slot into which discriminator `network`'s real-batch loss term stores (pos, neg, n): what
+        `losses.mse_const(..., count=)` takes.  Adaptive only."""
+        if self.adaptive is None:
+            raise RuntimeError("counter(): this Augment is not adaptive (adaptive=None): nothing counts")
+        if not (isinstance(network, (int, np.integer)) and 0 <= network < NETWORKS):
+            raise ValueError("network: 0 .. 3 (D1 .. D4), got %r" % (network,))
+        return self._counters[network]
 
     def set_clock(self, t):
         """The next iteration (the next `tick`) draws at t.  A copy on the current stream."""
@@ -215,8 +324,37 @@ class Augment:
 
     # ------------------------------------------------------------------ what was drawn
     def state(self):
-        """{clock, params (the table as it is on the device, decoded), records ((12, B, 12) numpy or None)}.  Synchronises."""
+        """{clock, params (the table as it is on the device, decoded), records ((12, B, 12) numpy or None)}; adaptive: also "ada"
+        (`decode_ada`: current p and thr, the parameters, accumulators, interval progress, updates, last_r, the last update's
+        totals and per-network triples).  Synchronises."""
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
-        return {"clock": int(self.clock.item()), "params": decode_table(self.table.cpu().numpy().view(np.uint32)),
-                "records": None if self.records is None else self.records.cpu().numpy()}
+        out = {"clock": int(self.clock.item()), "params": decode_table(self.table.cpu().numpy().view(np.uint32)),
+               "records": None if self.records is None else self.records.cpu().numpy()}
+        if self.adaptive is not None:
+            out["ada"] = decode_ada(self.ada.cpu().numpy())
+        return out
+
+    # ------------------------------------------------------------------ persistence (adaptive: p is state, it cannot be derived)
+    def checkpoint(self):
+        """What `PDGNTrainer.save` writes beside G.pth / D.pth: the state record's words, the slots, the table, the parameters."""
+        if self.adaptive is None:
+            raise RuntimeError("checkpoint(): this Augment is not adaptive: its state is derived (the clock) or constant (the table)")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        return {"ada_state": self.ada.cpu().clone(), "slots": self.slots.cpu().clone(), "table": self.table.cpu().clone(),
+                "params": dict(self.params), "adaptive": dict(self.adaptive)}
+
+    def restore(self, saved):
+        """`checkpoint()`'s dict back into this object, in place (same addresses).  Validates first."""
+        if self.adaptive is None:
+            raise RuntimeError("restore(): this Augment is not adaptive")
+        params = validate(**saved["params"])
+        adaptive = validate_adaptive(saved["adaptive"], params["p"])
+        ada, slots, table = saved["ada_state"], saved["slots"], saved["table"]
+        if (tuple(ada.shape), ada.dtype) != ((ADA_WORDS,), torch.int64) or (tuple(slots.shape), slots.dtype) != ((ADA_SLOT_WORDS,), torch.int32) \
+                or (tuple(table.shape), table.dtype) != ((TABLE_WORDS,), torch.int32):
+            raise ValueError("restore(): not an adaptive augmentation checkpoint")
+        with torch.no_grad():
+            self.ada.copy_(ada), self.slots.copy_(slots), self.table.copy_(table)
+        self.params, self.adaptive = params, adaptive

@@ -209,6 +209,56 @@ __global__ void augment_tick_kernel(unsigned long long *clock) {
     if (blockIdx.x == 0 && threadIdx.x == 0) clock[0] = clock[0] + 1ull;
 }
 
+// The adaptive tick (include/pdgn_hip.h: pdgn_ada_state): clock += 1, the four discriminators' slots folded into the accumulators and
+// zeroed, and -- once `interval` contributing iterations have accumulated -- one integer step of the threshold towards the target.
+// One thread: ~50 independent loads and as many stores, once per iteration.  No fence, no atomic: every writer of a slot is
+// stream-ordered before this launch and this launch before every reader of the table (the argument of the clock).
+__global__ void augment_tick_ada_kernel(unsigned long long *clock, pdgn_ada_state *st, int *slots, pdgn_aug_table *tab) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    clock[0] = clock[0] + 1ull;
+    unsigned long long c[12], P = 0, G = 0, N = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[3 * i + j] = (unsigned long long)(unsigned)slots[4 * i + j];
+        P += c[3 * i], G += c[3 * i + 1], N += c[3 * i + 2];
+    }
+#pragma unroll
+    for (int i = 0; i < PDGN_ADA_SLOT_WORDS; ++i) slots[i] = 0;
+    if (N == 0) return;                                          // an iteration that contributed nothing does not count
+    unsigned long long pos = st->pos + P, neg = st->neg + G, n = st->n + N, iters = st->iters + 1ull;
+    unsigned long long net[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) net[i] = st->net[i] + c[i];
+    if (iters < st->interval) {
+        st->pos = pos, st->neg = neg, st->n = n, st->iters = iters;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) st->net[i] = net[i];
+        return;
+    }
+    const double r = (double)((long long)pos - (long long)neg) / (double)n;
+    const unsigned long long q = (n << 24) / (4ull * st->span);
+    const long long step = (long long)(q < 1ull ? 1ull : q);
+    const double target = st->target;
+    long long thr = (long long)st->thr;
+    if (r > target) thr += step;
+    else if (r < target) thr -= step;
+    const long long lo = (long long)st->thr_min, hi = (long long)st->thr_max;
+    thr = thr < lo ? lo : thr > hi ? hi : thr;
+    st->thr = (unsigned long long)thr;
+    const unsigned long long mask = st->mask;
+    if (mask & 1ull) tab->thr_flip = (unsigned)thr;
+    if (mask & 2ull) tab->thr_rot = (unsigned)thr;
+    if (mask & 4ull) tab->thr_scale = (unsigned)thr;
+    if (mask & 8ull) tab->thr_trans = (unsigned)thr;
+    if (mask & 16ull) tab->thr_jitter = (unsigned)thr;
+    st->last_r = r, st->last_pos = pos, st->last_neg = neg, st->last_n = n;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) st->last_net[i] = net[i], st->net[i] = 0ull;
+    st->pos = st->neg = st->n = st->iters = 0ull;
+    st->updates = st->updates + 1ull;
+}
+
 // host-side checks only: nothing here touches the device
 static int aug_args(int B, int N, const float *in, float *out, float *affine, const pdgn_aug_table *table, const unsigned long long *clock,
                     unsigned long long seed, long long row0, int tag, int point_major, AugArgs &a) {
@@ -246,5 +296,15 @@ extern "C" int pdgn_augment_rows_bwd(int B, int N, const float *d_rows, float *d
 extern "C" int pdgn_augment_tick(unsigned long long *clock, pdgn_stream_t stream) {
     if (!clock || ((uintptr_t)clock & 7)) return PDGN_ERR_INVALID;
     hipLaunchKernelGGL(augment_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, clock);
+    return pdgn_launch_status();
+}
+
+extern "C" int pdgn_augment_tick_ada(unsigned long long *clock, pdgn_ada_state *state, int32_t *slots, pdgn_aug_table *table, long long interval,
+                                     long long span, long long thr_min, long long thr_max, pdgn_stream_t stream) {
+    if (!clock || !state || !slots || !table) return PDGN_ERR_INVALID;
+    if ((((uintptr_t)clock | (uintptr_t)state) & 7) || (((uintptr_t)slots | (uintptr_t)table) & 3)) return PDGN_ERR_INVALID;
+    if (interval < 1 || span < 1 || span > (1LL << 40) || thr_min < 0 || thr_min > thr_max || thr_max > (1LL << 24)) return PDGN_ERR_INVALID;
+    static_assert(sizeof(pdgn_ada_state) == 8 * PDGN_ADA_STATE_WORDS, "pdgn_ada_state: 40 64-bit words");
+    hipLaunchKernelGGL(augment_tick_ada_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, clock, state, slots, table);
     return pdgn_launch_status();
 }

@@ -42,6 +42,40 @@ __global__ __launch_bounds__(LS_THREADS) void mse_const_fwd_kernel(long long n, 
     if (threadIdx.x == 0) out[0] = scale * (s / (float)n);
 }
 
+// two integer block sums at once: wave shuffles, then the sixteen wave totals through shared memory; valid in thread 0
+__device__ __forceinline__ void ls_block_sum2(int &a, int &b) {
+    __shared__ int red2[2][LS_THREADS / PDGN_WAVE];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64), b += __shfl_xor(b, off, 64);
+    if (lane_id() == 0) red2[0][threadIdx.x / PDGN_WAVE] = a, red2[1][threadIdx.x / PDGN_WAVE] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = b = 0;
+        for (int w = 0; w < LS_THREADS / PDGN_WAVE; ++w) a += red2[0][w], b += red2[1][w];
+    }
+}
+
+// mse_const_fwd_kernel (the float sum in its order: out[0] is the same bits) + count = (#{x > bnd}, #{x < bnd}, n), STORED:
+// the adaptive augmentation's statistic on D's scores of the real batch (include/pdgn_hip.h).  NaN and x == bnd count to neither.
+__global__ __launch_bounds__(LS_THREADS) void mse_const_count_fwd_kernel(long long n, const float *__restrict__ x, float t, float scale,
+                                                                        float bnd, float *__restrict__ out, int *__restrict__ count) {
+    float s = 0.f;
+    int pos = 0, neg = 0;
+    for (long long i = threadIdx.x; i < n; i += LS_THREADS) {
+        const float v = x[i];
+        const float d = v - t;
+        s = __fmaf_rn(d, d, s);
+        pos += v > bnd;
+        neg += v < bnd;
+    }
+    s = ls_block_sum(s);
+    ls_block_sum2(pos, neg);
+    if (threadIdx.x == 0) {
+        out[0] = scale * (s / (float)n);
+        count[0] = pos, count[1] = neg, count[2] = (int)n;
+    }
+}
+
 // dx = g[0] * scale * 2 (x - t) / n
 __global__ __launch_bounds__(256) void mse_const_bwd_kernel(long long n, const float *__restrict__ x, float t, float scale,
                                                             const float *__restrict__ g, float *__restrict__ dx) {
@@ -59,6 +93,15 @@ extern "C" int pdgn_scaled_sum(long long n, const float *x, float scale, float *
 extern "C" int pdgn_mse_const(long long n, const float *x, float target, float scale, float *out, pdgn_stream_t stream) {
     if (n < 1) return PDGN_ERR_INVALID;
     hipLaunchKernelGGL(mse_const_fwd_kernel, dim3(1), dim3(LS_THREADS), 0, (hipStream_t)stream, n, x, target, scale, out);
+    return pdgn_launch_status();
+}
+
+extern "C" int pdgn_mse_const_count(long long n, const float *x, float target, float scale, float boundary, float *out, int32_t *count,
+                                    pdgn_stream_t stream) {
+    if (n < 1 || n > 0x7fffffffLL || !x || !out || !count) return PDGN_ERR_INVALID;
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)count) & 3) return PDGN_ERR_INVALID;
+    hipLaunchKernelGGL(mse_const_count_fwd_kernel, dim3(1), dim3(LS_THREADS), 0, (hipStream_t)stream, n, x, target, scale, boundary, out,
+                       count);
     return pdgn_launch_status();
 }
 

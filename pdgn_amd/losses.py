@@ -93,11 +93,14 @@ class MseConst(Function):
     (models/PDGNet_v2.py:186-190, 246-250) -- as one launch forward and one backward (csrc/loss_small.hip)."""
 
     @staticmethod
-    def forward(ctx, x, target, scale):
+    def forward(ctx, x, target, scale, count=None):
         x = x.contiguous()
         require(x, "x", F32)
         out = torch.empty((), dtype=F32, device=x.device)
-        check(_lib.lib().pdgn_mse_const(x.numel(), ptr(x), target, scale, ptr(out), stream_of(x)), "pdgn_mse_const")
+        if count is None:
+            check(_lib.lib().pdgn_mse_const(x.numel(), ptr(x), target, scale, ptr(out), stream_of(x)), "pdgn_mse_const")
+        else:                                                    # the same value bit for bit, and (#{x > 1/2}, #{x < 1/2}, n) stored into the slot
+            check(_lib.lib().pdgn_mse_const_count(x.numel(), ptr(x), target, scale, 0.5, ptr(out), ptr(count), stream_of(x)), "pdgn_mse_const_count")
         ctx.save_for_backward(x)
         ctx.cfg = (float(target), float(scale))
         return out
@@ -109,12 +112,17 @@ class MseConst(Function):
         dx = torch.empty_like(x)
         g = g.contiguous()
         check(_lib.lib().pdgn_mse_const_backward(x.numel(), ptr(x), target, scale, ptr(g), ptr(dx), stream_of(x)), "pdgn_mse_const_backward")
-        return dx, None, None
+        return dx, None, None, None
 
 
-def mse_const(x, target, scale=1.0):
-    """scale * mean((x - target)^2) (MseConst)."""
-    return MseConst.apply(x, float(target), float(scale))
+def mse_const(x, target, scale=1.0, count=None):
+    """scale * mean((x - target)^2) (MseConst).  count: None, or a slot of the adaptive augmentation (`Augment.counter(i)`: four int32
+    words on x's device) into which the same launch stores how many x lie above / below the decision boundary 0.5, and their number."""
+    if count is not None:
+        require(count, "count", torch.int32)
+        if count.numel() < 3 or count.device != x.device:
+            raise ValueError("count: at least three int32 words on %s" % (x.device,))
+    return MseConst.apply(x, float(target), float(scale), count)
 
 
 def chamfer_sum(x, y, scale=1.0):

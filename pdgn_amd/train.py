@@ -14,7 +14,10 @@ generator / the four discriminators instead of --learning_rate; --lr_schedule co
 updates, evaluated on the device (pdgn_amd/schedule.py); lr.csv beside the log.  --d_augment P (train): every cloud a discriminator
 sees goes through a random similarity transform drawn on the device, each component enabled per sample with probability P
 (pdgn_amd/augment.py); --aug_rotate DEG (default 180, about the y axis), --aug_scale S (1.25: log-uniform in [1/S, S]), --aug_flip [0|1]
-(1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.  --data_root: the HDF5 file (needs h5py), an .npz whose keys are "<synsetid>/<split>",
+(1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.
+--d_augment_target R (train, needs --d_augment): P is only the initial value; the device steers it from the discriminators' scores of the real
+batch towards r = R (ADA; DESIGN.md section 7i), with --ada_interval K (4), --ada_span CLOUDS (500000), --ada_p_min / --ada_p_max (0 / 0.8);
+aug.csv beside the log, <epoch>_<category>_aug.pth beside every checkpoint pair.  --data_root: the HDF5 file (needs h5py), an .npz whose keys are "<synsetid>/<split>",
 or a directory in the layout of ShapeNetCore.v2.PC15k (<synsetid>/<split>/*.npy, each (M,3)).  Clouds stored with M > --num_point points (PC15k: 15 000)
 are trained on a fresh draw of --num_point distinct points per cloud and visit, made inside the feed launch (data.BatchFeeder, pdgn_feed_batch_resample),
 from the leading --resample_pool P points (default: all M); --phase test and the reports take the LAST --num_point points of every stored cloud as
@@ -87,13 +90,21 @@ def build_parser():
     p.add_argument("--aug_flip", type=int, choices=[0, 1], nargs="?", const=1, default=argparse.SUPPRESS, help="mirror the x coordinate (default 1; 0: off)")
     p.add_argument("--aug_translate", type=float, default=argparse.SUPPRESS, metavar="T", help="translation, uniform in [-T, T] per coordinate (default 0.1)")
     p.add_argument("--aug_jitter", type=float, default=argparse.SUPPRESS, metavar="SIGMA", help="per-point Gaussian jitter (default 0: none)")
+    p.add_argument("--d_augment_target", type=float, default=argparse.SUPPRESS, metavar="R", help="adaptive discriminator augmentation (ADA, Karras et "
+                   "al. 2020): --d_augment becomes the INITIAL p, which the device then steers so that r = (scores above 1/2 - scores below) / "
+                   "scores, measured on the discriminators' outputs for the real batch, approaches R (the paper: 0.6); aug.csv beside the log")
+    p.add_argument("--ada_interval", type=int, default=argparse.SUPPRESS, metavar="K", help="iterations per adjustment of p (default 4)")
+    p.add_argument("--ada_span", type=int, default=argparse.SUPPRESS, metavar="CLOUDS", help="real clouds over which p may travel from 0 to 1 (default "
+                   "500000, the paper's: far too long for a category of a few dozen shapes -- give a few hundred epochs' worth of clouds there)")
+    p.add_argument("--ada_p_min", type=float, default=argparse.SUPPRESS, help="lower end of p's range (default 0)")
+    p.add_argument("--ada_p_max", type=float, default=argparse.SUPPRESS, help="upper end of p's range (default 0.8)")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags and --resample_pool are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too) and --resample_pool are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -113,6 +124,11 @@ class Args(argparse.Namespace):
     aug_flip = None
     aug_translate = None
     aug_jitter = None
+    d_augment_target = None                                      # (the others' defaults are augment.ADA_DEFAULTS: one place)
+    ada_interval = None
+    ada_span = None
+    ada_p_min = None
+    ada_p_max = None
     resample_pool = None
 
 
@@ -180,7 +196,31 @@ def parse_args(argv=None):
             validate(**augment_kwargs(args))
         except ValueError as e:
             p.error("--d_augment: %s" % e)
+    if args.d_augment_target is None:
+        for flag in ("ada_interval", "ada_span", "ada_p_min", "ada_p_max"):
+            if flag in given:
+                p.error("--%s needs --d_augment_target" % flag)
+    else:
+        if args.d_augment is None:
+            p.error("--d_augment_target needs --d_augment (the initial p)")
+        from .augment import validate_adaptive
+        try:
+            validate_adaptive(adaptive_kwargs(args), args.d_augment)
+        except ValueError as e:
+            p.error("--d_augment_target: %s" % e)
     return args
+
+
+def adaptive_kwargs(args):
+    """augment.Augment's `adaptive` from the command line (None without --d_augment_target): augment.ADA_DEFAULTS where a flag was not given."""
+    if args.d_augment_target is None:
+        return None
+    from .augment import ADA_DEFAULTS
+    kw = dict(ADA_DEFAULTS, target=args.d_augment_target)
+    for flag, name in (("ada_interval", "interval"), ("ada_span", "span"), ("ada_p_min", "p_min"), ("ada_p_max", "p_max")):
+        if getattr(args, flag) is not None:
+            kw[name] = getattr(args, flag)
+    return kw
 
 
 def augment_kwargs(args):
@@ -297,7 +337,10 @@ def make_trainer(args, device, batches_per_epoch=None):
 
 def _augment_arg(args):
     kw = augment_kwargs(args)
-    return None if kw is None else dict(kw, seed=args.seed)
+    if kw is None:
+        return None
+    ada = adaptive_kwargs(args)
+    return dict(kw, seed=args.seed) if ada is None else dict(kw, seed=args.seed, adaptive=ada)
 
 
 def _resume(args, trainer, ckpt):
@@ -351,7 +394,7 @@ def train(args):
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
                        grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
-                       lr_log=os.path.join(run_dir, "lr.csv"))
+                       lr_log=os.path.join(run_dir, "lr.csv"), aug_log=os.path.join(run_dir, "aug.csv"))
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()

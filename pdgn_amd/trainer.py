@@ -176,6 +176,7 @@ class FlatGrads:
                 early = self._early_done
 
                 def reduce(fg=self, group=group, early=early):
+                    fg._sum_also(group)
                     if early:
                         if fg.early_numel < fg.buf.numel():
                             dist.all_reduce(fg.buf[fg.early_numel:], op=dist.ReduceOp.SUM, group=group)
@@ -187,6 +188,7 @@ class FlatGrads:
                 if dist.get_world_size(group) > 1:
                     self.buf.div_(dist.get_world_size(group))
                 return
+            self._sum_also(group)
             if self._early_done:
                 if self.early_numel < self.buf.numel():
                     dist.all_reduce(self.buf[self.early_numel:], op=dist.ReduceOp.SUM, group=group)
@@ -196,6 +198,13 @@ class FlatGrads:
                 dist.all_reduce(self.buf, op=dist.ReduceOp.SUM, group=group)
             if dist.get_world_size(group) > 1:
                 self.buf.div_(dist.get_world_size(group))
+
+
+    also_sum = ()                                               # small integer tensors all-reduced (SUM) with this buffer, at its host point
+
+    def _sum_also(self, group=None):
+        for t in self.also_sum:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
 
 def _capturing(device):
@@ -574,7 +583,8 @@ class PDGNTrainer:
     an iteration -- goes through a random similarity transform drawn on the device: `aug` owns the parameter
     table, the clock and the optional record buffer; the iteration opens with ONE extra launch, the clock's tick; `set_augment`
     overwrites the table in place, `aug_state` reads it back.  The shape-preserving loss sees the un-augmented clouds.  None: `aug`
-    is None, no buffer, no launch, and the discriminators' forward is the code it was."""
+    is None, no buffer, no launch, and the discriminators' forward is the code it was.  With augment={..., "adaptive": {...}} p is
+    steered on the device: the four real-batch loss terms count into `aug.slots`, the tick folds them."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
                  discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
@@ -616,6 +626,10 @@ class PDGNTrainer:
         if self.distributed and self._buckets:
             self.gradG.arm_early()
         self.gradD = [FlatGrads(d.parameters()) for d in self.D]
+        if self.distributed and self.aug is not None and self.aug.adaptive is not None:
+            # the adaptive augmentation's counts are summed over the ranks where the generator's gradients are: that all-reduce is
+            # ordered behind all four real-batch terms (G's backward passes through every D after its update), and the next tick behind it
+            self.gradG.also_sum = [self.aug.slots]
         cap = self.device.type == "cuda"                     # device-side step counter: graph-capturable
         adam = lambda m, lr: torch.optim.Adam(m.parameters(), lr=lr, betas=(0.5, 0.999), capturable=cap, fused=cap and os.environ.get("PDGN_FUSED_ADAM", "1") == "1")
         self.optG, self.optD = adam(self.G, lr_g if self.per_network_lr else lr), [adam(d, lr_d if self.per_network_lr else lr) for d in self.D]
@@ -673,7 +687,8 @@ class PDGNTrainer:
         """Change augmentation parameters (augment.Augment's: p, rot_max_deg, scale_max, flip, trans_max, jitter_sigma, up_axis,
         flip_axis): validated, then written INTO the trainer's table -- the same tensor at the same address, which the launch list
         has baked in: the next `step_list()` (or eager step) draws with the new values, with no recapture.  Raises on a trainer
-        built without `augment` (it has no table, and its launches read none)."""
+        built without `augment` (it has no table, and its launches read none).  Adaptive: also target,
+        interval, span, p_min, p_max, written into the state record in place; p sets the current value."""
         if self.aug is None:
             raise RuntimeError("set_augment(): this trainer was built without augment; build it with one (e.g. augment={'p': 0.0})")
         self.aug.set(**changes)
@@ -681,7 +696,8 @@ class PDGNTrainer:
     def aug_state(self):
         """{clock, params, records}: the number of iterations begun, the table as it is on the device (thresholds of 2^24, axes,
         ranges in radians / log-scale) and, with record=True, the (12, B, 12) affine maps of the last iteration (row 3 * network +
-        role, role = real | fake | gen; per sample the 3 x 3 matrix row-major, then the translation).  Synchronises the device."""
+        role, role = real | fake | gen; per sample the 3 x 3 matrix row-major, then the translation); adaptive: also "ada"
+        (augment.decode_ada).  Synchronises the device."""
         if self.aug is None:
             raise RuntimeError("aug_state(): this trainer was built without augment")
         return self.aug.state()
@@ -808,7 +824,9 @@ class PDGNTrainer:
         """Writes `<epoch>_<category>_G.pth` / `_D.pth` with the reference's keys (:391-407) so that either code
         base can resume from the other's files.  With an averaged generator also `<epoch>_<category>_G_ema.pth`: G.pth's layout
         with the AVERAGED parameters under `G_model` (buffers: the live ones) plus `ema_decay`, so that either code base's
-        `--phase test --pretrain_model_G <epoch>_<category>_G_ema.pth` evaluates the averaged generator; returned third."""
+        `--phase test --pretrain_model_G <epoch>_<category>_G_ema.pth` evaluates the averaged generator; returned third.  With adaptive
+        augmentation also `<epoch>_<category>_aug.pth` (augment.Augment.checkpoint: the state record, the slots, the table, the
+        parameters); returned last.  G.pth / D.pth are what they were either way."""
         os.makedirs(checkpoint_dir, exist_ok=True)
         stem = os.path.join(checkpoint_dir, "%s_%s" % (index_epoch, category))
         held = hold_bn_counters(False)
@@ -821,6 +839,11 @@ class PDGNTrainer:
             dfile["D_model%d" % i] = self._ref_model_state(d)
             dfile["D_optimizer%d" % i] = self._ref_optim_state(o)
         torch.save(dfile, stem + "_D.pth")
+        extra = ()
+        if self.aug is not None and self.aug.adaptive is not None:
+            # p is state (it cannot be derived, unlike the clock): a sibling file, G.pth / D.pth stay what they were
+            torch.save(self.aug.checkpoint(), stem + "_aug.pth")
+            extra = (stem + "_aug.pth",)
         if self.ema is not None:
             model = self._ref_model_state(self.G)
             for (name, p), e in zip(self.G.named_parameters(), self._ema_in_module_order()):
@@ -828,8 +851,8 @@ class PDGNTrainer:
                 model["module." + name] = e.detach().cpu().clone()
             torch.save({"G_model": model, "G_optimizer": self._ref_optim_state(self.optG), "G_epoch": index_epoch,
                         "ema_decay": self.ema_decay}, stem + "_G_ema.pth")
-            return stem + "_G.pth", stem + "_D.pth", stem + "_G_ema.pth"
-        return stem + "_G.pth", stem + "_D.pth"
+            return (stem + "_G.pth", stem + "_D.pth", stem + "_G_ema.pth") + extra
+        return (stem + "_G.pth", stem + "_D.pth") + extra
 
     def _ema_in_module_order(self):
         """The averages in `G.named_parameters()` order (they are kept in the optimizer's, which is the same list today)."""
@@ -849,7 +872,8 @@ class PDGNTrainer:
         """Resume from a reference (or own) checkpoint pair; returns the stored epoch (:352, :374).
         A missing file raises FileNotFoundError (the reference calls exit(), :345-347).  With an averaged generator: the
         averages come from the sibling `..._G_ema.pth` of `..._G.pth` where it exists, else they start from the loaded
-        parameters; the warm-up of the decay needs no state of its own (it reads Adam's restored step count)."""
+        parameters; the warm-up of the decay needs no state of its own (it reads Adam's restored step count).  Adaptive augmentation:
+        its state comes from the sibling `..._aug.pth` where it exists, else it stays as constructed."""
         from .generator import load_reference_state_dict
         g = torch.load(path_G, map_location="cpu")
         d = torch.load(path_D, map_location="cpu")
@@ -870,6 +894,10 @@ class PDGNTrainer:
                         e.copy_(avg[name])
             else:
                 self._ema_from_parameters()
+        if self.aug is not None and self.aug.adaptive is not None:
+            sibling = str(path_G)[:-len("_G.pth")] + "_aug.pth" if str(path_G).endswith("_G.pth") else None
+            if sibling is not None and os.path.exists(sibling):  # (else: the constructed state)
+                self.aug.restore(torch.load(sibling, map_location="cpu"))
         self.sync_replicas()
         return g["G_epoch"]
 
@@ -919,10 +947,15 @@ class PDGNTrainer:
         if self.aug is None:
             lossD = losses.mse_const(D(st["reals"][i]), 1.0, 0.5) + losses.mse_const(D(st["fakes"][i]), 0.0, 0.5)
         else:
-            lossD = (losses.mse_const(D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5)
+            lossD = (losses.mse_const(D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5, self._aug_counter(i))
                      + losses.mse_const(D(st["fakes"][i], self.aug.at(i, "fake")), 0.0, 0.5))
         lossD.backward()
         st["out"]["d_loss%d" % (i + 1)] = lossD.detach()
+
+    def _aug_counter(self, i):
+        """Adaptive augmentation: the slot D_i's REAL-batch term counts into; None otherwise.  The fake and the
+        generator's terms never count."""
+        return self.aug.counter(i) if self.aug is not None and self.aug.adaptive is not None else None
 
     # The same update in two halves (overlapped schedule): lossD = mse(D(real), 1) / 2 + mse(D(fake), 0) / 2 (:186-190) is
     # a sum of two terms that share nothing but the parameters, and the REAL term does not depend on the generator at all.
@@ -934,7 +967,7 @@ class PDGNTrainer:
         D = self.D[i]
         self.gradD[i].begin()
         params = self.gradD[i].params
-        loss_r = losses.mse_const(D(st["reals"][i]) if self.aug is None else D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5)
+        loss_r = losses.mse_const(D(st["reals"][i]) if self.aug is None else D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5, self._aug_counter(i))
         st["d_half"][i] = (loss_r.detach(), torch.autograd.grad(loss_r, params))
 
     def _seg_d_fake(self, st, i):
@@ -1345,7 +1378,7 @@ class PDGNTrainer:
     LOSS_KEYS = ("d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss")
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None):
+            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None):
         """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
         `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
         them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
@@ -1374,7 +1407,9 @@ class PDGNTrainer:
 
         With augmentation the clock is set to (start_epoch - 1) * batches_per_epoch behind any capture_list
         warm-up: iteration i of epoch e draws at (e - 1) * nb + i, whether the run was interrupted or not.  The clock is derived,
-        not stored: checkpoints are what they were."""
+        not stored: checkpoints are what they were.  With ADAPTIVE augmentation (section 7i) `aug_log` (a path; default: aug.csv beside a
+        log given as a path, else none) gets one row -- epoch, clock, p, updates, last_r, r_D1 .. r_D4 (the last update's (pos - neg) / n
+        per discriminator) -- wherever lr.csv would get one.  Rank 0 only; without adaptive augmentation, no file."""
         import time
         if issue not in ("list", "eager"):
             raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
@@ -1412,8 +1447,31 @@ class PDGNTrainer:
                 if fresh:
                     rates_file.write(",".join(["epoch", "step_G"] + ["lr_%s" % k for k in PDGNTrainer.GUARD_KEYS]) + "\n")
 
+        ada_file, ada_epoch = None, None
+        if getattr(self, "aug", None) is not None and self.aug.adaptive is not None:
+            if aug_log is None and isinstance(log, (str, bytes, os.PathLike)):
+                aug_log = os.path.join(os.path.dirname(os.fspath(log)) or ".", "aug.csv")
+            if aug_log is not None and getattr(feeder, "rank", 0) == 0:
+                fresh = not os.path.exists(aug_log) or os.path.getsize(aug_log) == 0
+                ada_file = open(aug_log, "a")
+                if fresh:
+                    ada_file.write(",".join(["epoch", "clock", "p", "updates", "last_r"] + ["r_%s" % k for k in PDGNTrainer.GUARD_KEYS[1:]]) + "\n")
+
+        def ada_line(ep):
+            nonlocal ada_epoch
+            if ada_file is None or ada_epoch == ep:
+                return
+            ada_epoch = ep
+            state = self.aug_state()
+            a = state["ada"]
+            per = [(ps - ng) / n if n else float("nan") for ps, ng, n in a["last_net"]]
+            ada_file.write(",".join(["%d" % ep, "%d" % state["clock"], "%.17g" % a["p"], "%d" % a["updates"], "%.17g" % a["last_r"]]
+                                    + ["%.17g" % r for r in per]) + "\n")
+            ada_file.flush()
+
         def rates_line(ep):
             nonlocal rates_epoch
+            ada_line(ep)
             if rates_file is None or rates_epoch == ep:          # (the last epoch's checkpoint may be written twice: one row)
                 return
             rates_epoch = ep
@@ -1501,6 +1559,8 @@ class PDGNTrainer:
                 norms_file.close()
             if rates_file is not None:
                 rates_file.close()
+            if ada_file is not None:
+                ada_file.close()
         return epochs
 
     @staticmethod
