@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 35
+#define PDGN_ABI_VERSION 36
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -807,7 +807,7 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
  *   key     = (seed low 32, seed high 32)
  *   counter = (group j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8)
  *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order;
- *             6: the round keys of pdgn_feed_batch_resample, below)
+ *             6: the round keys of pdgn_feed_batch_resample, 7: the start index of pdgn_feed_fps_pyramid, both below)
  * A group is the four output words of one counter.  Index streams: word e of group j is column 4j + e, i = (word * N) >> 32
  * (bias of a point's probability at most N / 2^32 relative: 4.8e-7 at N = 2048).  Noise: group j gives columns 4j .. 4j+3 as
  * two Box-Muller pairs (words 0,1 and 2,3): u1 = ((w >> 8) + 1) * 2^-24 in (0, 1], u2 = (w' >> 8) * 2^-24 in [0, 1),
@@ -848,6 +848,39 @@ int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *da
 int pdgn_feed_batch_resample(int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
                              long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1,
                              float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ farthest-point sampling, register resident (csrc/fps.hip)
+ * The iteration of furthestsampling_cuda_launcher (lib/pointops/src/sampling/sampling_cuda_kernel.cu:59-168; pdgn_furthestsampling
+ * above keeps that launcher's signature) for a caller in front of every training iteration: one workgroup per cloud, the cloud
+ * and the running minimum distance in registers for the whole call -- global memory is read once and written once per selected
+ * index; there is no `temp` argument.  Same arithmetic as pdgn_furthestsampling: d = fma(dz,dz, fma(dy,dy, dx*dx)), the
+ * running minimum is fminf and starts at 1e10 (pointops.py:24), a round takes the point of the largest minimum, exact ties go
+ * to the LOWEST index -- so that from start 0 the output is index for index pdgn_furthestsampling's.  A point already taken
+ * has minimum 0 and is taken again only when every point has (fewer distinct points than m: the lowest index repeats).
+ * Supported n: 1 .. PDGN_FPS_MAX_N (what the registers of one workgroup hold); a larger n is PDGN_ERR_INVALID, not a slower path.
+ *
+ * pdgn_fps_order: xyz (b,n,3), start (b) int32 or NULL (= 0 for every cloud), order (b,m) int32:
+ *   order[:,0] = start, then m - 1 rounds; 1 <= m <= n.  start[.] must be in [0, n): it lives on the device and is the caller's to
+ *   validate (pdgn_amd.pointops.fps_order does, on the host); the kernel clamps what it finds into the range.
+ * PDGN_ERR_INVALID: b < 0, n < 1 or > PDGN_FPS_MAX_N, m < 1 or > n, a null or misaligned (4 bytes) xyz / order; b = 0 returns 0
+ * and launches nothing.  Checked on the host before anything is launched. */
+#define PDGN_FPS_MAX_N 8192
+int pdgn_fps_order(int b, int n, int m, const float *xyz, const int32_t *start, int32_t *order, pdgn_stream_t stream);
+
+/* The feeder's farthest-point pyramid (no reference counterpart: datasets_4point.py:370-380 draws the three sub-resolutions
+ * independently and with replacement, which is what pdgn_feed_batch does): the same kernel on the finest real batch the feed launch
+ * has just written, p4 (B,3,N) channel-major, r3 - 1 rounds per row, and in the same launch
+ *   pk[b,:,j] = p4[b,:, order[b,j]],  j < rk,  k = 1 2 3        (bit copies; p1, p2, p3 are (B,3,r1) (B,3,r2) (B,3,r3))
+ * so that p1 is the leading r1 columns of p2, p2 the leading r2 of p3 and every level is a farthest-point subset of the level above.
+ * order_out (B,r3) int32 may be NULL.  The start index of row b is word 0 of the Philox4x32-10 counter
+ *   (0, global row = row0 + b, t low 32, PDGN_FEED_TAG_FPS | (t >> 32 & 0xffffff) << 8),  key (seed low 32, seed high 32)
+ * (pdgn_feed_batch's layout; tag 7 is used by neither the feeder, 0 .. 6, nor the augmentation, PDGN_AUG_TAG_BASE ..), reduced to
+ * [0, N) by (word * N) >> 32.  A pure function of its arguments: ranks compose through row0 and a resumed epoch repeats.
+ * PDGN_ERR_INVALID: B < 1, N < 1 or > PDGN_FPS_MAX_N, not 1 <= r1 <= r2 <= r3 <= N, row0 < 0 or row0 + B > 2^32, a null or
+ * misaligned (4 bytes) p4 / p1 / p2 / p3.  Checked on the host before anything is launched. */
+#define PDGN_FEED_TAG_FPS 7
+int pdgn_feed_fps_pyramid(int B, int N, int r1, int r2, int r3, const float *p4, unsigned long long seed, unsigned long long t,
+                          long long row0, float *p1, float *p2, float *p3, int32_t *order_out, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ discriminator augmentation
  * A fresh random similarity transform plus jitter for every cloud in front of every discriminator call (DiffAugment, Zhao et al.

@@ -8,7 +8,8 @@ shape (which is also how the tests drive it: this image has no h5py).
 
 `BatchFeeder` is the training-side feed: the whole split stays on the device and ONE launch (csrc/feed.hip,
 pdgn_feed_batch) writes a batch -- shuffled clouds, the three sub-samplings, the transposes and both noise draws --
-into the buffers the training step reads.  Clouds stored denser than they are trained on (the 15 000 points per shape of
+into the buffers the training step reads (`subsample="fps"`: a second launch, csrc/fps.hip's pdgn_feed_fps_pyramid, replaces the
+three independent with-replacement sub-samplings by nested farthest-point subsets of the finest cloud).  Clouds stored denser than they are trained on (the 15 000 points per shape of
 ShapeNetCore.v2.PC15k) go through pdgn_feed_batch_resample: a fresh `num_point` subset of every cloud each time it is visited.
 """
 import os
@@ -193,12 +194,21 @@ class BatchFeeder:
     distinct points of its cloud's pool per iteration and the sub-resolutions draw from the pool (pdgn_feed_batch_resample);
     with neither, the launch is pdgn_feed_batch.  Batch i of `epoch` on `rank` of `world` takes the clouds order[(i * world + rank) * B ...] of
     `epoch_order(seed, epoch, S)`; global rows rank * B + b and the global iteration (epoch - 1) * batches_per_epoch + i index
-    the random streams, so that `world` ranks at batch B draw what one rank draws at batch B * world."""
+    the random streams, so that `world` ranks at batch B draw what one rank draws at batch B * world.
+    subsample: "random" (the default: the reference's three independent with-replacement draws, made by the feed launch) or "fps":
+    after the feed launch, unchanged, pdgn_feed_fps_pyramid on the same stream overwrites p1..p3 with the leading r1 / r2 / r3
+    points of a farthest-point order of the row's p4 (start index drawn per row and iteration) -- nested, evenly spread, without
+    duplicates where p4 has none; p4, z1, z2 are what "random" writes.  "fps" needs ascending sizes <= N and N <= FPS_MAX_N."""
 
     NOISE_DIM = 128
+    SUBSAMPLE = ("random", "fps")
+    FPS_MAX_N = 8192                                             # PDGN_FPS_MAX_N (include/pdgn_hip.h)
 
-    def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=None, pool=None):
+    def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=None, pool=None, subsample="random"):
         from . import _lib
+        if subsample not in self.SUBSAMPLE:
+            raise ValueError("subsample %r: one of %s" % (subsample, ", ".join(self.SUBSAMPLE)))
+        self.subsample = subsample
         if not isinstance(clouds, torch.Tensor):
             if getattr(clouds, "transform", None) is not None:
                 raise ValueError("BatchFeeder: the data set has a per-item transform; the device feed has no per-item Python hook")
@@ -220,6 +230,12 @@ class BatchFeeder:
             sizes = sizes[:3]
         if len(sizes) != 3 or min(sizes) < 1:
             raise ValueError("sizes: the three sub-resolutions (optionally followed by N), got %r" % (sizes,))
+        if subsample == "fps":
+            if not sizes[0] <= sizes[1] <= sizes[2] <= self.N:
+                raise ValueError('subsample="fps": the sizes must ascend and not exceed num_point = %d (each level is a prefix of '
+                                 "the next), got %r" % (self.N, sizes))
+            if self.N > self.FPS_MAX_N:
+                raise ValueError('subsample="fps": num_point %d, the farthest-point kernel holds at most %d points' % (self.N, self.FPS_MAX_N))
         self.clouds, self.sizes = clouds, sizes
         self.S = int(clouds.shape[0])
         self.B, self.seed, self.rank, self.world, self.sigma = int(batch_size), int(seed), int(rank), int(world), float(sigma)
@@ -232,6 +248,7 @@ class BatchFeeder:
         self._order_host = torch.empty(self.S, dtype=torch.int32).pin_memory()
         self._order_epoch = None
         self._fn = _lib.lib().pdgn_feed_batch_resample if self._resample else _lib.lib().pdgn_feed_batch
+        self._fps = _lib.lib().pdgn_feed_fps_pyramid if subsample == "fps" else None
         self._check = None
 
     @classmethod
@@ -261,7 +278,7 @@ class BatchFeeder:
         self._order_epoch = epoch
 
     def fill(self, epoch, i, reals, z1, z2):
-        """Batch i (0-based) of `epoch` (1-based) into the given tensors, on the current stream: one launch."""
+        """Batch i (0-based) of `epoch` (1-based) into the given tensors, on the current stream: one launch (subsample="fps": two)."""
         from . import _lib
         key = (tuple(t.data_ptr() for t in reals), z1.data_ptr(), z2.data_ptr())
         if key != self._check:                                   # (the same static buffers every iteration: checked once)
@@ -284,3 +301,8 @@ class BatchFeeder:
                             (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B, self.sigma,
                             _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
                             _lib.stream_of(self.clouds)), "pdgn_feed_batch_resample" if self._resample else "pdgn_feed_batch")
+        if self._fps is not None:                                # the same (seed, iteration, global row) as the feed launch: its own tag
+            _lib.check(self._fps(self.B, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(reals[3]),
+                                 self.seed & 0xFFFFFFFFFFFFFFFF, (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B,
+                                 _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), None, _lib.stream_of(self.clouds)),
+                       "pdgn_feed_fps_pyramid")

@@ -262,6 +262,37 @@ def furthestsampling(xyz, m):
     return idx
 
 
+FPS_MAX_N = 8192                                                 # PDGN_FPS_MAX_N (include/pdgn_hip.h)
+
+
+def fps_order(xyz, m, start=None):
+    """Farthest-point order of xyz (b,n,3), n <= FPS_MAX_N: (b,m) int32 with order[:,0] = start (default 0) and every later entry
+    the point farthest from the ones before it, exact ties to the lowest index -- from start 0 index for index what
+    `furthestsampling` returns, computed with the cloud in registers (csrc/fps.hip: the feeder's kernel).  start: None, an int or
+    a (b,) integer tensor, every entry in [0, n) (checked here, on the host: the kernel is never handed another)."""
+    require(xyz, "xyz", F32, 3)
+    b, n, c = xyz.shape
+    m = int(m)
+    if c != 3:
+        raise ValueError("xyz must be (b,n,3), got %s" % (tuple(xyz.shape),))
+    if not 1 <= n <= FPS_MAX_N:
+        raise ValueError("fps_order: n = %d, supported 1 .. %d (furthestsampling has no limit)" % (n, FPS_MAX_N))
+    if not 1 <= m <= n:
+        raise ValueError("fps_order: m = %d, need 1 <= m <= n = %d" % (m, n))
+    if start is not None:
+        if isinstance(start, torch.Tensor):
+            if start.dtype.is_floating_point or start.dtype == torch.bool or tuple(start.shape) != (b,):
+                raise ValueError("start: an int or a (b,) integer tensor")
+            start = start.to(device=xyz.device, dtype=I32).contiguous()
+        else:
+            start = torch.full((b,), int(start), dtype=I32, device=xyz.device)
+        if b and not (0 <= int(start.min()) and int(start.max()) < n):
+            raise ValueError("start: every entry in [0, %d)" % n)
+    order = torch.empty((b, m), dtype=I32, device=xyz.device)
+    check(_lib.lib().pdgn_fps_order(b, n, m, ptr(xyz), ptr(start), ptr(order), stream_of(xyz)), "pdgn_fps_order")
+    return order
+
+
 def featuredistribute(max_xyz, xyz):
     """pointops.py:201-222: index of the nearest max_xyz (b,n,3) point for every xyz (b,m,3) point."""
     require(max_xyz, "max_xyz", F32, 3)

@@ -21,7 +21,9 @@ aug.csv beside the log, <epoch>_<category>_aug.pth beside every checkpoint pair.
 or a directory in the layout of ShapeNetCore.v2.PC15k (<synsetid>/<split>/*.npy, each (M,3)).  Clouds stored with M > --num_point points (PC15k: 15 000)
 are trained on a fresh draw of --num_point distinct points per cloud and visit, made inside the feed launch (data.BatchFeeder, pdgn_feed_batch_resample),
 from the leading --resample_pool P points (default: all M); --phase test and the reports take the LAST --num_point points of every stored cloud as
-their reference clouds (disjoint from the pool whenever P <= M - num_point).
+their reference clouds (disjoint from the pool whenever P <= M - num_point).  --subsample fps (train): the three coarse real resolutions are
+nested farthest-point subsets of the finest cloud of the same row instead of three independent with-replacement draws (data.BatchFeeder, csrc/fps.hip;
+--num_point at most 8192); --subsample random is the default and the reference's.
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -100,11 +102,14 @@ def build_parser():
     p.add_argument("--ada_p_max", type=float, default=argparse.SUPPRESS, help="upper end of p's range (default 0.8)")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
+    p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
+                   "independent draws with replacement, as the reference's loader) or fps (nested farthest-point subsets of the finest cloud, one more "
+                   "launch per iteration)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too) and --resample_pool are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool and --subsample are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -130,6 +135,7 @@ class Args(argparse.Namespace):
     ada_p_min = None
     ada_p_max = None
     resample_pool = None
+    subsample = "random"
 
 
 def parse_args(argv=None):
@@ -159,6 +165,8 @@ def parse_args(argv=None):
         p.error("--guard_max_skips must be at least one")
     if args.resample_pool is not None and args.resample_pool < args.num_point:
         p.error("--resample_pool %d: at least --num_point %d" % (args.resample_pool, args.num_point))
+    if args.subsample == "fps" and args.num_point > 8192:
+        p.error("--subsample fps: --num_point %d, the farthest-point kernel holds at most 8192 points" % args.num_point)
     given = vars(args)
     for flag in ("lr_g", "lr_d"):
         rate = getattr(args, flag)
@@ -368,7 +376,7 @@ def train(args):
     if args.resample_pool is not None and args.resample_pool > stored:
         raise SystemExit("--resample_pool %d but the clouds of %s have %d points" % (args.resample_pool, args.data_root, stored))
     feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world,
-                                      num_point=n, pool=args.resample_pool)
+                                      num_point=n, pool=args.resample_pool, subsample=args.subsample)
     try:
         trainer = make_trainer(args, device, feeder.batches_per_epoch)
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
