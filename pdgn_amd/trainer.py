@@ -5,6 +5,8 @@ statistics, gradients summed onto GPU 0.  Here: one process per GPU, local batch
 BatchNorm statistics stay local (same semantics), and gradients are all-reduced over RCCL/xGMI
 as ONE flat fp32 buffer per network (G: 50.8 MB, D1-4: 6.8 MB) -- parameters' ``.grad`` tensors
 are views into that buffer, so there is no bucket copy in or out.
+
+The epoch loop over a feeder (`PDGNTrainer.fit`) and its logs are in pdgn_amd/fit.py.
 """
 import contextlib
 import ctypes
@@ -16,11 +18,13 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib
+from . import fit as _fit
 from . import schedule as _schedule
 from . import streams as _streams
 from .fused import clear_zero_colsum, flush_bn_counters, hold_bn_counters, release_zero_arena, reset_zero_arena
 from .generator import PointDiscriminator, PointGenerator
 from . import losses
+from .fit import GUARD_RECORD_FLOATS, GradGuardError          # (defined beside the loop that reads and raises them)
 from .losses import LocalPairLoss
 
 PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))   # get_local_pair calls :232-237
@@ -238,13 +242,6 @@ def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-GUARD_RECORD_FLOATS = 8             # sizeof(pdgn_guard_record) / 4 (include/pdgn_hip.h): norm, coef, applied, found_inf, two counters, two spare
-
-
-class GradGuardError(RuntimeError):
-    """`fit` saw `guard_max_skips` consecutive skipped updates of a network: its gradients have stopped being finite."""
-
-
 class GradGuard:
     """One network's gradient guard: the device-side record that pdgn_gradnorm_multi writes from the network's
     whole gradient list and the guarded optimizer launches read, the fp64 workspace of the reduction, and the clipping bound.
@@ -281,12 +278,7 @@ class GradGuard:
                                                   self.workspace.numel(), _lib.ptr(self.record), _lib.stream_of(grads[0])),
                    "pdgn_gradnorm_multi")
 
-    @staticmethod
-    def decode(words):
-        """{norm, coef, applied, skipped} from the 8 words of a record read back as fp32 (a host tensor): the two counters are
-        the running numbers of applied and skipped updates."""
-        ints = words.contiguous().view(torch.int32)
-        return {"norm": float(words[0]), "coef": float(words[1]), "applied": int(ints[4]) & 0xffffffff, "skipped": int(ints[5]) & 0xffffffff}
+    decode = staticmethod(_fit.decode_guard_record)
 
     def state(self):
         """The record as a dict (synchronises: a device-to-host copy on the current stream)."""
@@ -661,7 +653,7 @@ class PDGNTrainer:
         self._ema_from_parameters()
         self.sync_replicas()
 
-    GUARD_KEYS = ("G", "D1", "D2", "D3", "D4")
+    GUARD_KEYS = _fit.GUARD_KEYS
 
     def guard_state(self):
         """{network: {norm, coef, applied, skipped}} for G, D1..D4: norm and clip factor of each network's LAST gradient list, and
@@ -1373,9 +1365,7 @@ class PDGNTrainer:
         return st["out"]
 
     # ---------------------------------------------------------------- the training loop (models/PDGNet_v2.py:157-269)
-    LOG_FORMAT = ("Epoch: [%2d] [%4d/%4d] time: %2dm %2ds d_loss1: %.8f d_loss2: %.8f d_loss3: %.8f d_loss4: %.8f, "
-                  "g_loss: %.8f, similar_loss: %.8f")         # :259
-    LOSS_KEYS = ("d_loss1", "d_loss2", "d_loss3", "d_loss4", "g_loss", "similar_loss")
+    LOG_FORMAT, LOSS_KEYS = _fit.LOG_FORMAT, _fit.LOSS_KEYS
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
             on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None):
@@ -1410,163 +1400,8 @@ class PDGNTrainer:
         not stored: checkpoints are what they were.  With ADAPTIVE augmentation (section 7i) `aug_log` (a path; default: aug.csv beside a
         log given as a path, else none) gets one row -- epoch, clock, p, updates, last_r, r_D1 .. r_D4 (the last update's (pos - neg) / n
         per discriminator) -- wherever lr.csv would get one.  Rank 0 only; without adaptive augmentation, no file."""
-        import time
-        if issue not in ("list", "eager"):
-            raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
-        guarded = getattr(self, "guards", None) is not None
-        if guarded and int(guard_max_skips) < 1:
-            raise ValueError("guard_max_skips must be at least one, got %r" % (guard_max_skips,))
-        sink, opened = log, None
-        if isinstance(log, (str, bytes, os.PathLike)):
-            opened = open(log, "a")
-            sink = lambda line: (opened.write(line + "\n"), opened.flush())
-        nb = feeder.batches_per_epoch
-        cuda = self.device.type == "cuda"
-        nl, nk = len(self.LOSS_KEYS), len(PDGNTrainer.GUARD_KEYS)
-        host = torch.empty(2, nl + (nk * GUARD_RECORD_FLOATS if guarded else 0), dtype=torch.float32, pin_memory=cuda)
-        done = [torch.cuda.Event() for _ in range(2)] if cuda else None
-        pending, n, start = None, 0, time.time()
-        norms_file = None
-        if guarded:
-            if grad_norms is None and isinstance(log, (str, bytes, os.PathLike)):
-                grad_norms = os.path.join(os.path.dirname(os.fspath(log)) or ".", "grad_norms.csv")
-            if grad_norms is not None and getattr(feeder, "rank", 0) == 0:
-                fresh = not os.path.exists(grad_norms) or os.path.getsize(grad_norms) == 0
-                norms_file = open(grad_norms, "a")
-                if fresh:
-                    norms_file.write(",".join(["epoch", "iter"] + ["%s_%s" % (k, f) for k in PDGNTrainer.GUARD_KEYS for f in ("norm", "coef")]
-                                              + ["skipped_total"]) + "\n")
-            skipped_before, run_of_skips = None, [0] * nk
-        rates_file, rates_epoch = None, None
-        if getattr(self, "lr_table", None) is not None or getattr(self, "per_network_lr", False):
-            if lr_log is None and isinstance(log, (str, bytes, os.PathLike)):
-                lr_log = os.path.join(os.path.dirname(os.fspath(log)) or ".", "lr.csv")
-            if lr_log is not None and getattr(feeder, "rank", 0) == 0:
-                fresh = not os.path.exists(lr_log) or os.path.getsize(lr_log) == 0
-                rates_file = open(lr_log, "a")
-                if fresh:
-                    rates_file.write(",".join(["epoch", "step_G"] + ["lr_%s" % k for k in PDGNTrainer.GUARD_KEYS]) + "\n")
-
-        ada_file, ada_epoch = None, None
-        if getattr(self, "aug", None) is not None and self.aug.adaptive is not None:
-            if aug_log is None and isinstance(log, (str, bytes, os.PathLike)):
-                aug_log = os.path.join(os.path.dirname(os.fspath(log)) or ".", "aug.csv")
-            if aug_log is not None and getattr(feeder, "rank", 0) == 0:
-                fresh = not os.path.exists(aug_log) or os.path.getsize(aug_log) == 0
-                ada_file = open(aug_log, "a")
-                if fresh:
-                    ada_file.write(",".join(["epoch", "clock", "p", "updates", "last_r"] + ["r_%s" % k for k in PDGNTrainer.GUARD_KEYS[1:]]) + "\n")
-
-        def ada_line(ep):
-            nonlocal ada_epoch
-            if ada_file is None or ada_epoch == ep:
-                return
-            ada_epoch = ep
-            state = self.aug_state()
-            a = state["ada"]
-            per = [(ps - ng) / n if n else float("nan") for ps, ng, n in a["last_net"]]
-            ada_file.write(",".join(["%d" % ep, "%d" % state["clock"], "%.17g" % a["p"], "%d" % a["updates"], "%.17g" % a["last_r"]]
-                                    + ["%.17g" % r for r in per]) + "\n")
-            ada_file.flush()
-
-        def rates_line(ep):
-            nonlocal rates_epoch
-            ada_line(ep)
-            if rates_file is None or rates_epoch == ep:          # (the last epoch's checkpoint may be written twice: one row)
-                return
-            rates_epoch = ep
-            state = self.lr_state()
-            rates_file.write(",".join(["%d" % ep, "%d" % state["G"]["step"]] + ["%.17g" % state[k]["lr"] for k in PDGNTrainer.GUARD_KEYS]) + "\n")
-            rates_file.flush()
-
-        def flush():
-            slot, ep, idx = pending
-            if cuda:
-                done[slot].synchronize()
-            dt = time.time() - start
-            if sink is not None:
-                sink(self.LOG_FORMAT % ((ep, idx + 1, nb, dt / 60, dt % 60) + tuple(host[slot, :nl].tolist())))
-            if guarded:
-                guard_line(ep, idx, [GradGuard.decode(host[slot, nl + i * GUARD_RECORD_FLOATS:nl + (i + 1) * GUARD_RECORD_FLOATS]) for i in range(nk)])
-
-        def guard_line(ep, idx, recs):
-            nonlocal skipped_before
-            if norms_file is not None:
-                norms_file.write(",".join(["%d" % ep, "%d" % (idx + 1)] + ["%.9g" % r[f] for r in recs for f in ("norm", "coef")]
-                                          + ["%d" % sum(r["skipped"] for r in recs)]) + "\n")
-                norms_file.flush()
-            now = [r["skipped"] for r in recs]
-            if skipped_before is not None:                       # (the first line has nothing to compare with: capture_list's warm-up
-                for i in range(nk):                              #  iterations, an earlier fit, have counted too)
-                    run_of_skips[i] = run_of_skips[i] + 1 if now[i] != skipped_before[i] else 0
-            else:
-                for i in range(nk):
-                    run_of_skips[i] = 1 if recs[i]["applied"] + recs[i]["skipped"] > 0 and PDGNTrainer._last_skipped(recs[i]) else 0
-            skipped_before = now
-            worst = max(range(nk), key=lambda i: run_of_skips[i])
-            if run_of_skips[worst] >= int(guard_max_skips):
-                where = ""
-                if checkpoint_dir is not None and getattr(feeder, "rank", 0) == 0:
-                    where = "; checkpoint of the last finite parameters: " + self.save(checkpoint_dir, ep, category)[0]
-                raise GradGuardError("gradient guard: %s skipped %d consecutive updates (epoch %d, iteration %d): its gradients are "
-                                     "not finite%s" % (PDGNTrainer.GUARD_KEYS[worst], run_of_skips[worst], ep, idx + 1, where))
-
-        try:
-            if issue == "eager" or getattr(self, "_list", None) is None:
-                reals, z1, z2 = feeder.buffers()
-            if issue == "list" and getattr(self, "_list", None) is None and start_epoch <= epochs:
-                feeder.fill(start_epoch, 0, reals, z1, z2)
-                self.capture_list(reals, z1, z2)
-            if issue == "list":
-                st = self._static
-                reals, z1, z2 = st["reals"], st["z1"], st["z2"]
-            if getattr(self, "aug", None) is not None:
-                # iteration i of epoch e always draws at (e - 1) * nb + i, the feeder's global iteration: set behind capture_list's
-                # warm-up iterations (they tick too), so that a resumed epoch draws what the uninterrupted run drew
-                self.aug.set_clock((start_epoch - 1) * nb)
-            for epoch in range(start_epoch, epochs + 1):
-                for i in range(nb):
-                    feeder.fill(epoch, i, reals, z1, z2)
-                    out = self.step_list() if issue == "list" else self.step(reals, z1, z2)
-                    if sink is not None or guarded:
-                        slot = n & 1
-                        row = torch.stack([out[k] for k in self.LOSS_KEYS])
-                        host[slot].copy_(torch.cat([row, self.guard_buf.view(-1)]) if guarded else row, non_blocking=True)
-                        if cuda:
-                            done[slot].record(torch.cuda.current_stream(self.device))
-                        if pending is not None:
-                            flush()
-                        pending = (slot, epoch, i)
-                        n += 1
-                        if guarded and max(run_of_skips) >= int(guard_max_skips) - 1:
-                            flush()                              # one skip short of the end: this iteration's line now, not behind the next
-                            pending = None
-                if checkpoint_dir is not None and epoch % snapshot == 0 and getattr(feeder, "rank", 0) == 0:
-                    self.save(checkpoint_dir, epoch, category)
-                    rates_line(epoch)
-                if on_epoch is not None:
-                    on_epoch(epoch)
-                    rates_line(epoch)
-            if pending is not None:
-                flush()
-            if checkpoint_dir is not None and getattr(feeder, "rank", 0) == 0:
-                self.save(checkpoint_dir, epochs, category)           # (:268: always, whatever the snapshot period)
-                rates_line(epochs)
-        finally:
-            if opened is not None:
-                opened.close()
-            if norms_file is not None:
-                norms_file.close()
-            if rates_file is not None:
-                rates_file.close()
-            if ada_file is not None:
-                ada_file.close()
-        return epochs
-
-    @staticmethod
-    def _last_skipped(rec):
-        """Whether the record's LAST gradient list was not finite (norm is Inf or NaN exactly then)."""
-        return not (rec["norm"] == rec["norm"] and abs(rec["norm"]) != float("inf"))
+        return _fit.fit(self, feeder, epochs, start_epoch, snapshot, checkpoint_dir, category, issue, log, on_epoch, guard_max_skips,
+                        grad_norms, lr_log, aug_log)
 
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()

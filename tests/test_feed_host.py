@@ -1,6 +1,6 @@
 """CPU: the training feed's host side -- the Philox mirror against the published known answers, the epoch permutation, the
-(rank, world) schedule, the index draws, PDGNTrainer.fit's control flow on a recording trainer, the command line, and the
-exported entry point's host-side argument checks."""
+(rank, world) schedule, the index draws, the command line, and the exported entry point's host-side argument checks
+(PDGNTrainer.fit's control flow on a recording trainer: tests/test_fit_host.py)."""
 import ctypes
 import os
 import re
@@ -102,109 +102,6 @@ def test_normals_formula():
     assert abs(z.mean()) < 5 * 0.2 / np.sqrt(n) and abs(z.std() - 0.2) < 5 * 0.2 / np.sqrt(2 * n)
     assert np.isfinite(z).all()
     assert np.abs(fm.normals_from_words(w, 0.2, np.float32) - z).max() < 1e-6
-
-
-# ---------------------------------------------------------------------------- fit
-class RecordingTrainer:
-    """What PDGNTrainer.fit touches, recorded."""
-    device = torch.device("cpu")
-
-    def __init__(self, B, sizes, loaded_epoch=None):
-        from pdgn_amd.trainer import PDGNTrainer
-        self.LOG_FORMAT, self.LOSS_KEYS = PDGNTrainer.LOG_FORMAT, PDGNTrainer.LOSS_KEYS
-        self.calls, self.saves, self.fed = [], [], []
-        self.B, self.sizes = B, sizes
-        self._list, self._static = None, None
-
-    def capture_list(self, reals, z1, z2):
-        self.calls.append(("capture_list",))
-        self._static = {"reals": [r.clone() for r in reals], "z1": z1.clone(), "z2": z2.clone()}
-        self._list = object()
-        return self
-
-    def _losses(self, z1):
-        self.fed.append(z1.clone())
-        return {k: torch.tensor(float(len(self.fed)) + 0.125 * j) for j, k in enumerate(self.LOSS_KEYS)}
-
-    def step_list(self, *args, **kw):
-        self.calls.append(("step_list", args, kw))
-        return self._losses(self._static["z1"])
-
-    def step(self, reals, z1, z2):
-        self.calls.append(("step", len(reals)))
-        return self._losses(z1)
-
-    def save(self, checkpoint_dir, epoch, category="chair"):
-        self.saves.append((checkpoint_dir, epoch, category))
-
-
-class HostFeeder(fm.MirrorFeeder):
-    def buffers(self):
-        new = lambda *s: torch.empty(*s, dtype=torch.float32)
-        return [new(self.B, 3, r) for r in self.sizes + (self.N,)], new(self.B, 128), new(self.B, 128)
-
-
-REF_LINE = re.compile(r"^Epoch: \[ *(\d+)\] \[ *(\d+)/ *(\d+)\] time: +\d+m +\d+s d_loss1: (-?\d+\.\d{8}) d_loss2: (-?\d+\.\d{8}) "
-                      r"d_loss3: (-?\d+\.\d{8}) d_loss4: (-?\d+\.\d{8}), g_loss: (-?\d+\.\d{8}), similar_loss: (-?\d+\.\d{8})$")
-
-
-def _fit(**kw):
-    from pdgn_amd.trainer import PDGNTrainer
-    B, N, sizes = 4, 32, (4, 8, 16)
-    S = 3 * B + 1
-    clouds = np.random.default_rng(1).standard_normal((S, N, 3)).astype(np.float32)
-    feeder = HostFeeder(clouds, B, sizes, seed=17)
-    tr = RecordingTrainer(B, sizes)
-    lines = []
-    last = PDGNTrainer.fit(tr, feeder, log=lines.append, **kw)
-    return tr, feeder, lines, last
-
-
-def test_fit_list_steps_snapshots_and_log():
-    from pdgn_amd.trainer import PDGNTrainer
-    assert PDGNTrainer.LOG_FORMAT == ("Epoch: [%2d] [%4d/%4d] time: %2dm %2ds d_loss1: %.8f d_loss2: %.8f d_loss3: %.8f "
-                                      "d_loss4: %.8f, g_loss: %.8f, similar_loss: %.8f")        # models/PDGNet_v2.py:259
-    tr, feeder, lines, last = _fit(epochs=5, snapshot=2, checkpoint_dir="ck", category="chair")
-    assert last == 5
-    steps = [c for c in tr.calls if c[0] == "step_list"]
-    assert len(steps) == 5 * 3 and not any(c[0] == "step" for c in tr.calls)
-    assert all(c[1] == () and c[2] == {} for c in steps)                       # step_list() without tensors
-    assert tr.calls[0] == ("capture_list",) and sum(c[0] == "capture_list" for c in tr.calls) == 1
-    assert tr.saves == [("ck", 2, "chair"), ("ck", 4, "chair"), ("ck", 5, "chair")]   # snapshots + the final save
-    assert len(lines) == 15
-    for n, line in enumerate(lines):
-        m = REF_LINE.match(line)
-        assert m, line
-        assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (n // 3 + 1, n % 3 + 1, 3)
-        assert float(m.group(4)) == n + 1 and float(m.group(9)) == n + 1 + 0.625       # iteration n's own losses, in order
-    # what the step read is the mirror's batch of that iteration
-    for n, z in enumerate(tr.fed):
-        assert np.array_equal(z.numpy(), feeder.batch(n // 3 + 1, n % 3)[1].astype(np.float32))
-
-
-def test_fit_resume_starts_at_the_loaded_epoch():
-    tr, feeder, lines, last = _fit(epochs=4, start_epoch=3, snapshot=20, checkpoint_dir="ck")
-    assert last == 4 and len(lines) == 2 * 3
-    assert [int(REF_LINE.match(l).group(1)) for l in lines] == [3, 3, 3, 4, 4, 4]
-    assert tr.saves == [("ck", 4, "chair")]
-    assert np.array_equal(tr.fed[0].numpy(), feeder.batch(3, 0)[1].astype(np.float32))
-    # no checkpoint directory: nothing is saved; on_epoch sees every epoch
-    seen = []
-    tr, _, _, _ = _fit(epochs=2, snapshot=1, on_epoch=seen.append)
-    assert tr.saves == [] and seen == [1, 2]
-
-
-def test_fit_eager_and_log_to_a_path(tmp_path):
-    from pdgn_amd.trainer import PDGNTrainer
-    tr, feeder, lines, last = _fit(epochs=1, issue="eager")
-    assert [c[0] for c in tr.calls] == ["step"] * 3 and len(lines) == 3
-    path = tmp_path / "log_info.txt"
-    tr = RecordingTrainer(4, (4, 8, 16))
-    PDGNTrainer.fit(tr, feeder, 2, log=str(path))
-    got = path.read_text().splitlines()
-    assert len(got) == 6 and all(REF_LINE.match(l) for l in got)
-    with pytest.raises(ValueError):
-        PDGNTrainer.fit(tr, feeder, 1, issue="graph")
 
 
 # ---------------------------------------------------------------------------- the feeder's own checks
