@@ -49,6 +49,9 @@ __global__ __launch_bounds__(WGS_THREADS) void wgs_fwd_kernel(
 // take ids of one residue class, consecutive in launch order, and the re-reads hit that XCD's L2.
 #define WGS_CW 16          // default chunk width in float4 (64 channels); kernels are templated on it
 #define WGS_XU 4          // rows in flight per thread: all their index loads, then all their row loads
+#define WGS_BU 4          // adjoint at a chunk width of 64: in-edges whose row loads (up to min(T, P) each) a wave issues before it adds
+#define WGS_BU1 8         // ... where P = 1 (one row per in-edge)
+#define WGS_BUC 5         // ... and centre rows
 // Addressing: everything a task touches lies in ONE sample's slabs of Y / idx / out (tens of MB), so the kernels of this
 // mapping use raw buffer descriptors (scalar base per sample) with 32-bit byte offsets built from 24-bit multiplies, and
 // the row -> (point, position) split is one multiply-high by a host-computed reciprocal.  (The first version computed a
@@ -546,14 +549,17 @@ __global__ __launch_bounds__(WGS_THREADS) void wgs_bwd_csr_xcd_kernel(
     float *__restrict__ dY, unsigned *__restrict__ max_out) {
     typedef wgs_vec_t vec_t;
     constexpr int MAXT = TT ? TT : 8, JB = WGS_THREADS / 64, WGS_EL = 64 / CW;   // source points per block; edge lanes per column
+    constexpr bool WIDE = CW == 64;                           // one column group per lane: the wave-wide body below
     const int seq = blockIdx.x >> 3;
     const int task = (seq / bpt) * 8 + (blockIdx.x & 7);
     if (task >= ntasks) return;
     const int b = task / nchunk, chunk = task - b * nchunk;
     const int lane = threadIdx.x & 63, cvl = lane % CW, el = lane / CW;
     const int cv = chunk * CW + cvl;
-    const int j = (seq % bpt) * JB + (threadIdx.x >> 6);
-    if (j >= n) return;                                        // wave-uniform
+    const int jv = (seq % bpt) * JB + (threadIdx.x >> 6);
+    int j = jv;                                                // wave-uniform
+    if constexpr (WIDE) j = __builtin_amdgcn_readfirstlane(jv);   // (the scalar unit is told so)
+    if (j >= n) return;
     const bool cok = cv < CV;
     // one sample's slabs through buffer descriptors, 32-bit offsets (see wgs_fwd_xcd_kernel)
     const unsigned C4 = (unsigned)CV * 16u, PC4 = (unsigned)P * C4, cb = (unsigned)(cok ? cv : 0) * 16u, ldy4 = (unsigned)ldy * 4u;
@@ -565,43 +571,132 @@ __global__ __launch_bounds__(WGS_THREADS) void wgs_bwd_csr_xcd_kernel(
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) acc[t] = zero;
     const int e0 = rowptr[(long long)b * (n + 1) + j], e1 = rowptr[(long long)b * (n + 1) + j + 1];
-    for (int q = e0 + el; q < e1; q += 2 * WGS_EL) {           // this lane's edges, two at a time
-        const bool two = q + WGS_EL < e1;
-        const unsigned ra = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, q * 4, 0, 0);
-        const unsigned rb = two ? (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, (q + WGS_EL) * 4, 0, 0) : 0u;
-        const unsigned oa = wgs_mul24(ra >> 5, PC4) + cb, ob = wgs_mul24(rb >> 5, PC4) + cb;
-        const int sa = ra & 31, sb = two ? (int)(rb & 31) : -64;
-        vec_t va[MAXT], vb[MAXT];
-#pragma unroll
-        for (int t = 0; t < MAXT; ++t) {
-            const int pa = sa - t, pb = sb - t;                // out-of-window taps issue no load (exec-masked)
-            va[t] = ((TT || t < T) && pa >= 0 && pa < P) ? wgs_ld4(rsD, oa + wgs_mul24(pa, C4), 0) : zero;
-            vb[t] = ((TT || t < T) && pb >= 0 && pb < P) ? wgs_ld4(rsD, ob + wgs_mul24(pb, C4), 0) : zero;
-        }
-#pragma unroll
-        for (int t = 0; t < MAXT; ++t) acc[t] += va[t] + vb[t];
-    }
     vec_t ctr = zero;
-    if (offc >= 0)                                             // centre columns: the point's own P windows, split too
-        for (int p = el; p < P; p += WGS_EL) ctr += wgs_ld4(rsD, wgs_mul24(j, PC4) + wgs_mul24(p, C4) + cb, 0);
-    // sum over the four edge lanes (lanes l, l+16, l+32, l+48): afterwards every lane holds the totals
+    if constexpr (WIDE) {
+        // The wave is one column group wide, so an in-edge is wave-uniform: the records are loaded once, 64 at a time (lane l holds
+        // record q0 + l), and broadcast one by one into scalars -- the row's byte offset goes into the loads' scalar offset, the
+        // tap window is a scalar branch.  The row loads of WGS_BU edges (WGS_BU1 where P = 1: one load per edge) are all issued
+        // before the first add; the centre rows are fetched while the first records are on their way.  Lanes past the list
+        // hold slot 31, which lies outside every window (T + P - 1 <= k <= 31).
+        const int Tn = TT ? TT : T;
+        int q0 = e0;
+        unsigned rec = q0 + lane < e1 ? (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, lane * 4, q0 * 4, 0) : 31u;
+        if (offc >= 0) {
+            const unsigned sj = (unsigned)j * PC4;
+            for (int p0 = 0; p0 < P; p0 += WGS_BUC) {
+                vec_t c[WGS_BUC];
 #pragma unroll
-    for (int t = 0; t < MAXT; ++t)
-        if (TT || t < T) {
+                for (int u = 0; u < WGS_BUC; ++u)
+                    if (p0 + u < P) c[u] = wgs_ld4(rsD, cb, sj + (unsigned)(p0 + u) * C4);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v = acc[t][i];
-#pragma unroll
-                for (int m = CW; m < 64; m <<= 1) v += __shfl_xor(v, m);
-                acc[t][i] = v;
+                for (int u = 0; u < WGS_BUC; ++u)
+                    if (p0 + u < P) ctr += c[u];
             }
         }
+        while (q0 < e1) {
+            const int cnt = min(64, e1 - q0);
+            if (MAXT > 8 && P == 1) {                          // (conv2) an edge feeds the one tap t = s: WGS_BU1 rows in flight
+                for (int g = 0; g < cnt; g += WGS_BU1) {
+                    int s[WGS_BU1];
+                    vec_t v[WGS_BU1];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float v = ctr[i];
+                    for (int u = 0; u < WGS_BU1; ++u) {
+                        const unsigned r = (unsigned)__builtin_amdgcn_readlane((int)rec, g + u);
+                        s[u] = (int)(r & 31u);
+                        if (s[u] < Tn) v[u] = wgs_ld4(rsD, cb, (r >> 5) * C4);
+                    }
 #pragma unroll
-        for (int m = CW; m < 64; m <<= 1) v += __shfl_xor(v, m);
-        ctr[i] = v;
+                    for (int u = 0; u < WGS_BU1; ++u)
+#pragma unroll
+                        for (int t = 0; t < MAXT; ++t)
+                            if (s[u] == t && t < Tn) {
+                                asm volatile("" ::: "memory");   // keeps the scalar branch (if-converted, <10, 64> held 385 v_cndmask_b32 and 208 registers; so: 25, 128)
+                                acc[t] += v[u];
+                            }
+                }
+            } else {                                           // taps max(0, s-P+1) .. min(T-1, s), row s - t each
+                constexpr int UG = MAXT <= 6 ? WGS_BU : 2;
+                if constexpr (MAXT > 8) {                      // (ten taps with P > 1: no shape of the model; one row at a time)
+                    for (int g = 0; g < cnt; ++g) {
+                        const unsigned r = (unsigned)__builtin_amdgcn_readlane((int)rec, g);
+                        const int s = (int)(r & 31u), lo = max(0, s - P + 1), hi = min(Tn - 1, s);
+                        const unsigned so = (r >> 5) * PC4 + (unsigned)s * C4;
+#pragma unroll
+                        for (int t = 0; t < MAXT; ++t)
+                            if (t >= lo && t <= hi) {
+                                asm volatile("" ::: "memory");
+                                acc[t] += wgs_ld4(rsD, cb, so - (unsigned)t * C4);
+                            }
+                    }
+                } else
+                for (int g = 0; g < cnt; g += UG) {
+                    int lo[UG], hi[UG];
+                    unsigned so[UG];
+                    vec_t v[UG][MAXT];
+#pragma unroll
+                    for (int u = 0; u < UG; ++u) {
+                        const unsigned r = (unsigned)__builtin_amdgcn_readlane((int)rec, g + u);
+                        const int s = (int)(r & 31u);
+                        lo[u] = max(0, s - P + 1);
+                        hi[u] = min(Tn - 1, s);
+                        so[u] = (r >> 5) * PC4 + (unsigned)s * C4;
+                    }
+#pragma unroll
+                    for (int u = 0; u < UG; ++u)
+#pragma unroll
+                        for (int t = 0; t < MAXT; ++t)
+                            if (t >= lo[u] && t <= hi[u]) v[u][t] = wgs_ld4(rsD, cb, so[u] - (unsigned)t * C4);
+#pragma unroll
+                    for (int u = 0; u < UG; ++u)
+#pragma unroll
+                        for (int t = 0; t < MAXT; ++t)
+                            if (t >= lo[u] && t <= hi[u]) {
+                                asm volatile("" ::: "memory");   // (a branch again: a select would read rows that were never loaded)
+                                acc[t] += v[u][t];
+                            }
+                }
+            }
+            q0 += 64;
+            if (q0 < e1) rec = q0 + lane < e1 ? (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, lane * 4, q0 * 4, 0) : 31u;
+        }
+    } else {
+        for (int q = e0 + el; q < e1; q += 2 * WGS_EL) {           // this lane's edges, two at a time
+            const bool two = q + WGS_EL < e1;
+            const unsigned ra = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, q * 4, 0, 0);
+            const unsigned rb = two ? (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsE, (q + WGS_EL) * 4, 0, 0) : 0u;
+            const unsigned oa = wgs_mul24(ra >> 5, PC4) + cb, ob = wgs_mul24(rb >> 5, PC4) + cb;
+            const int sa = ra & 31, sb = two ? (int)(rb & 31) : -64;
+            vec_t va[MAXT], vb[MAXT];
+#pragma unroll
+            for (int t = 0; t < MAXT; ++t) {
+                const int pa = sa - t, pb = sb - t;                // out-of-window taps issue no load (exec-masked)
+                va[t] = ((TT || t < T) && pa >= 0 && pa < P) ? wgs_ld4(rsD, oa + wgs_mul24(pa, C4), 0) : zero;
+                vb[t] = ((TT || t < T) && pb >= 0 && pb < P) ? wgs_ld4(rsD, ob + wgs_mul24(pb, C4), 0) : zero;
+            }
+#pragma unroll
+            for (int t = 0; t < MAXT; ++t) acc[t] += va[t] + vb[t];
+        }
+        if (offc >= 0)                                             // centre columns: the point's own P windows, split too
+            for (int p = el; p < P; p += WGS_EL) ctr += wgs_ld4(rsD, wgs_mul24(j, PC4) + wgs_mul24(p, C4) + cb, 0);
+        // sum over the four edge lanes (lanes l, l+16, l+32, l+48): afterwards every lane holds the totals
+#pragma unroll
+        for (int t = 0; t < MAXT; ++t)
+            if (TT || t < T) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float v = acc[t][i];
+#pragma unroll
+                    for (int m = CW; m < 64; m <<= 1) v += __shfl_xor(v, m);
+                    acc[t][i] = v;
+                }
+            }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float v = ctr[i];
+#pragma unroll
+            for (int m = CW; m < 64; m <<= 1) v += __shfl_xor(v, m);
+            ctr[i] = v;
+        }
     }
     if (cok) {
         const unsigned oj = wgs_mul24(j, ldy4) + cb;
