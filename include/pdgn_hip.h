@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 36
+#define PDGN_ABI_VERSION 37
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -807,7 +807,8 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
  *   key     = (seed low 32, seed high 32)
  *   counter = (group j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8)
  *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order;
- *             6: the round keys of pdgn_feed_batch_resample, 7: the start index of pdgn_feed_fps_pyramid, both below)
+ *             6: the round keys of pdgn_feed_batch_resample, 7: the start index of pdgn_feed_fps_pyramid, 8 .. 11: the surface draws
+ *             of pdgn_feed_batch_mesh, 12: pdgn_sample_surface, all below)
  * A group is the four output words of one counter.  Index streams: word e of group j is column 4j + e, i = (word * N) >> 32
  * (bias of a point's probability at most N / 2^32 relative: 4.8e-7 at N = 2048).  Noise: group j gives columns 4j .. 4j+3 as
  * two Box-Muller pairs (words 0,1 and 2,3): u1 = ((w >> 8) + 1) * 2^-24 in (0, 1], u2 = (w' >> 8) * 2^-24 in [0, 1),
@@ -848,6 +849,44 @@ int pdgn_feed_batch(int B, int S, int N, int r1, int r2, int r3, const float *da
 int pdgn_feed_batch_resample(int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
                              long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1,
                              float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
+/* The same launch for shapes stored as TRIANGLE MESHES (the form ShapeNetCore is distributed in; no reference counterpart: the
+ * reference trains on a pre-sampled file): every output column of every resolution is a fresh i.i.d. point of the surface of the
+ * row's shape.  A mesh set is four device arrays:
+ *   verts    (V,3) float     the vertices of all S shapes, concatenated
+ *   faces    (F,3) int32     GLOBAL vertex indices
+ *   face_off (S+1) int32     shape c owns the faces [face_off[c], face_off[c+1]), F_c of them, F_c >= 1
+ *   alias    (F,2) uint32    per face the record (threshold, alias) of its shape's alias table (Walker 1977 / Vose 1991), alias a face
+ *                            index LOCAL to the shape; 8-byte aligned: one 8-byte load serves a draw
+ * Local row b takes shape c = order[first + b] (clamped as pdgn_feed_batch clamps).  Column j of resolution k (k = 0 .. 3: p1 .. p4)
+ * uses the four words w0 .. w3 of ONE Philox4x32-10 call, key (seed low 32, seed high 32),
+ *   counter = (j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8),  tag = 8 + k:
+ *   face     s = (w0 * F_c) >> 32;  f = w1 < alias[face_off[c] + s].threshold ? s : alias[face_off[c] + s].alias        (local to c)
+ *   inside   a = w2 >> 8, b = w3 >> 8;  if a + b > 2^24: a = 2^24 - a, b = 2^24 - b;  u = a * 2^-24, v = b * 2^-24
+ *            (integers up to 2^24: every value is exact in fp32, the fold cannot round; u, v >= 0 and u + v <= 1 exactly)
+ *   point    per coordinate, with (v0, v1, v2) the vertices of face f:  e1 = v1 - v0, e2 = v2 - v0,  p = (v0 + u * e1) + v * e2,
+ *            every operation rounded to fp32 on its own (never contracted to a fused multiply-add).
+ * A face is drawn with probability area / the shape's area up to the table's quantisation (thresholds are 32-bit: 2^-31 in total
+ * variation) and the bias of the slot draw (F_c / 2^32 relative); a face of threshold 0 that is nobody's alias is never drawn.  The four
+ * resolutions are independent draws (the mesh analogue of the reference's independent with-replacement sub-samplings).  z1, z2: exactly
+ * what pdgn_feed_batch writes for the same (seed, t, row0, sigma) (tags 3 4).  face_rec (B, r1 + r2 + r3 + N) int32, nullable
+ * (tests; NULL in production): the GLOBAL face index drawn for every output column, in the order p1 p2 p3 p4.  One thread owns four
+ * consecutive columns of one resolution (16-byte stores per channel where the row length is a multiple of 4 and the base 16-byte
+ * aligned); four dependent gathers per point (face_off, alias, faces, verts); no LDS, no atomics.  The kernel TRUSTS the table:
+ * F_c >= 1, vertex indices inside [0, V), alias < F_c are the caller's to guarantee (pdgn_amd.meshes.MeshSet does).
+ * PDGN_ERR_INVALID: pdgn_feed_batch's cases, a null verts / faces / face_off / alias, S < 1, V < 1, F < S, 3 F or 3 V beyond the int
+ * range, alias not 8-byte aligned (the others, face_rec included: 4 bytes); checked on the host before anything is launched. */
+int pdgn_feed_batch_mesh(int B, int S, int V, int F, int N, int r1, int r2, int r3, const float *verts, const int32_t *faces,
+                         const int32_t *face_off, const uint32_t *alias, const int32_t *order, long long first, unsigned long long seed,
+                         unsigned long long t, long long row0, float sigma, float *p1, float *p2, float *p3, float *p4, float *z1,
+                         float *z2, int32_t *face_rec, pdgn_stream_t stream);
+
+/* The same draw as an op (held-out and evaluation clouds): out (S,n,3) point-major, out[s, j] a point of the surface of shape s by
+ * the construction above from the counter (j, s, draw low 32, 12 | (draw >> 32 & 0xffffff) << 8): tag 12 keeps these streams apart
+ * from every training draw of the same seed.  face_rec (S,n) int32, nullable: the global face index of every point.
+ * PDGN_ERR_INVALID: S < 1, n < 1, a null or misaligned mesh pointer (as above) or out (4 bytes). */
+int pdgn_sample_surface(int S, int n, const float *verts, const int32_t *faces, const int32_t *face_off, const uint32_t *alias,
+                        unsigned long long seed, unsigned long long draw, float *out, int32_t *face_rec, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ farthest-point sampling, register resident (csrc/fps.hip)
  * The iteration of furthestsampling_cuda_launcher (lib/pointops/src/sampling/sampling_cuda_kernel.cu:59-168; pdgn_furthestsampling

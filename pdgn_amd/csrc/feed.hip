@@ -14,6 +14,12 @@
 // cloud's leading P points per row and iteration -- column j takes point pi(j), pi a keyed Feistel permutation of [0, P)
 // (construction in include/pdgn_hip.h; mirror: tests/resample_mirror.py) -- four 12-byte gathers per thread instead of 48
 // contiguous bytes; the sub-resolutions draw from the pool, the noise is pdgn_feed_batch's.
+//
+// pdgn_feed_batch_mesh / pdgn_sample_surface: the same launch for shapes stored as triangle meshes.  Every output column is a fresh
+// point of the row's surface: ONE Philox call per column picks a face through the shape's alias table (one 8-byte load: area-
+// proportional) and a point inside it (folded barycentric coordinates, exact in fp32); four dependent gathers per point (face_off,
+// alias record, face, vertices) instead of one, no LDS, no atomics; the noise is pdgn_feed_batch's (construction in
+// include/pdgn_hip.h; mirror: tests/mesh_mirror.py).
 #include "common.h"
 #include "philox.h"                                             // philox4x32_10, box_muller (shared with augment.hip)
 
@@ -23,6 +29,8 @@
 #define FEED_TAG_Z2 4u
 #define FEED_TAG_PERM 6u                                        // the round keys of the resampling permutation
 #define FEED_PERM_ROUNDS 6
+#define FEED_TAG_MESH 8u                                        // 8 .. 11: the surface draws of p1 .. p4 (pdgn_feed_batch_mesh)
+#define FEED_TAG_SURFACE 12u                                    // pdgn_sample_surface
 
 struct FeedArgs {
     int S, N, r[3];
@@ -52,6 +60,17 @@ __device__ __forceinline__ void store4(float *dst, int cols, bool vec, float a, 
     }
 }
 
+// group j of z1 (which = 0) / z2 (1) of local row b: columns 4j .. 4j+3, two Box-Muller pairs (every feed kernel's noise)
+__device__ __forceinline__ void feed_noise_group(int j, int which, int b, unsigned row, unsigned t_lo, unsigned t_hi24, unsigned k0, unsigned k1,
+                                                 float sigma, float *z) {
+    unsigned w[4];
+    philox4x32_10((unsigned)j, row, t_lo, (which ? FEED_TAG_Z2 : FEED_TAG_Z1) | (t_hi24 << 8), k0, k1, w);
+    float n0, n1, n2, n3;
+    box_muller(w[0], w[1], sigma, n0, n1);
+    box_muller(w[2], w[3], sigma, n2, n3);
+    *reinterpret_cast<float4 *>(z + (size_t)b * FEED_NOISE_DIM + 4 * j) = make_float4(n0, n1, n2, n3);   // (128 floats per row: 16-byte aligned whenever the base is; checked on the host)
+}
+
 // one pass of the Feistel network over [0, 2^(2h)): a bijection for any round function
 __device__ __forceinline__ unsigned feistel_pass(unsigned x, int h, const unsigned key[FEED_PERM_ROUNDS]) {
     unsigned L = x >> h, R = x & ((1u << h) - 1u);
@@ -74,12 +93,7 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
     unsigned w[4];
     if (q >= a.g[4]) {                                           // ---- noise: group j of z1 / z2 -> columns 4j .. 4j+3
         const int which = q >= a.g[5];
-        const int j = q - a.g[4 + which];
-        philox4x32_10((unsigned)j, row, a.t_lo, (which ? FEED_TAG_Z2 : FEED_TAG_Z1) | (a.t_hi24 << 8), a.k0, a.k1, w);
-        float n0, n1, n2, n3;
-        box_muller(w[0], w[1], a.sigma, n0, n1);
-        box_muller(w[2], w[3], a.sigma, n2, n3);
-        *reinterpret_cast<float4 *>(a.z[which] + (size_t)b * FEED_NOISE_DIM + 4 * j) = make_float4(n0, n1, n2, n3);   // (128 floats per row: 16-byte aligned whenever the base is; checked on the host)
+        feed_noise_group(q - a.g[4 + which], which, b, row, a.t_lo, a.t_hi24, a.k0, a.k1, a.sigma, a.z[which]);
         return;
     }
     const int c = min(max(a.order[a.first + b], 0), a.S - 1);    // (a permutation of [0, S) by contract; clamped so that a bad one cannot read outside data)
@@ -142,18 +156,23 @@ __global__ __launch_bounds__(FEED_THREADS) void feed_batch_kernel(FeedArgs a) {
         store4(dst + (size_t)ch * r, cols, (a.vec >> k) & 1, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
 }
 
+// what every feed entry point refuses (host-side checks only: nothing here touches the device)
+static bool feed_args_invalid(int B, int S, int N, int r1, int r2, int r3, const int32_t *order, long long first, long long row0,
+                              const float *p1, const float *p2, const float *p3, const float *p4, const float *z1, const float *z2) {
+    if (B <= 0 || B > 65535 || S <= 0 || N <= 0 || r1 <= 0 || r2 <= 0 || r3 <= 0) return true;
+    if (first < 0 || first > (long long)S - B) return true;                                   // first + B > S
+    if (row0 < 0 || row0 + B > 0x100000000LL) return true;                                    // the global row is one 32-bit counter word
+    if (!order || !p1 || !p2 || !p3 || !p4 || !z1 || !z2) return true;
+    if ((((uintptr_t)z1 | (uintptr_t)z2) & 15) || (((uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)p4) & 3)) return true;
+    return (long long)r1 + r2 + r3 + N > 0x7fffff00LL;
+}
+
 static int feed_launch(bool resample, int B, int S, int M, int P, int N, int r1, int r2, int r3, const float *data, const int32_t *order,
                        long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
                        float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
-    // host-side checks only: nothing here touches the device
-    if (B <= 0 || B > 65535 || S <= 0 || N <= 0 || r1 <= 0 || r2 <= 0 || r3 <= 0) return PDGN_ERR_INVALID;
-    if (N > P || P > M) return PDGN_ERR_INVALID;
-    if (first < 0 || first > (long long)S - B) return PDGN_ERR_INVALID;                       // first + B > S
-    if (row0 < 0 || row0 + B > 0x100000000LL) return PDGN_ERR_INVALID;                        // the global row is one 32-bit counter word
-    if (!data || !order || !p1 || !p2 || !p3 || !p4 || !z1 || !z2) return PDGN_ERR_INVALID;
-    if ((((uintptr_t)z1 | (uintptr_t)z2) & 15) || (((uintptr_t)data | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)p4) & 3))
-        return PDGN_ERR_INVALID;
-    if ((long long)M > 0x7fffffffLL / 3 || (long long)r1 + r2 + r3 + N > 0x7fffff00LL) return PDGN_ERR_INVALID;
+    if (feed_args_invalid(B, S, N, r1, r2, r3, order, first, row0, p1, p2, p3, p4, z1, z2)) return PDGN_ERR_INVALID;
+    if (N > P || P > M || !data || ((uintptr_t)data & 3)) return PDGN_ERR_INVALID;
+    if ((long long)M > 0x7fffffffLL / 3) return PDGN_ERR_INVALID;
     FeedArgs a;
     a.S = S, a.N = N, a.r[0] = r1, a.r[1] = r2, a.r[2] = r3;
     a.M = M, a.P = P;
@@ -197,4 +216,182 @@ extern "C" int pdgn_feed_batch_resample(int B, int S, int M, int P, int N, int r
                                         long long first, unsigned long long seed, unsigned long long t, long long row0, float sigma,
                                         float *p1, float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
     return feed_launch(true, B, S, M, P, N, r1, r2, r3, data, order, first, seed, t, row0, sigma, p1, p2, p3, p4, z1, z2, stream);
+}
+
+// ---------------------------------------------------------------------------- triangle meshes
+struct MeshRef {
+    const float *verts;                                          // (V,3), every shape's vertices
+    const int *faces;                                            // (F,3), global vertex indices
+    const int *face_off;                                         // (S+1)
+    const uint2 *alias;                                          // (F): (threshold, alias local to the shape)
+};
+
+// One point of the surface of the shape that owns the faces [base, base + Fc), from the four words of one Philox call: the face by
+// the alias table (w0: the slot, w1: against its threshold), the point by folded barycentric coordinates (w2, w3).  Every float
+// operation is rounded on its own (no contraction), so that plain fp32 numpy reproduces the bits.  Returns the global face index.
+__device__ __forceinline__ int mesh_point(const MeshRef &m, int base, unsigned Fc, const unsigned w[4], float p[3]) {
+    const unsigned s = __umulhi(w[0], Fc);
+    const uint2 rec = m.alias[(size_t)base + s];
+    const int f = base + (int)(w[1] < rec.x ? s : rec.y);
+    const int *face = m.faces + (size_t)f * 3;
+    const float *v0 = m.verts + (size_t)face[0] * 3, *v1 = m.verts + (size_t)face[1] * 3, *v2 = m.verts + (size_t)face[2] * 3;
+    unsigned a = w[2] >> 8, b = w[3] >> 8;
+    if (a + b > (1u << 24)) a = (1u << 24) - a, b = (1u << 24) - b;       // the other half of the parallelogram, mirrored back
+    const float u = (float)a * 5.9604644775390625e-8f, v = (float)b * 5.9604644775390625e-8f;   // (a, b <= 2^24: exact)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float e1 = __fsub_rn(v1[ch], v0[ch]), e2 = __fsub_rn(v2[ch], v0[ch]);
+        p[ch] = __fadd_rn(__fadd_rn(v0[ch], __fmul_rn(u, e1)), __fmul_rn(v, e2));
+    }
+    return f;
+}
+
+struct MeshFeedArgs {
+    int S, len[4];                                               // r1 r2 r3 N
+    int g[6];                                                    // as FeedArgs::g
+    int groups;
+    int vec;                                                     // bit k: output k takes 16-byte stores
+    MeshRef mesh;
+    const int *order;
+    long long first;
+    unsigned k0, k1, t_lo, t_hi24;
+    unsigned row0;
+    float sigma;
+    float *p[4];
+    float *z[2];
+    int *face_rec;                                               // (B, rec_stride) or null
+    int rec_at[4], rec_stride;                                   // where p_k's columns start in a row of face_rec
+};
+
+__global__ __launch_bounds__(FEED_THREADS) void feed_batch_mesh_kernel(MeshFeedArgs a) {
+    const int q = blockIdx.x * FEED_THREADS + threadIdx.x;
+    const int b = blockIdx.y;
+    if (q >= a.groups) return;
+    const unsigned row = a.row0 + (unsigned)b;
+    if (q >= a.g[4]) {
+        const int which = q >= a.g[5];
+        feed_noise_group(q - a.g[4 + which], which, b, row, a.t_lo, a.t_hi24, a.k0, a.k1, a.sigma, a.z[which]);
+        return;
+    }
+    const int c = min(max(a.order[a.first + b], 0), a.S - 1);
+    const int base = a.mesh.face_off[c];
+    const unsigned Fc = (unsigned)(a.mesh.face_off[c + 1] - base);
+    const int k = (q >= a.g[1]) + (q >= a.g[2]) + (q >= a.g[3]);
+    const int j = q - a.g[k];
+    const int r = a.len[k];
+    const int cols = min(4, r - 4 * j);
+    float v[12];
+    int f[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                                // (a column past the row's end is drawn like any other and not stored)
+        unsigned w[4];
+        philox4x32_10((unsigned)(4 * j + i), row, a.t_lo, (FEED_TAG_MESH + (unsigned)k) | (a.t_hi24 << 8), a.k0, a.k1, w);
+        f[i] = mesh_point(a.mesh, base, Fc, w, v + 3 * i);
+    }
+    float *dst = a.p[k] + (size_t)b * 3 * r + 4 * j;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        store4(dst + (size_t)ch * r, cols, (a.vec >> k) & 1, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
+    if (a.face_rec) {
+        int *rec = a.face_rec + (size_t)b * a.rec_stride + a.rec_at[k] + 4 * j;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i < cols) rec[i] = f[i];
+    }
+}
+
+struct SurfaceArgs {
+    int S, n, groups, vec;
+    MeshRef mesh;
+    unsigned k0, k1, d_lo, d_hi24;
+    float *out;
+    int *face_rec;
+};
+
+__global__ __launch_bounds__(FEED_THREADS) void sample_surface_kernel(SurfaceArgs a) {
+    const int j = blockIdx.x * FEED_THREADS + threadIdx.x;       // columns 4j .. 4j+3
+    if (j >= a.groups) return;
+    const int cols = min(4, a.n - 4 * j);
+    for (int s = blockIdx.y; s < a.S; s += gridDim.y) {
+        const int base = a.mesh.face_off[s];
+        const unsigned Fc = (unsigned)(a.mesh.face_off[s + 1] - base);
+        float v[12];
+        int f[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            unsigned w[4];
+            philox4x32_10((unsigned)(4 * j + i), (unsigned)s, a.d_lo, FEED_TAG_SURFACE | (a.d_hi24 << 8), a.k0, a.k1, w);
+            f[i] = mesh_point(a.mesh, base, Fc, w, v + 3 * i);
+        }
+        float *dst = a.out + ((size_t)s * a.n + (size_t)4 * j) * 3;                           // 48 contiguous bytes
+        if (a.vec) {                                             // (n a multiple of 4 and the base 16-byte aligned: so is every group)
+            float4 *d4 = reinterpret_cast<float4 *>(dst);
+            d4[0] = make_float4(v[0], v[1], v[2], v[3]), d4[1] = make_float4(v[4], v[5], v[6], v[7]), d4[2] = make_float4(v[8], v[9], v[10], v[11]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 12; ++i)
+                if (i < 3 * cols) dst[i] = v[i];
+        }
+        if (a.face_rec) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < cols) a.face_rec[(size_t)s * a.n + 4 * j + i] = f[i];
+        }
+    }
+}
+
+// null or misaligned mesh pointers: what both mesh entry points refuse
+static bool mesh_invalid(int S, const float *verts, const int32_t *faces, const int32_t *face_off, const uint32_t *alias, const int32_t *face_rec,
+                         MeshRef &m) {
+    if (S < 1 || !verts || !faces || !face_off || !alias) return true;
+    if ((((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)face_off | (uintptr_t)face_rec) & 3) || ((uintptr_t)alias & 7)) return true;
+    m.verts = verts, m.faces = faces, m.face_off = face_off, m.alias = reinterpret_cast<const uint2 *>(alias);
+    return false;
+}
+
+extern "C" int pdgn_feed_batch_mesh(int B, int S, int V, int F, int N, int r1, int r2, int r3, const float *verts, const int32_t *faces,
+                                    const int32_t *face_off, const uint32_t *alias, const int32_t *order, long long first,
+                                    unsigned long long seed, unsigned long long t, long long row0, float sigma, float *p1, float *p2,
+                                    float *p3, float *p4, float *z1, float *z2, int32_t *face_rec, pdgn_stream_t stream) {
+    MeshFeedArgs a;
+    if (feed_args_invalid(B, S, N, r1, r2, r3, order, first, row0, p1, p2, p3, p4, z1, z2)) return PDGN_ERR_INVALID;
+    if (mesh_invalid(S, verts, faces, face_off, alias, face_rec, a.mesh)) return PDGN_ERR_INVALID;
+    if (V < 1 || F < S || V > 0x7fffffff / 3 || F > 0x7fffffff / 3) return PDGN_ERR_INVALID;          // (every shape owns a face)
+    a.S = S;
+    const int len[4] = {r1, r2, r3, N};
+    float *const out[4] = {p1, p2, p3, p4};
+    int at = 0, rec = 0;
+    a.vec = 0;
+    for (int k = 0; k < 4; ++k) {
+        a.len[k] = len[k], a.g[k] = at, a.rec_at[k] = rec, a.p[k] = out[k];
+        at += (len[k] + 3) / 4, rec += len[k];
+        if (len[k] % 4 == 0 && !((uintptr_t)out[k] & 15)) a.vec |= 1 << k;
+    }
+    a.rec_stride = rec;
+    a.g[4] = at, a.g[5] = at + FEED_NOISE_DIM / 4;
+    a.groups = at + 2 * (FEED_NOISE_DIM / 4);
+    a.order = order, a.first = first;
+    a.k0 = (unsigned)seed, a.k1 = (unsigned)(seed >> 32);
+    a.t_lo = (unsigned)t, a.t_hi24 = (unsigned)(t >> 32) & 0xffffffu;
+    a.row0 = (unsigned)row0;
+    a.sigma = sigma;
+    a.z[0] = z1, a.z[1] = z2;
+    a.face_rec = face_rec;
+    hipLaunchKernelGGL(feed_batch_mesh_kernel, dim3(cdiv(a.groups, FEED_THREADS), B), dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    return pdgn_launch_status();
+}
+
+extern "C" int pdgn_sample_surface(int S, int n, const float *verts, const int32_t *faces, const int32_t *face_off,
+                                   const uint32_t *alias, unsigned long long seed, unsigned long long draw, float *out, int32_t *face_rec,
+                                   pdgn_stream_t stream) {
+    SurfaceArgs a;
+    if (mesh_invalid(S, verts, faces, face_off, alias, face_rec, a.mesh)) return PDGN_ERR_INVALID;
+    if (n < 1 || n > 0x7fffff00 || !out || ((uintptr_t)out & 3)) return PDGN_ERR_INVALID;
+    a.S = S, a.n = n, a.groups = (n + 3) / 4;
+    a.vec = n % 4 == 0 && !((uintptr_t)out & 15);
+    a.k0 = (unsigned)seed, a.k1 = (unsigned)(seed >> 32);
+    a.d_lo = (unsigned)draw, a.d_hi24 = (unsigned)(draw >> 32) & 0xffffffu;
+    a.out = out, a.face_rec = face_rec;
+    hipLaunchKernelGGL(sample_surface_kernel, dim3(cdiv(a.groups, FEED_THREADS), min(S, 65535)), dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    return pdgn_launch_status();
 }

@@ -10,7 +10,8 @@ shape (which is also how the tests drive it: this image has no h5py).
 pdgn_feed_batch) writes a batch -- shuffled clouds, the three sub-samplings, the transposes and both noise draws --
 into the buffers the training step reads (`subsample="fps"`: a second launch, csrc/fps.hip's pdgn_feed_fps_pyramid, replaces the
 three independent with-replacement sub-samplings by nested farthest-point subsets of the finest cloud).  Clouds stored denser than they are trained on (the 15 000 points per shape of
-ShapeNetCore.v2.PC15k) go through pdgn_feed_batch_resample: a fresh `num_point` subset of every cloud each time it is visited.
+ShapeNetCore.v2.PC15k) go through pdgn_feed_batch_resample: a fresh `num_point` subset of every cloud each time it is visited.  `MeshFeeder` is the same feed for shapes stored
+as triangle meshes (pdgn_amd.meshes.MeshSet; pdgn_feed_batch_mesh): every visit of a shape is a fresh i.i.d. sample of its surface.
 """
 import os
 import random
@@ -184,7 +185,96 @@ def batches_per_epoch(S, B, world=1):
     return int(S) // (int(B) * int(world))
 
 
-class BatchFeeder:
+class _Feeder:
+    """What the device feeds share: the (rank, world) schedule over `epoch_order`, the pinned upload of an epoch's order, the checks of the
+    buffers a batch is written into and the optional farthest-point launch behind the feed launch.  A subclass validates its own source,
+    calls `_setup` and implements `_launch(first, t, row0, reals, z1, z2)`: the feed launch itself."""
+
+    NOISE_DIM = 128
+    SUBSAMPLE = ("random", "fps")
+    FPS_MAX_N = 8192                                             # PDGN_FPS_MAX_N (include/pdgn_hip.h)
+
+    def _check_subsample(self, subsample):
+        if subsample not in self.SUBSAMPLE:
+            raise ValueError("subsample %r: one of %s" % (subsample, ", ".join(self.SUBSAMPLE)))
+        self.subsample = subsample
+
+    def _setup(self, device, S, batch_size, sizes, seed, rank, world, sigma, what="clouds"):
+        """self.N and self.subsample are set; everything else the schedule needs is set here."""
+        from . import _lib
+        sizes = tuple(int(r) for r in sizes)
+        if len(sizes) == 4 and sizes[3] == self.N:
+            sizes = sizes[:3]
+        if len(sizes) != 3 or min(sizes) < 1:
+            raise ValueError("sizes: the three sub-resolutions (optionally followed by N), got %r" % (sizes,))
+        if self.subsample == "fps":
+            if not sizes[0] <= sizes[1] <= sizes[2] <= self.N:
+                raise ValueError('subsample="fps": the sizes must ascend and not exceed num_point = %d (each level is a prefix of '
+                                 "the next), got %r" % (self.N, sizes))
+            if self.N > self.FPS_MAX_N:
+                raise ValueError('subsample="fps": num_point %d, the farthest-point kernel holds at most %d points' % (self.N, self.FPS_MAX_N))
+        self.device, self.sizes = device, sizes
+        self.S = int(S)
+        self.B, self.seed, self.rank, self.world, self.sigma = int(batch_size), int(seed), int(rank), int(world), float(sigma)
+        if self.B < 1 or self.world < 1 or not 0 <= self.rank < self.world:
+            raise ValueError("batch_size >= 1 and 0 <= rank < world, got %d, %d, %d" % (self.B, self.rank, self.world))
+        self.batches_per_epoch = batches_per_epoch(self.S, self.B, self.world)
+        if self.batches_per_epoch < 1:
+            raise ValueError("%d %s do not make one batch of %d x %d" % (self.S, what, self.B, self.world))
+        self._order = torch.empty(self.S, dtype=torch.int32, device=device)
+        self._order_host = torch.empty(self.S, dtype=torch.int32).pin_memory()
+        self._order_epoch = None
+        self._fps = _lib.lib().pdgn_feed_fps_pyramid if self.subsample == "fps" else None
+        self._check = None
+
+    def shapes(self):
+        """Shapes of (p1, p2, p3, p4, z)."""
+        return [(self.B, 3, r) for r in self.sizes + (self.N,)] + [(self.B, self.NOISE_DIM)]
+
+    def buffers(self):
+        """Fresh (reals, z1, z2) of the right shapes on the feeder's device."""
+        sh = self.shapes()
+        new = lambda s: torch.empty(s, dtype=torch.float32, device=self.device)
+        return [new(s) for s in sh[:4]], new(sh[4]), new(sh[4])
+
+    def _upload_order(self, epoch):
+        # the previous epoch's upload may not have run yet, and it reads the pinned staging buffer when it runs
+        if self._order_epoch is not None:
+            self._order_copied.synchronize()
+        self._order_host.copy_(torch.from_numpy(epoch_order(self.seed, epoch, self.S)))
+        self._order.copy_(self._order_host, non_blocking=True)
+        self._order_copied = torch.cuda.Event()
+        self._order_copied.record(torch.cuda.current_stream(self.device))
+        self._order_epoch = epoch
+
+    def fill(self, epoch, i, reals, z1, z2):
+        """Batch i (0-based) of `epoch` (1-based) into the given tensors, on the current stream: one launch (subsample="fps": two)."""
+        from . import _lib
+        key = (tuple(t.data_ptr() for t in reals), z1.data_ptr(), z2.data_ptr())
+        if key != self._check:                                   # (the same static buffers every iteration: checked once)
+            if len(reals) != 4:
+                raise ValueError("reals: four tensors (B,3,r1) (B,3,r2) (B,3,r3) (B,3,N)")
+            for t, name, shape in zip(list(reals) + [z1, z2], ("p1", "p2", "p3", "p4", "z1", "z2"), self.shapes() + [self.shapes()[4]]):
+                _lib.require(t, name, torch.float32, len(shape))
+                if tuple(t.shape) != shape:
+                    raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+                if t.device != self.device:
+                    raise _lib.PdgnHipError("%s is on %s, the %s on %s" % (name, t.device, self._WHAT, self.device))
+            self._check = key
+        if not 0 <= i < self.batches_per_epoch or epoch < 1:
+            raise IndexError("batch %d of epoch %d: an epoch has %d batches, epochs count from 1" % (i, epoch, self.batches_per_epoch))
+        if epoch != self._order_epoch:
+            self._upload_order(epoch)
+        t = (epoch - 1) * self.batches_per_epoch + i
+        self._launch((i * self.world + self.rank) * self.B, t, self.rank * self.B, reals, z1, z2)
+        if self._fps is not None:                                # the same (seed, iteration, global row) as the feed launch: its own tag
+            _lib.check(self._fps(self.B, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(reals[3]),
+                                 self.seed & 0xFFFFFFFFFFFFFFFF, t, self.rank * self.B,
+                                 _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), None, _lib.stream_of(reals[3])),
+                       "pdgn_feed_fps_pyramid")
+
+
+class BatchFeeder(_Feeder):
     """A device-resident split and the launch that turns it into training batches.
 
     clouds: (S, M, 3) fp32 device tensor (`ShapeNetCore.stack(device)`; `from_dataset` does that and refuses a data set with a
@@ -200,15 +290,11 @@ class BatchFeeder:
     points of a farthest-point order of the row's p4 (start index drawn per row and iteration) -- nested, evenly spread, without
     duplicates where p4 has none; p4, z1, z2 are what "random" writes.  "fps" needs ascending sizes <= N and N <= FPS_MAX_N."""
 
-    NOISE_DIM = 128
-    SUBSAMPLE = ("random", "fps")
-    FPS_MAX_N = 8192                                             # PDGN_FPS_MAX_N (include/pdgn_hip.h)
+    _WHAT = "clouds"
 
     def __init__(self, clouds, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=None, pool=None, subsample="random"):
         from . import _lib
-        if subsample not in self.SUBSAMPLE:
-            raise ValueError("subsample %r: one of %s" % (subsample, ", ".join(self.SUBSAMPLE)))
-        self.subsample = subsample
+        self._check_subsample(subsample)
         if not isinstance(clouds, torch.Tensor):
             if getattr(clouds, "transform", None) is not None:
                 raise ValueError("BatchFeeder: the data set has a per-item transform; the device feed has no per-item Python hook")
@@ -225,31 +311,9 @@ class BatchFeeder:
         if not self.N <= self.P <= self.M:
             raise ValueError("pool %d: at least num_point = %d and at most the %d stored points" % (self.P, self.N, self.M))
         self._resample = self.N != self.M or pool is not None
-        sizes = tuple(int(r) for r in sizes)
-        if len(sizes) == 4 and sizes[3] == self.N:
-            sizes = sizes[:3]
-        if len(sizes) != 3 or min(sizes) < 1:
-            raise ValueError("sizes: the three sub-resolutions (optionally followed by N), got %r" % (sizes,))
-        if subsample == "fps":
-            if not sizes[0] <= sizes[1] <= sizes[2] <= self.N:
-                raise ValueError('subsample="fps": the sizes must ascend and not exceed num_point = %d (each level is a prefix of '
-                                 "the next), got %r" % (self.N, sizes))
-            if self.N > self.FPS_MAX_N:
-                raise ValueError('subsample="fps": num_point %d, the farthest-point kernel holds at most %d points' % (self.N, self.FPS_MAX_N))
-        self.clouds, self.sizes = clouds, sizes
-        self.S = int(clouds.shape[0])
-        self.B, self.seed, self.rank, self.world, self.sigma = int(batch_size), int(seed), int(rank), int(world), float(sigma)
-        if self.B < 1 or self.world < 1 or not 0 <= self.rank < self.world:
-            raise ValueError("batch_size >= 1 and 0 <= rank < world, got %d, %d, %d" % (self.B, self.rank, self.world))
-        self.batches_per_epoch = batches_per_epoch(self.S, self.B, self.world)
-        if self.batches_per_epoch < 1:
-            raise ValueError("%d clouds do not make one batch of %d x %d" % (self.S, self.B, self.world))
-        self._order = torch.empty(self.S, dtype=torch.int32, device=clouds.device)
-        self._order_host = torch.empty(self.S, dtype=torch.int32).pin_memory()
-        self._order_epoch = None
+        self.clouds = clouds
+        self._setup(clouds.device, clouds.shape[0], batch_size, sizes, seed, rank, world, sigma)
         self._fn = _lib.lib().pdgn_feed_batch_resample if self._resample else _lib.lib().pdgn_feed_batch
-        self._fps = _lib.lib().pdgn_feed_fps_pyramid if subsample == "fps" else None
-        self._check = None
 
     @classmethod
     def from_dataset(cls, dataset, device, batch_size, sizes=(256, 512, 1024), seed=0, **kw):
@@ -257,52 +321,41 @@ class BatchFeeder:
             raise ValueError("BatchFeeder: the data set has a per-item transform; the device feed has no per-item Python hook")
         return cls(dataset.stack(device).float().contiguous(), batch_size, sizes, seed, **kw)
 
-    def shapes(self):
-        """Shapes of (p1, p2, p3, p4, z)."""
-        return [(self.B, 3, r) for r in self.sizes + (self.N,)] + [(self.B, self.NOISE_DIM)]
-
-    def buffers(self):
-        """Fresh (reals, z1, z2) of the right shapes on the clouds' device."""
-        sh = self.shapes()
-        new = lambda s: torch.empty(s, dtype=torch.float32, device=self.clouds.device)
-        return [new(s) for s in sh[:4]], new(sh[4]), new(sh[4])
-
-    def _upload_order(self, epoch):
-        # the previous epoch's upload may not have run yet, and it reads the pinned staging buffer when it runs
-        if self._order_epoch is not None:
-            self._order_copied.synchronize()
-        self._order_host.copy_(torch.from_numpy(epoch_order(self.seed, epoch, self.S)))
-        self._order.copy_(self._order_host, non_blocking=True)
-        self._order_copied = torch.cuda.Event()
-        self._order_copied.record(torch.cuda.current_stream(self.clouds.device))
-        self._order_epoch = epoch
-
-    def fill(self, epoch, i, reals, z1, z2):
-        """Batch i (0-based) of `epoch` (1-based) into the given tensors, on the current stream: one launch (subsample="fps": two)."""
+    def _launch(self, first, t, row0, reals, z1, z2):
         from . import _lib
-        key = (tuple(t.data_ptr() for t in reals), z1.data_ptr(), z2.data_ptr())
-        if key != self._check:                                   # (the same static buffers every iteration: checked once)
-            if len(reals) != 4:
-                raise ValueError("reals: four tensors (B,3,r1) (B,3,r2) (B,3,r3) (B,3,N)")
-            for t, name, shape in zip(list(reals) + [z1, z2], ("p1", "p2", "p3", "p4", "z1", "z2"), self.shapes() + [self.shapes()[4]]):
-                _lib.require(t, name, torch.float32, len(shape))
-                if tuple(t.shape) != shape:
-                    raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
-                if t.device != self.clouds.device:
-                    raise _lib.PdgnHipError("%s is on %s, the clouds on %s" % (name, t.device, self.clouds.device))
-            self._check = key
-        if not 0 <= i < self.batches_per_epoch or epoch < 1:
-            raise IndexError("batch %d of epoch %d: an epoch has %d batches, epochs count from 1" % (i, epoch, self.batches_per_epoch))
-        if epoch != self._order_epoch:
-            self._upload_order(epoch)
         dims = (self.B, self.S, self.M, self.P, self.N) if self._resample else (self.B, self.S, self.N)
         _lib.check(self._fn(*dims, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(self.clouds),
-                            _lib.ptr(self._order), (i * self.world + self.rank) * self.B, self.seed & 0xFFFFFFFFFFFFFFFF,
-                            (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B, self.sigma,
+                            _lib.ptr(self._order), first, self.seed & 0xFFFFFFFFFFFFFFFF, t, row0, self.sigma,
                             _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
                             _lib.stream_of(self.clouds)), "pdgn_feed_batch_resample" if self._resample else "pdgn_feed_batch")
-        if self._fps is not None:                                # the same (seed, iteration, global row) as the feed launch: its own tag
-            _lib.check(self._fps(self.B, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(reals[3]),
-                                 self.seed & 0xFFFFFFFFFFFFFFFF, (epoch - 1) * self.batches_per_epoch + i, self.rank * self.B,
-                                 _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), None, _lib.stream_of(self.clouds)),
-                       "pdgn_feed_fps_pyramid")
+
+
+class MeshFeeder(_Feeder):
+    """BatchFeeder for shapes stored as triangle meshes (pdgn_amd.meshes.MeshSet on the device): every visit of a shape is a fresh
+    i.i.d. sample of its surface, all four resolutions drawn independently inside ONE launch (csrc/feed.hip: pdgn_feed_batch_mesh);
+    the schedule, the random streams' indexing by global row and global iteration and the noise are BatchFeeder's.
+    subsample="fps": pdgn_feed_fps_pyramid behind the mesh launch overwrites p1..p3 with nested farthest-point subsets of the row's p4."""
+
+    _WHAT = "meshes"
+
+    def __init__(self, meshset, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=2048, subsample="random"):
+        from . import _lib
+        from .meshes import MeshSet
+        self._check_subsample(subsample)
+        if not isinstance(meshset, MeshSet):
+            raise TypeError("MeshFeeder takes a pdgn_amd.meshes.MeshSet on the device (MeshSet.from_meshes(...).to(device))")
+        _lib.require(meshset.verts, "the mesh set's vertices", torch.float32, 2)
+        self.N = int(num_point)
+        if self.N < 1:
+            raise ValueError("num_point %d: at least one" % self.N)
+        self.meshes = meshset
+        self._setup(meshset.verts.device, meshset.S, batch_size, sizes, seed, rank, world, sigma, what="shapes")
+        self._fn = _lib.lib().pdgn_feed_batch_mesh
+
+    def _launch(self, first, t, row0, reals, z1, z2, face_rec=None):
+        from . import _lib
+        m = self.meshes
+        _lib.check(self._fn(self.B, self.S, m.V, m.F, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(m.verts), _lib.ptr(m.faces),
+                            _lib.ptr(m.face_off), _lib.ptr(m.alias), _lib.ptr(self._order), first, self.seed & 0xFFFFFFFFFFFFFFFF, t, row0,
+                            self.sigma, _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1),
+                            _lib.ptr(z2), _lib.ptr(face_rec), _lib.stream_of(m.verts)), "pdgn_feed_batch_mesh")

@@ -1,0 +1,328 @@
+"""Triangle meshes as training data: the form ShapeNetCore is distributed in, resident on the device, so that every visit of a shape
+is a fresh i.i.d. sample of its surface (data.MeshFeeder -> csrc/feed.hip: pdgn_feed_batch_mesh).
+
+`load_obj` reads the geometry of a Wavefront .obj; `MeshSet` holds a set of shapes as the four arrays the kernels take -- vertices,
+global faces, the shapes' face ranges and one alias table (Walker 1977 / Vose 1991) per shape, which picks a face with probability
+proportional to its area from one 8-byte load -- normalised in closed form over the SURFACE; `MeshSet.sample` draws held-out clouds
+(pdgn_sample_surface).  `python -m pdgn_amd.meshes pack DIR OUT.npz` packs a directory <synsetid>/<split>/*.obj into one file.
+"""
+import os
+import sys
+
+import numpy as np
+
+NORMALIZE = (None, "shape_unit", "shape_bbox")
+SPLITS = ("train", "val", "test")
+
+
+def load_obj(path):
+    """(verts float32 (V,3), faces int32 (F,3)) of a Wavefront .obj: `v` and `f` lines only; `f a/b/c` and `f a//c` forms (the vertex
+    index is the first field), negative indices (relative to the vertices read so far), polygons as triangle fans; everything else
+    (vn, vt, g, usemtl, comments, ...) is ignored.  An index outside the file's vertices is a ValueError."""
+    verts, faces, where = [], [], []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError("%s:%d: a vertex has three coordinates" % (path, ln))
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            elif tok[0] == "f":
+                idx = []
+                for field in tok[1:]:
+                    i = int(field.split("/", 1)[0])
+                    if i == 0 or -i > len(verts):
+                        raise ValueError("%s:%d: vertex index %d of %d vertices read so far" % (path, ln, i, len(verts)))
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                if len(idx) < 3:
+                    raise ValueError("%s:%d: a face has at least three vertices" % (path, ln))
+                for k in range(1, len(idx) - 1):
+                    faces.append((idx[0], idx[k], idx[k + 1]))
+                    where.append(ln)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if faces.size and faces.max() >= len(verts):
+        bad = int(np.argmax(faces.max(axis=1) >= len(verts)))
+        raise ValueError("%s:%d: vertex index %d, the file has %d vertices" % (path, where[bad], int(faces[bad].max()) + 1, len(verts)))
+    return np.asarray(verts, dtype=np.float32).reshape(-1, 3), faces.astype(np.int32)
+
+
+def face_areas(verts, faces):
+    """Triangle areas in fp64."""
+    v = np.asarray(verts, dtype=np.float64)
+    v0, v1, v2 = v[faces[:, 0]], v[faces[:, 1]], v[faces[:, 2]]
+    return 0.5 * np.linalg.norm(np.cross(v1 - v0, v2 - v0), axis=1)
+
+
+def alias_table(area):
+    """Vose's alias method in fp64 for one shape: (threshold uint32 (F), alias uint32 (F)).  A draw takes a slot s uniformly and a word
+    w uniformly in [0, 2^32): face s where w < threshold[s], else face alias[s]; so face f has probability
+    (threshold[f] + sum over slots g with alias[g] = f of (2^32 - threshold[g])) / (F 2^32), area[f] / sum(area) up to the rounding of the
+    thresholds to 32 bits (2 * 2^-32 over all faces together).  A face of area zero has threshold 0 and is nobody's alias: never drawn.
+    A slot that keeps every draw has threshold 2^32 - 1 and is its own alias."""
+    area = np.asarray(area, dtype=np.float64)
+    F = area.shape[0]
+    total = float(area.sum())
+    if not (F >= 1 and np.all(area >= 0.0) and np.isfinite(total) and total > 0.0):
+        raise ValueError("alias_table: areas must be finite, not negative and not all zero")
+    p = (area * (F / total)).tolist()
+    prob, alias = [1.0] * F, list(range(F))
+    small = sorted((i for i in range(F) if p[i] < 1.0), key=lambda i: p[i] == 0.0)       # (popped from the end: the empty faces first)
+    large = [i for i in range(F) if p[i] >= 1.0]
+    while small and large:
+        s, l = small.pop(), large[-1]
+        prob[s], alias[s] = p[s], l
+        p[l] = (p[l] + p[s]) - 1.0
+        if p[l] < 1.0:
+            small.append(large.pop())
+    for s in small:                                              # (rounding left them just below one: they keep every draw)
+        assert area[s] > 0.0
+    thr = np.minimum(np.floor(np.asarray(prob) * 4294967296.0 + 0.5), 4294967295.0).astype(np.uint32)
+    return thr, np.asarray(alias, dtype=np.uint32)
+
+
+def _per_shape(values, face_off):
+    """Sums of per-face rows over every shape's face range."""
+    return np.add.reduceat(values, face_off[:-1], axis=0)
+
+
+def surface_statistics(verts, faces, face_off, area=None):
+    """Per shape, over its SURFACE (uniform density on the faces, in fp64): (centroid (S,3), std (S)) -- the limits, for infinitely many
+    surface samples, of the per-axis mean and of the standard deviation of all coordinates pooled about their pooled mean, which is
+    what data.normalize_clouds(., "shape_unit") takes as shift and scale.  Triangle moments: E[x] = s / 3, E[x x^T] = (sum_i v_i v_i^T +
+    s s^T) / 12 with s = v0 + v1 + v2, area-weighted over the shape."""
+    v = np.asarray(verts, dtype=np.float64)
+    area = face_areas(v, faces) if area is None else area
+    tri = v[faces]                                               # (F,3 corners,3)
+    s = tri.sum(axis=1)
+    total = _per_shape(area, face_off)
+    centroid = _per_shape(area[:, None] * s / 3.0, face_off) / total[:, None]
+    second = _per_shape(area * ((tri * tri).sum(axis=(1, 2)) + (s * s).sum(axis=1)) / 12.0, face_off) / total      # E[x^2 + y^2 + z^2]
+    pooled = centroid.sum(axis=1) / 3.0
+    return centroid, np.sqrt(np.maximum(second / 3.0 - pooled * pooled, 0.0))
+
+
+class MeshSet:
+    """S shapes as the device arrays of pdgn_feed_batch_mesh / pdgn_sample_surface (include/pdgn_hip.h): verts (V,3) fp32, faces (F,3)
+    int32 global vertex indices, face_off (S+1) int32, alias (F,2) int32 holding the bits of the uint32 records (threshold, alias local
+    to the shape); shift (S,3) / scale (S) fp32: the normalisation that was applied ((raw - shift) / scale).  Built by `from_meshes` /
+    `from_arrays`, which guarantee what the kernels trust: every shape owns a face of positive area, every index is inside the vertex
+    array, every alias inside its shape."""
+
+    def __init__(self, verts, faces, face_off, alias, shift, scale, normalize=None):
+        self.verts, self.faces, self.face_off, self.alias, self.shift, self.scale = verts, faces, face_off, alias, shift, scale
+        self.normalize = normalize
+        self.S, self.V, self.F = int(face_off.shape[0]) - 1, int(verts.shape[0]), int(faces.shape[0])
+
+    # ------------------------------------------------------------------ construction (host, numpy)
+    @classmethod
+    def from_meshes(cls, meshes, normalize=None, names=None):
+        """meshes: a list of (verts (V_c,3), faces (F_c,3) indices into that shape's own vertices)."""
+        meshes = list(meshes)
+        if not meshes:
+            raise ValueError("MeshSet: no shapes")
+        name = (lambda c: "shape %d" % c) if names is None else (lambda c: "shape %d (%s)" % (c, names[c]))
+        verts, faces, face_off, at = [], [], [0], 0
+        for c, (v, f) in enumerate(meshes):
+            v, f = np.asarray(v), np.asarray(f)
+            if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+                raise ValueError("%s: vertices are (V,3) and faces (F,3), got %s and %s" % (name(c), v.shape, f.shape))
+            if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
+                raise ValueError("%s: a face names vertex %d, the shape has %d vertices" % (name(c), int(f.max() if f.max() >= v.shape[0] else f.min()), v.shape[0]))
+            if not np.isfinite(v).all():
+                raise ValueError("%s: vertex %d is not finite" % (name(c), int(np.argmax(~np.isfinite(v).all(axis=1)))))
+            verts.append(v.astype(np.float32, copy=False))
+            faces.append(f.astype(np.int64) + at)
+            at += v.shape[0]
+            face_off.append(face_off[-1] + f.shape[0])
+        return cls.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.asarray(face_off), normalize, names)
+
+    @classmethod
+    def from_arrays(cls, verts, faces, face_off, normalize=None, names=None):
+        """From the concatenated form (what `pack` stores): verts (V,3), faces (F,3) GLOBAL indices, face_off (S+1)."""
+        import torch
+        if normalize not in NORMALIZE:
+            raise ValueError("MeshSet: normalize %r -- meshes take None, 'shape_unit' or 'shape_bbox' (global_unit, shape_half and shape_34 "
+                             "are defined on stored clouds only)" % (normalize,))
+        name = (lambda c: "shape %d" % c) if names is None else (lambda c: "shape %d (%s)" % (c, names[c]))
+        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+        face_off = np.asarray(face_off, dtype=np.int64).reshape(-1)
+        S, V, F = face_off.shape[0] - 1, verts.shape[0], faces.shape[0]
+        if S < 1 or face_off[0] != 0 or face_off[-1] != F or np.any(np.diff(face_off) < 0):
+            raise ValueError("MeshSet: face_off must ascend from 0 to the number of faces over at least one shape")
+        if 3 * max(V, F) > 0x7FFFFFFF:
+            raise ValueError("MeshSet: %d vertices and %d faces, the kernels index 3 V and 3 F with 32 bits" % (V, F))
+        shape_of = np.repeat(np.arange(S), np.diff(face_off))
+        if F and (faces.min() < 0 or faces.max() >= V):
+            c = int(shape_of[np.argmax((faces.min(axis=1) < 0) | (faces.max(axis=1) >= V))])
+            raise ValueError("%s: a face names a vertex outside the %d vertices" % (name(c), V))
+        used = np.zeros(V, dtype=bool)
+        used[faces.reshape(-1)] = True
+        owner = np.full(V, -1, dtype=np.int64)
+        owner[faces.reshape(-1)] = np.repeat(shape_of, 3)
+        if np.any(owner[faces] != shape_of[:, None]):
+            raise ValueError("MeshSet: two shapes share a vertex; every shape brings its own vertices")
+        bad = used & ~np.isfinite(verts).all(axis=1)
+        if bad.any():
+            raise ValueError("%s: vertex %d is not finite" % (name(int(owner[np.argmax(bad)])), int(np.argmax(bad))))
+        area = face_areas(verts, faces)
+        for c in range(S):
+            if not np.any(area[face_off[c]:face_off[c + 1]] > 0.0):
+                raise ValueError("%s: no face of positive area (%d faces)" % (name(c), face_off[c + 1] - face_off[c]))
+        # the normalisation, over the surface
+        if normalize == "shape_unit":
+            shift, scale = surface_statistics(verts, faces, face_off, area)
+        elif normalize == "shape_bbox":                          # data.normalize_clouds' expressions, in fp32, on the vertices of the faces of positive area
+            shift, scale = np.zeros((S, 3), np.float32), np.ones(S, np.float32)
+            for c in range(S):
+                f = faces[face_off[c]:face_off[c + 1]][area[face_off[c]:face_off[c + 1]] > 0.0]
+                lo, hi = verts[f.reshape(-1)].min(axis=0), verts[f.reshape(-1)].max(axis=0)
+                shift[c], scale[c] = (lo + hi) / np.float32(2), (hi - lo).max() / np.float32(2)
+        else:
+            shift, scale = np.zeros((S, 3)), np.ones(S)
+        if normalize is not None:
+            if not np.all(scale > 0):
+                raise ValueError("%s: its surface has no extent" % name(int(np.argmin(scale > 0))))
+            own = np.where(used, owner, 0)
+            moved = ((verts.astype(np.float64) - np.asarray(shift, np.float64)[own]) / np.asarray(scale, np.float64)[own][:, None]).astype(np.float32)
+            verts = np.where(used[:, None], moved, verts)
+            area = face_areas(verts, faces)                      # (a uniform scale per shape: the same table up to rounding; built from what is drawn from)
+        alias = np.empty((F, 2), dtype=np.uint32)
+        for c in range(S):
+            a, b = face_off[c], face_off[c + 1]
+            alias[a:b, 0], alias[a:b, 1] = alias_table(area[a:b])
+        t = torch.from_numpy
+        return cls(t(verts), t(faces.astype(np.int32)), t(face_off.astype(np.int32)), t(alias.view(np.int32)),
+                   t(np.asarray(shift, np.float32)), t(np.asarray(scale, np.float32)), normalize)
+
+    # ------------------------------------------------------------------ storage and placement
+    _FIELDS = ("verts", "faces", "face_off", "alias", "shift", "scale")
+
+    def save(self, path):
+        np.savez(path, normalize=np.asarray("" if self.normalize is None else self.normalize),
+                 **{k: getattr(self, k).cpu().numpy() for k in self._FIELDS})
+
+    @classmethod
+    def load(cls, path):
+        import torch
+        with np.load(path) as f:
+            mode = str(f["normalize"])
+            return cls(*(torch.from_numpy(f[k]) for k in cls._FIELDS), normalize=mode or None)
+
+    def to(self, device):
+        return MeshSet(*(getattr(self, k).to(device).contiguous() for k in self._FIELDS), normalize=self.normalize)
+
+    def alias_records(self):
+        """(threshold, alias) as two uint32 numpy arrays (F)."""
+        rec = self.alias.cpu().numpy().view(np.uint32)
+        return rec[:, 0].copy(), rec[:, 1].copy()
+
+    # ------------------------------------------------------------------ held-out draws
+    def sample(self, n, seed, draw=0, return_faces=False):
+        """(S,n,3): n i.i.d. points of every shape's surface (pdgn_sample_surface), a pure function of (seed, draw); its streams are
+        apart from every training draw of the same seed.  return_faces: also the (S,n) int32 global face index of every point."""
+        import torch
+        from . import _lib
+        _lib.require(self.verts, "the mesh set's vertices", torch.float32, 2)
+        out = torch.empty(self.S, int(n), 3, dtype=torch.float32, device=self.verts.device)
+        rec = torch.empty(self.S, int(n), dtype=torch.int32, device=self.verts.device) if return_faces else None
+        _lib.check(_lib.lib().pdgn_sample_surface(self.S, int(n), _lib.ptr(self.verts), _lib.ptr(self.faces), _lib.ptr(self.face_off),
+                                                  _lib.ptr(self.alias), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF,
+                                                  _lib.ptr(out), _lib.ptr(rec), _lib.stream_of(self.verts)), "pdgn_sample_surface")
+        return (out, rec) if return_faces else out
+
+
+# ---------------------------------------------------------------------------- directories and packed files
+def read_obj_root(root, synsetids=None):
+    """A directory <synsetid>/<split>/*.obj -> {synsetid: {split: (verts, faces GLOBAL within the split, face_off)}}, the files of a
+    split in sorted name order; raw geometry.  synsetids: these categories only."""
+    out = {}
+    for sid in sorted(os.listdir(root)):
+        if not os.path.isdir(os.path.join(root, sid)) or (synsetids is not None and sid not in synsetids):
+            continue
+        for split in SPLITS:
+            folder = os.path.join(root, sid, split)
+            if not os.path.isdir(folder):
+                continue
+            verts, faces, face_off, at = [], [], [0], 0
+            for fname in sorted(n for n in os.listdir(folder) if n.endswith(".obj")):
+                v, f = load_obj(os.path.join(folder, fname))
+                verts.append(v)
+                faces.append(f + np.int32(at))
+                at += v.shape[0]
+                face_off.append(face_off[-1] + f.shape[0])
+            if verts:
+                out.setdefault(sid, {})[split] = (np.concatenate(verts, 0), np.concatenate(faces, 0).astype(np.int32),
+                                                  np.asarray(face_off, dtype=np.int32))
+    if not out:
+        raise ValueError("%s: no <synsetid>/<split>/*.obj meshes found" % (root,))
+    return out
+
+
+def pack(root, out_path):
+    """Write the directory's meshes as one .npz with the keys "<synsetid>/<split>/{verts,faces,face_off}" (raw, un-normalised)."""
+    arrays = {}
+    for sid, splits in read_obj_root(root).items():
+        for split, (v, f, off) in splits.items():
+            arrays["%s/%s/verts" % (sid, split)], arrays["%s/%s/faces" % (sid, split)], arrays["%s/%s/face_off" % (sid, split)] = v, f, off
+    np.savez(out_path, **arrays)
+    return sorted(arrays)
+
+
+def load_packed(path, synsetids=None):
+    """The mapping `read_obj_root` returns, from a file `pack` wrote."""
+    out = {}
+    with np.load(path) as f:
+        for key in f.files:
+            sid, split, what = key.split("/")
+            if what == "verts" and (synsetids is None or sid in synsetids):
+                out.setdefault(sid, {})[split] = tuple(f["%s/%s/%s" % (sid, split, k)] for k in ("verts", "faces", "face_off"))
+    return out
+
+
+def is_mesh_root(path):
+    """Whether a --data_root holds meshes: an .npz with "<synsetid>/<split>/verts" keys, or a directory with a <synsetid>/<split>/*.obj."""
+    path = str(path)
+    if os.path.isdir(path):
+        for sid in sorted(os.listdir(path)):
+            for split in SPLITS:
+                folder = os.path.join(path, sid, split)
+                if os.path.isdir(folder) and any(n.endswith(".obj") for n in os.listdir(folder)):
+                    return True
+        return False
+    if path.endswith(".npz") and os.path.exists(path):
+        with np.load(path) as f:
+            return any(k.count("/") == 2 and k.endswith("/verts") for k in f.files)
+    return False
+
+
+def open_mesh_root(path, synsetids=None):
+    return read_obj_root(str(path), synsetids) if os.path.isdir(path) else load_packed(path, synsetids)
+
+
+def split_meshset(root, split, normalize=None):
+    """One MeshSet of a split over every category of an opened root, categories in sorted order."""
+    parts = [root[sid][split] for sid in sorted(root) if split in root[sid]]
+    if not parts:
+        raise ValueError("the mesh data has no %r split" % split)
+    verts, faces, face_off, at, fat = [], [], [np.zeros(1, np.int64)], 0, 0
+    for v, f, off in parts:
+        verts.append(v)
+        faces.append(f.astype(np.int64) + at)
+        face_off.append(off[1:].astype(np.int64) + fat)
+        at, fat = at + v.shape[0], fat + int(off[-1])
+    return MeshSet.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.concatenate(face_off, 0), normalize)
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) != 3 or argv[0] != "pack":
+        raise SystemExit("usage: python -m pdgn_amd.meshes pack DIR OUT.npz")
+    keys = pack(argv[1], argv[2])
+    print("packed %d arrays into %s" % (len(keys), argv[2]))
+
+
+if __name__ == "__main__":
+    main()

@@ -23,7 +23,11 @@ are trained on a fresh draw of --num_point distinct points per cloud and visit, 
 from the leading --resample_pool P points (default: all M); --phase test and the reports take the LAST --num_point points of every stored cloud as
 their reference clouds (disjoint from the pool whenever P <= M - num_point).  --subsample fps (train): the three coarse real resolutions are
 nested farthest-point subsets of the finest cloud of the same row instead of three independent with-replacement draws (data.BatchFeeder, csrc/fps.hip;
---num_point at most 8192); --subsample random is the default and the reference's.
+--num_point at most 8192); --subsample random is the default and the reference's.  --data_root may also hold triangle MESHES -- a directory <synsetid>/<split>/*.obj, or the
+.npz that `python -m pdgn_amd.meshes pack DIR OUT.npz` makes of one: the train split then stays on the device as meshes, normalised over
+its surface, and every visit of a shape is a fresh i.i.d. sample of its surface (data.MeshFeeder, pdgn_feed_batch_mesh; DESIGN.md section 7k);
+--phase test and the reports take draw 0 of --num_point surface points of every raw test / val mesh as their reference clouds;
+--resample_pool does not apply.
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -49,7 +53,8 @@ def build_parser():
     p.add_argument("--optimizer", default="adam", help="accepted and ignored, as in the reference")
     p.add_argument("--debug", type=bool, default=True, help="accepted and ignored, as in the reference")
     p.add_argument("--data_root", default="/opt/data/private/shapenet/shapenet.hdf5", help="shapenet.hdf5, an .npz with '<synsetid>/<split>' keys, or a "
-                   "directory <synsetid>/<split>/*.npy (ShapeNetCore.v2.PC15k)")
+                   "directory <synsetid>/<split>/*.npy (ShapeNetCore.v2.PC15k); meshes: a directory <synsetid>/<split>/*.obj or the .npz "
+                   "`python -m pdgn_amd.meshes pack` makes of one")
     p.add_argument("--log_info", default="log_info.txt")
     p.add_argument("--model_dir", help="model dir (required)")
     p.add_argument("--checkpoint_dir", default="checkpoint")
@@ -315,6 +320,32 @@ def load_split(args, split, scale_mode, tail=None):
     return ShapeNetCore(cates, split, scale_mode, src, tail=tail)
 
 
+def _mesh_root(args):
+    """The opened mesh data of --data_root ({synsetid: {split: (verts, faces, face_off)}}, of --choice's category only), or None where
+    --data_root holds clouds."""
+    from . import meshes
+    from .data import cate_to_synsetid
+    if not meshes.is_mesh_root(args.data_root):
+        return None
+    if args.choice is not None and args.choice not in cate_to_synsetid:
+        raise SystemExit("--choice %s: not a ShapeNetCore category" % args.choice)
+    root = meshes.open_mesh_root(args.data_root, None if args.choice is None else {cate_to_synsetid[args.choice]})
+    if not root:
+        raise SystemExit("--choice %s: %s has no meshes of that category" % (args.choice, args.data_root))
+    return root
+
+
+def reference_clouds(args, split, device, mesh_root=None):
+    """The (S, num_point, 3) reference clouds of the test phase and the reports, normalised by --normalize: the LAST num_point points of
+    every stored cloud, or -- for meshes -- draw 0 of num_point surface points of every raw mesh of the split (MeshSet.sample: streams
+    of their own, apart from every training draw), which then go through the same point normalisation."""
+    if mesh_root is None:
+        return load_split(args, split, args.normalize, tail=args.num_point).stack(device).float().contiguous()
+    from .data import normalize_point_clouds
+    from .meshes import split_meshset
+    return normalize_point_clouds(split_meshset(mesh_root, split).to(device).sample(args.num_point, args.seed, draw=0), args.normalize).contiguous()
+
+
 def init_dist(device):
     """(rank, world): from the process group under torch.distributed.run, else (0, 1)."""
     import torch.distributed as dist
@@ -359,15 +390,10 @@ def _resume(args, trainer, ckpt):
     return trainer.load(os.path.join(ckpt, args.pretrain_model_G), os.path.join(ckpt, args.pretrain_model_D))
 
 
-def train(args):
+def _cloud_feeder(args, device, rank, world):
     from .data import BatchFeeder
-    rank, world, device = init_dist(args.device)
-    run_dir = os.path.join(args.checkpoint_dir, args.model_dir)
-    ckpt = os.path.join(run_dir, args.network)
-    os.makedirs(ckpt, exist_ok=True)
-    torch.manual_seed(args.seed)                                 # the networks' initial weights
-    dset = load_split(args, "train", "shape_unit")
     n = args.num_point
+    dset = load_split(args, "train", "shape_unit")
     stored = int(dset.pointclouds[0]["pointcloud"].shape[0])
     if stored < n:
         raise SystemExit("--num_point %d but the clouds of %s have %d points" % (n, args.data_root, stored))
@@ -375,8 +401,39 @@ def train(args):
         raise SystemExit("--resample_pool: the clouds of %s have exactly --num_point %d points, there is nothing to draw" % (args.data_root, n))
     if args.resample_pool is not None and args.resample_pool > stored:
         raise SystemExit("--resample_pool %d but the clouds of %s have %d points" % (args.resample_pool, args.data_root, stored))
-    feeder = BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world,
+    return BatchFeeder.from_dataset(dset, device, args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world,
                                       num_point=n, pool=args.resample_pool, subsample=args.subsample)
+
+
+def _mesh_feeder(args, mesh_root, device, rank, world):
+    """Meshes: the train split normalised over its surface (the cloud path's 'shape_unit'), resident on the device; every visit is a
+    fresh surface sample (data.MeshFeeder)."""
+    from .data import MeshFeeder
+    from .meshes import split_meshset
+    if args.resample_pool is not None:
+        raise SystemExit("--resample_pool: %s holds meshes -- every visit of a shape already draws fresh points from its whole surface, "
+                         "there is no stored pool to restrict" % args.data_root)
+    n = args.num_point
+    try:
+        ms = split_meshset(mesh_root, "train", "shape_unit")
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (args.data_root, e))
+    return MeshFeeder(ms.to(device), args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world, num_point=n,
+                      subsample=args.subsample)
+
+
+def train(args):
+    rank, world, device = init_dist(args.device)
+    run_dir = os.path.join(args.checkpoint_dir, args.model_dir)
+    ckpt = os.path.join(run_dir, args.network)
+    os.makedirs(ckpt, exist_ok=True)
+    torch.manual_seed(args.seed)                                 # the networks' initial weights
+    n = args.num_point
+    mesh_root = _mesh_root(args)
+    if mesh_root is not None:
+        feeder = _mesh_feeder(args, mesh_root, device, rank, world)
+    else:
+        feeder = _cloud_feeder(args, device, rank, world)
     try:
         trainer = make_trainer(args, device, feeder.batches_per_epoch)
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
@@ -396,7 +453,7 @@ def train(args):
     reporter = None
     if args.report_every > 0 and rank == 0:
         from .report import SnapshotReporter
-        val = load_split(args, "val", args.normalize, tail=n).stack(device).float().contiguous()
+        val = reference_clouds(args, "val", device, mesh_root)
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
@@ -423,7 +480,7 @@ def test(args):
     torch.manual_seed(args.seed)                                 # seed_all (:282)
     np.random.seed(args.seed)
     random.seed(args.seed)
-    ref = load_split(args, "test", args.normalize, tail=args.num_point).stack(device).float().contiguous()
+    ref = reference_clouds(args, "test", device, _mesh_root(args))
     trainer.G.eval()
     gen, results, raw = evaluation.generate_and_evaluate(trainer.G, ref, args.batch_size, normalize=args.normalize, return_raw=True)
     np.save(os.path.join(save_dir, "nonormal_out.npy"), raw.cpu().numpy())
