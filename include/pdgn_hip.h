@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 37
+#define PDGN_ABI_VERSION 38
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1061,6 +1061,39 @@ int pdgn_augment_tick_ada(unsigned long long *clock, pdgn_ada_state *state, int3
 long long pdgn_render_workspace_bytes(int rows, int cols, int cell);
 int pdgn_render_sheet(int rows, int cols, const float *const *clouds, const int *npoints, int channel_major, const float *view,
                       int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ exact EMD (csrc/auction.hip)
+ * The assignment problem between two clouds of n points each, cost |a_i - b_j| (Euclidean, what pdgn_matchcost sums), solved in
+ * integers by a forward auction with epsilon scaling: one workgroup per pair, all state in LDS, bids resolved by 64-bit integer
+ * atomic maxima on packed keys, so the result is bitwise repeatable.  No reference counterpart.
+ *   quantum  q = cmax * 2^-pdgn_auction_quantum_bits(), cmax the diagonal of the bounding box of both clouds; integer cost
+ *            rint(|a_i - b_j| / q), recomputed from the coordinates at every look (no n x n matrix), times n + 1 so that the last
+ *            phase (epsilon = 1) ends at an optimum of the integer problem: within n q of the true optimum.
+ *   assign   (b,n) int32: assign[p][i] = j, point b_j of cloud p of xyz2 is matched to point a_i of xyz1; always a permutation
+ *   cost     (b): the sum of the unquantised fp32 distances of that assignment, in a fixed order (NaN: see status 2)
+ *   status   (b) int32: 0 the optimum of the integer problem; 1 a cap was reached (16 n + 64 rounds in a phase,
+ *            pdgn_auction_max_bids(n) bids in all, or a bid of 2^51): what was assigned stays, the rest is completed in index order;
+ *            2 decided before any loop: no finite positive quantum, q < 2^-126 (all points equal, or an extent so small that the
+ *            fp32 diagonal -- whose squares are denormal below extents of 2^-63 and vanish near 2^-75 -- is under 2^-106: cost of
+ *            the identity; a coordinate or the diagonal not finite: cost NaN), the identity permutation
+ *   bids     (b) long long or NULL: bids made, <= pdgn_auction_max_bids(n) = 64 n phases(n) (no launch; -1 for an unsupported n)
+ * Supported n: 1 .. PDGN_AUCTION_MAX_N (56 bytes of LDS per point: 112 KB); a larger n is PDGN_ERR_INVALID, not a slower path.
+ * pdgn_auction_assign_indexed: pair p = (cloud ia[p] of xyz1, cloud ib[p] of xyz2), cost and status only -- the same kernel, the
+ * same bits as the batched entry point on the same pairs.
+ * pdgn_auction_cost_grad: the adjoint of `cost` at a fixed assignment, g (b) the upstream gradient:
+ *   grad1[p][i] = g[p] (a_i - b_j) / sqrt(max(|a_i - b_j|^2, 1e-20)), j = assign[p][i];  grad2[p][j] = -grad1[p][i]
+ * (pdgn_matchcost_grad's clamp).  Every row is stored once, nothing is added; an index outside [0, n) stores no row.
+ * PDGN_ERR_INVALID: b / npairs < 0, n < 1 or > PDGN_AUCTION_MAX_N, a null pointer (bids excepted) or one not 4-byte (bids: 8-byte)
+ * aligned; b = 0 returns 0 and launches nothing.  Allocates nothing, one launch on `stream`. */
+#define PDGN_AUCTION_MAX_N 2048
+int pdgn_auction_quantum_bits(void);
+long long pdgn_auction_max_bids(int n);
+int pdgn_auction_assign(int b, int n, const float *xyz1, const float *xyz2, int32_t *assign, float *cost, int32_t *status,
+                        long long *bids, pdgn_stream_t stream);
+int pdgn_auction_assign_indexed(int npairs, int n, const float *xyz1, const int32_t *ia, const float *xyz2, const int32_t *ib,
+                                float *cost, int32_t *status, pdgn_stream_t stream);
+int pdgn_auction_cost_grad(int b, int n, const float *xyz1, const float *xyz2, const int32_t *assign, const float *g, float *grad1,
+                           float *grad2, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ from ._lib import check, ptr, require, stream_of
 
 F32, I32 = torch.float32, torch.int32
 _MAX_PAIRS = 32768          # per launch (grid.y limit of the Chamfer kernel, scratch of the EMD kernel)
+_MAX_AUCTION_PAIRS = 2048   # per launch of the exact EMD: 8 workgroups per CU -- about a second at 2048 points, about 20 s if every pair runs to its cap
 
 
 def _pair_lists(S, R, start, stop, device):
@@ -45,12 +46,23 @@ def shard_pairs(total, fill, group=None):
     return tuple(full)
 
 
-def pairwise_emd_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False, group=None):
+EMD_KINDS = ("approx", "auction")
+
+
+def _emd_kind(emd):
+    if emd not in EMD_KINDS:
+        raise ValueError("emd must be one of %s, got %r" % (EMD_KINDS, emd))
+    return emd
+
+
+def pairwise_emd_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False, group=None, emd="approx"):
     """_pairwise_EMD_CD_ (:85-121): all_cd, all_emd of shape (N_sample, N_ref).
     CD = mean_i min_j P + mean_j min_i P with the Gram-form P of distChamfer (:35-45);
     EMD = match_cost / N (:26-31).  `batch_size` is accepted for signature parity and ignored.
-    shard_over_ranks: every rank of `group` holds the same two sets and computes 1/world of the pairs (`shard_pairs`)."""
-    return _pairwise(sample_pcs, ref_pcs, True, shard_over_ranks, group)
+    shard_over_ranks: every rank of `group` holds the same two sets and computes 1/world of the pairs (`shard_pairs`).
+    emd: "approx" -- the reference's approxmatch (pdgn_emd_cost_indexed), what published numbers use -- or "auction": the exact
+    matching of equal-sized clouds (pdgn_auction_assign_indexed), its cost / N."""
+    return _pairwise(sample_pcs, ref_pcs, True, shard_over_ranks, group, _emd_kind(emd))[:2]
 
 
 def pairwise_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False, group=None):
@@ -59,17 +71,21 @@ def pairwise_cd(sample_pcs, ref_pcs, batch_size=None, shard_over_ranks=False, gr
     return _pairwise(sample_pcs, ref_pcs, False, shard_over_ranks, group)[0]
 
 
-def _pairwise(sample_pcs, ref_pcs, with_emd, shard_over_ranks, group):
+def _pairwise(sample_pcs, ref_pcs, with_emd, shard_over_ranks, group, emd="approx"):
     require(sample_pcs, "sample_pcs", F32, 3)
     require(ref_pcs, "ref_pcs", F32, 3)
     S, N, _ = sample_pcs.shape
     R, M, _ = ref_pcs.shape
     dev = sample_pcs.device
     L = _lib.lib()
+    auction = with_emd and emd == "auction"
+    if auction and N != M:
+        raise ValueError("emd=\"auction\" matches clouds of equal size (got %d and %d points)" % (N, M))
 
     def fill(lo, hi):
         cd = torch.empty(hi - lo, dtype=F32, device=dev)
         emd = torch.empty(hi - lo if with_emd else 0, dtype=F32, device=dev)
+        status = torch.empty(hi - lo if auction else 0, dtype=I32, device=dev)
         for start in range(lo, hi, _MAX_PAIRS):
             stop = min(hi, start + _MAX_PAIRS)
             npairs = stop - start
@@ -85,23 +101,34 @@ def _pairwise(sample_pcs, ref_pcs, with_emd, shard_over_ranks, group):
             cd[start - lo:stop - lo] = miny.mean(dim=1) + minx.mean(dim=1)
             if not with_emd:
                 continue
+            if auction:
+                out = torch.empty((npairs,), dtype=F32, device=dev)
+                for first in range(0, npairs, _MAX_AUCTION_PAIRS):             # (a pair's result does not depend on the launch it is in)
+                    count = min(npairs - first, _MAX_AUCTION_PAIRS)
+                    check(L.pdgn_auction_assign_indexed(count, N, ptr(sample_pcs), ptr(ia[first:]), ptr(ref_pcs), ptr(ib[first:]), ptr(out[first:]),
+                                                        ptr(status[start - lo + first:]), stream_of(sample_pcs)), "pdgn_auction_assign_indexed")
+                emd[start - lo:stop - lo] = out / float(N)
+                continue
             temp = torch.empty(L.pdgn_emd_cost_temp_floats(npairs, N, M), dtype=F32, device=dev)
             out = torch.empty((npairs,), dtype=F32, device=dev)
             check(L.pdgn_emd_cost_indexed(npairs, N, M, ptr(sample_pcs), ptr(ia), ptr(ref_pcs), ptr(ib), ptr(temp),
                                           ptr(out), stream_of(sample_pcs)), "pdgn_emd_cost_indexed")
             emd[start - lo:stop - lo] = out / float(N)
-        return (cd, emd) if with_emd else (cd,)
+        return (cd, emd, status) if auction else (cd, emd) if with_emd else (cd,)
 
     out = shard_pairs(S * R, fill, group) if shard_over_ranks else fill(0, S * R)
-    return tuple(t.view(S, R) for t in out)
+    mats = tuple(t.view(S, R) for t in out[:2])
+    return mats + (int((out[2] != 0).sum()) if auction else 0,) if with_emd else mats
 
 
-def emd_cd(sample_pcs, ref_pcs, batch_size=None, reduced=True):
-    """EMD_CD (:48-82): paired (i, i) Chamfer and EMD."""
+def emd_cd(sample_pcs, ref_pcs, batch_size=None, reduced=True, emd="approx"):
+    """EMD_CD (:48-82): paired (i, i) Chamfer and EMD (emd: as in `pairwise_emd_cd`)."""
     S = sample_pcs.shape[0]
     assert S == ref_pcs.shape[0], "REF:%d SMP:%d" % (ref_pcs.shape[0], S)
     from .losses import chamfer_min
-    from .structural_losses import emd_cost
+    from .structural_losses import emd_cost, exact_emd_cost
+    if _emd_kind(emd) == "auction":
+        emd_cost = exact_emd_cost
     minx, miny = chamfer_min(sample_pcs.contiguous(), ref_pcs.contiguous())
     cd = miny.mean(dim=1) + minx.mean(dim=1)
     emd = emd_cost(sample_pcs.contiguous(), ref_pcs.contiguous()) / float(sample_pcs.shape[1])
@@ -149,18 +176,25 @@ def reduce_metrics(all_dist, Mxx, Mxy, Myy, tag="CD"):
     return results
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=False, shard_over_ranks=False, group=None):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=False, shard_over_ranks=False, group=None, emd="approx"):
     """compute_all_metrics (:172-200): MMD / COV (CD and EMD) and 1-NNA from three all-pairs passes.
-    shard_over_ranks: all ranks call with the same sets, each computes 1/world of every matrix (`shard_pairs`)."""
+    shard_over_ranks: all ranks call with the same sets, each computes 1/world of every matrix (`shard_pairs`).
+    emd: as in `pairwise_emd_cd`; under "auction" the dict has one more key, "emd-capped": the number of pairs, over the three
+    matrices, whose auction did not end at an optimum (a tensor like the other entries)."""
     results = {}
-    kw = {"shard_over_ranks": shard_over_ranks, "group": group}
-    M_rs_cd, M_rs_emd = pairwise_emd_cd(sample_pcs, ref_pcs, **kw)
+    def matrices(a, b):                                          # (all_cd, all_emd, pairs not at an optimum: 0 under "approx")
+        return _pairwise(a, b, True, shard_over_ranks, group, emd)
+
+    _emd_kind(emd)
+    M_rs_cd, M_rs_emd, c_rs = matrices(sample_pcs, ref_pcs)
     results.update({"%s-CD" % k: v for k, v in lgan_mmd_cov(M_rs_cd.t()).items()})
     results.update({"%s-EMD" % k: v for k, v in lgan_mmd_cov(M_rs_emd.t()).items()})
-    M_rr_cd, M_rr_emd = pairwise_emd_cd(ref_pcs, ref_pcs, **kw)
-    M_ss_cd, M_ss_emd = pairwise_emd_cd(sample_pcs, sample_pcs, **kw)
+    M_rr_cd, M_rr_emd, c_rr = matrices(ref_pcs, ref_pcs)
+    M_ss_cd, M_ss_emd, c_ss = matrices(sample_pcs, sample_pcs)
     results.update({"1-NN-CD-%s" % k: v for k, v in knn(M_rr_cd, M_rs_cd, M_ss_cd, 1).items() if "acc" in k})
     results.update({"1-NN-EMD-%s" % k: v for k, v in knn(M_rr_emd, M_rs_emd, M_ss_emd, 1).items() if "acc" in k})
+    if emd == "auction":
+        results["emd-capped"] = torch.tensor(float(c_rs + c_rr + c_ss)).to(M_rs_emd)
     return results
 
 
@@ -243,14 +277,14 @@ def generate_clouds(generator, n, batch_size, normalize=None, rng=None, device=N
 
 
 @torch.no_grad()
-def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=None, with_jsd=True, return_raw=False):
+def generate_and_evaluate(generator, ref_pcs, batch_size, normalize=None, rng=None, with_jsd=True, return_raw=False, emd="approx"):
     """PDGNet_v2.test: draw ceil(N_ref / batch_size) batches of z ~ N(0, 1) (:304 -- sigma 1, unlike training's
     0.2), keep the finest cloud of each, truncate to N_ref, normalise like the reference set (`normalize` =
     the data set's scale mode: shape_unit / shape_bbox / None), then compute_all_metrics (+ 'jsd').
     Returns (generated clouds (N_ref, N, 3), results dict of floats-on-device); with return_raw also, third, the clouds as
-    generated, before the normalisation (the reference's `nonormal_out.npy`, :309)."""
+    generated, before the normalisation (the reference's `nonormal_out.npy`, :309).  emd: as in `compute_all_metrics`."""
     gen_pcs, raw = generate_clouds(generator, ref_pcs.shape[0], batch_size, normalize, rng, ref_pcs.device)
-    results = compute_all_metrics(gen_pcs, ref_pcs, batch_size)
+    results = compute_all_metrics(gen_pcs, ref_pcs, batch_size, emd=emd)
     if with_jsd:
         results["jsd"] = jsd_between_point_cloud_sets(gen_pcs, ref_pcs)
     return (gen_pcs, results, raw) if return_raw else (gen_pcs, results)

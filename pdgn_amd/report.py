@@ -166,11 +166,12 @@ class SnapshotReporter:
     """`fit(on_epoch=SnapshotReporter(...))`: at every epoch that is a multiple of `every`, on rank 0, write
     `<out_dir>/preview_<epoch>.png` (`rows` samples down; the generator's four resolutions and a column of reference clouds
     across) and append a row to `<out_dir>/metrics.csv` (epoch, `QUICK_KEYS` -- with full=True `FULL_KEYS`, through
-    compute_all_metrics and its EMD passes -- and the seconds the report took).  The preview's noise and the metrics' noise
+    compute_all_metrics and its EMD passes, the approximate EMD or with emd="auction" the exact one and an `emd-capped` column --
+    and the seconds the report took).  The preview's noise and the metrics' noise
     come from generators seeded the same way at every report, so sheets and rows are comparable across epochs.  Training
     state is left as found; the generator's train / eval flag is put back."""
 
-    def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1):
+    def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1, emd="approx"):
         _lib.require(ref_pcs, "ref_pcs", torch.float32, 3)
         self.trainer, self.ref, self.out_dir = trainer, ref_pcs, str(out_dir)
         self.every, self.batch_size, self.normalize, self.seed = int(every), int(batch_size), normalize, int(seed)
@@ -178,7 +179,13 @@ class SnapshotReporter:
         if self.rows < 1:
             raise ValueError("a report needs at least one row and one reference cloud")
         self.cache = {}
+        from .evaluation import EMD_KINDS
+        if emd not in EMD_KINDS:
+            raise ValueError("emd must be one of %s, got %r" % (EMD_KINDS, emd))
+        self.emd = emd
         self.keys = FULL_KEYS if self.full else QUICK_KEYS
+        if self.full and self.emd == "auction":                  # the exact EMD's rows say how many pairs did not end at an optimum
+            self.keys = self.keys + ("emd-capped",)
         self.last = None                                         # (epoch, {key: float}, seconds) of the latest report
 
     def _generator(self, offset):
@@ -204,7 +211,7 @@ class SnapshotReporter:
                 z = torch.randn(self.rows, 128, generator=self._generator(0), device=dev)
                 sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True)
                 if self.full:
-                    _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1))
+                    _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1), emd=self.emd)
                 else:
                     results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
                 results = {k: float(results[k]) for k in self.keys}
