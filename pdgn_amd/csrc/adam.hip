@@ -10,6 +10,7 @@
 //     p <- p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // with the bias corrections in fp64 from the step count t that torch keeps as a device tensor (read here, incremented by the caller).
 #include "common.h"
+#include <type_traits>
 
 #define ADAM_THREADS 256
 #define ADAM_CHUNK 4096            // elements per workgroup: four float4 per thread
@@ -235,112 +236,99 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_ema_guard_multi_kernel(cons
     adam_chunk<true, true>(a, lr, beta1d, beta2d, eps, ema_decay, step, guard);
 }
 
+// ---- the host side all the multi-tensor launches of this file share.  A list is walked MAXT tensors per launch (MAXT: the length of
+// the argument struct's columns); every launch's chunk count is checked before the first launch.
+// Chunks of the whole list, or -1 where one launch's MAXT tensors have more than 2^30 - 1 of them (every n[i] >= 1 is the caller's to check).
+static long long list_chunks(int ntensors, const long long *n, int maxt) {
+    long long total = 0;
+    for (int t0 = 0; t0 < ntensors; t0 += maxt) {
+        long long chunks = 0;
+        for (int i = t0; i < ntensors && i < t0 + maxt; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        if (chunks > 0x3fffffffLL) return -1;
+        total += chunks;
+    }
+    return total;
+}
+
+// Per launch: n[] and chunk0[] of an Args filled, its tail padded (null pointers, 0 elements, a first chunk no workgroup reaches), then
+// launch(a, t0, chunks) sets the pointer columns a.x[i] <- x[t0 + i] for i < a.ntensors and launches `chunks` workgroups.  PDGN_ERR_INVALID
+// before anything is launched, else 0: the launches are issued, their status is the caller's to ask for.
+template <class Args, class Launch>
+static int for_each_launch(int ntensors, const long long *n, Launch launch) {
+    constexpr int MAXT = (int)(sizeof(Args::n) / sizeof(long long));
+    if (list_chunks(ntensors, n, MAXT) < 0) return PDGN_ERR_INVALID;
+    for (int t0 = 0; t0 < ntensors; t0 += MAXT) {
+        Args a = {};
+        a.ntensors = ntensors - t0 < MAXT ? ntensors - t0 : MAXT;
+        long long chunks = 0;
+        for (int i = 0; i < a.ntensors; ++i) {
+            a.n[i] = n[t0 + i];
+            a.chunk0[i] = (int)chunks;
+            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+        }
+        for (int i = a.ntensors; i < MAXT; ++i) a.chunk0[i] = 0x7fffffff;
+        launch(a, t0, (unsigned)chunks);
+    }
+    return 0;
+}
+
 // One Adam step of `ntensors` fp32 tensors (p, g, m, v: HOST arrays of device pointers; n: their element counts), in
 // ceil(ntensors / 72) launches of one workgroup per 4096 elements.  step (device): the step count t >= 1 of THIS update as one
 // float (torch's `state["step"]` after its increment).  Replaces torch._fused_adam_ / optimizer.step() of the reference's five Adam
-// optimisers (models/PDGNet_v2.py:121-125) for lists without weight decay, amsgrad or maximize.
+// optimisers (models/PDGNet_v2.py:121-125, 186-226, 256) for lists without weight decay, amsgrad or maximize.
 // (a guard record is read with dword loads: the address the guarded entry points refuse.  `guard` null = the unguarded kernel.)
 static bool guard_misplaced(const pdgn_guard_record *guard) { return ((uintptr_t)guard & 3) != 0; }
 // (a schedule is read with 8-byte loads.  `sched` null = the kernel without one.)
 static bool sched_misplaced(const double *sched) { return ((uintptr_t)sched & 7) != 0; }
 
-static int adam_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
-                             double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
-                             const double *sched, pdgn_stream_t stream) {
-    if (ntensors < 1 || !p || !g || !m || !v || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
-        !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.))
+// Args = AdamEmaArgs: the averages e (HOST array of device pointers) updated in the same launches, ceil(ntensors / 64) of them: p, m, v
+// are pdgn_adam_multi's bits; e <- e + (1 - d_t) (p_new - e) as written at ema_one_minus_decay above.  No reference counterpart (the
+// reference keeps no averaged generator).  Args = AdamArgs: e and ema_decay are not read.
+template <class Args>
+static int adam_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
+                             const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay, const float *step,
+                             const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream) {
+    constexpr bool EMA = std::is_same<Args, AdamEmaArgs>::value;
+    if (ntensors < 1 || !p || !g || !m || !v || (EMA && !e) || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
+        !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || (EMA && !(ema_decay >= 0. && ema_decay < 1.)))
         return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
-        if (!p[i] || !g[i] || !m[i] || !v[i] || n[i] < 1 || (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i]) & 3))
+        if (!p[i] || !g[i] || !m[i] || !v[i] || (EMA && !e[i]) || n[i] < 1 ||
+            (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (EMA ? (uintptr_t)e[i] : 0)) & 3))
             return PDGN_ERR_INVALID;
     if (guard_misplaced(guard) || sched_misplaced(sched)) return PDGN_ERR_INVALID;
-    for (int t0 = 0; t0 < ntensors; t0 += ADAM_MAXT) {                      // every launch's chunk count is checked before the first launch
-        long long chunks = 0;
-        for (int i = t0; i < ntensors && i < t0 + ADAM_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
-    }
-    for (int t0 = 0; t0 < ntensors; t0 += ADAM_MAXT) {
-        AdamArgs a;
-        a.ntensors = ntensors - t0 < ADAM_MAXT ? ntensors - t0 : ADAM_MAXT;
-        long long chunks = 0;
+    const int rc = for_each_launch<Args>(ntensors, n, [&](Args &a, int t0, unsigned chunks) {
         for (int i = 0; i < a.ntensors; ++i) {
             a.p[i] = (float *)p[t0 + i]; a.g[i] = (const float *)g[t0 + i]; a.m[i] = (float *)m[t0 + i]; a.v[i] = (float *)v[t0 + i];
-            a.n[i] = n[t0 + i];
-            a.chunk0[i] = (int)chunks;
-            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+            if constexpr (EMA) a.e[i] = (float *)e[t0 + i];
         }
-        for (int i = a.ntensors; i < ADAM_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        if (sched && guard)
-            hipLaunchKernelGGL(adam_guard_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
-                               beta2, eps, step, guard, sched);
-        else if (sched)
-            hipLaunchKernelGGL(adam_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2,
-                               eps, step, sched);
-        else if (guard)
-            hipLaunchKernelGGL(adam_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2,
-                               eps, step, guard);
-        else
-            hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps, step);
-    }
-    return pdgn_launch_status();
+        const dim3 grid(chunks), block(ADAM_THREADS);
+        const hipStream_t s = (hipStream_t)stream;
+        if constexpr (EMA) {
+            if (sched && guard) hipLaunchKernelGGL(adam_ema_guard_sched_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, ema_decay, step, guard, sched);
+            else if (sched) hipLaunchKernelGGL(adam_ema_sched_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, ema_decay, step, sched);
+            else if (guard) hipLaunchKernelGGL(adam_ema_guard_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, ema_decay, step, guard);
+            else hipLaunchKernelGGL(adam_ema_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, ema_decay, step);
+        } else {
+            if (sched && guard) hipLaunchKernelGGL(adam_guard_sched_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, step, guard, sched);
+            else if (sched) hipLaunchKernelGGL(adam_sched_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, step, sched);
+            else if (guard) hipLaunchKernelGGL(adam_guard_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, step, guard);
+            else hipLaunchKernelGGL(adam_multi_kernel, grid, block, 0, s, a, lr, beta1, beta2, eps, step);
+        }
+    });
+    return rc ? rc : pdgn_launch_status();
 }
 
 extern "C" int pdgn_adam_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, const long long *n,
                                double lr, double beta1, double beta2, double eps, const float *step, pdgn_stream_t stream) {
-    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, nullptr, nullptr, stream);
+    return adam_multi_launch<AdamArgs>(ntensors, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, 0., step, nullptr, nullptr, stream);
 }
 
-// pdgn_adam_multi with the averages e (HOST array of device pointers) updated in the same launches, ceil(ntensors / 64) of them:
-// p, m, v are pdgn_adam_multi's bits; e <- e + (1 - d_t) (p_new - e) as written at ema_one_minus_decay above.  No reference
-// counterpart (the reference keeps no averaged generator).
-static int adam_ema_multi_launch(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
-                                 const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
-                                 const float *step, const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream) {
-    if (ntensors < 1 || !p || !g || !m || !v || !e || !n || !step || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) ||
-        !(beta2 >= 0. && beta2 < 1.) || !(eps >= 0.) || !(ema_decay >= 0. && ema_decay < 1.))
-        return PDGN_ERR_INVALID;
-    for (int i = 0; i < ntensors; ++i)
-        if (!p[i] || !g[i] || !m[i] || !v[i] || !e[i] || n[i] < 1 ||
-            (((uintptr_t)p[i] | (uintptr_t)g[i] | (uintptr_t)m[i] | (uintptr_t)v[i] | (uintptr_t)e[i]) & 3))
-            return PDGN_ERR_INVALID;
-    if (guard_misplaced(guard) || sched_misplaced(sched)) return PDGN_ERR_INVALID;
-    for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {                  // every launch's chunk count is checked before the first launch
-        long long chunks = 0;
-        for (int i = t0; i < ntensors && i < t0 + ADAM_EMA_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
-    }
-    for (int t0 = 0; t0 < ntensors; t0 += ADAM_EMA_MAXT) {
-        AdamEmaArgs a;
-        a.ntensors = ntensors - t0 < ADAM_EMA_MAXT ? ntensors - t0 : ADAM_EMA_MAXT;
-        long long chunks = 0;
-        for (int i = 0; i < a.ntensors; ++i) {
-            a.p[i] = (float *)p[t0 + i]; a.g[i] = (const float *)g[t0 + i]; a.m[i] = (float *)m[t0 + i]; a.v[i] = (float *)v[t0 + i];
-            a.e[i] = (float *)e[t0 + i];
-            a.n[i] = n[t0 + i];
-            a.chunk0[i] = (int)chunks;
-            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        }
-        for (int i = a.ntensors; i < ADAM_EMA_MAXT; ++i) { a.p[i] = a.m[i] = a.v[i] = a.e[i] = nullptr; a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        if (sched && guard)
-            hipLaunchKernelGGL(adam_ema_guard_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr,
-                               beta1, beta2, eps, ema_decay, step, guard, sched);
-        else if (sched)
-            hipLaunchKernelGGL(adam_ema_sched_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
-                               beta2, eps, ema_decay, step, sched);
-        else if (guard)
-            hipLaunchKernelGGL(adam_ema_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1,
-                               beta2, eps, ema_decay, step, guard);
-        else
-            hipLaunchKernelGGL(adam_ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, lr, beta1, beta2, eps,
-                               ema_decay, step);
-    }
-    return pdgn_launch_status();
-}
-
+// pdgn_adam_multi with the averages (adam_multi_launch<AdamEmaArgs> above).
 extern "C" int pdgn_adam_ema_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
                                    const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
                                    const float *step, pdgn_stream_t stream) {
-    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, nullptr, nullptr, stream);
+    return adam_multi_launch<AdamEmaArgs>(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, nullptr, nullptr, stream);
 }
 
 // The two launches above behind a gradient guard (pdgn_gradnorm_multi below, on the same stream in front of them): every workgroup
@@ -350,14 +338,14 @@ extern "C" int pdgn_adam_guard_multi(int ntensors, void *const *p, const void *c
                                      double lr, double beta1, double beta2, double eps, const float *step, const pdgn_guard_record *guard,
                                      pdgn_stream_t stream) {
     if (!guard) return PDGN_ERR_INVALID;
-    return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, nullptr, stream);
+    return adam_multi_launch<AdamArgs>(ntensors, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, 0., step, guard, nullptr, stream);
 }
 
 extern "C" int pdgn_adam_ema_guard_multi(int ntensors, void *const *p, const void *const *g, void *const *m, void *const *v, void *const *e,
                                          const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
                                          const float *step, const pdgn_guard_record *guard, pdgn_stream_t stream) {
     if (!guard) return PDGN_ERR_INVALID;
-    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, nullptr, stream);
+    return adam_multi_launch<AdamEmaArgs>(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, nullptr, stream);
 }
 
 // The four launches above with a learning-rate schedule (lr_factor at the top of this file): the rate in the arithmetic is
@@ -368,8 +356,8 @@ extern "C" int pdgn_adam_sched_multi(int ntensors, void *const *p, const void *c
                                      const long long *n, double lr, double beta1, double beta2, double eps, double ema_decay,
                                      const float *step, const pdgn_guard_record *guard, const double *sched, pdgn_stream_t stream) {
     if (!sched) return PDGN_ERR_INVALID;
-    if (!e) return adam_multi_launch(ntensors, p, g, m, v, n, lr, beta1, beta2, eps, step, guard, sched, stream);
-    return adam_ema_multi_launch(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, sched, stream);
+    if (!e) return adam_multi_launch<AdamArgs>(ntensors, p, g, m, v, nullptr, n, lr, beta1, beta2, eps, 0., step, guard, sched, stream);
+    return adam_multi_launch<AdamEmaArgs>(ntensors, p, g, m, v, e, n, lr, beta1, beta2, eps, ema_decay, step, guard, sched, stream);
 }
 
 // out2[0..1] <- {f, lr_eff}, out_lr32[0] <- (float)lr_eff of the update about to happen (lr_eval_kernel above): one thread, on `stream`.
@@ -383,7 +371,7 @@ extern "C" int pdgn_lr_eval(const double *sched, double lr, const float *step, c
 }
 
 // ---- the same walk for a plain copy: dst[i] <- src[i] for a list of fp32 tensors (the pack of a network's fresh gradients into the
-// flat all-reduce buffer, trainer.FlatGrads: torch._foreach_copy_ takes 82 us for the generator's 160 tensors / 50.8 MB)
+// flat all-reduce buffer, optim.FlatGrads: torch._foreach_copy_ takes 82 us for the generator's 160 tensors / 50.8 MB)
 #define COPY_MAXT 128               // tensors per launch (28 bytes of arguments each)
 struct CopyArgs {
     float *d[COPY_MAXT];
@@ -429,20 +417,11 @@ extern "C" int pdgn_copy_multi(int ntensors, void *const *dst, const void *const
     if (ntensors < 1 || !dst || !src || !n) return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
         if (!dst[i] || !src[i] || n[i] < 1 || (((uintptr_t)dst[i] | (uintptr_t)src[i]) & 3)) return PDGN_ERR_INVALID;
-    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
-        CopyArgs a;
-        a.ntensors = ntensors - t0 < COPY_MAXT ? ntensors - t0 : COPY_MAXT;
-        long long chunks = 0;
-        for (int i = 0; i < a.ntensors; ++i) {
-            a.d[i] = (float *)dst[t0 + i]; a.s[i] = (const float *)src[t0 + i]; a.n[i] = n[t0 + i];
-            a.chunk0[i] = (int)chunks;
-            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-            if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
-        }
-        for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.d[i] = nullptr; a.s[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        hipLaunchKernelGGL(copy_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a);
-    }
-    return pdgn_launch_status();
+    const int rc = for_each_launch<CopyArgs>(ntensors, n, [&](CopyArgs &a, int t0, unsigned chunks) {
+        for (int i = 0; i < a.ntensors; ++i) { a.d[i] = (float *)dst[t0 + i]; a.s[i] = (const float *)src[t0 + i]; }
+        hipLaunchKernelGGL(copy_multi_kernel, dim3(chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a);
+    });
+    return rc ? rc : pdgn_launch_status();
 }
 
 // ---- the same walk for the average alone: e[i] <- e[i] + (1 - d_t) (p[i] - e[i]), where the optimizer step in front of it was not
@@ -637,27 +616,13 @@ static int ema_multi_launch(int ntensors, void *const *e, const void *const *p, 
     if (ntensors < 1 || !e || !p || !n || !step || !(ema_decay >= 0. && ema_decay < 1.)) return PDGN_ERR_INVALID;
     for (int i = 0; i < ntensors; ++i)
         if (!e[i] || !p[i] || n[i] < 1 || (((uintptr_t)e[i] | (uintptr_t)p[i]) & 3)) return PDGN_ERR_INVALID;
-    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
-        long long chunks = 0;
-        for (int i = t0; i < ntensors && i < t0 + COPY_MAXT; ++i) chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        if (chunks > 0x3fffffffLL) return PDGN_ERR_INVALID;
-    }
-    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
-        EmaArgs a;
-        a.ntensors = ntensors - t0 < COPY_MAXT ? ntensors - t0 : COPY_MAXT;
-        long long chunks = 0;
-        for (int i = 0; i < a.ntensors; ++i) {
-            a.e[i] = (float *)e[t0 + i]; a.p[i] = (const float *)p[t0 + i]; a.n[i] = n[t0 + i];
-            a.chunk0[i] = (int)chunks;
-            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        }
-        for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.e[i] = nullptr; a.p[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        if (guard)
-            hipLaunchKernelGGL(ema_guard_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step, guard);
-        else
-            hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, ema_decay, step);
-    }
-    return pdgn_launch_status();
+    const int rc = for_each_launch<EmaArgs>(ntensors, n, [&](EmaArgs &a, int t0, unsigned chunks) {
+        for (int i = 0; i < a.ntensors; ++i) { a.e[i] = (float *)e[t0 + i]; a.p[i] = (const float *)p[t0 + i]; }
+        const dim3 grid(chunks), block(ADAM_THREADS);
+        if (guard) hipLaunchKernelGGL(ema_guard_multi_kernel, grid, block, 0, (hipStream_t)stream, a, ema_decay, step, guard);
+        else hipLaunchKernelGGL(ema_multi_kernel, grid, block, 0, (hipStream_t)stream, a, ema_decay, step);
+    });
+    return rc ? rc : pdgn_launch_status();
 }
 
 extern "C" int pdgn_ema_multi(int ntensors, void *const *e, const void *const *p, const long long *n, double ema_decay, const float *step,
@@ -674,17 +639,9 @@ extern "C" int pdgn_ema_guard_multi(int ntensors, void *const *e, const void *co
 
 static long long gradnorm_chunks(int ntensors, const long long *n) {
     if (ntensors < 1 || !n) return -1;
-    long long total = 0;
-    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
-        long long chunks = 0;
-        for (int i = t0; i < ntensors && i < t0 + COPY_MAXT; ++i) {
-            if (n[i] < 1) return -1;
-            chunks += (n[i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        }
-        if (chunks > 0x3fffffffLL) return -1;
-        total += chunks;
-    }
-    return total;
+    for (int i = 0; i < ntensors; ++i)
+        if (n[i] < 1) return -1;
+    return list_chunks(ntensors, n, COPY_MAXT);
 }
 
 // Doubles of workspace pdgn_gradnorm_multi takes for this list: one per 4096-element chunk of every tensor; -1 for an invalid list.
@@ -701,19 +658,11 @@ extern "C" int pdgn_gradnorm_multi(int ntensors, const void *const *g, const lon
     for (int i = 0; i < ntensors; ++i)
         if (!g[i] || ((uintptr_t)g[i] & 3)) return PDGN_ERR_INVALID;
     long long done = 0;
-    for (int t0 = 0; t0 < ntensors; t0 += COPY_MAXT) {
-        GradArgs a;
-        a.ntensors = ntensors - t0 < COPY_MAXT ? ntensors - t0 : COPY_MAXT;
-        long long chunks = 0;
-        for (int i = 0; i < a.ntensors; ++i) {
-            a.g[i] = (const float *)g[t0 + i]; a.n[i] = n[t0 + i];
-            a.chunk0[i] = (int)chunks;
-            chunks += (n[t0 + i] + ADAM_CHUNK - 1) / ADAM_CHUNK;
-        }
-        for (int i = a.ntensors; i < COPY_MAXT; ++i) { a.g[i] = nullptr; a.n[i] = 0; a.chunk0[i] = 0x7fffffff; }
-        hipLaunchKernelGGL(gradnorm_partial_kernel, dim3((unsigned)chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, workspace + done);
+    for_each_launch<GradArgs>(ntensors, n, [&](GradArgs &a, int t0, unsigned chunks) {
+        for (int i = 0; i < a.ntensors; ++i) a.g[i] = (const float *)g[t0 + i];
+        hipLaunchKernelGGL(gradnorm_partial_kernel, dim3(chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, a, workspace + done);
         done += chunks;
-    }
+    });
     hipLaunchKernelGGL(gradnorm_final_kernel, dim3(1), dim3(ADAM_THREADS), 0, (hipStream_t)stream, (const double *)workspace, total, max_norm,
                        record);
     return pdgn_launch_status();

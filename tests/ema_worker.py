@@ -76,7 +76,7 @@ def trainer_scenario(eager_steps=3, list_steps=3):
     assert all(torch.isfinite(v).item() for v in out.values())
     check("list")
     own = os.environ.get("PDGN_OWN_ADAM", "1") == "1"
-    assert (tr._stepG._table is not None) == own                                 # which optimizer kernel ran
+    assert (tr._stepG.route == "own") == own                                     # which optimizer kernel ran
     return tr, reals, z1, z2
 
 

@@ -255,7 +255,7 @@ def test_every_route_applies_the_scheduled_rate():
     assert lean.lists and float(lean.lr32) == lm.lr32(LR, tab, 1) and lean.lr_out.cpu().numpy()[1] == lm.lr_eff(LR, tab, 1)
     # 2: the lean route on the own kernel -- the fp64 rate, evaluated inside the launch (no pdgn_lr_eval: lr32 is still update 1's)
     assert both(2, float(lm.lr_eff(LR, tab, 2)))
-    assert lean._table is not None and float(lean.lr32) == lm.lr32(LR, tab, 1)
+    assert lean.route == "own" and float(lean.lr32) == lm.lr32(LR, tab, 1)
     # 3: the lean route with the own kernel switched off on the instances -- torch._fused_adam_ with the scalar as its lr
     lean._OWN = twin._OWN = False
     assert both(3, float(lm.lr32(LR, tab, 3)))

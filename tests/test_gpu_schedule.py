@@ -317,15 +317,14 @@ def test_own_adam_kernel_equals_torch_fused_adam():
     lean = LeanAdamStep(ob)
     assert lean._OWN
     used = []
-    orig = lean._own_adam
-    lean._own_adam = lambda *a: used.append(orig(*a)) or used[-1]
     for it in range(5):
         grads = [torch.randn(n, device="cuda", generator=g) * (10.0 ** ((i % 7) - 4)) for i, n in enumerate(sizes)]
         for p, q, gr in zip(pa, pb, grads):
             p.grad, q.grad = gr.clone(), gr.clone()
         oa.step()
         lean.step()
-    assert used and all(used), used                       # steps 2..5 ran on the own kernel (the first is the optimizer's own)
+        used.append(lean.route)
+    assert used == ["public"] + ["own"] * 4, used         # steps 2..5 ran on the own kernel (the first is the optimizer's own)
     for i, (p, q) in enumerate(zip(pa, pb)):
         assert torch.allclose(p, q, rtol=3e-7, atol=1e-9), (i, (p - q).abs().max().item())      # an ulp of the parameter: five updates of <= lr each
         for key in ("exp_avg", "exp_avg_sq"):

@@ -55,7 +55,7 @@ def optimizer_only(ema, steps):
     for _ in range(steps + 1):                                   # (the first one is the optimizer's own step)
         lean.step()
     torch.cuda.synchronize()
-    assert lean._table is not None
+    assert lean.route == "own"
     print("parameters %d in %d tensors" % (sum(p.numel() for p in params), len(params)))
 
 
