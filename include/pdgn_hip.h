@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 38
+#define PDGN_ABI_VERSION 39
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1094,6 +1094,33 @@ int pdgn_auction_assign_indexed(int npairs, int n, const float *xyz1, const int3
                                 float *cost, int32_t *status, pdgn_stream_t stream);
 int pdgn_auction_cost_grad(int b, int n, const float *xyz1, const float *xyz2, const int32_t *assign, const float *g, float *grad1,
                            float *grad2, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ visible faces of a mesh set (csrc/visible.hip)
+ * Which faces of the shapes of a mesh set (verts, faces, face_off: as pdgn_feed_batch_mesh takes them) can be seen from NV
+ * orthographic views: per (shape, view) a depth buffer of R x R pixels in LDS, filled by integer minima, and one depth test per face
+ * against it.  The header block of csrc/visible.hip is the normative definition (snap to integers, pass 1, pass 2, the fallback of a
+ * face that covers no pixel centre); tests/visible_mirror.py spells it in numpy.  No reference counterpart.
+ *   frame  (S,4) float, device: per shape the centre (3) and the radius rho > 0 of a ball that holds its vertices
+ *   views  (NV,3,3) float, device: per view the rows e_x, e_y (image axes) and e_z (depth: the view looks along +e_z, a smaller e_z . p
+ *          is nearer the eye); orthonormal is the caller's to guarantee, 1 <= NV <= PDGN_VISIBLE_MAX_VIEWS
+ *   R      PDGN_VISIBLE_MIN_RES .. PDGN_VISIBLE_MAX_RES; 4 R^2 bytes of LDS per workgroup
+ *   mask   (F) uint32, cleared here on `stream`, then bit v of mask[f] is set when face f passes in view v.  A face of zero area in 3D,
+ *          or one that names a vertex outside [0, V), keeps 0.
+ * The two biases of the test, in depth quanta of rho 2^-20: PDGN_VISIBLE_BIAS_COVER (a face that covers pixel centres: two layers
+ * closer than rho 2^-10 are one surface) and pdgn_mesh_visibility_bias_small(R) = floor(3 2^20 / R) (a face that covers none: the depth
+ * a face at 45 degrees spans over 1.5 pixels; PDGN_ERR_INVALID for an unsupported R).
+ * The result is a pure function of the arguments, bit for bit: integer minima and integer ORs only.  One memset and one launch of S NV
+ * workgroups on `stream`; before them the radii are read back once (the call waits for `stream`: a once-per-run pass, not for capture).
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: S, V or F < 1, 3 V, 3 F or S NV beyond the int range, NV or R outside their
+ * ranges, a null pointer or one not 4-byte aligned, a radius that is not finite or not positive. */
+#define PDGN_VISIBLE_MAX_VIEWS 32
+#define PDGN_VISIBLE_MIN_RES 16
+#define PDGN_VISIBLE_MAX_RES 192
+#define PDGN_VISIBLE_BIAS_COVER 1024
+int pdgn_mesh_visibility_bias_cover(void);
+int pdgn_mesh_visibility_bias_small(int R);
+int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off, const float *frame,
+                         const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

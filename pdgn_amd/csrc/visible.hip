@@ -1,0 +1,271 @@
+// visible.hip -- pdgn_mesh_visibility: which faces of a triangle mesh can be seen from a ring of viewpoints.  Per (shape, view) an
+// orthographic depth buffer in LDS and a per-face depth test against it; bit v of mask[f] says that face f passes in view v.  The
+// faces whose mask is 0 get weight 0 in the alias table (pdgn_amd/meshes.py), so the feed kernel never draws from them: the surface
+// sampled is the one that can be seen.  Runs once per run or once per `pack`.
+//
+// THE DEFINITION (normative; tests/visible_mirror.py spells the same function in numpy).  Shape c has the frame (centre ctr, radius
+// rho); view v has the rows e_x, e_y, e_z; the image is R x R pixels.
+//   Snap.   For a vertex p:  d = p - ctr;  x = ((e_x0 d0 + e_x1 d1) + e_x2 d2), y and z likewise with e_y and e_z; every fp32
+//           subtraction, product and sum is rounded on its own, never contracted.  With s = R 2^7 (exact in fp32):
+//             X = (int) clamp(rint((x / rho) s), -s, s) + s         in [0, 2^8 R]: pixel units with 8 sub-pixel bits
+//             Y likewise;   Z = (int) clamp(rint((z / rho) 2^20), -2^20, 2^20) + 2^20      in [0, 2^21]; a smaller Z is nearer the eye
+//           (x / rho is the correctly rounded fp32 quotient, rint rounds halves to even, a NaN clamps to the lower end.)  After the snap
+//           nothing is floating point.
+//   Dead.   A face of zero area in 3D is skipped in both passes: e1 = v1 - v0, e2 = v2 - v0 and n = e1 x e2 (n_x = e1_y e2_z - e1_z e2_y,
+//           ...) in fp64, every operation rounded on its own, all three components zero -- the host's face_areas(verts, faces) == 0.  So
+//           is a face that names a vertex outside [0, V).
+//   Pass 1. Every pixel starts at 0xffffffff.  With edge(A, B, P) = (B.x - A.x)(P.y - A.y) - (B.y - A.y)(P.x - A.x) in int64: A2 =
+//           edge(P0, P1, P2); where A2 < 0, P1 and P2 (and their Z) change places and A2 its sign.  A face with A2 != 0 looks at the
+//           pixel centres C = ((2 px + 1) 2^7, (2 py + 1) 2^7), 0 <= px, py < R, of its bounding box: C is COVERED when w0 = edge(P1, P2, C),
+//           w1 = edge(P2, P0, C) and w2 = edge(P0, P1, C) are all >= 0 (edges inclusive, faces two-sided: no back-face culling); there
+//           Zp = floor((w0 Z0 + w1 Z1 + w2 Z2) / A2)  (below 2^55) and  buf[py R + px] = min(buf[py R + px], Zp).
+//           A face with A2 = 0, or one that covers no centre, writes nothing: it cannot occlude.
+//   Pass 2. After one barrier.  A face that covers centres PASSES when Zp <= buf + PDGN_VISIBLE_BIAS_COVER at any of them.  A face that
+//           covers none (edge-on in this view, or smaller than a pixel) is tested once, at the pixel (min(Xc >> 8, R - 1), min(Yc >> 8, R - 1))
+//           that holds the integer centroid Xc = floor((X0 + X1 + X2) / 3), Yc likewise, with Zc = floor((Z0 + Z1 + Z2) / 3): it passes when
+//           Zc <= buf + pdgn_mesh_visibility_bias_small(R) = floor(3 2^20 / R), where an empty pixel (0xffffffff) lets everything pass.
+//           A face that passes ORs 1 << v into mask[f].
+// Everything the result depends on is an integer minimum or an integer OR: two runs agree bit for bit and a permutation of a shape's
+// faces permutes its masks.
+//
+// THE KERNEL.  One workgroup of 256 threads per (shape, view), view fastest in the grid, so that the NV workgroups that gather the same
+// vertices run next to each other and hit in L2.  The depth buffer is dynamic LDS, 4 R^2 bytes (64 KB at R = 128: two workgroups per
+// CU; 144 KB at R = 192: one).  Faces are taken 256 at a time, a lane per face: a face whose clipped bounding box holds at most
+// VIS_SMALL_BOX pixels is rasterised by its lane; a larger one is appended to an LDS list and, after a barrier, taken by a whole wave
+// whose lanes stride over the pixels of its box (a face as large as the image is 16 384 centres at R = 128: 256 per lane).  The two
+// passes are the same sweep with atomicMin (ds_min_u32) in the first and a compare in the second.  The division by A2 is an fp64
+// estimate corrected by one step either way with the integer remainder: exact.
+#include "common.h"
+
+#define VIS_THREADS 256
+#define VIS_WAVES (VIS_THREADS / PDGN_WAVE)
+#define VIS_SMALL_BOX 32
+#define VIS_EMPTY 0xffffffffu
+
+struct VisArgs {
+    const float *verts;
+    const int32_t *faces, *face_off;
+    const float *frame, *views;
+    uint32_t *mask;
+    int V, F, NV, R, bias_small;
+};
+
+struct VisFace {
+    int x0, y0, z0, x1, y1, z1, x2, y2, z2;
+    int bx, by, bw, bh;                                          // the clipped pixel box; bw * bh = 0: no centre to look at
+    long long a2;
+    double ra2;
+};
+
+struct VisView {
+    float ex[3], ey[3], ez[3], c[3], rho;
+    int R;
+};
+
+__device__ __forceinline__ float vis_dot(const float *e, float d0, float d1, float d2) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(e[0], d0), __fmul_rn(e[1], d1)), __fmul_rn(e[2], d2));
+}
+
+__device__ __forceinline__ int vis_quant(float t, float rho, float s) {
+    const float q = rintf(__fmul_rn(t / rho, s));
+    return (int)fminf(fmaxf(q, -s), s) + (int)s;                 // (fmaxf drops a NaN: the lower end)
+}
+
+__device__ __forceinline__ void vis_snap(const VisView &w, const float *p, int &X, int &Y, int &Z) {
+    const float d0 = __fsub_rn(p[0], w.c[0]), d1 = __fsub_rn(p[1], w.c[1]), d2 = __fsub_rn(p[2], w.c[2]);
+    const float s = (float)(w.R << 7);
+    X = vis_quant(vis_dot(w.ex, d0, d1, d2), w.rho, s);
+    Y = vis_quant(vis_dot(w.ey, d0, d1, d2), w.rho, s);
+    Z = vis_quant(vis_dot(w.ez, d0, d1, d2), w.rho, 1048576.f);
+}
+
+__device__ __forceinline__ long long vis_edge(int ax, int ay, int bx, int by, int px, int py) {
+    return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
+}
+
+// Gather and snap face f.  False: the face is dead (zero area in 3D, or an index outside the vertices).
+__device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int f, VisFace &t) {
+    const int i0 = a.faces[3 * (size_t)f], i1 = a.faces[3 * (size_t)f + 1], i2 = a.faces[3 * (size_t)f + 2];
+    if ((unsigned)i0 >= (unsigned)a.V || (unsigned)i1 >= (unsigned)a.V || (unsigned)i2 >= (unsigned)a.V) return false;
+    const float *q0 = a.verts + 3 * (size_t)i0, *q1 = a.verts + 3 * (size_t)i1, *q2 = a.verts + 3 * (size_t)i2;
+    const float p0[3] = {q0[0], q0[1], q0[2]}, p1[3] = {q1[0], q1[1], q1[2]}, p2[3] = {q2[0], q2[1], q2[2]};
+    {
+        const double ux = __dsub_rn((double)p1[0], (double)p0[0]), uy = __dsub_rn((double)p1[1], (double)p0[1]), uz = __dsub_rn((double)p1[2], (double)p0[2]);
+        const double vx = __dsub_rn((double)p2[0], (double)p0[0]), vy = __dsub_rn((double)p2[1], (double)p0[1]), vz = __dsub_rn((double)p2[2], (double)p0[2]);
+        const double nx = __dsub_rn(__dmul_rn(uy, vz), __dmul_rn(uz, vy));
+        const double ny = __dsub_rn(__dmul_rn(uz, vx), __dmul_rn(ux, vz));
+        const double nz = __dsub_rn(__dmul_rn(ux, vy), __dmul_rn(uy, vx));
+        if (nx == 0.0 && ny == 0.0 && nz == 0.0) return false;
+    }
+    vis_snap(w, p0, t.x0, t.y0, t.z0);
+    vis_snap(w, p1, t.x1, t.y1, t.z1);
+    vis_snap(w, p2, t.x2, t.y2, t.z2);
+    t.a2 = vis_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+    if (t.a2 < 0) {
+        int s;
+        s = t.x1, t.x1 = t.x2, t.x2 = s;
+        s = t.y1, t.y1 = t.y2, t.y2 = s;
+        s = t.z1, t.z1 = t.z2, t.z2 = s;
+        t.a2 = -t.a2;
+    }
+    t.bw = t.bh = 0, t.bx = t.by = 0, t.ra2 = 0.0;
+    if (t.a2 != 0) {
+        // the centres (2 p + 1) 2^7 inside [lo, hi]: p from ceil((lo - 128) / 256) to floor((hi - 128) / 256), clipped to the image
+        const int xlo = min(t.x0, min(t.x1, t.x2)), xhi = max(t.x0, max(t.x1, t.x2));
+        const int ylo = min(t.y0, min(t.y1, t.y2)), yhi = max(t.y0, max(t.y1, t.y2));
+        const int px0 = (xlo + 127) >> 8, px1 = min((xhi - 128) >> 8, w.R - 1);
+        const int py0 = (ylo + 127) >> 8, py1 = min((yhi - 128) >> 8, w.R - 1);
+        if (px1 >= px0 && py1 >= py0) t.bx = px0, t.by = py0, t.bw = px1 - px0 + 1, t.bh = py1 - py0 + 1;
+        t.ra2 = 1.0 / (double)t.a2;
+    }
+    return true;
+}
+
+// floor(num / den) for 0 <= num < 2^55, 0 < den < 2^34 and a quotient of at most 2^21: the fp64 estimate is off by less than one
+__device__ __forceinline__ long long vis_div(long long num, long long den, double rden) {
+    long long q = (long long)((double)num * rden);
+    long long r = num - q * den;
+    if (r < 0) --q, r += den;
+    if (r >= den) ++q;
+    return q;
+}
+
+// The pixels start, start + step, ... (row-major in the box) of face t.  TEST false: pass 1, minima into buf.  TEST true: pass 2; returns
+// whether the face passed at one of these pixels, covered whether one of them was covered.
+template <bool TEST>
+__device__ __forceinline__ bool vis_scan(const VisFace &t, unsigned *buf, int R, int start, int step, bool &covered) {
+    const int n = t.bw * t.bh;
+    const int qy = step / t.bw, qx = step - qy * t.bw;
+    int iy = start / t.bw, ix = start - iy * t.bw;
+    bool pass = false;
+    for (int k = start; k < n; k += step) {
+        const int px = t.bx + ix, py = t.by + iy;
+        const int cx = (2 * px + 1) << 7, cy = (2 * py + 1) << 7;
+        const long long w0 = vis_edge(t.x1, t.y1, t.x2, t.y2, cx, cy);
+        const long long w1 = vis_edge(t.x2, t.y2, t.x0, t.y0, cx, cy);
+        const long long w2 = t.a2 - w0 - w1;                     // = edge(P0, P1, C): the three sum to A2 identically
+        if ((w0 | w1 | w2) >= 0) {
+            const long long zp = vis_div(w0 * t.z0 + w1 * t.z1 + w2 * t.z2, t.a2, t.ra2);
+            if (TEST) {
+                covered = true;
+                if (zp <= (long long)buf[py * R + px] + PDGN_VISIBLE_BIAS_COVER) {
+                    pass = true;
+                    break;
+                }
+            } else {
+                atomicMin(buf + py * R + px, (unsigned)zp);
+            }
+        }
+        ix += qx, iy += qy;
+        if (ix >= t.bw) ix -= t.bw, ++iy;
+    }
+    return pass;
+}
+
+__device__ __forceinline__ bool vis_fallback(const VisFace &t, const unsigned *buf, int R, int bias_small) {
+    const int px = min((t.x0 + t.x1 + t.x2) / 3 >> 8, R - 1), py = min((t.y0 + t.y1 + t.y2) / 3 >> 8, R - 1);
+    return (long long)((t.z0 + t.z1 + t.z2) / 3) <= (long long)buf[py * R + px] + bias_small;
+}
+
+extern __shared__ unsigned vis_buf[];
+
+template <bool TEST>
+__device__ __forceinline__ void vis_pass(const VisArgs &a, const VisView &w, int f0, int f1, unsigned bit, int *s_list, int *s_cnt) {
+    const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int par = 0;
+    for (int base = f0; base < f1; base += VIS_THREADS, par ^= 1) {
+        // ---- a lane per face: the small ones here, the large ones onto the list
+        const int f = base + tid;
+        VisFace t;
+        if (f < f1 && vis_load(a, w, f, t)) {
+            const int n = t.bw * t.bh;
+            if (n > VIS_SMALL_BOX) {
+                s_list[atomicAdd(&s_cnt[par], 1)] = f;
+            } else {
+                bool covered = false, pass = false;
+                if (n > 0) pass = vis_scan<TEST>(t, vis_buf, w.R, 0, 1, covered);
+                if (TEST) {
+                    if (!covered) pass = vis_fallback(t, vis_buf, w.R, a.bias_small);
+                    if (pass) atomicOr(a.mask + f, bit);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- a wave per large face
+        const int cnt = s_cnt[par];
+        if (tid == 0) s_cnt[par ^ 1] = 0;                        // (last read before the barrier that ended the previous sweep)
+        for (int e = wave; e < cnt; e += VIS_WAVES) {
+            const int g = __builtin_amdgcn_readfirstlane(s_list[e]);
+            vis_load(a, w, g, t);                                // (it was alive when it was listed)
+            bool covered = false;
+            const bool pass = vis_scan<TEST>(t, vis_buf, w.R, lane, PDGN_WAVE, covered);
+            if (TEST) {
+                const bool any_pass = __any(pass), any_cov = __any(covered);
+                if (lane == 0 && (any_cov ? any_pass : vis_fallback(t, vis_buf, w.R, a.bias_small))) atomicOr(a.mask + g, bit);
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;                 // (the next pass starts from parity 0 again)
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(VIS_THREADS) void visible_kernel(VisArgs a) {
+    __shared__ int s_list[VIS_THREADS];
+    __shared__ int s_cnt[2];
+    const int tid = threadIdx.x;
+    const int shape = blockIdx.x / a.NV, view = blockIdx.x - shape * a.NV;
+    VisView w;
+    const float *e = a.views + 9 * view, *fr = a.frame + 4 * (size_t)shape;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w.ex[i] = e[i], w.ey[i] = e[3 + i], w.ez[i] = e[6 + i], w.c[i] = fr[i];
+    w.rho = fr[3], w.R = a.R;
+    const int f0 = max(a.face_off[shape], 0), f1 = min(a.face_off[shape + 1], a.F);
+    for (int i = tid; i < a.R * a.R; i += VIS_THREADS) vis_buf[i] = VIS_EMPTY;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    vis_pass<false>(a, w, f0, f1, 0u, s_list, s_cnt);            // (its last sweep ends with the barrier between the passes)
+    vis_pass<true>(a, w, f0, f1, 1u << view, s_list, s_cnt);
+}
+
+extern "C" int pdgn_mesh_visibility_bias_cover(void) { return PDGN_VISIBLE_BIAS_COVER; }
+
+extern "C" int pdgn_mesh_visibility_bias_small(int R) {
+    if (R < PDGN_VISIBLE_MIN_RES || R > PDGN_VISIBLE_MAX_RES) return PDGN_ERR_INVALID;
+    return (3 << 20) / R;
+}
+
+extern "C" int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off,
+                                    const float *frame, const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream) {
+    // host-side checks: nothing is launched and nothing written before all of them have passed
+    if (S < 1 || V < 1 || F < 1 || NV < 1 || NV > PDGN_VISIBLE_MAX_VIEWS || R < PDGN_VISIBLE_MIN_RES || R > PDGN_VISIBLE_MAX_RES)
+        return PDGN_ERR_INVALID;
+    if (3LL * V > 0x7fffffffLL || 3LL * F > 0x7fffffffLL || (long long)S * NV > 0x7fffffffLL) return PDGN_ERR_INVALID;
+    if (!verts || !faces || !face_off || !frame || !views || !mask) return PDGN_ERR_INVALID;
+    if (((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)face_off | (uintptr_t)frame | (uintptr_t)views | (uintptr_t)mask) & 3)
+        return PDGN_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    {   // the radii, read back once (16 S bytes; the stream is waited for): a frame the snap would divide by is refused here
+        float *host = (float *)malloc(sizeof(float) * 4 * (size_t)S);
+        if (!host) return PDGN_ERR_INVALID;
+        hipError_t e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipMemcpy(host, frame, sizeof(float) * 4 * (size_t)S, hipMemcpyDeviceToHost);
+        bool ok = e == hipSuccess;
+        for (int c = 0; ok && c < S; ++c) ok = host[4 * c + 3] > 0.f && host[4 * c + 3] <= 3.4028234e38f;      // (false for a NaN)
+        free(host);
+        if (e != hipSuccess) return (int)e;
+        if (!ok) return PDGN_ERR_INVALID;
+    }
+    VisArgs a;
+    a.verts = verts, a.faces = faces, a.face_off = face_off, a.frame = frame, a.views = views, a.mask = mask;
+    a.V = V, a.F = F, a.NV = NV, a.R = R, a.bias_small = (3 << 20) / R;
+    const size_t lds = (size_t)R * R * 4;
+    if (lds > 48 * 1024) {                                       // (beside it the kernel's static 1 KB: the attribute is the dynamic part alone)
+        hipError_t e = hipFuncSetAttribute((const void *)visible_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipError_t e = hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)F, s);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(visible_kernel, dim3(S * NV), dim3(VIS_THREADS), lds, s, a);
+    return pdgn_launch_status();
+}

@@ -5,6 +5,10 @@ is a fresh i.i.d. sample of its surface (data.MeshFeeder -> csrc/feed.hip: pdgn_
 global faces, the shapes' face ranges and one alias table (Walker 1977 / Vose 1991) per shape, which picks a face with probability
 proportional to its area from one 8-byte load -- normalised in closed form over the SURFACE; `MeshSet.sample` draws held-out clouds
 (pdgn_sample_surface).  `python -m pdgn_amd.meshes pack DIR OUT.npz` packs a directory <synsetid>/<split>/*.obj into one file.
+
+Visible-surface sampling: `face_visibility` asks the device which faces some view of a ring can see
+(csrc/visible.hip: pdgn_mesh_visibility); a `MeshSet` built with `visible=mask` gives the others weight zero wherever the area is used,
+so they are never drawn.  `pack --visible` stores the masks beside the meshes.
 """
 import os
 import sys
@@ -103,22 +107,101 @@ def surface_statistics(verts, faces, face_off, area=None):
     return centroid, np.sqrt(np.maximum(second / 3.0 - pooled * pooled, 0.0))
 
 
+# ---------------------------------------------------------------------------- visible faces (csrc/visible.hip)
+def _directions():
+    """The 26 directions of {-1,0,1}^3 without the origin: the 6 axes, then the 8 corners, then the 12 edge midpoints."""
+    grid = [(x, y, z) for x in (1, 0, -1) for y in (1, 0, -1) for z in (1, 0, -1) if (x, y, z) != (0, 0, 0)]
+    return np.asarray(sorted(grid, key=lambda d: ({1: 0, 3: 1, 2: 2}[abs(d[0]) + abs(d[1]) + abs(d[2])],)), dtype=np.float64)
+
+
+def view_bases(directions):
+    """(NV,3,3) fp32 rows (e_x, e_y, e_z) of the views that look at the centre FROM the given directions (NV,3): e_z = -d / |d| (depth
+    grows away from the eye), e_x = a x e_z normalised with a the coordinate axis of the smallest |d| component (the first of equals),
+    e_y = e_z x e_x; in fp64, rounded to fp32 at the end."""
+    d = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    norm = np.linalg.norm(d, axis=1)
+    if not (d.shape[0] >= 1 and np.all(np.isfinite(d)) and np.all(norm > 0)):
+        raise ValueError("view_bases: directions are finite and not zero")
+    ez = -d / norm[:, None]
+    a = np.eye(3)[np.argmin(np.abs(ez), axis=1)]
+    ex = np.cross(a, ez)
+    ex /= np.linalg.norm(ex, axis=1)[:, None]
+    ey = np.cross(ez, ex)
+    return np.ascontiguousarray((np.stack([ex, ey, ez], 1) + 0.0).astype(np.float32))      # (+ 0.0: no negative zeros)
+
+
+def default_views(n=26):
+    """The view table of `face_visibility`: n = 6 (the axes), 14 (and the corners) or 26 (and the edge midpoints) directions."""
+    if n not in (6, 14, 26):
+        raise ValueError("default_views: 6, 14 or 26 views, got %r" % (n,))
+    return view_bases(_directions()[:n])
+
+
+def shape_frames(verts, faces, face_off):
+    """(S,4) fp32 (centre, radius) per shape: the centre of the box of the vertices of its faces of positive area, and the largest
+    distance of such a vertex from it times (1 + 2^-10), in fp64; (0, 0, 0, 1) for a shape without such a face."""
+    v = np.asarray(verts, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    area = face_areas(v, faces)
+    out = np.zeros((len(face_off) - 1, 4), dtype=np.float64)
+    out[:, 3] = 1.0
+    for c in range(out.shape[0]):
+        f = faces[face_off[c]:face_off[c + 1]][area[face_off[c]:face_off[c + 1]] > 0.0]
+        if f.shape[0]:
+            p = v[np.unique(f)]
+            ctr = (p.min(axis=0) + p.max(axis=0)) / 2.0
+            out[c, :3], out[c, 3] = ctr, np.sqrt(((p - ctr) ** 2).sum(axis=1).max()) * (1.0 + 2.0 ** -10)
+    return out.astype(np.float32)
+
+
+def face_visibility(verts, faces, face_off, views=26, resolution=128, device=None):
+    """mask (F) uint32 numpy: bit v set where face f passes the depth test of view v (pdgn_mesh_visibility; the definition is the header
+    block of csrc/visible.hip).  views: 6 / 14 / 26 (`default_views`), an (NV,3) array of directions to look from, or an (NV,3,3) table
+    of bases; raw or normalised geometry alike (the frame of `shape_frames` makes the result the same up to the snap)."""
+    import torch
+    from . import _lib
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    face_off = np.ascontiguousarray(face_off, dtype=np.int32).reshape(-1)
+    S, V, F = face_off.shape[0] - 1, verts.shape[0], faces.shape[0]
+    if S < 1 or face_off[0] != 0 or face_off[-1] != F or np.any(np.diff(face_off) < 0):
+        raise ValueError("face_visibility: face_off must ascend from 0 to the number of faces over at least one shape")
+    if F and (faces.min() < 0 or faces.max() >= V):
+        raise ValueError("face_visibility: a face names a vertex outside the %d vertices" % V)
+    table = default_views(views) if np.ndim(views) == 0 else np.asarray(views)
+    table = view_bases(table) if table.ndim == 2 else np.ascontiguousarray(table, dtype=np.float32)
+    if table.ndim != 3 or table.shape[1:] != (3, 3):
+        raise ValueError("face_visibility: views are a count, (NV,3) directions or (NV,3,3) bases, got %s" % (table.shape,))
+    frame = shape_frames(verts, faces, face_off)
+    dev = torch.device("cuda" if device is None else device)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    d_verts, d_faces, d_off, d_frame, d_views = t(verts), t(faces), t(face_off), t(frame), t(table)
+    _lib.require(d_verts, "the vertices", torch.float32, 2)
+    mask = torch.zeros(F, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().pdgn_mesh_visibility(S, V, F, _lib.ptr(d_verts), _lib.ptr(d_faces), _lib.ptr(d_off), _lib.ptr(d_frame),
+                                               _lib.ptr(d_views), int(table.shape[0]), int(resolution), _lib.ptr(mask),
+                                               _lib.stream_of(d_verts)), "pdgn_mesh_visibility")
+    return mask.cpu().numpy().view(np.uint32)
+
+
 class MeshSet:
     """S shapes as the device arrays of pdgn_feed_batch_mesh / pdgn_sample_surface (include/pdgn_hip.h): verts (V,3) fp32, faces (F,3)
     int32 global vertex indices, face_off (S+1) int32, alias (F,2) int32 holding the bits of the uint32 records (threshold, alias local
     to the shape); shift (S,3) / scale (S) fp32: the normalisation that was applied ((raw - shift) / scale).  Built by `from_meshes` /
     `from_arrays`, which guarantee what the kernels trust: every shape owns a face of positive area, every index is inside the vertex
-    array, every alias inside its shape."""
+    array, every alias inside its shape.  visible (F) or None: the view masks the set was built with -- a face whose mask is 0 has
+    weight zero in the table (threshold 0, nobody's alias: never drawn) and in the normalisation."""
 
-    def __init__(self, verts, faces, face_off, alias, shift, scale, normalize=None):
+    def __init__(self, verts, faces, face_off, alias, shift, scale, normalize=None, visible=None):
         self.verts, self.faces, self.face_off, self.alias, self.shift, self.scale = verts, faces, face_off, alias, shift, scale
         self.normalize = normalize
+        self.visible = visible                                   # (F) int32, the bits of the uint32 masks of `face_visibility`, or None
         self.S, self.V, self.F = int(face_off.shape[0]) - 1, int(verts.shape[0]), int(faces.shape[0])
 
     # ------------------------------------------------------------------ construction (host, numpy)
     @classmethod
-    def from_meshes(cls, meshes, normalize=None, names=None):
-        """meshes: a list of (verts (V_c,3), faces (F_c,3) indices into that shape's own vertices)."""
+    def from_meshes(cls, meshes, normalize=None, names=None, visible=None):
+        """meshes: a list of (verts (V_c,3), faces (F_c,3) indices into that shape's own vertices); visible: as `from_arrays`."""
         meshes = list(meshes)
         if not meshes:
             raise ValueError("MeshSet: no shapes")
@@ -136,11 +219,12 @@ class MeshSet:
             faces.append(f.astype(np.int64) + at)
             at += v.shape[0]
             face_off.append(face_off[-1] + f.shape[0])
-        return cls.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.asarray(face_off), normalize, names)
+        return cls.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.asarray(face_off), normalize, names, visible)
 
     @classmethod
-    def from_arrays(cls, verts, faces, face_off, normalize=None, names=None):
-        """From the concatenated form (what `pack` stores): verts (V,3), faces (F,3) GLOBAL indices, face_off (S+1)."""
+    def from_arrays(cls, verts, faces, face_off, normalize=None, names=None, visible=None):
+        """From the concatenated form (what `pack` stores): verts (V,3), faces (F,3) GLOBAL indices, face_off (S+1).  visible: (F) masks
+        (`face_visibility`); a face whose mask is 0 counts as a face of area zero in the table, the normalisation and the vertex box."""
         import torch
         if normalize not in NORMALIZE:
             raise ValueError("MeshSet: normalize %r -- meshes take None, 'shape_unit' or 'shape_bbox' (global_unit, shape_half and shape_34 "
@@ -171,8 +255,20 @@ class MeshSet:
         for c in range(S):
             if not np.any(area[face_off[c]:face_off[c + 1]] > 0.0):
                 raise ValueError("%s: no face of positive area (%d faces)" % (name(c), face_off[c + 1] - face_off[c]))
+        if visible is not None:
+            visible = np.ascontiguousarray(np.asarray(visible).astype(np.uint32, copy=False)).reshape(-1)
+            if visible.shape[0] != F:
+                raise ValueError("MeshSet: %d visibility masks for %d faces" % (visible.shape[0], F))
+            area = np.where(visible != 0, area, 0.0)
+            for c in range(S):
+                if not np.any(area[face_off[c]:face_off[c + 1]] > 0.0):
+                    raise ValueError("%s: no visible face of positive area (%d faces, every mask is 0)" % (name(c), face_off[c + 1] - face_off[c]))
         # the normalisation, over the surface
-        if normalize == "shape_unit":
+        if normalize == "shape_unit" and visible is not None:      # over the visible faces alone: the sums of a set that holds no others, bit for bit
+            keep = visible != 0
+            kept_off = np.concatenate([[0], np.cumsum(_per_shape(keep.astype(np.int64), face_off))])
+            shift, scale = surface_statistics(verts, faces[keep], kept_off, area[keep])
+        elif normalize == "shape_unit":
             shift, scale = surface_statistics(verts, faces, face_off, area)
         elif normalize == "shape_bbox":                          # data.normalize_clouds' expressions, in fp32, on the vertices of the faces of positive area
             shift, scale = np.zeros((S, 3), np.float32), np.ones(S, np.float32)
@@ -189,30 +285,47 @@ class MeshSet:
             moved = ((verts.astype(np.float64) - np.asarray(shift, np.float64)[own]) / np.asarray(scale, np.float64)[own][:, None]).astype(np.float32)
             verts = np.where(used[:, None], moved, verts)
             area = face_areas(verts, faces)                      # (a uniform scale per shape: the same table up to rounding; built from what is drawn from)
+            if visible is not None:
+                area = np.where(visible != 0, area, 0.0)
         alias = np.empty((F, 2), dtype=np.uint32)
         for c in range(S):
             a, b = face_off[c], face_off[c + 1]
             alias[a:b, 0], alias[a:b, 1] = alias_table(area[a:b])
         t = torch.from_numpy
         return cls(t(verts), t(faces.astype(np.int32)), t(face_off.astype(np.int32)), t(alias.view(np.int32)),
-                   t(np.asarray(shift, np.float32)), t(np.asarray(scale, np.float32)), normalize)
+                   t(np.asarray(shift, np.float32)), t(np.asarray(scale, np.float32)), normalize,
+                   None if visible is None else t(visible.view(np.int32).copy()))
 
     # ------------------------------------------------------------------ storage and placement
     _FIELDS = ("verts", "faces", "face_off", "alias", "shift", "scale")
 
     def save(self, path):
+        extra = {} if self.visible is None else {"visible": self.visible.cpu().numpy()}
         np.savez(path, normalize=np.asarray("" if self.normalize is None else self.normalize),
-                 **{k: getattr(self, k).cpu().numpy() for k in self._FIELDS})
+                 **{k: getattr(self, k).cpu().numpy() for k in self._FIELDS}, **extra)
 
     @classmethod
     def load(cls, path):
         import torch
         with np.load(path) as f:
             mode = str(f["normalize"])
-            return cls(*(torch.from_numpy(f[k]) for k in cls._FIELDS), normalize=mode or None)
+            return cls(*(torch.from_numpy(f[k]) for k in cls._FIELDS), normalize=mode or None,
+                       visible=torch.from_numpy(f["visible"]) if "visible" in f.files else None)
 
     def to(self, device):
-        return MeshSet(*(getattr(self, k).to(device).contiguous() for k in self._FIELDS), normalize=self.normalize)
+        return MeshSet(*(getattr(self, k).to(device).contiguous() for k in self._FIELDS), normalize=self.normalize,
+                       visible=None if self.visible is None else self.visible.to(device).contiguous())
+
+    def visible_stats(self):
+        """What the masks leave out: {"faces", "hidden" (S) int64, "kept" (S) the share of every shape's area that is still drawn from,
+        "total_faces", "total_hidden", "total_kept" (of the summed area)}; without masks nothing is hidden."""
+        verts, faces, off = self.verts.cpu().numpy(), self.faces.cpu().numpy().astype(np.int64), self.face_off.cpu().numpy().astype(np.int64)
+        area = face_areas(verts, faces)
+        seen = np.ones(self.F, dtype=bool) if self.visible is None else self.visible.cpu().numpy() != 0
+        total, kept = _per_shape(area, off), _per_shape(np.where(seen, area, 0.0), off)
+        hidden = _per_shape((~seen).astype(np.int64), off)
+        return {"faces": np.diff(off), "hidden": hidden, "kept": kept / total, "total_faces": self.F, "total_hidden": int(hidden.sum()),
+                "total_kept": float(kept.sum() / total.sum())}
 
     def alias_records(self):
         """(threshold, alias) as two uint32 numpy arrays (F)."""
@@ -261,12 +374,16 @@ def read_obj_root(root, synsetids=None):
     return out
 
 
-def pack(root, out_path):
-    """Write the directory's meshes as one .npz with the keys "<synsetid>/<split>/{verts,faces,face_off}" (raw, un-normalised)."""
+def pack(root, out_path, visible=None):
+    """Write the directory's meshes as one .npz with the keys "<synsetid>/<split>/{verts,faces,face_off}" (raw, un-normalised).
+    visible: a dict of `face_visibility` options (views, resolution, device) -- one more array "<synsetid>/<split>/visible" per split,
+    the (F) uint32 masks, computed on the device; None: the file is what it was before the masks existed."""
     arrays = {}
     for sid, splits in read_obj_root(root).items():
         for split, (v, f, off) in splits.items():
             arrays["%s/%s/verts" % (sid, split)], arrays["%s/%s/faces" % (sid, split)], arrays["%s/%s/face_off" % (sid, split)] = v, f, off
+            if visible is not None:
+                arrays["%s/%s/visible" % (sid, split)] = face_visibility(v, f, off, **visible)
     np.savez(out_path, **arrays)
     return sorted(arrays)
 
@@ -279,6 +396,17 @@ def load_packed(path, synsetids=None):
             sid, split, what = key.split("/")
             if what == "verts" and (synsetids is None or sid in synsetids):
                 out.setdefault(sid, {})[split] = tuple(f["%s/%s/%s" % (sid, split, k)] for k in ("verts", "faces", "face_off"))
+    return out
+
+
+def load_packed_visible(path, synsetids=None):
+    """{synsetid: {split: (F) uint32 masks}} of the splits of a packed file that `pack --visible` stored masks for (empty: none)."""
+    out = {}
+    with np.load(path) as f:
+        for key in f.files:
+            sid, split, what = key.split("/")
+            if what == "visible" and (synsetids is None or sid in synsetids):
+                out.setdefault(sid, {})[split] = f[key].astype(np.uint32, copy=False)
     return out
 
 
@@ -298,29 +426,74 @@ def is_mesh_root(path):
     return False
 
 
+class MeshRoot(dict):
+    """The mapping `open_mesh_root` returns; `visible`: what `load_packed_visible` found beside the meshes ({} for a directory)."""
+    visible = {}
+
+
 def open_mesh_root(path, synsetids=None):
-    return read_obj_root(str(path), synsetids) if os.path.isdir(path) else load_packed(path, synsetids)
+    if os.path.isdir(path):
+        return MeshRoot(read_obj_root(str(path), synsetids))
+    root = MeshRoot(load_packed(path, synsetids))
+    root.visible = load_packed_visible(path, synsetids)
+    return root
 
 
-def split_meshset(root, split, normalize=None):
-    """One MeshSet of a split over every category of an opened root, categories in sorted order."""
+def has_stored_visible(root, split):
+    """Whether every category of an opened root that has the split has stored masks for it."""
+    stored = getattr(root, "visible", {})
+    sids = [sid for sid in sorted(root) if split in root[sid]]
+    return bool(sids) and all(split in stored.get(sid, {}) for sid in sids)
+
+
+def split_meshset(root, split, normalize=None, visible=None):
+    """One MeshSet of a split over every category of an opened root (`open_mesh_root`, or the path of one), categories in sorted order.
+    visible: None (every face is drawn from), a dict of `face_visibility` options (views, resolution, device: the masks are computed
+    now) or "stored" (the masks `pack --visible` wrote; an error where the data holds none)."""
+    if isinstance(root, (str, os.PathLike)):
+        root = open_mesh_root(root)
     parts = [root[sid][split] for sid in sorted(root) if split in root[sid]]
     if not parts:
         raise ValueError("the mesh data has no %r split" % split)
+    if visible is not None and not isinstance(visible, dict) and visible != "stored":
+        raise ValueError("split_meshset: visible is None, a dict of face_visibility options or 'stored', got %r" % (visible,))
+    if visible == "stored" and not has_stored_visible(root, split):
+        raise ValueError("visible='stored': the mesh data holds no visibility masks for its %r split (python -m pdgn_amd.meshes pack DIR "
+                         "OUT.npz --visible writes them)" % split)
     verts, faces, face_off, at, fat = [], [], [np.zeros(1, np.int64)], 0, 0
     for v, f, off in parts:
         verts.append(v)
         faces.append(f.astype(np.int64) + at)
         face_off.append(off[1:].astype(np.int64) + fat)
         at, fat = at + v.shape[0], fat + int(off[-1])
-    return MeshSet.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.concatenate(face_off, 0), normalize)
+    verts, faces, face_off = np.concatenate(verts, 0), np.concatenate(faces, 0), np.concatenate(face_off, 0)
+    mask = None
+    if visible == "stored":
+        mask = np.concatenate([root.visible[sid][split] for sid in sorted(root) if split in root[sid]], 0)
+    elif visible is not None:
+        mask = face_visibility(verts, faces, face_off, **visible)
+    return MeshSet.from_arrays(verts, faces, face_off, normalize, visible=mask)
+
+
+USAGE = "usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]"
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    if len(argv) != 3 or argv[0] != "pack":
-        raise SystemExit("usage: python -m pdgn_amd.meshes pack DIR OUT.npz")
-    keys = pack(argv[1], argv[2])
+    if len(argv) < 3 or argv[0] != "pack":
+        raise SystemExit(USAGE)
+    opts, rest, given = {"views": 26, "resolution": 128}, argv[3:], False
+    while rest:
+        flag = rest.pop(0)
+        if flag == "--visible":
+            given = True
+        elif flag in ("--views", "--resolution") and rest and rest[0].isdigit():
+            opts[flag[2:]] = int(rest.pop(0))
+        else:
+            raise SystemExit(USAGE)
+    if not given and opts != {"views": 26, "resolution": 128}:
+        raise SystemExit("--views and --resolution go with --visible\n" + USAGE)
+    keys = pack(argv[1], argv[2], opts if given else None)
     print("packed %d arrays into %s" % (len(keys), argv[2]))
 
 

@@ -27,7 +27,8 @@ nested farthest-point subsets of the finest cloud of the same row instead of thr
 .npz that `python -m pdgn_amd.meshes pack DIR OUT.npz` makes of one: the train split then stays on the device as meshes, normalised over
 its surface, and every visit of a shape is a fresh i.i.d. sample of its surface (data.MeshFeeder, pdgn_feed_batch_mesh; DESIGN.md section 7k);
 --phase test and the reports take draw 0 of --num_point surface points of every raw test / val mesh as their reference clouds;
---resample_pool does not apply.
+--resample_pool does not apply.  --mesh_visible on | compute (meshes only): the faces that none of --mesh_views orthographic views can see
+get weight zero, for the train split and the reference draws alike (pdgn_mesh_visibility).
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -113,11 +114,18 @@ def build_parser():
     p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
                    "independent draws with replacement, as the reference's loader) or fps (nested farthest-point subsets of the finest cloud, one more "
                    "launch per iteration)")
+    p.add_argument("--mesh_visible", choices=["off", "on", "compute"], default=argparse.SUPPRESS, help="meshes: draw from the VISIBLE surface only -- "
+                   "the faces that one of a ring of orthographic views can see (pdgn_mesh_visibility, DESIGN.md section 7m), for the train split and "
+                   "the reference draws alike; on: the masks `pack --visible` stored where the file has them, computed at start-up otherwise; "
+                   "compute: always computed; off (default): every face")
+    p.add_argument("--mesh_views", type=int, choices=[6, 14, 26], default=argparse.SUPPRESS, help="--mesh_visible: views of the ring (default 26)")
+    p.add_argument("--mesh_visible_res", type=int, default=argparse.SUPPRESS, metavar="R", help="--mesh_visible: pixels per side of a view's "
+                   "depth buffer, 16 .. 192 (default 128)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool, --subsample and --emd are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool, --subsample, --emd and the --mesh_visible flags are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -145,6 +153,9 @@ class Args(argparse.Namespace):
     ada_p_max = None
     resample_pool = None
     subsample = "random"
+    mesh_visible = "off"
+    mesh_views = 26
+    mesh_visible_res = 128
 
 
 def parse_args(argv=None):
@@ -179,6 +190,10 @@ def parse_args(argv=None):
     if args.subsample == "fps" and args.num_point > 8192:
         p.error("--subsample fps: --num_point %d, the farthest-point kernel holds at most 8192 points" % args.num_point)
     given = vars(args)
+    if args.mesh_visible == "off" and ("mesh_views" in given or "mesh_visible_res" in given):
+        p.error("--mesh_views and --mesh_visible_res go with --mesh_visible on / compute")
+    if not 16 <= args.mesh_visible_res <= 192:
+        p.error("--mesh_visible_res %d: 16 .. 192 (the depth buffer of a view lives in one workgroup's LDS)" % args.mesh_visible_res)
     for flag in ("lr_g", "lr_d"):
         rate = getattr(args, flag)
         if rate is not None and not (rate >= 0.0 and rate != float("inf")):
@@ -332,6 +347,9 @@ def _mesh_root(args):
     from . import meshes
     from .data import cate_to_synsetid
     if not meshes.is_mesh_root(args.data_root):
+        if args.mesh_visible != "off":
+            raise SystemExit("--mesh_visible %s: %s holds point clouds -- visibility is decided per face of a mesh, and stored clouds carry no "
+                             "faces; give a mesh --data_root or drop the flag" % (args.mesh_visible, args.data_root))
         return None
     if args.choice is not None and args.choice not in cate_to_synsetid:
         raise SystemExit("--choice %s: not a ShapeNetCore category" % args.choice)
@@ -341,6 +359,21 @@ def _mesh_root(args):
     return root
 
 
+def _visible_meshset(args, mesh_root, split, normalize, device):
+    """split_meshset under --mesh_visible, with the one line on standard output that says what the masks left out."""
+    from .meshes import has_stored_visible, split_meshset
+    if args.mesh_visible == "off":
+        return split_meshset(mesh_root, split, normalize)
+    stored = args.mesh_visible == "on" and has_stored_visible(mesh_root, split)
+    ms = split_meshset(mesh_root, split, normalize, visible="stored" if stored else
+                       {"views": args.mesh_views, "resolution": args.mesh_visible_res, "device": device})
+    st = ms.visible_stats()
+    print("--mesh_visible %s, %s split (%s): %d of %d faces hidden, %.2f %% of the area kept" % (
+        args.mesh_visible, split, "stored masks" if stored else "%d views at %d" % (args.mesh_views, args.mesh_visible_res),
+        st["total_hidden"], st["total_faces"], 100.0 * st["total_kept"]))
+    return ms
+
+
 def reference_clouds(args, split, device, mesh_root=None):
     """The (S, num_point, 3) reference clouds of the test phase and the reports, normalised by --normalize: the LAST num_point points of
     every stored cloud, or -- for meshes -- draw 0 of num_point surface points of every raw mesh of the split (MeshSet.sample: streams
@@ -348,8 +381,7 @@ def reference_clouds(args, split, device, mesh_root=None):
     if mesh_root is None:
         return load_split(args, split, args.normalize, tail=args.num_point).stack(device).float().contiguous()
     from .data import normalize_point_clouds
-    from .meshes import split_meshset
-    return normalize_point_clouds(split_meshset(mesh_root, split).to(device).sample(args.num_point, args.seed, draw=0), args.normalize).contiguous()
+    return normalize_point_clouds(_visible_meshset(args, mesh_root, split, None, device).to(device).sample(args.num_point, args.seed, draw=0), args.normalize).contiguous()
 
 
 def init_dist(device):
@@ -415,13 +447,12 @@ def _mesh_feeder(args, mesh_root, device, rank, world):
     """Meshes: the train split normalised over its surface (the cloud path's 'shape_unit'), resident on the device; every visit is a
     fresh surface sample (data.MeshFeeder)."""
     from .data import MeshFeeder
-    from .meshes import split_meshset
     if args.resample_pool is not None:
         raise SystemExit("--resample_pool: %s holds meshes -- every visit of a shape already draws fresh points from its whole surface, "
                          "there is no stored pool to restrict" % args.data_root)
     n = args.num_point
     try:
-        ms = split_meshset(mesh_root, "train", "shape_unit")
+        ms = _visible_meshset(args, mesh_root, "train", "shape_unit", device)
     except ValueError as e:
         raise SystemExit("%s: %s" % (args.data_root, e))
     return MeshFeeder(ms.to(device), args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world, num_point=n,
@@ -478,6 +509,7 @@ def test(args):
     from . import evaluation
     device = torch.device(args.device)
     ckpt = os.path.join(args.checkpoint_dir, args.model_dir, args.network)
+    mesh_root = _mesh_root(args)                                 # (first: a flag that does not fit the data is refused before anything is built)
     trainer = make_trainer(args, device)
     if _resume(args, trainer, ckpt) is None:
         print(" [!] Load failed...")                             # (:275-276: the reference goes on with the initial weights too)
@@ -486,7 +518,7 @@ def test(args):
     torch.manual_seed(args.seed)                                 # seed_all (:282)
     np.random.seed(args.seed)
     random.seed(args.seed)
-    ref = reference_clouds(args, "test", device, _mesh_root(args))
+    ref = reference_clouds(args, "test", device, mesh_root)
     trainer.G.eval()
     gen, results, raw = evaluation.generate_and_evaluate(trainer.G, ref, args.batch_size, normalize=args.normalize, return_raw=True,
                                                          emd=args.emd)
