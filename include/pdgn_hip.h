@@ -170,7 +170,21 @@ int pdgn_window_gather_sum_backward_csr(int b, int n, int k, int ldy, int T, int
  * pdgn_bn_eval_stats: the same `stats` from the running statistics (eval mode).
  * pre_bias (may be NULL, c floats): the bias of the conv / linear layer that produced x when the caller left it
  * OUT of x (BatchNorm(x + b) == BatchNorm(x), so the GEMM needs no bias epilogue); it only enters the running mean
- * (training) and the effective mean (eval), which keeps nn.BatchNorm's buffers identical to the reference's. */
+ * (training) and the effective mean (eval), which keeps nn.BatchNorm's buffers identical to the reference's.
+ *
+ * What each entry point writes of its scratch (tests/test_gpu_bn.py holds them to it; a call that returns -1 writes nothing at all).
+ * pdgn_bn_scratch_floats(rows, c) = gy*2c + 2c, gy the row blocks of the launch geometry; the region has two tenants:
+ *   pdgn_bn_stats                     writes the gy partial rows [sum (x - x[0]) | sum (x - x[0])^2] of 2c floats each and leaves
+ *                                     the 2c floats behind them untouched
+ *   pdgn_bn_stats_from_partials       reads gy rows [sum x | sum x^2] of 2c floats (no pivot) and writes nothing to scratch
+ *   pdgn_bn_act_backward              writes the gy partial rows [sum dz | sum dz*xhat] AND, behind them, the 2c coefficients [ca | cb]
+ *                                     of dx = scale*dz - ca - cb*x (both zero when training == 0): every float of the region
+ *   pdgn_bn_stats_from_gemm_partials  reads the first ceil(rows / block_rows) partial rows only -- the rows beyond them (nparts may be
+ *                                     larger) are never read -- the last of which covers rows - (that many - 1)*block_rows rows; in its
+ *                                     two-launch forms it writes all pdgn_bn_blocks_scratch_doubles(c, nparts) doubles of its fp64
+ *                                     scratch (slices that hold no partial row write zeros), in the one-launch form, or with
+ *                                     scratch == NULL, none; the two give the same statistics
+ *   pdgn_bn_eval_stats                has no scratch; running_mean / running_var are inputs */
 long long pdgn_bn_scratch_floats(long long rows, int c);
 int pdgn_bn_stats(long long rows, int c, float eps, float momentum, const float *x, const float *gamma,
                   const float *beta, const float *pre_bias, float *running_mean, float *running_var,
@@ -209,19 +223,30 @@ int pdgn_bn_act_backward(long long rows, int c, int act, int training, const flo
 /* BatchNorm + activation + max-pool over the n rows of each sample (the tail of the PointNet-style
  * discriminators, models/PDGNet_v2.py:886-911): x (b*n, c) -> ymax / yarg (b, c); the activated tensor
  * is never written.  stats from pdgn_bn_stats / pdgn_bn_eval_stats over all b*n rows.
- * scratch: pdgn_bn_maxpool_scratch_floats(b, c) floats. */
+ * scratch: pdgn_bn_maxpool_scratch_floats(b, c) floats (per sample and split: c maxima, then, behind all of them, c int32 rows).
+ *
+ * Ties.  Both forms return the same ymax bits for the same stats; they may name different rows where several rows attain it:
+ *   pdgn_bn_act_maxpool        yarg = the LOWEST row whose activated value act(fma(x, scale, shift)) equals ymax
+ *   pdgn_bn_stats_act_maxpool  yarg = the lowest row attaining the largest x of the sample where scale >= 0 (a scale of exactly 0
+ *                              included), the lowest row attaining the smallest x where scale < 0; ymax is that row's activated value
+ * The two differ where different x give the same activated bits: under ReLU's plateau (every z <= 0: the first form names row 0 of
+ * the sample), at scale == 0, and where fma(x, scale, shift) rounds two x to one value.  Where one row alone attains ymax both name it.
+ * Either yarg is a valid input of the adjoint below: the gradient flows to the row it names. */
 long long pdgn_bn_maxpool_scratch_floats(int b, int c);
 int pdgn_bn_act_maxpool(int b, int n, int c, int act, const float *x, const float *stats, float *scratch,
                         float *ymax, int32_t *yarg, pdgn_stream_t stream);
 /* Training mode without statistics from the producer: batch statistics (stats (4c) out; running statistics updated as by pdgn_bn_stats)
  * AND the pooled output in one pass over x -- the pass keeps per (sample, split, channel) the largest and the smallest x and picks by
- * the sign of the channel's scale afterwards (act(scale x + shift) is monotone in x).  scratch: pdgn_bn_stats_maxpool_scratch_floats. */
+ * the sign of the channel's scale afterwards (act(scale x + shift) is monotone in x).  scratch: pdgn_bn_stats_maxpool_scratch_floats
+ * (b*16 partial rows of 2c floats, pivot x[0], then maxima, their rows, minima, their rows: b*16*c each). */
 long long pdgn_bn_stats_maxpool_scratch_floats(int b, int c);
 int pdgn_bn_stats_act_maxpool(int b, int n, int c, int act, float eps, float momentum, const float *x, const float *gamma,
                               const float *beta, const float *pre_bias, float *running_mean, float *running_var, float *scratch,
                               float *stats, float *ymax, int32_t *yarg, pdgn_stream_t stream);
 /* Its adjoint in one streaming pass: dx (b*n, c) from dout (b, c); bsums (2c) = [dbeta | dgamma];
- * scratch: b*c + 2c floats. */
+ * scratch: b*c + 2c floats, all written: dz (b, c) = dout*act'(z at row yarg), then the coefficients [ca | cb] of
+ * dx = (n == yarg ? scale*dz : 0) - ca - cb*x.  act' is decided by z > 0 here and in pdgn_bn_act_backward: at z == 0 it is the
+ * negative side's (0 for ReLU, 0.01 for LeakyReLU). */
 int pdgn_bn_act_maxpool_backward(int b, int n, int c, int act, int training, const float *x,
                                  const float *dout, const int32_t *yarg, const float *stats,
                                  float *scratch, float *bsums, float *dx, pdgn_stream_t stream);
