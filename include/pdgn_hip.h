@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 39
+#define PDGN_ABI_VERSION 40
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -119,7 +119,9 @@ int pdgn_emd_cost(int b, int n, int m, const float *xyz1, const float *xyz2, flo
  * Feature-space kNN graph of models/PDGNet_v2.py:447-458 / :488-502 (get_edge_features[_xyz]):
  * x (b,f,n) channels-first -> idx (b,n,k) int32 = ranks 1..k of the row-wise ascending order of
  * (-2<x_i,x_j> + |x_i|^2) + |x_j|^2 (rank 0 dropped; ties by index).  sqnorm (b,n) is scratch.
- * f <= 256, k <= 31, n >= k+1. */
+ * f <= 256, k <= 31.  n <= k (no reference counterpart: its slice [1 : k+1] of n sorted entries comes back short and the gather
+ * fails): ranks 1 .. n-1 fill the leading slots and the remaining k - (n - 1) slots repeat rank 0, the point itself wherever it is
+ * its own nearest -- an edge of length zero; this is what lets a generator start from fewer base points than it has neighbours. */
 int pdgn_feature_knn(int b, int f, int n, int k, const float *x, float *sqnorm, int32_t *idx,
                      pdgn_stream_t stream);
 
@@ -833,7 +835,7 @@ int pdgn_nndistance_grad_det(int b, int n, const float *xyz1, int m, const float
  *   counter = (group j, global row = row0 + b, t low 32, tag | (t >> 32 & 0xffffff) << 8)
  *   tag     = 0, 1, 2: the index streams of p1, p2, p3;  3, 4: z1, z2  (5: the host's epoch permutation, pdgn_amd.data.epoch_order;
  *             6: the round keys of pdgn_feed_batch_resample, 7: the start index of pdgn_feed_fps_pyramid, 8 .. 11: the surface draws
- *             of pdgn_feed_batch_mesh, 12: pdgn_sample_surface, all below)
+ *             of pdgn_feed_batch_mesh, 12: pdgn_sample_surface, 13: the round keys of pdgn_sample_ragged, all below)
  * A group is the four output words of one counter.  Index streams: word e of group j is column 4j + e, i = (word * N) >> 32
  * (bias of a point's probability at most N / 2^32 relative: 4.8e-7 at N = 2048).  Noise: group j gives columns 4j .. 4j+3 as
  * two Box-Muller pairs (words 0,1 and 2,3): u1 = ((w >> 8) + 1) * 2^-24 in (0, 1], u2 = (w' >> 8) * 2^-24 in [0, 1),
@@ -912,6 +914,45 @@ int pdgn_feed_batch_mesh(int B, int S, int V, int F, int N, int r1, int r2, int 
  * PDGN_ERR_INVALID: S < 1, n < 1, a null or misaligned mesh pointer (as above) or out (4 bytes). */
 int pdgn_sample_surface(int S, int n, const float *verts, const int32_t *faces, const int32_t *face_off, const uint32_t *alias,
                         unsigned long long seed, unsigned long long draw, float *out, int32_t *face_rec, pdgn_stream_t stream);
+
+/* The same launch for clouds that store DIFFERENT numbers of points (part-annotation sets, scans, the output of any surface sampler with
+ * a density target; no reference counterpart for the device feed: PartDataset.__getitem__, datasets_4point.py:76-96, which draws
+ * np.random.choice(len, n, replace = len <= n) per item on the host, is the nearest thing).  A ragged set is two device arrays:
+ *   points   (T,3) float      the points of all S shapes, back to back
+ *   off      (S+1) int64      shape c owns the points [off[c], off[c+1]), M_c = off[c+1] - off[c] of them, M_c >= 1; 8-byte aligned
+ * All integer arithmetic is exact; the Philox layout, key and tags are pdgn_feed_batch's.  Local row b takes shape c = order[first + b]
+ * (clamped as pdgn_feed_batch clamps); lo = off[c] clamped into [0, T], M_c = off[c+1] - lo clamped into [0, T - lo] -- a bad table reads
+ * other points than it names, never outside points; a row with M_c = 0 (only reachable with a table pdgn_amd.clouds.CloudSet refuses)
+ * writes zeros to its columns of p1 .. p4.
+ *   p4[b,:,j]       = points[lo + pi_c(j mod M_c)],  j < N, pi_c the keyed Feistel permutation of pdgn_feed_batch_resample with P
+ *                     replaced by M_c: h_c = (max(2, bit length of M_c - 1) + 1) / 2 computed per row, the six round keys from the
+ *                     counters (0 | 1, global row, t low 32, 6 | (t >> 32 & 0xffffff) << 8), cycle-walked into [0, M_c).
+ *                     M_c >= N: N DISTINCT points of the shape, a fresh subset per visit.  M_c < N: every stored point appears
+ *                     floor(N / M_c) or ceil(N / M_c) times -- the whole short cloud, its duplicates spread evenly, no new random
+ *                     stream.  (The reference draws such a cloud fully WITH replacement, which leaves about a fraction
+ *                     (1 - 1/M_c)^N of its points out of the item: holes.  Here nothing stored is left out.)
+ *   pk[b,:,j]       = points[lo + ((word * M_c) >> 32)]: pdgn_feed_batch's counters and tags 0 1 2, WITH replacement from the whole
+ *                     shape, independently of p4;
+ *   z1, z2          exactly what pdgn_feed_batch writes for the same (seed, t, row0, sigma) (tags 3 4).
+ * On a set whose shapes all store M points every output byte equals pdgn_feed_batch_resample(M = P = M); W ranks at batch B draw what
+ * one rank draws at B * W; a resumed epoch is fed what an uninterrupted one is.  Geometry is pdgn_feed_batch_resample's: one thread
+ * owns four consecutive columns of one row (four 12-byte gathers, a 16-byte store per channel where the row length is a multiple of 4
+ * and the base 16-byte aligned), blockIdx.y is the row, no LDS, no atomics; offsets into points are 64-bit.
+ * PDGN_ERR_INVALID: pdgn_feed_batch's cases, a null points or off, off not 8-byte or points not 4-byte aligned, T < 1, T > 2^31 - 1
+ * (a shape's count -- the domain of its permutation and the operand of the multiply-high -- is one 31-bit number; with 64-bit
+ * offsets 3 T itself needs no smaller bound: 2^31 - 1 points are 24 GiB); checked on the host before anything is launched. */
+int pdgn_feed_batch_ragged(int B, int S, int N, int r1, int r2, int r3, const float *points, const long long *off, long long T,
+                           const int32_t *order, long long first, unsigned long long seed, unsigned long long t, long long row0,
+                           float sigma, float *p1, float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream);
+
+/* The same draw as an op (the reference clouds of the test phase and the reports): out (S,n,3) point-major,
+ *   out[s, j, :] = points[off[s] + pi_s(j mod M_s)],
+ * pi_s as above with the round keys from the counters (0 | 1, s, draw low 32, 13 | (draw >> 32 & 0xffffff) << 8), key (seed low 32,
+ * seed high 32): tag 13 keeps these streams apart from every training draw of the same seed; a pure function of (seed, draw).  The
+ * range of a shape is clamped as above.
+ * PDGN_ERR_INVALID: S < 1, n < 1, a null or misaligned points / off (as above) or out (4 bytes), T < 1, T > 2^31 - 1. */
+int pdgn_sample_ragged(int S, int n, const float *points, const long long *off, long long T, unsigned long long seed,
+                       unsigned long long draw, float *out /* (S,n,3) */, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ farthest-point sampling, register resident (csrc/fps.hip)
  * The iteration of furthestsampling_cuda_launcher (lib/pointops/src/sampling/sampling_cuda_kernel.cu:59-168; pdgn_furthestsampling

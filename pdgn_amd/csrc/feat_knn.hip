@@ -388,15 +388,51 @@ static int launch_fk(int b, int f, int n, int k, const float *x, const float *sq
     return pdgn_launch_status();
 }
 
+// Clouds of n <= k points (the base levels of a generator for very few points): one thread per point walks the row-wise ascending
+// order of the same key, (-2 <x_i,x_j> + |x_i|^2) + |x_j|^2 with ties by index, by repeated selection (n <= 31: no list is kept);
+// rank 0 is dropped, ranks 1 .. n-1 fill the leading slots and the k - (n - 1) slots no point is left for repeat rank 0 -- the point
+// itself wherever it is its own nearest, an edge of length zero.
+__global__ __launch_bounds__(64) void fk_small_kernel(int f, int n, int k, const float *__restrict__ x, const float *__restrict__ sq,
+                                                      int *__restrict__ idx) {
+    const int bs = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *X = x + (size_t)bs * f * n;
+    const float *SQ = sq + (size_t)bs * n;
+    int *out = idx + ((size_t)bs * n + i) * k;
+    float prev_d = 0.f;
+    int prev_j = -1, first = i;
+    for (int r = 0; r < n; ++r) {
+        float best_d = 0.f;
+        int best_j = -1;
+        for (int j = 0; j < n; ++j) {
+            float dot = 0.f;
+            for (int c = 0; c < f; ++c) dot = __fmaf_rn(X[(size_t)c * n + i], X[(size_t)c * n + j], dot);
+            const float d = __fadd_rn(__fadd_rn(__fmul_rn(-2.f, dot), SQ[i]), SQ[j]);
+            const bool after = prev_j < 0 || d > prev_d || (d == prev_d && j > prev_j);
+            if (after && (best_j < 0 || d < best_d)) best_d = d, best_j = j;     // (ascending j: the lower index wins a tie)
+        }
+        if (best_j < 0) best_j = first;                          // (a key that compares with nothing: not finite)
+        prev_d = best_d, prev_j = best_j;
+        if (r == 0) first = best_j;
+        else out[r - 1] = best_j;
+    }
+    for (int r = n - 1; r < k; ++r) out[r] = first;
+}
+
 extern "C" int pdgn_feature_knn(int b, int f, int n, int k, const float *x, float *sqnorm,
                                 int32_t *idx, pdgn_stream_t stream) {
-    if (b < 0 || f < 1 || f > 256 || n < 1 || k < 1 || k > FK_MAX_K || n < k + 1 || b > 65535)
+    if (b < 0 || f < 1 || f > 256 || n < 1 || k < 1 || k > FK_MAX_K || b > 65535)
         return PDGN_ERR_INVALID;
     if (b == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(sqnorm_kernel, dim3(cdiv(n, 256), b), dim3(256), 0, s, f, n, x, sqnorm);
     int rc = pdgn_launch_status();
     if (rc) return rc;
+    if (n < k + 1) {                                             // fewer points than ranks: the small-cloud kernel above
+        hipLaunchKernelGGL(fk_small_kernel, dim3(cdiv(n, 64), b), dim3(64), 0, s, f, n, k, x, sqnorm, idx);
+        return pdgn_launch_status();
+    }
     const int fh = (f + 1) / 2;
     if (fh <= 16) return launch_fk<16>(b, f, n, k, x, sqnorm, idx, s);
     if (fh <= 32) return launch_fk<32>(b, f, n, k, x, sqnorm, idx, s);

@@ -20,6 +20,13 @@
 // proportional) and a point inside it (folded barycentric coordinates, exact in fp32); four dependent gathers per point (face_off,
 // alias record, face, vertices) instead of one, no LDS, no atomics; the noise is pdgn_feed_batch's (construction in
 // include/pdgn_hip.h; mirror: tests/mesh_mirror.py).
+//
+// pdgn_feed_batch_ragged / pdgn_sample_ragged: the same launch for clouds that store DIFFERENT numbers of points (one (T,3) array and an
+// (S+1) int64 offset table).  A kernel of its own beside feed_batch_kernel<>, with that kernel's geometry and helpers: the row's range
+// (two 8-byte loads, clamped into the array) replaces the row stride, the Feistel half width is computed per row from the row's own
+// count, column j of p4 takes point pi(j mod M_c) -- N distinct points of a long cloud, the whole of a short one with its duplicates
+// spread evenly -- and the sub-resolutions draw from the whole shape; 64-bit offsets into the points (construction in
+// include/pdgn_hip.h; mirror: tests/ragged_mirror.py).
 #include "common.h"
 #include "philox.h"                                             // philox4x32_10, box_muller (shared with augment.hip)
 
@@ -31,6 +38,7 @@
 #define FEED_PERM_ROUNDS 6
 #define FEED_TAG_MESH 8u                                        // 8 .. 11: the surface draws of p1 .. p4 (pdgn_feed_batch_mesh)
 #define FEED_TAG_SURFACE 12u                                    // pdgn_sample_surface
+#define FEED_TAG_RAGGED 13u                                     // the round keys of pdgn_sample_ragged
 
 struct FeedArgs {
     int S, N, r[3];
@@ -393,5 +401,191 @@ extern "C" int pdgn_sample_surface(int S, int n, const float *verts, const int32
     a.d_lo = (unsigned)draw, a.d_hi24 = (unsigned)(draw >> 32) & 0xffffffu;
     a.out = out, a.face_rec = face_rec;
     hipLaunchKernelGGL(sample_surface_kernel, dim3(cdiv(a.groups, FEED_THREADS), min(S, 65535)), dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    return pdgn_launch_status();
+}
+
+// ---------------------------------------------------------------------------- ragged clouds
+struct RaggedRef {
+    const float *points;                                         // (T,3), every shape's points back to back
+    const long long *off;                                        // (S+1): shape c owns the points [off[c], off[c+1])
+    long long T;
+};
+
+// The points [lo, lo + M) of shape c.  lo is clamped into [0, T] and M into [0, T - lo]: a table that does not ascend inside [0, T] reads
+// other points than it names, never outside the array (T <= 2^31 - 1, checked on the host: M is a 31-bit count).
+__device__ __forceinline__ void ragged_range(const RaggedRef &r, int c, long long &lo, unsigned &M) {
+    const long long a = r.off[c], e = r.off[c + 1];
+    lo = min(max(a, 0LL), r.T);
+    M = (unsigned)max(min(max(e, 0LL), r.T) - lo, 0LL);
+}
+
+// bits of one Feistel half for a domain of M >= 1 points: (max(2, bit length of M - 1) + 1) / 2, what feed_launch computes from P
+__device__ __forceinline__ int ragged_half_bits(unsigned M) {
+    const int bits = M > 1u ? 32 - __clz((int)(M - 1u)) : 0;
+    return (max(bits, 2) + 1) >> 1;
+}
+
+// six round keys: words 0 1 2 3 of the counter (0, c1, c2, c3) and words 0 1 of (1, c1, c2, c3)
+__device__ __forceinline__ void ragged_keys(unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned key[8]) {
+    philox4x32_10(0u, c1, c2, c3, k0, k1, key);
+    philox4x32_10(1u, c1, c2, c3, k0, k1, key + 4);
+}
+
+// columns col0 .. col0 + 3 take the points pi((col0 + i) mod M) of the shape [lo, lo + M), M >= 1, pi the keyed Feistel permutation of [0, M)
+__device__ __forceinline__ void ragged_perm4(const RaggedRef &r, long long lo, unsigned M, unsigned col0, int cols, const unsigned key[8],
+                                             float v[12]) {
+    const int h = ragged_half_bits(M);
+    unsigned at = col0 % M;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned x = i < cols ? at : 0u;                         // (< M: inside the domain, and on a cycle that comes back below M)
+        do x = feistel_pass(x, h, key); while (x >= M);
+        const float *pt = r.points + (size_t)(lo + (long long)x) * 3;   // lo + x < lo + M <= T
+        v[3 * i] = pt[0], v[3 * i + 1] = pt[1], v[3 * i + 2] = pt[2];
+        at = at + 1u == M ? 0u : at + 1u;
+    }
+}
+
+struct RaggedFeedArgs {
+    int S, len[4];                                               // r1 r2 r3 N
+    int g[6];                                                    // as FeedArgs::g
+    int groups;
+    int vec;                                                     // bit k: output k takes 16-byte stores
+    RaggedRef set;
+    const int *order;
+    long long first;
+    unsigned k0, k1, t_lo, t_hi24;
+    unsigned row0;
+    float sigma;
+    float *p[4];
+    float *z[2];
+};
+
+__global__ __launch_bounds__(FEED_THREADS) void feed_batch_ragged_kernel(RaggedFeedArgs a) {
+    const int q = blockIdx.x * FEED_THREADS + threadIdx.x;       // the group of row b this thread owns
+    const int b = blockIdx.y;
+    if (q >= a.groups) return;
+    const unsigned row = a.row0 + (unsigned)b;
+    if (q >= a.g[4]) {                                           // ---- noise: pdgn_feed_batch's
+        const int which = q >= a.g[5];
+        feed_noise_group(q - a.g[4 + which], which, b, row, a.t_lo, a.t_hi24, a.k0, a.k1, a.sigma, a.z[which]);
+        return;
+    }
+    const int c = min(max(a.order[a.first + b], 0), a.S - 1);    // (clamped as feed_batch_kernel clamps)
+    long long lo;
+    unsigned M;
+    ragged_range(a.set, c, lo, M);
+    const int k = (q >= a.g[1]) + (q >= a.g[2]) + (q >= a.g[3]);
+    const int j = q - a.g[k];
+    const int r = a.len[k];
+    const int cols = min(4, r - 4 * j);
+    float v[12];
+    if (M == 0u) {                                               // (a table CloudSet refuses: the row is zeros, nothing is read)
+#pragma unroll
+        for (int i = 0; i < 12; ++i) v[i] = 0.f;
+    } else if (k == 3) {                                         // ---- columns 4j .. 4j+3 of p4: the points pi(4j mod M) ..
+        unsigned key[8];
+        ragged_keys(row, a.t_lo, FEED_TAG_PERM | (a.t_hi24 << 8), a.k0, a.k1, key);
+        ragged_perm4(a.set, lo, M, (unsigned)(4 * j), cols, key, v);
+    } else {                                                     // ---- a sub-resolution: i = umulhi(word, M), with replacement from the whole shape
+        unsigned w[4];
+        philox4x32_10((unsigned)j, row, a.t_lo, (unsigned)k | (a.t_hi24 << 8), a.k0, a.k1, w);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float *pt = a.set.points + (size_t)(lo + (long long)__umulhi(w[i], M)) * 3;
+            v[3 * i] = pt[0], v[3 * i + 1] = pt[1], v[3 * i + 2] = pt[2];
+        }
+    }
+    float *dst = a.p[k] + (size_t)b * 3 * r + 4 * j;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        store4(dst + (size_t)ch * r, cols, (a.vec >> k) & 1, v[ch], v[3 + ch], v[6 + ch], v[9 + ch]);
+}
+
+struct RaggedSampleArgs {
+    int S, n, groups, vec;
+    RaggedRef set;
+    unsigned k0, k1, d_lo, d_hi24;
+    float *out;
+};
+
+__global__ __launch_bounds__(FEED_THREADS) void sample_ragged_kernel(RaggedSampleArgs a) {
+    const int j = blockIdx.x * FEED_THREADS + threadIdx.x;       // columns 4j .. 4j+3
+    if (j >= a.groups) return;
+    const int cols = min(4, a.n - 4 * j);
+    for (int s = blockIdx.y; s < a.S; s += gridDim.y) {
+        long long lo;
+        unsigned M;
+        ragged_range(a.set, s, lo, M);
+        float v[12];
+        if (M == 0u) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) v[i] = 0.f;
+        } else {
+            unsigned key[8];
+            ragged_keys((unsigned)s, a.d_lo, FEED_TAG_RAGGED | (a.d_hi24 << 8), a.k0, a.k1, key);
+            ragged_perm4(a.set, lo, M, (unsigned)(4 * j), cols, key, v);
+        }
+        float *dst = a.out + ((size_t)s * a.n + (size_t)4 * j) * 3;                           // 48 contiguous bytes
+        if (a.vec) {                                             // (n a multiple of 4 and the base 16-byte aligned: so is every group)
+            float4 *d4 = reinterpret_cast<float4 *>(dst);
+            d4[0] = make_float4(v[0], v[1], v[2], v[3]), d4[1] = make_float4(v[4], v[5], v[6], v[7]), d4[2] = make_float4(v[8], v[9], v[10], v[11]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 12; ++i)
+                if (i < 3 * cols) dst[i] = v[i];
+        }
+    }
+}
+
+// what both ragged entry points refuse of the set itself.  T <= 2^31 - 1: a shape's count, the domain of its permutation and the operand of
+// the multiply-high, is one 31-bit number; the offsets into points, 3 (lo + x), are 64-bit, so 3 T itself has no bound of its own
+static bool ragged_invalid(int S, const float *points, const long long *off, long long T, RaggedRef &r) {
+    if (S < 1 || !points || !off) return true;
+    if (((uintptr_t)points & 3) || ((uintptr_t)off & 7)) return true;
+    if (T < 1 || T > 0x7fffffffLL) return true;
+    r.points = points, r.off = off, r.T = T;
+    return false;
+}
+
+extern "C" int pdgn_feed_batch_ragged(int B, int S, int N, int r1, int r2, int r3, const float *points, const long long *off, long long T,
+                                      const int32_t *order, long long first, unsigned long long seed, unsigned long long t, long long row0,
+                                      float sigma, float *p1, float *p2, float *p3, float *p4, float *z1, float *z2, pdgn_stream_t stream) {
+    RaggedFeedArgs a;
+    if (feed_args_invalid(B, S, N, r1, r2, r3, order, first, row0, p1, p2, p3, p4, z1, z2)) return PDGN_ERR_INVALID;
+    if (ragged_invalid(S, points, off, T, a.set)) return PDGN_ERR_INVALID;
+    a.S = S;
+    const int len[4] = {r1, r2, r3, N};
+    float *const out[4] = {p1, p2, p3, p4};
+    int at = 0;
+    a.vec = 0;
+    for (int k = 0; k < 4; ++k) {
+        a.len[k] = len[k], a.g[k] = at, a.p[k] = out[k];
+        at += (len[k] + 3) / 4;
+        if (len[k] % 4 == 0 && !((uintptr_t)out[k] & 15)) a.vec |= 1 << k;
+    }
+    a.g[4] = at, a.g[5] = at + FEED_NOISE_DIM / 4;
+    a.groups = at + 2 * (FEED_NOISE_DIM / 4);
+    a.order = order, a.first = first;
+    a.k0 = (unsigned)seed, a.k1 = (unsigned)(seed >> 32);
+    a.t_lo = (unsigned)t, a.t_hi24 = (unsigned)(t >> 32) & 0xffffffu;
+    a.row0 = (unsigned)row0;
+    a.sigma = sigma;
+    a.z[0] = z1, a.z[1] = z2;
+    hipLaunchKernelGGL(feed_batch_ragged_kernel, dim3(cdiv(a.groups, FEED_THREADS), B), dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
+    return pdgn_launch_status();
+}
+
+extern "C" int pdgn_sample_ragged(int S, int n, const float *points, const long long *off, long long T, unsigned long long seed,
+                                  unsigned long long draw, float *out, pdgn_stream_t stream) {
+    RaggedSampleArgs a;
+    if (ragged_invalid(S, points, off, T, a.set)) return PDGN_ERR_INVALID;
+    if (n < 1 || n > 0x7fffff00 || !out || ((uintptr_t)out & 3)) return PDGN_ERR_INVALID;
+    a.S = S, a.n = n, a.groups = (n + 3) / 4;
+    a.vec = n % 4 == 0 && !((uintptr_t)out & 15);
+    a.k0 = (unsigned)seed, a.k1 = (unsigned)(seed >> 32);
+    a.d_lo = (unsigned)draw, a.d_hi24 = (unsigned)(draw >> 32) & 0xffffffu;
+    a.out = out;
+    hipLaunchKernelGGL(sample_ragged_kernel, dim3(cdiv(a.groups, FEED_THREADS), min(S, 65535)), dim3(FEED_THREADS), 0, (hipStream_t)stream, a);
     return pdgn_launch_status();
 }

@@ -12,6 +12,7 @@ into the buffers the training step reads (`subsample="fps"`: a second launch, cs
 three independent with-replacement sub-samplings by nested farthest-point subsets of the finest cloud).  Clouds stored denser than they are trained on (the 15 000 points per shape of
 ShapeNetCore.v2.PC15k) go through pdgn_feed_batch_resample: a fresh `num_point` subset of every cloud each time it is visited.  `MeshFeeder` is the same feed for shapes stored
 as triangle meshes (pdgn_amd.meshes.MeshSet; pdgn_feed_batch_mesh): every visit of a shape is a fresh i.i.d. sample of its surface.
+`RaggedFeeder` is the same feed for shapes that store different numbers of points (pdgn_amd.clouds.CloudSet; pdgn_feed_batch_ragged).
 """
 import os
 import random
@@ -359,3 +360,39 @@ class MeshFeeder(_Feeder):
                             _lib.ptr(m.face_off), _lib.ptr(m.alias), _lib.ptr(self._order), first, self.seed & 0xFFFFFFFFFFFFFFFF, t, row0,
                             self.sigma, _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1),
                             _lib.ptr(z2), _lib.ptr(face_rec), _lib.stream_of(m.verts)), "pdgn_feed_batch_mesh")
+
+
+class RaggedFeeder(_Feeder):
+    """BatchFeeder for shapes that store different numbers of points (pdgn_amd.clouds.CloudSet on the device): ONE launch (csrc/feed.hip:
+    pdgn_feed_batch_ragged) writes the batch -- the finest output of a row is a fresh draw of num_point distinct points of its shape where
+    the shape stores that many, and the whole shape with evenly spread duplicates where it stores fewer; the sub-resolutions draw with
+    replacement from the whole shape; the schedule, the random streams' indexing by global row and global iteration and the noise are
+    BatchFeeder's.  subsample="fps": pdgn_feed_fps_pyramid behind the launch overwrites p1..p3 with nested farthest-point subsets of the
+    row's p4."""
+
+    _WHAT = "clouds"
+
+    def __init__(self, cloudset, batch_size, sizes, seed, rank=0, world=1, sigma=0.2, num_point=2048, subsample="random"):
+        from . import _lib
+        from .clouds import CloudSet
+        self._check_subsample(subsample)
+        if not isinstance(cloudset, CloudSet):
+            raise TypeError("RaggedFeeder takes a pdgn_amd.clouds.CloudSet on the device (CloudSet.from_clouds(...).to(device))")
+        _lib.require(cloudset.points, "the cloud set's points", torch.float32, 2)
+        _lib.require(cloudset.off, "the cloud set's offsets", torch.int64, 1)
+        if cloudset.off.device != cloudset.points.device:
+            raise _lib.PdgnHipError("the cloud set's offsets are on %s, its points on %s" % (cloudset.off.device, cloudset.points.device))
+        self.N = int(num_point)
+        if self.N < 1:
+            raise ValueError("num_point %d: at least one" % self.N)
+        self.clouds = cloudset
+        self._setup(cloudset.points.device, cloudset.S, batch_size, sizes, seed, rank, world, sigma, what="shapes")
+        self._fn = _lib.lib().pdgn_feed_batch_ragged
+
+    def _launch(self, first, t, row0, reals, z1, z2):
+        from . import _lib
+        c = self.clouds
+        _lib.check(self._fn(self.B, self.S, self.N, self.sizes[0], self.sizes[1], self.sizes[2], _lib.ptr(c.points), _lib.ptr(c.off), c.T,
+                            _lib.ptr(self._order), first, self.seed & 0xFFFFFFFFFFFFFFFF, t, row0, self.sigma,
+                            _lib.ptr(reals[0]), _lib.ptr(reals[1]), _lib.ptr(reals[2]), _lib.ptr(reals[3]), _lib.ptr(z1), _lib.ptr(z2),
+                            _lib.stream_of(c.points)), "pdgn_feed_batch_ragged")

@@ -29,6 +29,11 @@ its surface, and every visit of a shape is a fresh i.i.d. sample of its surface 
 --phase test and the reports take draw 0 of --num_point surface points of every raw test / val mesh as their reference clouds;
 --resample_pool does not apply.  --mesh_visible on | compute (meshes only): the faces that none of --mesh_views orthographic views can see
 get weight zero, for the train split and the reference draws alike (pdgn_mesh_visibility).
+--data_root may also hold RAGGED clouds, shapes that store different numbers of points -- the .npz that `python -m pdgn_amd.clouds pack DIR OUT.npz`
+makes of a directory <synsetid>/<split>/* of .npy / .pts / .xyz / .txt clouds (it identifies itself), or such a directory under --ragged: the train split
+stays on the device as one point array and an offset table, and every visit of a shape is a fresh draw of --num_point of its points, or all of them with
+evenly spread duplicates where it stores fewer (data.RaggedFeeder, pdgn_feed_batch_ragged; DESIGN.md section 7n); --min_points K drops shorter shapes at load;
+--phase test and the reports take draw 0 of --num_point points of every raw test / val shape; --resample_pool and --mesh_visible do not apply.
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -55,7 +60,8 @@ def build_parser():
     p.add_argument("--debug", type=bool, default=True, help="accepted and ignored, as in the reference")
     p.add_argument("--data_root", default="/opt/data/private/shapenet/shapenet.hdf5", help="shapenet.hdf5, an .npz with '<synsetid>/<split>' keys, or a "
                    "directory <synsetid>/<split>/*.npy (ShapeNetCore.v2.PC15k); meshes: a directory <synsetid>/<split>/*.obj or the .npz "
-                   "`python -m pdgn_amd.meshes pack` makes of one")
+                   "`python -m pdgn_amd.meshes pack` makes of one; ragged clouds: the .npz `python -m pdgn_amd.clouds pack` makes of a directory "
+                   "<synsetid>/<split>/* of .npy / .pts / .xyz / .txt clouds, or that directory under --ragged")
     p.add_argument("--log_info", default="log_info.txt")
     p.add_argument("--model_dir", help="model dir (required)")
     p.add_argument("--checkpoint_dir", default="checkpoint")
@@ -121,11 +127,16 @@ def build_parser():
     p.add_argument("--mesh_views", type=int, choices=[6, 14, 26], default=argparse.SUPPRESS, help="--mesh_visible: views of the ring (default 26)")
     p.add_argument("--mesh_visible_res", type=int, default=argparse.SUPPRESS, metavar="R", help="--mesh_visible: pixels per side of a view's "
                    "depth buffer, 16 .. 192 (default 128)")
+    p.add_argument("--ragged", action="store_true", default=argparse.SUPPRESS, help="read the directory --data_root as ragged clouds: "
+                   "<synsetid>/<split>/* of .npy / .pts / .xyz / .txt files that store different numbers of points (a packed ragged .npz "
+                   "identifies itself and needs no flag)")
+    p.add_argument("--min_points", type=int, default=argparse.SUPPRESS, metavar="K", help="ragged clouds: drop the shapes that store fewer than K "
+                   "points at load (default 1: none)")
     return p
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool, --subsample, --emd and the --mesh_visible flags are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool, --subsample, --emd, the --mesh_visible flags, --ragged and --min_points are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -156,6 +167,8 @@ class Args(argparse.Namespace):
     mesh_visible = "off"
     mesh_views = 26
     mesh_visible_res = 128
+    ragged = False
+    min_points = 1
 
 
 def parse_args(argv=None):
@@ -192,6 +205,8 @@ def parse_args(argv=None):
     given = vars(args)
     if args.mesh_visible == "off" and ("mesh_views" in given or "mesh_visible_res" in given):
         p.error("--mesh_views and --mesh_visible_res go with --mesh_visible on / compute")
+    if args.min_points < 1:
+        p.error("--min_points %d: at least one" % args.min_points)
     if not 16 <= args.mesh_visible_res <= 192:
         p.error("--mesh_visible_res %d: 16 .. 192 (the depth buffer of a view lives in one workgroup's LDS)" % args.mesh_visible_res)
     for flag in ("lr_g", "lr_d"):
@@ -341,6 +356,52 @@ def load_split(args, split, scale_mode, tail=None):
     return ShapeNetCore(cates, split, scale_mode, src, tail=tail)
 
 
+def _ragged_root(args):
+    """The opened ragged data of --data_root ({synsetid: {split: [clouds]}}, of --choice's category only): a packed ragged .npz, or a
+    directory under --ragged; None where --data_root holds anything else.  Decided before open_data_root is reached, and the flags that
+    cannot apply are refused here, before anything is built."""
+    from . import clouds
+    from .data import cate_to_synsetid
+    packed = clouds.is_ragged_root(args.data_root)
+    if not packed and not args.ragged:
+        if "min_points" in vars(args):
+            raise SystemExit("--min_points: %s does not hold ragged clouds (a packed ragged .npz, or a directory under --ragged) -- every other "
+                             "storage form has one count per data set, there is nothing to drop" % args.data_root)
+        return None
+    if not packed and not os.path.isdir(args.data_root):
+        raise SystemExit("--ragged: %s is neither a directory <synsetid>/<split>/* of clouds nor the .npz `python -m pdgn_amd.clouds pack` "
+                         "makes of one" % args.data_root)
+    if args.mesh_visible != "off":
+        raise SystemExit("--mesh_visible %s: %s holds ragged point clouds -- visibility is decided per face of a mesh, and stored clouds carry "
+                         "no faces; give a mesh --data_root or drop the flag" % (args.mesh_visible, args.data_root))
+    if args.resample_pool is not None:
+        raise SystemExit("--resample_pool: %s holds ragged clouds -- every shape has its own count and every visit draws from all of its "
+                         "points, there is no common leading pool to restrict" % args.data_root)
+    if args.choice is not None and args.choice not in cate_to_synsetid:
+        raise SystemExit("--choice %s: not a ShapeNetCore category" % args.choice)
+    try:
+        root = clouds.open_ragged_root(args.data_root, None if args.choice is None else {cate_to_synsetid[args.choice]})
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (args.data_root, e))
+    if not root:
+        raise SystemExit("--choice %s: %s has no clouds of that category" % (args.choice, args.data_root))
+    return root
+
+
+def _ragged_cloudset(args, ragged_root, split, normalize):
+    """split_cloudset under --min_points, with the one line on standard output that says what was dropped and how the counts lie."""
+    from .clouds import split_cloudset
+    try:
+        cs = split_cloudset(ragged_root, split, normalize, min_points=args.min_points)
+    except ValueError as e:
+        raise SystemExit("%s: %s" % (args.data_root, e))
+    st = cs.stats(args.num_point)
+    print("ragged clouds, %s split: %d shapes dropped by --min_points %d; %d shapes, %d points, counts min %d / median %g / max %d, "
+          "%d shapes store fewer than --num_point %d" % (split, cs.dropped, args.min_points, st["shapes"], st["points"], st["min"],
+                                                          st["median"], st["max"], st["shorter"], st["n"]))
+    return cs
+
+
 def _mesh_root(args):
     """The opened mesh data of --data_root ({synsetid: {split: (verts, faces, face_off)}}, of --choice's category only), or None where
     --data_root holds clouds."""
@@ -374,10 +435,16 @@ def _visible_meshset(args, mesh_root, split, normalize, device):
     return ms
 
 
-def reference_clouds(args, split, device, mesh_root=None):
+def reference_clouds(args, split, device, mesh_root=None, ragged_root=None):
     """The (S, num_point, 3) reference clouds of the test phase and the reports, normalised by --normalize: the LAST num_point points of
     every stored cloud, or -- for meshes -- draw 0 of num_point surface points of every raw mesh of the split (MeshSet.sample: streams
-    of their own, apart from every training draw), which then go through the same point normalisation."""
+    of their own, apart from every training draw), which then go through the same point normalisation; for ragged clouds draw 0 of
+    num_point points of every raw shape of the split (CloudSet.sample), normalised the same way -- no held-out tail: the counts differ,
+    and the splits are different shapes."""
+    if ragged_root is not None:
+        from .data import normalize_point_clouds
+        return normalize_point_clouds(_ragged_cloudset(args, ragged_root, split, None).to(device).sample(args.num_point, args.seed, draw=0),
+                                      args.normalize).contiguous()
     if mesh_root is None:
         return load_split(args, split, args.normalize, tail=args.num_point).stack(device).float().contiguous()
     from .data import normalize_point_clouds
@@ -459,6 +526,16 @@ def _mesh_feeder(args, mesh_root, device, rank, world):
                       subsample=args.subsample)
 
 
+def _ragged_feeder(args, ragged_root, device, rank, world):
+    """Ragged clouds: the train split normalised cloud by cloud (the cloud path's 'shape_unit'), resident on the device; every visit is
+    a fresh draw of the shape's own points (data.RaggedFeeder)."""
+    from .data import RaggedFeeder
+    n = args.num_point
+    cs = _ragged_cloudset(args, ragged_root, "train", "shape_unit")
+    return RaggedFeeder(cs.to(device), args.batch_size, (n // 8, n // 4, n // 2), args.seed, rank=rank, world=world, num_point=n,
+                        subsample=args.subsample)
+
+
 def train(args):
     rank, world, device = init_dist(args.device)
     run_dir = os.path.join(args.checkpoint_dir, args.model_dir)
@@ -466,8 +543,11 @@ def train(args):
     os.makedirs(ckpt, exist_ok=True)
     torch.manual_seed(args.seed)                                 # the networks' initial weights
     n = args.num_point
-    mesh_root = _mesh_root(args)
-    if mesh_root is not None:
+    ragged_root = _ragged_root(args)
+    mesh_root = None if ragged_root is not None else _mesh_root(args)
+    if ragged_root is not None:
+        feeder = _ragged_feeder(args, ragged_root, device, rank, world)
+    elif mesh_root is not None:
         feeder = _mesh_feeder(args, mesh_root, device, rank, world)
     else:
         feeder = _cloud_feeder(args, device, rank, world)
@@ -490,7 +570,7 @@ def train(args):
     reporter = None
     if args.report_every > 0 and rank == 0:
         from .report import SnapshotReporter
-        val = reference_clouds(args, "val", device, mesh_root)
+        val = reference_clouds(args, "val", device, mesh_root, ragged_root)
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd)
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
@@ -509,7 +589,8 @@ def test(args):
     from . import evaluation
     device = torch.device(args.device)
     ckpt = os.path.join(args.checkpoint_dir, args.model_dir, args.network)
-    mesh_root = _mesh_root(args)                                 # (first: a flag that does not fit the data is refused before anything is built)
+    ragged_root = _ragged_root(args)                             # (first: a flag that does not fit the data is refused before anything is built)
+    mesh_root = None if ragged_root is not None else _mesh_root(args)
     trainer = make_trainer(args, device)
     if _resume(args, trainer, ckpt) is None:
         print(" [!] Load failed...")                             # (:275-276: the reference goes on with the initial weights too)
@@ -518,7 +599,7 @@ def test(args):
     torch.manual_seed(args.seed)                                 # seed_all (:282)
     np.random.seed(args.seed)
     random.seed(args.seed)
-    ref = reference_clouds(args, "test", device, mesh_root)
+    ref = reference_clouds(args, "test", device, mesh_root, ragged_root)
     trainer.G.eval()
     gen, results, raw = evaluation.generate_and_evaluate(trainer.G, ref, args.batch_size, normalize=args.normalize, return_raw=True,
                                                          emd=args.emd)
