@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 40
+#define PDGN_ABI_VERSION 41
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -552,6 +552,33 @@ int pdgn_mse_const_count(long long n, const float *x, float target, float scale,
                          pdgn_stream_t stream);
 int pdgn_mse_const_backward(long long n, const float *x, float target, float scale, const float *g, float *dx,
                             pdgn_stream_t stream);
+/* The hinge and the non-saturating logistic GAN objectives on a discriminator's raw scores (logits), siblings of the pdgn_mse_const
+ * trio: the same launch shapes (one workgroup of 1024 forward; the backward's grid rule) and the same fixed summation order --
+ * thread t adds its elements t, t + 1024, ... in that order with plain fp32 additions, then the xor butterfly 32 .. 1 over a wave and
+ * the sixteen wave totals in index order.  Least squares has no kind here: it stays on pdgn_mse_const (0 is reserved for it).
+ *   pdgn_gan_term: out[0] = scale * (s / (float)n), s = sum_i f(x[i]);
+ *     hinge:    d_real f = max(0, 1 - x), d_fake f = max(0, 1 + x), g f = -x; with v = 1 -+ x: f = v > 0 ? v : (v == v ? 0 : v);
+ *     logistic: f = softplus(t) = fmaxf(t, 0) + log1pf(expf(-fabsf(t))), t = -x for d_real and g, t = x for d_fake.
+ *   pdgn_gan_term_backward: dx[i] = c * f'(x[i]), c = g[0] * scale / (float)n evaluated left to right (g: the upstream gradient, a
+ *     device scalar); hinge: f' = -1 (d_real) / +1 (d_fake) where v > 0, else 0 -- the forward's own test, so the kink x = 1
+ *     (x = -1) has f' = 0 --, g: f' = -1; logistic: f' = sigma(x) (d_fake), -sigma(-x) (d_real, g), sigma(t) from e = expf(-fabsf(t))
+ *     as 1 / (1 + e) for t >= 0 and e / (1 + e) otherwise.
+ *   pdgn_gan_term_count: pdgn_gan_term plus the three counts of pdgn_mse_const_count against `boundary` (0 for a logit), stored the
+ *     same way into the caller's slot (word 3 not touched; integer block sums, no atomics); out[0] is bit for bit pdgn_gan_term's.
+ * A NaN score gives a NaN out[0] and a NaN dx[i] in every kind and role (a hinge written fmaxf(0, v) would hide it from the
+ * gradient guard); +-inf give the IEEE results of the expressions above.  Every operation is its own fp32 rounding.  Replaces
+ * nothing in the reference (models/PDGNet_v2.py:186-190, 246-250 is least squares only).
+ * PDGN_ERR_INVALID: n < 1, a kind or role not listed here, a null or 4-byte-misaligned pointer; pdgn_gan_term_count: n >= 2^31. */
+#define PDGN_GAN_HINGE 1
+#define PDGN_GAN_LOGISTIC 2
+#define PDGN_GAN_D_REAL 0
+#define PDGN_GAN_D_FAKE 1
+#define PDGN_GAN_G 2
+int pdgn_gan_term(long long n, const float *x, int kind, int role, float scale, float *out, pdgn_stream_t stream);
+int pdgn_gan_term_count(long long n, const float *x, int kind, int role, float scale, float boundary, float *out, int32_t *count,
+                        pdgn_stream_t stream);
+int pdgn_gan_term_backward(long long n, const float *x, int kind, int role, float scale, const float *g, float *dx,
+                           pdgn_stream_t stream);
 
 /* All-pairs evaluation (evaluation/evaluation_metrics.py:85-121 expands every sample against every
  * reference batch): the same kernels over explicit pair lists, pair p = (cloud ia[p] of the first
@@ -1059,8 +1086,9 @@ int pdgn_augment_tick(unsigned long long *clock, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ adaptive discriminator augmentation (ADA, Karras et al. 2020)
  * The probability p behind the table's thresholds, steered on the device from the discriminators' own outputs on the real batch.
- * The discriminators are least-squares (real -> 1, fake -> 0; decision boundary 0.5); per iteration and discriminator i the
- * real-batch loss term (pdgn_mse_const_count) stores pos_i = #{x > 0.5}, neg_i = #{x < 0.5}, n_i = n into slot i of
+ * The statistic is taken against the objective's decision boundary b: least squares (real -> 1, fake -> 0) has b = 0.5, the hinge
+ * and the logistic objectives score with a logit and have b = 0, the paper's sign.  Per iteration and discriminator i the
+ * real-batch loss term (pdgn_mse_const_count, pdgn_gan_term_count) stores pos_i = #{x > b}, neg_i = #{x < b}, n_i = n into slot i of
  * `slots`, a contiguous int32[16] of its own (4 words per discriminator, word 3 unused; separate from the state so that it can be
  * all-reduced (SUM) across ranks).  pdgn_augment_tick_ada, which opens every iteration in place of pdgn_augment_tick:
  *   clock[0] += 1

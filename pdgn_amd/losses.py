@@ -125,6 +125,79 @@ def mse_const(x, target, scale=1.0, count=None):
     return MseConst.apply(x, float(target), float(scale), count)
 
 
+GAN_LOSSES = ("lsgan", "hinge", "logistic")
+_GAN_KINDS = {"hinge": 1, "logistic": 2}                        # PDGN_GAN_HINGE, PDGN_GAN_LOGISTIC (0: least squares, which is mse_const)
+_GAN_ROLES = {"d_real": 0, "d_fake": 1, "g": 2}                 # PDGN_GAN_D_REAL, PDGN_GAN_D_FAKE, PDGN_GAN_G
+
+
+class GanTerm(Function):
+    """scale * mean f(x) of a discriminator's raw scores x for the hinge or the non-saturating logistic objective (include/pdgn_hip.h:
+    pdgn_gan_term) -- like MseConst one launch forward and one backward (csrc/loss_small.hip), in the same summation order."""
+
+    @staticmethod
+    def forward(ctx, x, kind, role, scale, count=None):
+        x = x.contiguous()
+        require(x, "x", F32)
+        out = torch.empty((), dtype=F32, device=x.device)
+        if count is None:
+            check(_lib.lib().pdgn_gan_term(x.numel(), ptr(x), kind, role, scale, ptr(out), stream_of(x)), "pdgn_gan_term")
+        else:                                                    # the same value bit for bit, and (#{x > 0}, #{x < 0}, n) stored into the slot
+            check(_lib.lib().pdgn_gan_term_count(x.numel(), ptr(x), kind, role, scale, 0.0, ptr(out), ptr(count), stream_of(x)), "pdgn_gan_term_count")
+        ctx.save_for_backward(x)
+        ctx.cfg = (kind, role, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        kind, role, scale = ctx.cfg
+        dx = torch.empty_like(x)
+        g = g.contiguous()
+        check(_lib.lib().pdgn_gan_term_backward(x.numel(), ptr(x), kind, role, scale, ptr(g), ptr(dx), stream_of(x)), "pdgn_gan_term_backward")
+        return dx, None, None, None, None
+
+
+def gan_term(x, kind, role, scale=1.0, count=None):
+    """scale * mean f(x) (GanTerm) of raw scores x.  kind "hinge": f = max(0, 1 - x) for role "d_real", max(0, 1 + x) for "d_fake", -x for
+    "g"; kind "logistic" (non-saturating): f = softplus(-x), softplus(x), softplus(-x).  A NaN score gives a NaN term and a NaN gradient.
+    count: as mse_const's, with the decision boundary of a logit, 0."""
+    if kind not in _GAN_KINDS:
+        raise ValueError("kind: 'hinge' or 'logistic', got %r" % (kind,))
+    if role not in _GAN_ROLES:
+        raise ValueError("role: 'd_real', 'd_fake' or 'g', got %r" % (role,))
+    if count is not None:
+        require(count, "count", torch.int32)
+        if count.numel() < 3 or count.device != x.device:
+            raise ValueError("count: at least three int32 words on %s" % (x.device,))
+    return GanTerm.apply(x, _GAN_KINDS[kind], _GAN_ROLES[role], float(scale), count)
+
+
+def decision_boundary(objective):
+    """The score at which a discriminator trained on `objective` is undecided: 1/2 between least squares' targets 0 and 1, 0 for a logit.
+    The adaptive augmentation's statistic counts the real batch's scores above and below it."""
+    if objective not in GAN_LOSSES:
+        raise ValueError("objective: one of %s, got %r" % (", ".join(GAN_LOSSES), objective))
+    return 0.5 if objective == "lsgan" else 0.0
+
+
+_LSGAN = {"d_real": (1.0, 0.5), "d_fake": (0.0, 0.5), "g": (1.0, 1.0)}     # (target, scale): models/PDGNet_v2.py:186-190, 246-250
+
+
+def adversarial(x, objective, role, count=None):
+    """One adversarial term of the training step on the scores x = D(cloud), with the objective's own scale: "lsgan" is the reference's
+    mse(x, 1) / 2, mse(x, 0) / 2 and mse(x, 1) -- `mse_const`, reached through this module's attribute --, "hinge" and "logistic" the
+    textbook forms (gan_term at scale 1, without the reference's 1/2).  count: the real-batch term's slot of the adaptive augmentation;
+    it counts against decision_boundary(objective)."""
+    if objective not in GAN_LOSSES:
+        raise ValueError("objective: one of %s, got %r" % (", ".join(GAN_LOSSES), objective))
+    if role not in _GAN_ROLES:
+        raise ValueError("role: 'd_real', 'd_fake' or 'g', got %r" % (role,))
+    if objective == "lsgan":
+        target, scale = _LSGAN[role]
+        return mse_const(x, target, scale) if count is None else mse_const(x, target, scale, count)
+    return gan_term(x, objective, role, 1.0, count)
+
+
 def chamfer_sum(x, y, scale=1.0):
     """scale * ChamferLoss-style sum of both directions' minima (utils/chamfer_loss.py:16-20)."""
     return ChamferSum.apply(x, y, scale)

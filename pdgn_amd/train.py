@@ -17,7 +17,10 @@ sees goes through a random similarity transform drawn on the device, each compon
 (1: mirror x), --aug_translate T (0.1), --aug_jitter SIGMA (0) change its ranges and need --d_augment.
 --d_augment_target R (train, needs --d_augment): P is only the initial value; the device steers it from the discriminators' scores of the real
 batch towards r = R (ADA; DESIGN.md section 7i), with --ada_interval K (4), --ada_span CLOUDS (500000), --ada_p_min / --ada_p_max (0 / 0.8);
-aug.csv beside the log, <epoch>_<category>_aug.pth beside every checkpoint pair.  --data_root: the HDF5 file (needs h5py), an .npz whose keys are "<synsetid>/<split>",
+aug.csv beside the log, <epoch>_<category>_aug.pth beside every checkpoint pair.  r counts the scores above the objective's decision boundary
+against those below it: 1/2 under --gan_loss lsgan, 0 otherwise.  --gan_loss lsgan|hinge|logistic (train): the adversarial objective of all twelve terms
+of an iteration -- lsgan (default) is the reference's least squares; hinge and logistic (non-saturating) read the discriminators' outputs as logits
+(losses.adversarial); no launch is added, checkpoints are unchanged.  --data_root: the HDF5 file (needs h5py), an .npz whose keys are "<synsetid>/<split>",
 or a directory in the layout of ShapeNetCore.v2.PC15k (<synsetid>/<split>/*.npy, each (M,3)).  Clouds stored with M > --num_point points (PC15k: 15 000)
 are trained on a fresh draw of --num_point distinct points per cloud and visit, made inside the feed launch (data.BatchFeeder, pdgn_feed_batch_resample),
 from the leading --resample_pool P points (default: all M); --phase test and the reports take the LAST --num_point points of every stored cloud as
@@ -108,13 +111,17 @@ def build_parser():
     p.add_argument("--aug_translate", type=float, default=argparse.SUPPRESS, metavar="T", help="translation, uniform in [-T, T] per coordinate (default 0.1)")
     p.add_argument("--aug_jitter", type=float, default=argparse.SUPPRESS, metavar="SIGMA", help="per-point Gaussian jitter (default 0: none)")
     p.add_argument("--d_augment_target", type=float, default=argparse.SUPPRESS, metavar="R", help="adaptive discriminator augmentation (ADA, Karras et "
-                   "al. 2020): --d_augment becomes the INITIAL p, which the device then steers so that r = (scores above 1/2 - scores below) / "
-                   "scores, measured on the discriminators' outputs for the real batch, approaches R (the paper: 0.6); aug.csv beside the log")
+                   "al. 2020): --d_augment becomes the INITIAL p, which the device then steers so that r = (scores above the objective's decision "
+                   "boundary - scores below it) / scores, measured on the discriminators' outputs for the real batch, approaches R (the paper: "
+                   "0.6); the boundary is 1/2 under --gan_loss lsgan and 0 otherwise; aug.csv beside the log")
     p.add_argument("--ada_interval", type=int, default=argparse.SUPPRESS, metavar="K", help="iterations per adjustment of p (default 4)")
     p.add_argument("--ada_span", type=int, default=argparse.SUPPRESS, metavar="CLOUDS", help="real clouds over which p may travel from 0 to 1 (default "
                    "500000, the paper's: far too long for a category of a few dozen shapes -- give a few hundred epochs' worth of clouds there)")
     p.add_argument("--ada_p_min", type=float, default=argparse.SUPPRESS, help="lower end of p's range (default 0)")
     p.add_argument("--ada_p_max", type=float, default=argparse.SUPPRESS, help="upper end of p's range (default 0.8)")
+    p.add_argument("--gan_loss", choices=["lsgan", "hinge", "logistic"], default=argparse.SUPPRESS, help="the adversarial objective: lsgan "
+                   "(default: the reference's least squares against 1 / 0), hinge, or logistic (non-saturating); the latter two read the "
+                   "discriminators' outputs as logits; no launch is added")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
     p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
@@ -136,7 +143,7 @@ def build_parser():
 
 
 class Args(argparse.Namespace):
-    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --resample_pool, --subsample, --emd, the --mesh_visible flags, --ragged and --min_points are listed (vars(), the log's first line) only where
+    """The parsed command line.  --ema_decay, the gradient guard's, the learning-rate, the augmentation flags (the adaptive ones too), --gan_loss, --resample_pool, --subsample, --emd, the --mesh_visible flags, --ragged and --min_points are listed (vars(), the log's first line) only where
     they were given: a run without them has the namespace, and writes the log line, of the time before the flags existed; reading
     them gives the defaults below then."""
     ema_decay = 0.0
@@ -162,6 +169,7 @@ class Args(argparse.Namespace):
     ada_span = None
     ada_p_min = None
     ada_p_max = None
+    gan_loss = "lsgan"
     resample_pool = None
     subsample = "random"
     mesh_visible = "off"
@@ -476,7 +484,7 @@ def make_trainer(args, device, batches_per_epoch=None):
                        clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None,
                        lr_g=args.lr_g if args.phase == "train" else None, lr_d=args.lr_d if args.phase == "train" else None,
                        lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None,
-                       augment=_augment_arg(args) if args.phase == "train" else None)
+                       augment=_augment_arg(args) if args.phase == "train" else None, gan_loss=args.gan_loss)
 
 
 def _augment_arg(args):
@@ -556,6 +564,8 @@ def train(args):
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
         raise SystemExit(str(e))
     trainer.train()
+    if rank == 0 and trainer.gan_loss != "lsgan":
+        print("# adversarial objective: %s (scores are logits; decision boundary 0)" % trainer.gan_loss)
     start = _resume(args, trainer, ckpt) or 1
     log = None
     if rank == 0:

@@ -70,11 +70,20 @@ class PDGNTrainer:
     table, the clock and the optional record buffer; the iteration opens with ONE extra launch, the clock's tick; `set_augment`
     overwrites the table in place, `aug_state` reads it back.  The shape-preserving loss sees the un-augmented clouds.  None: `aug`
     is None, no buffer, no launch, and the discriminators' forward is the code it was.  With augment={..., "adaptive": {...}} p is
-    steered on the device: the four real-batch loss terms count into `aug.slots`, the tick folds them."""
+    steered on the device: the four real-batch loss terms count into `aug.slots`, the tick folds them.
+
+    gan_loss: the adversarial objective of all twelve terms of an iteration (losses.adversarial): "lsgan", the
+    reference's least squares and the default -- the launches it always had --, "hinge" or "logistic" (non-saturating), on the
+    discriminators' raw scores; `gan_loss` keeps the name.  The kind is baked into the launches (a captured list keeps the one it was
+    captured with), adds none, and is not written into checkpoints.  The adaptive augmentation counts the real scores against the
+    objective's decision boundary: 1/2 under "lsgan", 0 otherwise."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
                  discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
-                 lr_g=None, lr_d=None, lr_schedule=None, augment=None):
+                 lr_g=None, lr_d=None, lr_schedule=None, augment=None, gan_loss="lsgan"):
+        if gan_loss not in losses.GAN_LOSSES:                    # (raises before anything is allocated)
+            raise ValueError("gan_loss must be one of %s, got %r" % (", ".join(losses.GAN_LOSSES), gan_loss))
+        self.gan_loss = gan_loss
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
@@ -428,13 +437,13 @@ class PDGNTrainer:
     #   4: Adam D4 + G(z2), local-pair losses, D(gen), backward    -> all-reduce grad G
     #   5: Adam G (:256)
     def _seg_d(self, st, i):
-        D = self.D[i]
+        D, obj = self.D[i], self.gan_loss
         self.gradD[i].begin()
         if self.aug is None:
-            lossD = losses.mse_const(D(st["reals"][i]), 1.0, 0.5) + losses.mse_const(D(st["fakes"][i]), 0.0, 0.5)
+            lossD = losses.adversarial(D(st["reals"][i]), obj, "d_real") + losses.adversarial(D(st["fakes"][i]), obj, "d_fake")
         else:
-            lossD = (losses.mse_const(D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5, self._aug_counter(i))
-                     + losses.mse_const(D(st["fakes"][i], self.aug.at(i, "fake")), 0.0, 0.5))
+            lossD = (losses.adversarial(D(st["reals"][i], self.aug.at(i, "real")), obj, "d_real", self._aug_counter(i))
+                     + losses.adversarial(D(st["fakes"][i], self.aug.at(i, "fake")), obj, "d_fake"))
         lossD.backward()
         st["out"]["d_loss%d" % (i + 1)] = lossD.detach()
 
@@ -453,14 +462,14 @@ class PDGNTrainer:
         D = self.D[i]
         self.gradD[i].begin()
         params = self.gradD[i].params
-        loss_r = losses.mse_const(D(st["reals"][i]) if self.aug is None else D(st["reals"][i], self.aug.at(i, "real")), 1.0, 0.5, self._aug_counter(i))
+        loss_r = losses.adversarial(D(st["reals"][i]) if self.aug is None else D(st["reals"][i], self.aug.at(i, "real")), self.gan_loss, "d_real", self._aug_counter(i))
         st["d_half"][i] = (loss_r.detach(), torch.autograd.grad(loss_r, params))
 
     def _seg_d_fake(self, st, i):
         D = self.D[i]
         fg = self.gradD[i]
         fg.resume()
-        loss_f = losses.mse_const(D(st["fakes"][i]) if self.aug is None else D(st["fakes"][i], self.aug.at(i, "fake")), 0.0, 0.5)
+        loss_f = losses.adversarial(D(st["fakes"][i]) if self.aug is None else D(st["fakes"][i], self.aug.at(i, "fake")), self.gan_loss, "d_fake")
         loss_r, g_real = st["d_half"][i]
         st.setdefault("keep", []).append(loss_r)            # (it may have been computed on another stream than this half runs on: it must
                                                             #  not return to that stream's pool before the sum below has RUN)
@@ -491,7 +500,7 @@ class PDGNTrainer:
             self._freeze_D(True)
             gen = self.G(self._z(st, "z2"))
             similar = self.similar_loss(gen)
-            g_loss = [losses.mse_const(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), 1.0) for i in range(4)]
+            g_loss = [losses.adversarial(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), self.gan_loss, "g") for i in range(4)]
             adv = 1.2 * g_loss[0] + 1.2 * g_loss[1] + 1.2 * g_loss[2] + g_loss[3]
             lossG = adv + 0.1 * similar
             # MSE is a batch MEAN, the shape loss a batch SUM (chamfer_loss.py:16-20): to reproduce
@@ -654,7 +663,7 @@ class PDGNTrainer:
             side = self._side[level]
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                g_loss[level] = losses.mse_const(self.D[level](cloud) if self.aug is None else self.D[level](cloud, self.aug.at(level, "gen")), 1.0)
+                g_loss[level] = losses.adversarial(self.D[level](cloud) if self.aug is None else self.D[level](cloud, self.aug.at(level, "gen")), self.gan_loss, "g")
 
         def tail(level, cloud):
             gen_so_far.append(cloud)
@@ -673,7 +682,7 @@ class PDGNTrainer:
             for i, side in enumerate(self._side):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    g_loss[i] = losses.mse_const(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), 1.0)
+                    g_loss[i] = losses.adversarial(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), self.gan_loss, "g")
         for side in self._side:
             main.wait_stream(side)
         main.wait_stream(self._side_lp)
