@@ -1,6 +1,7 @@
 """Autograd wrappers of the fused channels-last kernels of libpdgn_hip.so (bnact.hip)."""
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 from ._fn import Function
@@ -19,24 +20,42 @@ def _scratch_floats(L, rows, C):
     return n
 
 
+# Hand-overs between autograd nodes that no autograd edge carries: a backward LEAVES a fact about a tensor it returns, the backward
+# that receives that tensor TAKES it.  One mechanism for all of them: keyed by data pointer, validated through a weak reference to
+# the marked tensor (a recycled address is not the tensor), popped on use; each channel adds its own rule for which OTHER tensor
+# objects -- views autograd made on the way -- still stand for the marked one.
+class HandOver:
+    def __init__(self, accepts):
+        self.accepts, self.pending = accepts, {}                 # accepts(presented, marked): another object, the same elements?
+
+    def leave(self, tensor, payload=True):
+        self.pending[tensor.data_ptr()] = (weakref.ref(tensor), payload)
+
+    def take(self, tensor):
+        """The payload left for `tensor`, or None; either way the entry at its address is gone."""
+        ref, payload = self.pending.pop(tensor.data_ptr(), (None, None))
+        src = ref() if ref is not None else None
+        return payload if src is not None and (src is tensor or self.accepts(tensor, src)) else None
+
+    def clear(self):
+        self.pending.clear()
+
+    def __len__(self):                                           # (falsy when nothing is pending, like the dictionary it owns)
+        return len(self.pending)
+
+
 # The gradient of a training-mode BatchNorm with respect to its input has zero column sums:
 #   dx = g*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))  =>  sum_rows dx = -g*rstd*mean(dz*xhat)*sum_rows(xhat) = 0,
 # so the bias of the conv / linear layer that FEEDS the BatchNorm (all conv2dbr-style pairs of the reference)
 # has an identically zero gradient; what a row-sum of dx would return is fp32 rounding residue.  The BatchNorm
 # backward marks its dx, and the producer's backward (LinearCL, EdgeGatherSum) skips that full pass over dy.
-# Keyed by data pointer, validated through a weak reference to the marked tensor (same object or a view of it).
-_ZERO_COLSUM = {}
-
-
-def mark_zero_colsum(dx):
-    _ZERO_COLSUM[dx.data_ptr()] = weakref.ref(dx)
+# Accepted: the marked tensor or a view of it with as many elements and the same last dimension.
+_ZERO_COLSUM = HandOver(lambda dy, src: dy._base is src and dy.numel() == src.numel() and dy.shape[-1] == src.shape[-1])
+mark_zero_colsum = _ZERO_COLSUM.leave                            # (dx)
 
 
 def has_zero_colsum(dy):
-    ref = _ZERO_COLSUM.pop(dy.data_ptr(), None)
-    src = ref() if ref is not None else None
-    return src is not None and (src is dy or dy._base is src) and dy.numel() == src.numel() \
-        and dy.shape[-1] == src.shape[-1]
+    return _ZERO_COLSUM.take(dy) is not None
 
 
 def clear_zero_colsum():
@@ -45,33 +64,21 @@ def clear_zero_colsum():
     _GRAD_MAXIMA.clear()
 
 
-# A third side channel of the same kind: a backward that WRITES a large gradient (EdgeGatherSum's dY, 1.8 GB at stage 4) leaves its
-# ROW maxima (an int32 (rows,) tensor of bit patterns, csrc/wgs.hip) for the two-part contraction of the layer that receives it
-# (LinearCL.backward: the input gradient of the per-point product scales dY row by row) -- it would scan the whole tensor otherwise.
-# Keyed and validated like _ZERO_COLSUM; taken once.
-_GRAD_MAXIMA = {}
+# A backward that WRITES a large gradient (EdgeGatherSum's dY, 1.8 GB at stage 4) leaves its ROW maxima (an int32 (rows,) tensor of
+# bit patterns, csrc/wgs.hip) for the two-part contraction of the layer that receives it (LinearCL.backward: the input gradient of
+# the per-point product scales dY row by row) -- it would scan the whole tensor otherwise.  Accepted: the same elements -- the
+# marked tensor, or a view of the same storage that starts where it starts, has as many elements and is, like it, contiguous (a
+# reshape: a view of it or a sibling view of its base).
+_GRAD_MAXIMA = HandOver(lambda dy, src: dy.numel() == src.numel() and dy.is_contiguous() and src.is_contiguous()
+                        and (dy._base is src or (dy._base is not None and dy._base is src._base)))
+mark_maxima, take_maxima = _GRAD_MAXIMA.leave, _GRAD_MAXIMA.take     # (g, slot) / (dy) -> slot or None
 
 
-def mark_maxima(g, slot):
-    _GRAD_MAXIMA[g.data_ptr()] = (weakref.ref(g), slot)
-
-
-def take_maxima(dy):
-    ent = _GRAD_MAXIMA.pop(dy.data_ptr(), None)
-    if ent is None:
-        return None
-    src = ent[0]()
-    # the same elements: the marked tensor itself, or a view of the same storage that starts where it starts, has as many
-    # elements and is, like it, contiguous (a reshape)
-    same = src is not None and (src is dy or (dy.numel() == src.numel() and dy.is_contiguous() and src.is_contiguous()
-                                              and (dy._base is src or (dy._base is not None and dy._base is src._base))))
-    return ent[1] if same else None
-
-
-# A second side channel of the same kind: BNActMaxPool's backward, when the dense layer in front of it is frozen, computes
-# that layer's INPUT gradient itself (pdgn_dense_bn_maxpool_input_grad: the dense (rows, C) dx is never formed) and hands
-# LinearCL's backward a zero-stride placeholder of dx's shape; the input gradient travels here, keyed like _ZERO_COLSUM.
-_INPUT_GRADS = {}
+# BNActMaxPool's backward, when the dense layer in front of it is frozen, computes that layer's INPUT gradient itself
+# (pdgn_dense_bn_maxpool_input_grad: the dense (rows, C) dx is never formed) and hands LinearCL's backward a zero-stride placeholder
+# of dx's shape; the input gradient travels here.  Accepted: a zero-stride tensor (take_input_grad asks for no other) of the
+# placeholder's shape that is it, a view of it or a view of the NaN it expands.
+_INPUT_GRADS = HandOver(lambda dy, src: (dy._base is src or dy._base is src._base) and dy.shape == src.shape)
 _CLOSED_TAIL = os.environ.get("PDGN_CLOSED_TAIL", "1") == "1"    # A/B switch
 _STATS_MAX = os.environ.get("PDGN_STATS_MAX", "1") == "1"        # A/B switch: statistics + extremes of the max-pool tail in one pass
 _CLOSED_DW = os.environ.get("PDGN_CLOSED_DW", "1") == "1"        # A/B switch: also with a trainable layer (its weight gradient)
@@ -97,7 +104,7 @@ def _placeholder_with_input_grad(rows, C, dh, dw, device):
     i = pool[1]
     pool[1] = (i + 1) % 256
     tok = pool[0][i:i + 1].expand(rows, C)
-    _INPUT_GRADS[tok.data_ptr()] = (weakref.ref(tok), (dh, dw))
+    _INPUT_GRADS.leave(tok, (dh, dw))
     return tok
 
 
@@ -106,11 +113,7 @@ def is_placeholder(dy):
 
 
 def take_input_grad(dy):
-    hit = _INPUT_GRADS.pop(dy.data_ptr(), None) if dy.stride(0) == 0 else None
-    if hit is None:
-        return None
-    src = hit[0]()
-    return hit[1] if src is not None and (src is dy or dy._base is src or dy._base is src._base) and dy.shape == src.shape else None
+    return _INPUT_GRADS.take(dy) if dy.stride(0) == 0 else None
 
 
 # gemm_tn accumulates split partial sums with atomics, so every weight gradient starts from zeros (and the
@@ -317,6 +320,10 @@ def interleave_rows(y2d, n):
 # weight gradient dW = dy^T x on pdgn_gemm_tn_big (the same kernels) or pdgn_gemm_tn (csrc/gemm_tn.hip, small outputs).
 # No BLAS library, no run-time back-end selection.  Below that row count (the 35-row per-sample layers) torch's
 # default matmul is used as it is.
+# Which family runs a layer -- pre-split planes, the thin kernels, the own NT kernel, torch -- is decided ONCE per call, by
+# dense_route: linear_cl hands its record (DenseRoute: the route, whether the launch emits BatchNorm partials and over how many
+# rows each, whether x's row maxima are handed in) to LinearCL.forward, which executes it and keeps it for the backward;
+# stat_block_rows reads the same record.  gemm_nt and gemm_nt_planes are one frame (_nt_frame) around their entry points.
 _OWN_MIN_ROWS = 1024
 _TN_BIG = os.environ.get("PDGN_TN_BIG", "1") == "1"            # A/B switch: weight gradients of >= 128 x 64 outputs on pdgn_gemm_tn_big
 
@@ -460,36 +467,47 @@ def _rp_takes(m, n, k, parts, plain):
     return parts == 2 and plain and _lib.lib().pdgn_gemm_nt_ps_row_panel(m, n, k, 2, 1) == 1
 
 
-def planes_fit(P, m, n, k, with_stats=False, plain=False):
+def planes_fit(P, m, n, k, with_stats=False, plain=False, panel=None):
     """Whether planes P can serve the product (m, n, k): three-part planes always; two-part ones (which run on the 256 x 128 tile
     whatever the launch model picks, or -- short reductions without bias / addend: plain -- on the row-panel kernel) unless the
     launch emits BatchNorm partials and neither the row-panel kernel takes it nor the model's pick -- whose geometry the partials'
-    consumers were told -- is the 256 x 128 tile."""
-    return (P.shape[0] == 3 or not with_stats or _rp_takes(m, n, k, P.shape[0], plain) or (_lib.lib().pdgn_gemm_nt_config(m, n, k, 1) & 15) == 0)
+    consumers were told -- is the 256 x 128 tile.  panel: _rp_takes' answer, from a caller that has asked already."""
+    return (P.shape[0] == 3 or not with_stats or (_rp_takes(m, n, k, P.shape[0], plain) if panel is None else panel)
+            or (_lib.lib().pdgn_gemm_nt_config(m, n, k, 1) & 15) == 0)
+
+
+def _nt_frame(entry, a, n, k, bias, addend, want_stats, max_a, parts, stat_rows, launch):
+    """What gemm_nt and gemm_nt_planes share, around the one call each of them makes: `entry` goes to GEMM_LOG; a's columns (and the
+    addend's) are padded to multiples of 4; out (m, n) and, with want_stats, the partials (stat_rows(L) rows) are allocated; the
+    tail workspace (parts: of the planes, None for a plain weight) and a's maxima are handed to the library for the NEXT call, which
+    is launch(L, a, bias, addend, its pitch, out, part).  n, k: the launch's (padded) sizes.  Returns (out, part)."""
+    _slots(a)
+    if GEMM_LOG is not None:
+        GEMM_LOG.append(entry)
+    m = a.shape[0]
+    ap = _pad_cols(a)
+    L = _lib.lib()
+    out = torch.empty((m, n), dtype=F32, device=a.device)
+    part = torch.empty((stat_rows(L), 3 * n), dtype=F32, device=a.device) if want_stats else None
+    b = bias.detach().contiguous() if bias is not None else None
+    if addend is not None:
+        addend = _pad_cols(addend)
+    ws = _tail_workspace(L, m, n, k, want_stats, a.device, parts=parts)     # (kept alive to the end of this function: the launch is issued by then)
+    _hand_maxima(L, max_a)
+    launch(L, ap, b, addend, addend.stride(0) if addend is not None else 0, out, part)
+    return out, part
 
 
 def gemm_nt_planes(a, P, n, k, bias=None, addend=None, want_stats=False, max_a=None):
     """a (m, k) @ W^T for a weight given as its planes P [parts][n][ld] (Planes.p of W, or Planes.t for the product with W itself:
     then n, k are W^T's; two-part planes: max_a = a's maxima when the caller has them, operand_maxima); everything else as gemm_nt."""
-    _slots(a)
-    m = a.shape[0]
-    if GEMM_LOG is not None:
-        GEMM_LOG.append(("nt", m, n, k))
-    ap = _pad_cols(a)
-    L = _lib.lib()
-    out = torch.empty((m, n), dtype=F32, device=a.device)
-    part = None
-    if want_stats:
-        part = torch.empty((L.pdgn_gemm_nt_ps_stat_rows(m, n, k, P.shape[0], 1 if (bias is None and addend is None) else 0),
-                            3 * n), dtype=F32, device=a.device)
-    b = bias.detach().contiguous() if bias is not None else None
-    if addend is not None:
-        addend = _pad_cols(addend)
-    ws = _tail_workspace(L, m, n, k, want_stats, a.device, parts=P.shape[0])
-    _hand_maxima(L, max_a)
-    check(L.pdgn_gemm_nt_ps(m, n, k, ptr(ap), ap.stride(0), ptr(P), P.shape[2], P.shape[1] * P.shape[2], P.shape[0],
-                            ptr(b), ptr(addend), addend.stride(0) if addend is not None else 0, ptr(out), n, ptr(part), None, 0, 1, 0,
-                            None, 0, stream_of(a)), "pdgn_gemm_nt_ps")
+    m, parts, plain = a.shape[0], P.shape[0], 1 if (bias is None and addend is None) else 0
+
+    def launch(L, ap, b, add, ldadd, out, part):
+        check(L.pdgn_gemm_nt_ps(m, n, k, ptr(ap), ap.stride(0), ptr(P), P.shape[2], P.shape[1] * P.shape[2], parts, ptr(b), ptr(add), ldadd,
+                                ptr(out), n, ptr(part), None, 0, 1, 0, None, 0, stream_of(a)), "pdgn_gemm_nt_ps")
+    out, part = _nt_frame(("nt", m, n, k), a, n, k, bias, addend, want_stats, max_a, parts,
+                          lambda L: L.pdgn_gemm_nt_ps_stat_rows(m, n, k, parts, plain), launch)
     return (out, part) if want_stats else out
 
 
@@ -499,39 +517,23 @@ def gemm_nt(a, w, bias=None, addend=None, want_stats=False, w_transposed=False, 
     of 4 (the xyz layers: k = 3, the heads' last conv: n = 3) are zero-padded for the launch.  want_stats: also returns
     the BatchNorm partials of the result ((parts, 3n) fp32, block-shifted: per-column sum (x - pv) | sum (x - pv)^2 | pv of
     row blocks of pdgn_gemm_nt_stat_block_rows(m, n, k) rows, pv = the block's first row)."""
-    _slots(a)
     m, k = a.shape
     n = w.shape[1] if w_transposed else w.shape[0]
-    if GEMM_LOG is not None:
-        GEMM_LOG.append(("nn" if w_transposed else "nt", m, n, k))
-    ap = _pad_cols(a)
-    kp = ap.shape[1]
-    np_ = (n + 3) // 4 * 4
-    if w_transposed:
-        wp = _pad_cols(w)                                          # (k, n) -> (k, np_)
-        if kp != k:
-            wp = torch.nn.functional.pad(wp, (0, 0, 0, kp - k))
-    else:
-        wp = _pad_cols(w)
-    if np_ != n and not w_transposed:
-        wp = torch.nn.functional.pad(wp, (0, 0, 0, np_ - n))
+    kp, np_ = (k + 3) // 4 * 4, (n + 3) // 4 * 4
+    wp = _pad_cols(w)                                              # (n, k) -> (n, kp), transposed: (k, n) -> (k, np_)
+    rows = (kp - k) if w_transposed else (np_ - n)
+    if rows:
+        wp = torch.nn.functional.pad(wp, (0, 0, 0, rows))
     if np_ != n:
         bias = torch.nn.functional.pad(bias, (0, np_ - n)) if bias is not None else None
         addend = torch.nn.functional.pad(addend, (0, np_ - n)) if addend is not None else None
-    if addend is not None:
-        addend = _pad_cols(addend)
-    L = _lib.lib()
-    out = torch.empty((m, np_), dtype=F32, device=a.device)
-    part = None
-    if want_stats:
-        part = torch.empty((L.pdgn_gemm_nt_stat_rows(m, np_, kp), 3 * np_), dtype=F32, device=a.device)
-    b = bias.detach().contiguous() if bias is not None else None
-    fn = L.pdgn_gemm_nn if w_transposed else L.pdgn_gemm_nt
-    ws = _tail_workspace(L, m, np_, kp, want_stats, a.device)       # (kept alive to the end of this function: the launch is issued by then)
-    _hand_maxima(L, max_a)
-    check(fn(m, np_, kp, ptr(ap), ap.stride(0), ptr(wp), wp.stride(0), ptr(b), ptr(addend),
-             addend.stride(0) if addend is not None else 0, ptr(out), np_, ptr(part), stream_of(a)),
-          "pdgn_gemm_nn" if w_transposed else "pdgn_gemm_nt")
+    name = "pdgn_gemm_nn" if w_transposed else "pdgn_gemm_nt"
+
+    def launch(L, ap, b, add, ldadd, out, part):
+        check(getattr(L, name)(m, np_, kp, ptr(ap), ap.stride(0), ptr(wp), wp.stride(0), ptr(b), ptr(add), ldadd, ptr(out), np_, ptr(part),
+                               stream_of(a)), name)
+    out, part = _nt_frame(("nn" if w_transposed else "nt", m, n, k), a, np_, kp, bias, addend, want_stats, max_a, None,
+                          lambda L: L.pdgn_gemm_nt_stat_rows(m, np_, kp), launch)
     if np_ != n:
         out = out[:, :n].contiguous()
     return (out, part) if want_stats else out
@@ -546,32 +548,30 @@ def gemm_tn(dy, x, max_dy=None, max_x=None):
     if GEMM_LOG is not None:
         GEMM_LOG.append(("tn", m, n, k))
     dyp, xp = _pad_cols(dy), _pad_cols(x)
-    nk = dyp.shape[1] * xp.shape[1]
+    np_, kp = dyp.shape[1], xp.shape[1]
+    L = _lib.lib()
     # (long reductions -- >= 150 k rows -- also with 16 K .. 64 K outputs: 0.85-0.88x pdgn_gemm_tn's time, r03_gemm_shapes.txt)
-    if _TN_BIG and dyp.shape[1] >= 64 and xp.shape[1] >= 64 and (65536 if (m < 150000 or not _lib.matrix_core_mode()) else 16384) <= nk <= _tn_big_max():
+    if _TN_BIG and np_ >= 64 and kp >= 64 and (65536 if (m < 150000 or not _lib.matrix_core_mode()) else 16384) <= np_ * kp <= _tn_big_max():
         # mid-sized outputs (4 .. 64 tiles of 128 x 128): the stream-K launch of the pdgn_gemm_nt kernel with both operands
         # transposed balances them better than pdgn_gemm_tn's split (measured, tools/gemm_shapes.py: 0.70-0.94x its time);
         # smaller outputs (and, on the fp32 kernels, the two largest ones: conv2's dense half, the per-point GEMM) stay on
         # pdgn_gemm_tn
-        L = _lib.lib()
-        need = L.pdgn_gemm_tn_big_workspace_floats(m, dyp.shape[1], xp.shape[1])
+        need = L.pdgn_gemm_tn_big_workspace_floats(m, np_, kp)
         if need > 0:                                               # the k slices' partial tiles: summed in a fixed order, no atomics
             ws = torch.empty(need, dtype=F32, device=dy.device)
             check(L.pdgn_gemm_set_tail_workspace(ptr(ws), need), "pdgn_gemm_set_tail_workspace")
-            dwp = torch.empty((dyp.shape[1], xp.shape[1]), dtype=F32, device=dy.device)
+            dwp = torch.empty((np_, kp), dtype=F32, device=dy.device)
         else:
-            dwp = _zeros((dyp.shape[1], xp.shape[1]), dy.device)   # a slice of the backward pass's zero arena: no fill launch here
+            dwp = _zeros((np_, kp), dy.device)                     # a slice of the backward pass's zero arena: no fill launch here
         _hand_maxima(L, max_dy, max_x)
-        check(_lib.lib().pdgn_gemm_tn_big(m, dyp.shape[1], xp.shape[1], ptr(dyp), dyp.stride(0), ptr(xp),
-                                          xp.stride(0), ptr(dwp), 0 if need > 0 else 1, stream_of(dy)), "pdgn_gemm_tn_big")      # (not zero-filled when the workspace form is expected: the atomic form, should the library take it after all, fills it itself)
-        return dwp if (dyp.shape[1] == n and xp.shape[1] == k) else dwp[:n, :k]
-    if dyp.stride(0) != dyp.shape[1]:
-        dyp = dyp.contiguous()
-    if xp.stride(0) != xp.shape[1]:
-        xp = xp.contiguous()
-    dwp = _zeros((dyp.shape[1], xp.shape[1]), dy.device)
-    check(_lib.lib().pdgn_gemm_tn(m, dyp.shape[1], xp.shape[1], ptr(dyp), ptr(xp), ptr(dwp), stream_of(dy)), "pdgn_gemm_tn")
-    return dwp if (dyp.shape[1] == n and xp.shape[1] == k) else dwp[:n, :k]
+        # (not zero-filled when the workspace form is expected: the atomic form, should the library take it after all, fills it itself)
+        check(L.pdgn_gemm_tn_big(m, np_, kp, ptr(dyp), dyp.stride(0), ptr(xp), xp.stride(0), ptr(dwp), 0 if need > 0 else 1, stream_of(dy)),
+              "pdgn_gemm_tn_big")
+    else:
+        dyp, xp = (t if t.stride(0) == t.shape[1] else t.contiguous() for t in (dyp, xp))
+        dwp = _zeros((np_, kp), dy.device)
+        check(L.pdgn_gemm_tn(m, np_, kp, ptr(dyp), ptr(xp), ptr(dwp), stream_of(dy)), "pdgn_gemm_tn")
+    return dwp if (np_ == n and kp == k) else dwp[:n, :k]
 
 
 def _thin_ok(x, n, k):
@@ -611,63 +611,68 @@ def thin_tn(dy, x, want_db):
     return dw, db
 
 
-def _planes_taken(x, weight, planes, want_stats, plain):
-    """Whether LinearCL's forward multiplies against the pre-split planes (the same question stat_block_rows asks)."""
-    return (planes is not None and x.is_cuda and x.shape[0] >= _PLANES_MIN_ROWS and planes.shape == tuple(weight.shape)
-            and x.shape[1] == weight.shape[1] and x.shape[1] % 4 == 0
-            and planes_fit(planes.p, x.shape[0], weight.shape[0], weight.shape[1], want_stats, plain))
+_PLANES_MIN_ROWS = 4096        # below this a contraction is a few tiles: the split kernel's launches would cost more than they save
+
+
+class DenseRoute(NamedTuple):
+    """What dense_route decided for one dense call; LinearCL.forward executes it, its backward and linear_cl read it."""
+    route: str                  # "planes" (pdgn_gemm_nt_ps) | "thin" (pdgn_thin_nt) | "own" (pdgn_gemm_nt) | "torch"
+    stats: bool = False         # the launch emits the BatchNorm partials of y
+    block_rows: int = 0         # ... each of them over this many rows of y (0: no partials)
+    x_maxima: bool = False      # "planes": a two-part product off the row-panel kernel -- x's row maxima are handed to the launch
+
+
+def dense_route(x, weight, bias=None, addend=None, planes=None, want_stats=False):
+    """Which kernel family runs y = x weight^T (+ bias) (+ addend), decided HERE and nowhere else; launches nothing, and asks the
+    library's launch model each question once (no library at all for a tensor that is not on the device)."""
+    m, (n, k) = x.shape[0], weight.shape
+    if not x.is_cuda:
+        return DenseRoute("torch")
+    plain = bias is None and addend is None
+    if planes is not None and m >= _PLANES_MIN_ROWS and planes.shape == (n, k) and x.shape[1] == k and k % 4 == 0:
+        parts = planes.p.shape[0]
+        panel = _rp_takes(m, n, k, parts, plain)
+        if planes_fit(planes.p, m, n, k, want_stats, plain, panel):
+            # (a two-part product scales x row by row: its row maxima from the producer, or one scan -- or, on the row-panel kernel,
+            # taken inside the launch: a wave holds whole rows)
+            block = _lib.lib().pdgn_gemm_nt_ps_stat_block_rows(m, n, k, parts, 1 if plain else 0) if want_stats else 0
+            return DenseRoute("planes", bool(want_stats), block, parts == 2 and not panel)
+    if m < _OWN_MIN_ROWS:
+        return DenseRoute("torch")
+    if addend is None and weight.is_contiguous() and _thin_ok(x, n, k):
+        stats = bool(want_stats) and k <= 4                        # (the n <= 4 form has no statistics epilogue)
+        return DenseRoute("thin", stats, _lib.lib().pdgn_thin_stat_block_rows() if stats else 0)
+    stats = bool(want_stats) and n % 4 == 0                        # (a padded result: no partials, the consumer makes its own pass)
+    return DenseRoute("own", stats, _lib.lib().pdgn_gemm_nt_stat_block_rows(m, (n + 3) // 4 * 4, (k + 3) // 4 * 4) if stats else 0)
 
 
 class LinearCL(Function):
     """y = x @ W^T (+ b) (+ addend) for point-major rows x (M, C_in): the reference's Conv2d / Conv1d / Linear layers
-    (models/PDGNet_v2.py:559-625, 835-862, 886-1014) as row-matrix products on the hand-written MFMA kernels (see above)."""
+    (models/PDGNet_v2.py:559-625, 835-862, 886-1014) as row-matrix products on the hand-written MFMA kernels (see above).
+    route: dense_route's record for these arguments; returns (y, partials) when route.stats, else y."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, addend, want_stats=False, planes=None, x_max=None, x_cmax=None):
+    def forward(ctx, x, weight, bias, addend, route, planes=None, x_max=None, x_cmax=None):
         ctx.save_for_backward(x, weight)
         ctx.set_materialize_grads(False)          # no zero-filled "gradient" of the statistics partials (a launch per call)
-        ctx.has_bias = bias is not None
-        ctx.has_addend = addend is not None
-        ctx.planes_t = None
-        ctx.max_x = None
+        ctx.has_bias, ctx.has_addend, ctx.route = bias is not None, addend is not None, route
+        ctx.planes_t = planes.t if route.route == "planes" else None
         ctx.max_x_cols = x_cmax                                # x's column maxima when its producer computed them (the weight gradient's scale)
-        if _planes_taken(x, weight, planes, want_stats, bias is None and addend is None):
+        n, k = weight.shape
+        if route.route == "planes":
             # the weight arrives pre-split (Planes): no split work for it in the kernel, forward and input gradient
-            n, k = weight.shape
-            ctx.thin = False
-            ctx.planes_t = planes.t
-            # (a two-part product scales x row by row: its row maxima from the producer, or one scan -- or, on the row-panel kernel,
-            # taken inside the launch: a wave holds whole rows)
-            xm = None
-            if planes.parts_p == 2 and not _rp_takes(x.shape[0], n, k, 2, bias is None and addend is None):
-                xm = x_max if x_max is not None else operand_maxima(x)
-            ctx.max_x = xm
-            if want_stats:
-                y, part = gemm_nt_planes(x, planes.p, n, k, bias, addend, want_stats=True, max_a=xm)
-                ctx.mark_non_differentiable(part)
-                return y, part
-            return gemm_nt_planes(x, planes.p, n, k, bias, addend, max_a=xm)
-        ctx.thin = bool(x.is_cuda and x.shape[0] >= _OWN_MIN_ROWS and addend is None and weight.is_contiguous()
-                        and _thin_ok(x, weight.shape[0], weight.shape[1]))
-        if ctx.thin:
-            n, k = weight.shape
-            if want_stats and k <= 4:
-                y, part = thin_nt(x, weight, k, 1, n, bias, want_stats=True)
-                ctx.mark_non_differentiable(part)
-                return y, part
-            y = thin_nt(x, weight, k, 1, n, bias)
-            return (y, None) if want_stats else y
-        if x.is_cuda and x.shape[0] >= _OWN_MIN_ROWS:
-            xm = None                                              # (the library scans both operands itself where two parts pay)
-            if want_stats and weight.shape[0] % 4 == 0:
-                y, part = gemm_nt(x, weight, bias, addend, want_stats=True, max_a=xm)
-                ctx.mark_non_differentiable(part)
-                return y, part
-            y = gemm_nt(x, weight, bias, addend, max_a=xm)
-            return (y, None) if want_stats else y
-        y = torch.nn.functional.linear(x, weight, bias)
-        y = y + addend if addend is not None else y
-        return (y, None) if want_stats else y
+            xm = (x_max if x_max is not None else operand_maxima(x)) if route.x_maxima else None
+            y = gemm_nt_planes(x, planes.p, n, k, bias, addend, want_stats=route.stats, max_a=xm)
+        elif route.route == "thin":
+            y = thin_nt(x, weight, k, 1, n, bias, want_stats=route.stats)
+        elif route.route == "own":
+            y = gemm_nt(x, weight, bias, addend, want_stats=route.stats)     # (the library scans both operands itself where two parts pay)
+        else:
+            y = torch.nn.functional.linear(x, weight, bias)
+            return y + addend if addend is not None else y
+        if route.stats:
+            ctx.mark_non_differentiable(y[1])
+        return y
 
     @staticmethod
     def backward(ctx, dy, *unused):
@@ -680,51 +685,52 @@ class LinearCL(Function):
         if is_placeholder(dy):
             raise RuntimeError("LinearCL.backward: received BNActMaxPool's gradient placeholder without the gradient it stands for "
                                "(another consumer of the layer's output, a hook or a copy sits between the two nodes)")
-        zero_db = ctx.has_bias and ctx.needs_input_grad[2] and has_zero_colsum(dy)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        zero_db = need_db and has_zero_colsum(dy)
         dy = dy.contiguous()
-        own = dy.is_cuda and dy.shape[0] >= _OWN_MIN_ROWS
+        m, (n, k) = dy.shape[0], weight.shape
         dx = dw = db = None
-        if ctx.thin:
-            n, k = weight.shape
-            if ctx.needs_input_grad[0]:
+        if ctx.route.route == "thin":
+            if need_dx:
                 dx = thin_nt(dy, weight, 1, k, k)                  # dX = dY W: W'[j, kk] = weight[kk, j]
-            want_db = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:
+            if need_dw:
                 xc = x if (x.stride(1) == 1 and (k <= 4 or (x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0))) else x.contiguous()
-                dw, db = thin_tn(dy, xc, want_db and not zero_db)
-                if want_db and zero_db:
+                dw, db = thin_tn(dy, xc, need_db and not zero_db)
+                if zero_db:
                     db = _zeros((n,), dy.device)
-            elif want_db:
+            elif need_db:
                 db = _zeros((n,), dy.device) if zero_db else group_colsum(dy)[0]
             return dx, dw, db, None, None, None, None, None
+        own = ctx.route.route != "torch"
+        # decided once, for the maxima and for the launch: dX = dY W = dY (W^T)^T through the transposed planes
+        dx_planes = need_dx and own and ctx.planes_t is not None and n % 4 == 0 and planes_fit(ctx.planes_t, m, k, n)
         # two-part products (mode "x2", where they pay): the input gradient dX = dY W scales dY row by row, the weight gradient
         # dW = dY^T X scales dY and X column by column (its kernel takes both transposed); dy is scanned ONCE for both
         dy_rows = dy_cols = x_cols = None
-        if own and _lib.gemm_mode() == "x2" and dy.shape[1] % 4 == 0:
-            m_, n_, k_ = dy.shape[0], weight.shape[0], weight.shape[1]
+        if own and _lib.gemm_mode() == "x2" and n % 4 == 0:
             dy_rows = take_maxima(dy)                              # left behind by the backward that wrote dy (EdgeGatherSum), or None
-            dx_two = (ctx.needs_input_grad[0] and ctx.planes_t is not None and ctx.planes_t.shape[0] == 2
-                      and planes_fit(ctx.planes_t, m_, k_, n_))
-            scan_dy_rows = dx_two and dy_rows is None
+            scan_rows = dx_planes and ctx.planes_t.shape[0] == 2 and dy_rows is None
             xs = x if x.stride(1) == 1 else None
-            dw_two = (ctx.needs_input_grad[1] and xs is not None and _maxima_ok(dy) and _maxima_ok(xs)
-                      and two_part(n_, k_, m_, (0 if scan_dy_rows else m_ * n_ * 4) + (0 if ctx.max_x_cols is not None else m_ * k_ * 4)))
-            if scan_dy_rows or dw_two:
-                r_, c_ = operand_maxima(dy, rows=True, cols=True) if (scan_dy_rows and dw_two) else \
-                    ((operand_maxima(dy), None) if scan_dy_rows else (None, operand_maxima(dy, rows=False, cols=True)))
-                dy_rows = r_ if scan_dy_rows else dy_rows
-                dy_cols = c_
-            if dw_two:
+            dw_two = (need_dw and xs is not None and _maxima_ok(dy) and _maxima_ok(xs)
+                      and two_part(n, k, m, (0 if scan_rows else m * n * 4) + (0 if ctx.max_x_cols is not None else m * k * 4)))
+            if scan_rows and dw_two:
+                dy_rows, dy_cols = operand_maxima(dy, rows=True, cols=True)
+            elif scan_rows:
+                dy_rows = operand_maxima(dy)
+            elif dw_two:
+                dy_cols = operand_maxima(dy, rows=False, cols=True)
+            if dw_two:                                             # x's column maxima: from its producer, or one scan
                 x_cols = ctx.max_x_cols if ctx.max_x_cols is not None else operand_maxima(xs, rows=False, cols=True)
-        if ctx.needs_input_grad[0]:
-            if ctx.planes_t is not None and own and dy.shape[1] % 4 == 0 and planes_fit(ctx.planes_t, dy.shape[0], weight.shape[1], weight.shape[0]):
-                dx = gemm_nt_planes(dy, ctx.planes_t, weight.shape[1], weight.shape[0], max_a=dy_rows)      # dX = dY W = dY (W^T)^T
-            else:
-                dx = gemm_nt(dy, weight, w_transposed=True, max_a=dy_rows) if own else dy.matmul(weight)      # (where two parts pay the library scans what is not handed in)
-        if ctx.needs_input_grad[1]:
+        if need_dx:
+            if dx_planes:
+                dx = gemm_nt_planes(dy, ctx.planes_t, k, n, max_a=dy_rows)
+            else:                                                  # (where two parts pay the library scans what is not handed in)
+                dx = gemm_nt(dy, weight, w_transposed=True, max_a=dy_rows) if own else dy.matmul(weight)
+        if need_dw:
             dw = gemm_tn(dy, x, dy_cols, x_cols) if own else dy.t().matmul(x)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = _zeros((dy.shape[1],), dy.device) if zero_db else group_colsum(dy)[0]
+        if need_db:
+            db = _zeros((n,), dy.device) if zero_db else group_colsum(dy)[0]
         return dx, dw, db, (dy if ctx.has_addend and ctx.needs_input_grad[3] else None), None, None, None, None
 
 
@@ -886,34 +892,23 @@ class HeadMLP(Function):
         return dx, dg, dW0, group_colsum(drb)[0], dW2, db2, dW3, db3, None
 
 
-_PLANES_MIN_ROWS = 4096        # below this a contraction is a few tiles: the split kernel's launches would cost more than they save
-
-
 def linear_cl(x2d, weight, bias=None, addend=None, want_stats=None, planes=None, x_max=None, x_cmax=None):
     """Dense layer on point-major rows (see LinearCL); `addend` (M, C_out) is added in the GEMM's epilogue.
     x_max: x2d's partial maxima when its producer computed them (bilateral_weighting's want_max), for a two-part product.
     want_stats (True / False, not None): returns the PAIR (y, partials) -- with True the BatchNorm partial sums of y from
-    the GEMM's epilogue, for bn_act / bilateral_weighting's `partials` argument (no statistics pass over y); None when
-    this call did not produce them."""
+    the GEMM's epilogue and the rows each of them covers, for bn_act / bilateral_weighting's `partials` argument (no statistics
+    pass over y); None when this call did not produce them."""
+    route = dense_route(x2d, weight, bias, addend, planes, bool(want_stats))
+    y = LinearCL.apply(x2d, weight, bias, addend, route, planes, x_max, x_cmax)
     if want_stats is None:
-        return LinearCL.apply(x2d, weight, bias, addend, False, planes, x_max, x_cmax)
-    if want_stats:
-        y, part = LinearCL.apply(x2d, weight, bias, addend, True, planes, x_max, x_cmax)
-        return y, ((part, stat_block_rows(x2d, weight, addend, planes, bias)) if part is not None else None)
-    return LinearCL.apply(x2d, weight, bias, addend, False, planes, x_max, x_cmax), None
+        return y
+    return (y[0], (y[1], route.block_rows)) if route.stats else (y, None)
 
 
 def stat_block_rows(x2d, weight, addend=None, planes=None, bias=None):
-    """Rows of y = x2d weight^T each partial-statistics row of LinearCL's epilogue covers: the same question the launch asked
-    (the same deterministic launch model on the same padded sizes), so the block size travels with the partials as a value."""
-    L = _lib.lib()
-    n, k = weight.shape
-    plain = bias is None and addend is None
-    if _planes_taken(x2d, weight, planes, True, plain):
-        return int(L.pdgn_gemm_nt_ps_stat_block_rows(x2d.shape[0], n, k, planes.p.shape[0], 1 if plain else 0))
-    if addend is None and weight.is_contiguous() and _thin_ok(x2d, n, k):
-        return int(L.pdgn_thin_stat_block_rows())
-    return int(L.pdgn_gemm_nt_stat_block_rows(x2d.shape[0], (n + 3) // 4 * 4, (k + 3) // 4 * 4))
+    """Rows of y = x2d weight^T each partial-statistics row of LinearCL's epilogue covers (a readout of dense_route for the call
+    with want_stats; 0 where that call emits no partials)."""
+    return dense_route(x2d, weight, bias, addend, planes, True).block_rows
 
 
 class SoftmaxSlotsPermute(Function):
