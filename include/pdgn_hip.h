@@ -611,6 +611,7 @@ int pdgn_sample_bias_backward(int b, int ldy, int nspec, const int *T, const int
 /* nn.Sequential(Linear, [BatchNorm1d,] [LeakyReLU | ReLU]) on r <= 64 rows in one launch (the generator's per-sample
  * global branches and first layer, models/PDGNet_v2.py:704-707, 825-828): x (r,k), W (n,k), y (r,n); k <= 1024.
  * bn_mode 0: no BatchNorm; 1: batch statistics (running_mean / running_var updated when given); 2: running statistics.
+ * running_var takes the unbiased variance, var r / (r - 1); with r == 1 (where torch raises) the biased one, 0: y == act(beta).
  * pre (r,n) and stat (2n: mean | invstd) are written for the adjoint (may be NULL).  Backward: dpre (r,n) = gradient
  * wrt the linear output (the caller forms dx = dpre W), dgamma, dbeta, dbias (n), dW (n,k); any of those four may be NULL. */
 int pdgn_small_mlp_forward(int r, int k, int n, int act, int bn_mode, float eps, float momentum, const float *x,

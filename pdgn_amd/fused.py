@@ -1128,8 +1128,9 @@ class SmallLinearBNAct(Function):
         R, K, N, act, bn_mode, has_bias, has_bn = ctx.cfg
         dy = dy.contiguous()
         dev = dy.device
-        if not has_bn and not any(ctx.needs_input_grad[1:3]) and _FROZEN_HEAD:
-            # frozen Linear (+ activation): only the input gradient is wanted -- one launch (no dpre, no second product)
+        if bn_mode == 0 and not any(ctx.needs_input_grad[1:3]) and _FROZEN_HEAD:
+            # frozen Linear (+ activation), no BatchNorm (bn_mode, not gamma: affine=False normalises too): only the input gradient
+            # is wanted -- one launch (no dpre, no second product)
             if not ctx.needs_input_grad[0]:
                 return (None,) * 11
             dx = skinny_nn_masked(dy, pre, act, weight) if act else dy.matmul(weight)
@@ -1188,13 +1189,16 @@ _SKINNY_HEAD = os.environ.get("PDGN_SKINNY_HEAD", "1") == "1"    # A/B switch
 
 def small_sequential(seq, x, training):
     """nn.Sequential of (Linear [, BatchNorm1d] [, LeakyReLU | ReLU]) groups applied to x (R, K): on a GPU, with at
-    most 64 rows, every group is one fused launch (SmallLinearBNAct); otherwise the modules run as they are."""
+    most 64 rows, every group is one fused launch (SmallLinearBNAct); otherwise (wider or taller than the launch's LDS holds, a
+    LeakyReLU slope other than 0.01, BatchNorm1d(momentum=None)) the modules run as they are."""
     mods = list(seq)
     fusable = x.is_cuda and x.dim() == 2 and x.shape[0] <= 64 and all(
         isinstance(m, (torch.nn.Linear, torch.nn.BatchNorm1d, torch.nn.LeakyReLU, torch.nn.ReLU)) for m in mods)
     if fusable:
         fusable = all(m.in_features <= 1024 and x.shape[0] * (m.in_features + 4) * 4 + 1024 <= 160 * 1024
                       for m in mods if isinstance(m, torch.nn.Linear))
+    if fusable:                                               # momentum=None is a cumulative average: no fixed factor fits it
+        fusable = all(m.momentum is not None for m in mods if isinstance(m, torch.nn.BatchNorm1d))
     if not fusable:
         return seq(x)
     i = 0
@@ -1223,7 +1227,7 @@ def small_sequential(seq, x, training):
             x = SmallLinearBNAct.apply(x, lin.weight, lin.bias, bn.weight, bn.bias,
                                        bn.running_mean if bn.track_running_stats else None,
                                        bn.running_var if bn.track_running_stats else None, 1 if use_batch else 2,
-                                       bn.momentum if bn.momentum is not None else 0.1, bn.eps, act)
+                                       bn.momentum, bn.eps, act)
         elif _SKINNY_HEAD and _sk_ok(x, lin.weight) and lin.in_features % 4 == 0:
             x = SkinnyLinearAct.apply(x, lin.weight, lin.bias, act)
         else:
