@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 41
+#define PDGN_ABI_VERSION 42
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1216,6 +1216,32 @@ int pdgn_mesh_visibility_bias_cover(void);
 int pdgn_mesh_visibility_bias_small(int R);
 int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off, const float *frame,
                          const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ repulsion regulariser and spacing statistics (csrc/repulsion.hip)
+ * Every point of a cloud against every other point of the SAME cloud, in one launch: the repulsion term of the point-upsampling
+ * literature (PU-Net) in a polynomial form, its gradient, and the squared distance to the nearest other point.  The header block of
+ * csrc/repulsion.hip is the normative statement of the operation order; tests/repulsion_mirror.py spells it in numpy.  No reference
+ * counterpart.  xyz (b,n,3); inv_h2 = 1 / h^2 for the radius h > 0.  Per point i, over j = 0 .. n-1 ascending, j != i:
+ *   d = x_i - x_j, d2 = (dx dx + dy dy) + dz dz, nn2_i = min(nn2_i, d2), t = 1 - d2 inv_h2, and where !(t <= 0): s_i += t t, g_i += t d
+ * every fp32 operation rounded on its own.  A NaN coordinate makes s_i and g_i NaN (it fails `t <= 0`).
+ *   s          (b,n) workspace, always written: s_i
+ *   loss       (1): (float)(T / (double)(b n)), T = sum_c (double)P_c over the clouds c ascending; P_c = sum_i s_i of cloud c in the
+ *              fixed fp32 order of one wave (csrc/repulsion.hip: 64 lane sums over i = lane, lane + 64, ..., then a butterfly)
+ *   per_cloud  (b) or NULL: (float)((double)P_c / n)
+ *   grad       (b,n,3) or NULL: coef * g_i, d loss / d x_i for coef = -8 inv_h2 / (b n) (each unordered pair is in the sum twice and
+ *              the derivative is gathered per point: nothing is scattered, nothing is added atomically); the caller computes coef
+ *              in fp64 and rounds it once
+ *   nn2        (b,n) or NULL: +inf for n = 1
+ * Results do not depend on the launch geometry (pdgn_repulsion_chunk() is the number of points staged in LDS at a time: tests put
+ * n on either side of it).  Two launches on `stream` (all pairs, then the reduction), no atomics, nothing allocated.
+ * pdgn_repulsion_backward: dxyz[k] = g[0] * grad[k] for k < count (the saved grad times the upstream device scalar), one launch.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1 or > PDGN_REPULSION_MAX_N, b n beyond 2^28, inv_h2 (or coef)
+ * not finite or inv_h2 not positive, count < 1, a null pointer (per_cloud, grad, nn2 excepted) or one not 4-byte aligned. */
+#define PDGN_REPULSION_MAX_N 8192
+int pdgn_repulsion_chunk(void);
+int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, float coef, float *s, float *loss, float *per_cloud, float *grad,
+                   float *nn2, pdgn_stream_t stream);
+int pdgn_repulsion_backward(long long count, const float *grad, const float *g, float *dxyz, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -198,6 +198,26 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=Fal
     return results
 
 
+# ---------------------------------------------------------------------------- spacing (no reference counterpart)
+@torch.no_grad()
+def spacing_stats(clouds, batch=64):
+    """How evenly the points of each cloud are spread, from the distance d_i of every point to the nearest OTHER point of its cloud
+    (the all-pairs launch of losses.repulsion with no gradient: pdgn_repulsion, `batch` clouds per launch).  clouds (S,N,3), N >= 2 ->
+    {"nn_mean": the mean over clouds of the per-cloud mean of d, "nn_cv": the mean over clouds of the per-cloud coefficient of variation
+    std(d) / mean(d) (population std; 0.52 for a Poisson sample of a surface, towards 0 as the spacing evens out), "nn_min": the smallest
+    d, "duplicates": the number of points with d == 0}, Python numbers.  The reductions are fp64 torch ops on the device."""
+    from .losses import repulsion_pass
+    require(clouds, "clouds", F32, 3)
+    S, N, _ = clouds.shape
+    if S < 1 or N < 2 or int(batch) < 1:
+        raise ValueError("spacing_stats takes at least one cloud of at least two points and a positive batch, got %s, batch %r" % (tuple(clouds.shape), batch))
+    nn2 = torch.cat([repulsion_pass(clouds[lo:lo + int(batch)], 1.0, grad=False, nn2=True)[3] for lo in range(0, S, int(batch))])
+    d = nn2.double().sqrt()
+    mean = d.mean(dim=1)
+    return {"nn_mean": float(mean.mean()), "nn_cv": float((d.std(dim=1, unbiased=False) / mean).mean()), "nn_min": float(d.min()),
+            "duplicates": int((nn2 == 0).sum())}
+
+
 # ---------------------------------------------------------------------------- JSD (evaluation_metrics.py:206-321)
 def unit_cube_grid_point_cloud(resolution, clip_sphere=False, device="cpu"):
     """Cell centres of a resolution^3 grid over the unit cube (:206-224); clip_sphere keeps |c| <= 0.5."""

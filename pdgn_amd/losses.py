@@ -198,6 +198,83 @@ def adversarial(x, objective, role, count=None):
     return gan_term(x, objective, role, 1.0, count)
 
 
+REPULSION_MAX_POINTS = 8192                                      # PDGN_REPULSION_MAX_N
+
+
+def repulsion_constants(radius, b, n):
+    """(inv_h2, coef) of pdgn_repulsion for b clouds of n points at radius h: 1 / h^2 and -8 / (h^2 b n), each computed in fp64; the
+    call rounds each once to fp32."""
+    radius = float(radius)
+    if not (radius > 0.0 and radius < float("inf")):
+        raise ValueError("radius must be positive and finite, got %r" % (radius,))
+    inv = 1.0 / (radius * radius)
+    return inv, -8.0 * inv / (float(b) * float(n))
+
+
+def repulsion_pass(x, radius, grad=True, nn2=False, per_cloud=False):
+    """The all-pairs launch on x (B,N,3), point-major and contiguous: (loss 0-dim, per_cloud (B) | None, grad (B,N,3) | None,
+    nn2 (B,N) | None); an output that is not asked for is passed as NULL and not computed.  No autograd (losses.repulsion is the
+    differentiable form; evaluation.spacing_stats the metric)."""
+    require(x, "x", F32, 3)
+    b, n, three = x.shape
+    if three != 3:
+        raise ValueError("x must be (B,N,3), got %s" % (tuple(x.shape),))
+    if not 1 <= n <= REPULSION_MAX_POINTS:
+        raise ValueError("repulsion takes clouds of 1 to %d points, got %d" % (REPULSION_MAX_POINTS, n))
+    inv, coef = repulsion_constants(radius, b, n)
+    s = torch.empty((b, n), dtype=F32, device=x.device)
+    loss = torch.empty((), dtype=F32, device=x.device)
+    pc = torch.empty((b,), dtype=F32, device=x.device) if per_cloud else None
+    g = torch.empty((b, n, 3), dtype=F32, device=x.device) if grad else None
+    nn = torch.empty((b, n), dtype=F32, device=x.device) if nn2 else None
+    check(_lib.lib().pdgn_repulsion(b, n, ptr(x), inv, coef, ptr(s), ptr(loss), ptr(pc), ptr(g), ptr(nn), stream_of(x)), "pdgn_repulsion")
+    return loss, pc, g, nn
+
+
+class Repulsion(Function):
+    """x (B,N,3) -> (1 / (B N)) sum_b sum_i sum_{j != i} max(0, 1 - |x_i - x_j|^2 / h^2)^2 as ONE autograd node (csrc/repulsion.hip):
+    the forward launch computes the gradient too and saves it, the backward multiplies it by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, x, radius):
+        loss, _, g, _ = repulsion_pass(x, radius)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, up):
+        g, = ctx.saved_tensors
+        dx = torch.empty_like(g)
+        up = up.contiguous()
+        check(_lib.lib().pdgn_repulsion_backward(g.numel(), ptr(g), ptr(up), ptr(dx), stream_of(g)), "pdgn_repulsion_backward")
+        return dx, None
+
+
+def repulsion(cloud, radius):
+    """The repulsion regulariser of a batch of clouds: the batch MEAN over clouds and points of
+    s_i = sum_{j != i} max(0, 1 - |x_i - x_j|^2 / radius^2)^2 -- zero when no two points of a cloud are closer than `radius`.
+    cloud: (B,3,N) as the generator returns it (its transpose is the contiguous point-major memory: no copy), or point-major (B,N,3);
+    (B,3,3) reads as (B,3,N).  One launch and the reduction forward, one launch backward; every sum in a fixed order (bitwise
+    repeatable); a NaN coordinate gives a NaN loss and NaN gradients for its cloud."""
+    if not isinstance(cloud, torch.Tensor) or cloud.dim() != 3 or 3 not in cloud.shape[1:]:
+        raise ValueError("cloud must be a (B,3,N) or (B,N,3) tensor")
+    x = cloud.transpose(1, 2) if cloud.shape[1] == 3 else cloud
+    return Repulsion.apply(x.contiguous(), float(radius))
+
+
+def repulsion_radii(radius, sizes):
+    """The radius per level: radius * sqrt(N_finest / N_l) for the point counts `sizes` -- `radius` is the finest level's, and points
+    spread over a surface have spacing proportional to N^-1/2."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 1:
+        raise ValueError("sizes: at least one positive point count, got %r" % (sizes,))
+    radius = float(radius)
+    if not (radius > 0.0 and radius < float("inf")):
+        raise ValueError("radius must be positive and finite, got %r" % (radius,))
+    finest = max(sizes)
+    return [radius * (float(finest) / float(n)) ** 0.5 for n in sizes]
+
+
 def chamfer_sum(x, y, scale=1.0):
     """scale * ChamferLoss-style sum of both directions' minima (utils/chamfer_loss.py:16-20)."""
     return ChamferSum.apply(x, y, scale)

@@ -169,9 +169,15 @@ class SnapshotReporter:
     compute_all_metrics and its EMD passes, the approximate EMD or with emd="auction" the exact one and an `emd-capped` column --
     and the seconds the report took).  The preview's noise and the metrics' noise
     come from generators seeded the same way at every report, so sheets and rows are comparable across epochs.  Training
-    state is left as found; the generator's train / eval flag is put back."""
+    state is left as found; the generator's train / eval flag is put back.  spacing=True: every report also appends epoch, gen nn_mean,
+    gen nn_cv, val nn_mean, val nn_cv, gen duplicates -- evaluation.spacing_stats of as many generated clouds as there are reference clouds
+    (the metrics' noise stream, normalised like them) and of the reference clouds -- to `<out_dir>/spacing.csv` (DESIGN.md section 7p);
+    metrics.csv is what it was."""
 
-    def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1, emd="approx"):
+    SPACING_HEADER = ("epoch", "gen nn_mean", "gen nn_cv", "val nn_mean", "val nn_cv", "gen duplicates")
+
+    def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1, emd="approx",
+                 spacing=False):
         _lib.require(ref_pcs, "ref_pcs", torch.float32, 3)
         self.trainer, self.ref, self.out_dir = trainer, ref_pcs, str(out_dir)
         self.every, self.batch_size, self.normalize, self.seed = int(every), int(batch_size), normalize, int(seed)
@@ -187,6 +193,8 @@ class SnapshotReporter:
         if self.full and self.emd == "auction":                  # the exact EMD's rows say how many pairs did not end at an optimum
             self.keys = self.keys + ("emd-capped",)
         self.last = None                                         # (epoch, {key: float}, seconds) of the latest report
+        self.spacing = bool(spacing)
+        self.last_spacing = None                                 # (epoch, generated clouds' stats, reference clouds' stats)
 
     def _generator(self, offset):
         return torch.Generator(device=self.ref.device).manual_seed(self.seed + offset)
@@ -216,6 +224,11 @@ class SnapshotReporter:
                     results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
                 results = {k: float(results[k]) for k in self.keys}
                 image = sheet.cpu().numpy()
+                if self.spacing:
+                    if "val_spacing" not in self.cache:          # (the reference set does not change between reports)
+                        self.cache["val_spacing"] = ev.spacing_stats(self.ref, self.batch_size)
+                    gen_pcs, _ = ev.generate_clouds(G, self.ref.shape[0], self.batch_size, self.normalize, self._generator(1), dev)
+                    spacing = (ev.spacing_stats(gen_pcs, self.batch_size), self.cache["val_spacing"])
         finally:
             G.train(was_training)
             G.restore_forward_hints(hints)
@@ -229,6 +242,16 @@ class SnapshotReporter:
                 f.write(",".join(("epoch",) + self.keys + ("seconds",)) + "\n")
             f.write(",".join([str(epoch)] + ["%.9g" % results[k] for k in self.keys] + ["%.3f" % seconds]) + "\n")
         self.last = (epoch, results, seconds)
+        if self.spacing:
+            gen, val = spacing
+            path = os.path.join(self.out_dir, "spacing.csv")
+            fresh = not os.path.exists(path) or os.path.getsize(path) == 0
+            with open(path, "a") as f:
+                if fresh:
+                    f.write(",".join(self.SPACING_HEADER) + "\n")
+                f.write(",".join([str(epoch)] + ["%.9g" % v for v in (gen["nn_mean"], gen["nn_cv"], val["nn_mean"], val["nn_cv"])]
+                                 + ["%d" % gen["duplicates"]]) + "\n")
+            self.last_spacing = (epoch, gen, val)
         return self.last
 
 

@@ -37,6 +37,11 @@ makes of a directory <synsetid>/<split>/* of .npy / .pts / .xyz / .txt clouds (i
 stays on the device as one point array and an offset table, and every visit of a shape is a fresh draw of --num_point of its points, or all of them with
 evenly spread duplicates where it stores fewer (data.RaggedFeeder, pdgn_feed_batch_ragged; DESIGN.md section 7n); --min_points K drops shorter shapes at load;
 --phase test and the reports take draw 0 of --num_point points of every raw test / val shape; --resample_pool and --mesh_visible do not apply.
+--repulsion W (train): the generator's loss gains W times a repulsion term on every generated cloud of --repulsion_levels (default 1,2,3,4), which
+is zero when no two points of a cloud are closer than the level's radius (losses.repulsion); --repulsion_radius H is the radius at
+--num_point points -- without it the radius is calibrated once before training, --repulsion_radius_factor (1) times the mean nearest-neighbour distance
+of up to 64 clouds the feeder itself produces, and printed; repulsion.csv beside the log.  --report_spacing (needs --report_every): the reports also
+append nearest-neighbour spacing statistics of the generated and the val clouds to report/spacing.csv.
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -122,6 +127,18 @@ def build_parser():
     p.add_argument("--gan_loss", choices=["lsgan", "hinge", "logistic"], default=argparse.SUPPRESS, help="the adversarial objective: lsgan "
                    "(default: the reference's least squares against 1 / 0), hinge, or logistic (non-saturating); the latter two read the "
                    "discriminators' outputs as logits; no launch is added")
+    p.add_argument("--repulsion", type=float, default=argparse.SUPPRESS, metavar="W", help="repulsion regulariser: the generator's loss gains W times the "
+                   "sum over the levels of the batch mean of sum_{j != i} max(0, 1 - |x_i - x_j|^2 / h^2)^2 over every generated cloud "
+                   "(losses.repulsion, DESIGN.md section 7p); repulsion.csv beside the log")
+    p.add_argument("--repulsion_radius", type=float, default=argparse.SUPPRESS, metavar="H", help="--repulsion: the radius h at --num_point points (a coarser "
+                   "level of N points gets h sqrt(num_point / N)); default: calibrated once before training, --repulsion_radius_factor times the mean "
+                   "nearest-neighbour distance of up to 64 clouds the feeder produces")
+    p.add_argument("--repulsion_radius_factor", type=float, default=argparse.SUPPRESS, metavar="K", help="--repulsion without --repulsion_radius: the "
+                   "calibrated radius is K times the mean nearest-neighbour distance (default 1)")
+    p.add_argument("--repulsion_levels", type=str, default=argparse.SUPPRESS, metavar="L,..", help="--repulsion: the levels that carry the term, 1 (the "
+                   "coarsest) .. 4 (--num_point points), comma separated (default 1,2,3,4)")
+    p.add_argument("--report_spacing", action="store_true", default=argparse.SUPPRESS, help="reports also append the nearest-neighbour spacing statistics of "
+                   "the generated and of the val clouds to report/spacing.csv (evaluation.spacing_stats); needs --report_every")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
     p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
@@ -177,6 +194,11 @@ class Args(argparse.Namespace):
     mesh_visible_res = 128
     ragged = False
     min_points = 1
+    repulsion = None
+    repulsion_radius = None                                      # (None: calibrated from the feeder's clouds)
+    repulsion_radius_factor = 1.0
+    repulsion_levels = "1,2,3,4"
+    report_spacing = False
 
 
 def parse_args(argv=None):
@@ -253,6 +275,27 @@ def parse_args(argv=None):
             validate(**augment_kwargs(args))
         except ValueError as e:
             p.error("--d_augment: %s" % e)
+    if args.repulsion is None:
+        for flag in ("repulsion_radius", "repulsion_radius_factor", "repulsion_levels"):
+            if flag in given:
+                p.error("--%s needs --repulsion" % flag)
+    else:
+        if not (args.repulsion >= 0.0 and args.repulsion != float("inf")):
+            p.error("--repulsion %r: a finite weight, not negative" % args.repulsion)
+        if args.repulsion_radius is not None and not (args.repulsion_radius > 0.0 and args.repulsion_radius != float("inf")):
+            p.error("--repulsion_radius %r: a finite positive radius" % args.repulsion_radius)
+        if args.repulsion_radius is not None and "repulsion_radius_factor" in given:
+            p.error("--repulsion_radius_factor scales the CALIBRATED radius: it does not go with --repulsion_radius")
+        if not (args.repulsion_radius_factor > 0.0 and args.repulsion_radius_factor != float("inf")):
+            p.error("--repulsion_radius_factor %r: a finite positive factor" % args.repulsion_radius_factor)
+        try:
+            repulsion_levels(args)
+        except ValueError as e:
+            p.error("--repulsion_levels: %s" % e)
+        if args.num_point > 8192:
+            p.error("--repulsion: --num_point %d, the all-pairs kernel holds at most 8192 points" % args.num_point)
+    if args.report_spacing and not args.report_every:
+        p.error("--report_spacing needs --report_every")
     if args.d_augment_target is None:
         for flag in ("ada_interval", "ada_span", "ada_p_min", "ada_p_max"):
             if flag in given:
@@ -266,6 +309,46 @@ def parse_args(argv=None):
         except ValueError as e:
             p.error("--d_augment_target: %s" % e)
     return args
+
+
+def repulsion_levels(args):
+    """--repulsion_levels "1,3,4" (1 the coarsest .. 4 the finest) -> the trainer's (0, 2, 3); raises ValueError on anything else."""
+    try:
+        levels = [int(w) for w in str(args.repulsion_levels).split(",")]
+    except ValueError:
+        raise ValueError("%r: comma-separated integers 1 .. 4" % (args.repulsion_levels,)) from None
+    if not levels or len(set(levels)) != len(levels) or min(levels) < 1 or max(levels) > 4:
+        raise ValueError("%r: distinct levels from 1 (the coarsest) to 4 (the finest)" % (args.repulsion_levels,))
+    return tuple(sorted(l - 1 for l in levels))
+
+
+def calibrate_repulsion_radius(feeder, factor=1.0, clouds=64):
+    """The radius of --repulsion without --repulsion_radius: `factor` times the mean nearest-neighbour distance (evaluation.spacing_stats)
+    of up to `clouds` finest-resolution clouds that the feeder itself produces -- the leading batches of epoch 1, into buffers of its own.
+    Under data parallelism rank 0's value goes to every rank."""
+    import torch.distributed as dist
+    from .evaluation import spacing_stats
+    reals, z1, z2 = feeder.buffers()
+    got = []
+    for i in range(min(feeder.batches_per_epoch, -(-int(clouds) // reals[3].shape[0]))):
+        feeder.fill(1, i, reals, z1, z2)
+        got.append(reals[3].transpose(1, 2).contiguous())
+    pcs = torch.cat(got)[:int(clouds)].contiguous()
+    radius = float(factor) * spacing_stats(pcs)["nn_mean"]
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        t = torch.tensor([radius], dtype=torch.float64, device=pcs.device)
+        dist.broadcast(t, 0)
+        radius = float(t.item())
+    if not (radius > 0.0 and radius != float("inf")):
+        raise SystemExit("--repulsion: the calibrated radius is %r (the feeder's clouds have no spacing to measure); give --repulsion_radius" % radius)
+    return radius, pcs.shape[0]
+
+
+def repulsion_arg(args, radius=None):
+    """PDGNTrainer's `repulsion` from the command line (None without --repulsion); radius: the calibrated one where --repulsion_radius was not given."""
+    if args.repulsion is None:
+        return None
+    return {"weight": args.repulsion, "radius": args.repulsion_radius if args.repulsion_radius is not None else radius, "levels": repulsion_levels(args)}
 
 
 def adaptive_kwargs(args):
@@ -472,7 +555,7 @@ def init_dist(device):
     return 0, 1, torch.device(device)
 
 
-def make_trainer(args, device, batches_per_epoch=None):
+def make_trainer(args, device, batches_per_epoch=None, repulsion=None):
     from .generator import PointGenerator
     from .trainer import PDGNTrainer
     base = args.num_point // 16
@@ -484,7 +567,8 @@ def make_trainer(args, device, batches_per_epoch=None):
                        clip_grad_norm=args.clip_grad_norm if args.phase == "train" else None,
                        lr_g=args.lr_g if args.phase == "train" else None, lr_d=args.lr_d if args.phase == "train" else None,
                        lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None,
-                       augment=_augment_arg(args) if args.phase == "train" else None, gan_loss=args.gan_loss)
+                       augment=_augment_arg(args) if args.phase == "train" else None, gan_loss=args.gan_loss,
+                       repulsion=repulsion if args.phase == "train" else None)
 
 
 def _augment_arg(args):
@@ -559,11 +643,20 @@ def train(args):
         feeder = _mesh_feeder(args, mesh_root, device, rank, world)
     else:
         feeder = _cloud_feeder(args, device, rank, world)
+    radius = None
+    if args.repulsion is not None and args.repulsion_radius is None:
+        radius, used = calibrate_repulsion_radius(feeder, args.repulsion_radius_factor)
+        if rank == 0:
+            print("# repulsion radius: %.9g (%g x the mean nearest-neighbour distance of %d clouds of %d points)"
+                  % (radius, args.repulsion_radius_factor, used, n))
     try:
-        trainer = make_trainer(args, device, feeder.batches_per_epoch)
+        trainer = make_trainer(args, device, feeder.batches_per_epoch, repulsion_arg(args, radius))
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
         raise SystemExit(str(e))
     trainer.train()
+    if rank == 0 and trainer.repulsion is not None:
+        print("# repulsion: weight %g, radius %.9g, levels %s" % (trainer.repulsion["weight"], trainer.repulsion["radius"],
+                                                                  ",".join(str(l + 1) for l in trainer.repulsion["levels"])))
     if rank == 0 and trainer.gan_loss != "lsgan":
         print("# adversarial objective: %s (scores are logits; decision boundary 0)" % trainer.gan_loss)
     start = _resume(args, trainer, ckpt) or 1
@@ -582,11 +675,13 @@ def train(args):
         from .report import SnapshotReporter
         val = reference_clouds(args, "val", device, mesh_root, ragged_root)
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
-                                    args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd)
+                                    args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd,
+                                    **({"spacing": True} if args.report_spacing else {}))
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
                        grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
-                       lr_log=os.path.join(run_dir, "lr.csv"), aug_log=os.path.join(run_dir, "aug.csv"))
+                       lr_log=os.path.join(run_dir, "lr.csv"), aug_log=os.path.join(run_dir, "aug.csv"),
+                       **({"repulsion_log": os.path.join(run_dir, "repulsion.csv")} if trainer.repulsion is not None else {}))
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()

@@ -76,14 +76,23 @@ class PDGNTrainer:
     reference's least squares and the default -- the launches it always had --, "hinge" or "logistic" (non-saturating), on the
     discriminators' raw scores; `gan_loss` keeps the name.  The kind is baked into the launches (a captured list keeps the one it was
     captured with), adds none, and is not written into checkpoints.  The adaptive augmentation counts the real scores against the
-    objective's decision boundary: 1/2 under "lsgan", 0 otherwise."""
+    objective's decision boundary: 1/2 under "lsgan", 0 otherwise.
+
+    repulsion: None, or {"weight": w, "radius": h, "levels": (0, 1, 2, 3)} (levels optional).  With one, the generator's loss gains
+    w * sum_l losses.repulsion(gen_l, h_l) over the named levels of pass #2's clouds: h is the finest level's
+    radius, h_l = losses.repulsion_radii's.  The term is a batch MEAN like the adversarial ones, so data parallelism needs no factor
+    for it.  `out["g_loss"]` includes it, `out["repulsion_loss"]` is the unweighted sum over the levels, `repulsion_state()` reads the
+    per-level values; `set_repulsion(weight=...)` overwrites the weight in place (a captured list follows), a new radius needs a
+    recapture.  Every sum of the term runs in a fixed order: under `set_deterministic` it adds no non-determinism of its own (the
+    step's other sums still warn).  None: `repulsion` is None, no buffer, no launch, the same list and the same six `out` keys."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
                  discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
-                 lr_g=None, lr_d=None, lr_schedule=None, augment=None, gan_loss="lsgan"):
+                 lr_g=None, lr_d=None, lr_schedule=None, augment=None, gan_loss="lsgan", repulsion=None):
         if gan_loss not in losses.GAN_LOSSES:                    # (raises before anything is allocated)
             raise ValueError("gan_loss must be one of %s, got %r" % (", ".join(losses.GAN_LOSSES), gan_loss))
         self.gan_loss = gan_loss
+        self.repulsion = None if repulsion is None else self._check_repulsion(repulsion)     # (raises before anything is allocated)
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
@@ -148,6 +157,9 @@ class PDGNTrainer:
         self.overlap = cap and os.environ.get("PDGN_OVERLAP", "1") == "1"
         self._side = None
         self._lw = {}
+        if self.repulsion is not None:
+            self._rep_buf = torch.zeros(4, dtype=torch.float32, device=self.device)       # the last iteration's value per level
+            self._rep_zero = torch.zeros((), dtype=torch.float32, device=self.device)     # (a level that is not in `levels`)
         for ws in {1, world_size() if self.distributed else 1}:
             self._loss_weights(ws)
         self._early_tail = os.environ.get("PDGN_EARLY_TAIL", "1") == "1"
@@ -167,6 +179,65 @@ class PDGNTrainer:
             torch.cuda.synchronize(self.device)
         host = self.guard_buf.cpu()
         return {k: GradGuard.decode(host[i]) for i, k in enumerate(self.GUARD_KEYS)}
+
+    @staticmethod
+    def _check_repulsion(cfg):
+        """{"weight", "radius", "levels"} validated: weight finite and >= 0, radius finite and > 0, levels a non-empty ascending
+        subset of (0, 1, 2, 3)."""
+        if not isinstance(cfg, dict) or set(cfg) - {"weight", "radius", "levels"} or not {"weight", "radius"} <= set(cfg):
+            raise ValueError("repulsion: None or {'weight': w, 'radius': h, 'levels': (0, 1, 2, 3)}, got %r" % (cfg,))
+        weight, radius = float(cfg["weight"]), float(cfg["radius"])
+        if not (0.0 <= weight < float("inf")):
+            raise ValueError("repulsion weight must be finite and not negative, got %r" % (cfg["weight"],))
+        if not (0.0 < radius < float("inf")):
+            raise ValueError("repulsion radius must be finite and positive, got %r" % (cfg["radius"],))
+        levels = tuple(int(l) for l in cfg.get("levels", (0, 1, 2, 3)))
+        if not levels or list(levels) != sorted(set(levels)) or levels[0] < 0 or levels[-1] > 3:
+            raise ValueError("repulsion levels: a non-empty ascending subset of (0, 1, 2, 3), got %r" % (cfg.get("levels"),))
+        return {"weight": weight, "radius": radius, "levels": levels}
+
+    def set_repulsion(self, weight=None, radius=None):
+        """Change the repulsion term.  weight: written INTO the loss-weight vectors -- the tensors a launch list has baked in: the
+        next `step_list()` (or eager step) uses it, with no recapture.  radius: a launch ARGUMENT, so a captured list or graph keeps
+        the one it was captured with: raises while one exists.  Raises on a trainer built without `repulsion`."""
+        if self.repulsion is None:
+            raise RuntimeError("set_repulsion(): this trainer was built without repulsion; build it with one (e.g. weight 0.0)")
+        fresh = self._check_repulsion({"weight": self.repulsion["weight"] if weight is None else weight,
+                                       "radius": self.repulsion["radius"] if radius is None else radius,
+                                       "levels": self.repulsion["levels"]})
+        if radius is not None and fresh["radius"] != self.repulsion["radius"] and (
+                getattr(self, "_list", None) is not None or getattr(self, "_graphs", None)):
+            raise RuntimeError("set_repulsion(radius=...): the radius is an argument of the captured launches; capture again with the new one")
+        self.repulsion = fresh
+        with torch.no_grad():
+            for w in self._lw.values():
+                w[5:].fill_(fresh["weight"])
+
+    def repulsion_state(self):
+        """{weight, radius, levels, radii, per_level, total}: the parameters, the radius of each of the four levels for the last
+        iteration's cloud sizes (None before the first), and the last iteration's unweighted value per level (0 for a level that is not
+        in `levels`) with their sum.  Synchronises the device."""
+        if self.repulsion is None:
+            raise RuntimeError("repulsion_state(): this trainer was built without repulsion")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        per = [float(v) for v in self._rep_buf.cpu()]
+        return dict(self.repulsion, radii=self.__dict__.get("_rep_radii"), per_level=per, total=float(sum(per)))
+
+    def _repulsion_radii(self, sizes):
+        """The four levels' radii for these point counts (cached: the same sizes every iteration)."""
+        key = (self.repulsion["radius"],) + tuple(int(n) for n in sizes)
+        if self.__dict__.get("_rep_key") != key:
+            self._rep_key, self._rep_radii = key, losses.repulsion_radii(key[0], key[1:])
+        return self._rep_radii
+
+    def _repulsion_total(self, rep):
+        """The four per-level values (0-dim tensors, or None for a level that is off) -> their unweighted sum; the values are kept
+        in the trainer's 4-float buffer for `repulsion_state`."""
+        vals = torch.stack([r if r is not None else self._rep_zero for r in rep])
+        # (an elementwise launch, not copy_: a captured 16-byte copy_ is a memcpy node of a shape the launch list does not re-issue)
+        torch.add(vals.detach(), self._rep_zero, out=self._rep_buf)
+        return vals.sum()
 
     def set_lr_schedule(self, knots):
         """Replace the schedule: the knots are validated and written INTO the trainer's table -- the same tensor at the same
@@ -401,7 +472,10 @@ class PDGNTrainer:
         is a batch SUM, so under data parallelism it is scaled by the world size before the mean all-reduce."""
         w = self._lw.get(ws)
         if w is None:                                            # created outside any graph capture (see __init__)
-            w = self._lw[ws] = torch.tensor([1.2, 1.2, 1.2, 1.0, 0.1 * ws], dtype=torch.float32, device=self.device)
+            base = [1.2, 1.2, 1.2, 1.0, 0.1 * ws]
+            if self.repulsion is not None:                       # one more entry of the weighted sum: a batch mean, no world-size factor
+                base.append(self.repulsion["weight"])
+            w = self._lw[ws] = torch.tensor(base, dtype=torch.float32, device=self.device)
         return w
 
     def _freeze_D(self, frozen):
@@ -502,6 +576,11 @@ class PDGNTrainer:
             similar = self.similar_loss(gen)
             g_loss = [losses.adversarial(self.D[i](gen[i]) if self.aug is None else self.D[i](gen[i], self.aug.at(i, "gen")), self.gan_loss, "g") for i in range(4)]
             adv = 1.2 * g_loss[0] + 1.2 * g_loss[1] + 1.2 * g_loss[2] + g_loss[3]
+            if self.repulsion is not None:
+                radii = self._repulsion_radii([c.shape[2] for c in gen])
+                rep = self._repulsion_total([losses.repulsion(gen[l], radii[l]) if l in self.repulsion["levels"] else None for l in range(4)])
+                adv = adv + self._lw[1][5] * rep                 # (the weight as the device holds it: set_repulsion reaches a captured graph)
+                st["out"]["repulsion_loss"] = rep.detach()
             lossG = adv + 0.1 * similar
             # MSE is a batch MEAN, the shape loss a batch SUM (chamfer_loss.py:16-20): to reproduce
             # one reference step at the global batch, scale the sum term by world_size before the
@@ -658,6 +737,13 @@ class PDGNTrainer:
         # are also the first adjoints autograd issues -- the ones block 4's backward waits for.
         terms, own, g_loss, gen_so_far = {}, {}, [None] * 4, []
         early = self._early_tail
+        rep, rep_on = [None] * 4, self.repulsion is not None
+        # (the levels arrive one at a time; the generator's clouds have the real batch's point counts -- D_k sees both)
+        radii = self._repulsion_radii([r.shape[2] for r in st["reals"]]) if rep_on else None
+
+        def repel(level, cloud):                            # level l's all-pairs launch, on the local-pair stream (which has waited for `main`)
+            if level in self.repulsion["levels"]:
+                rep[level] = losses.repulsion(cloud, radii[level])
 
         def d_gen(level, cloud):                            # D_k(G(z2)_k) behind D_k's update, on D_k's stream
             side = self._side[level]
@@ -667,10 +753,13 @@ class PDGNTrainer:
 
         def tail(level, cloud):
             gen_so_far.append(cloud)
-            if level >= 1:
+            if level >= 1 or rep_on:
                 self._side_lp.wait_stream(main)
                 with torch.cuda.stream(self._side_lp):
-                    terms.update(self.similar_terms(gen_so_far, [(a, level) for a in range(level)], own))
+                    if level >= 1:
+                        terms.update(self.similar_terms(gen_so_far, [(a, level) for a in range(level)], own))
+                    if rep_on:
+                        repel(level, cloud)
             d_gen(level, cloud)
 
         gen = self.G(self._z(st, "z2"), stage_hook=tail if early else None)
@@ -679,6 +768,9 @@ class PDGNTrainer:
             self._side_lp.wait_stream(main)
             with torch.cuda.stream(self._side_lp):
                 terms = self.similar_terms(gen, PAIRS)
+                if rep_on:
+                    for level in range(4):
+                        repel(level, gen[level])
             for i, side in enumerate(self._side):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -691,7 +783,10 @@ class PDGNTrainer:
         # 1.2*(g1+g2+g3) + g4 + 0.1*similar (:254) as one weighted sum: this sits between the joins and the backward,
         # where every launch is on the critical path (three launches here and one in backward instead of eight and five)
         ws = st["ws"]
-        terms = torch.stack(g_loss + [similar])
+        if rep_on:                                          # one more entry of the weighted sum; its weight is the vector's last element
+            repulsion = self._repulsion_total(rep)
+            st["out"]["repulsion_loss"] = repulsion.detach()
+        terms = torch.stack(g_loss + [similar] + ([repulsion] if rep_on else []))
         lossG = (terms * self._loss_weights(1)).sum()
         (lossG if ws == 1 else (terms * self._loss_weights(ws)).sum()).backward()
         mark("backward")
@@ -871,7 +966,7 @@ class PDGNTrainer:
     LOG_FORMAT, LOSS_KEYS = _fit.LOG_FORMAT, _fit.LOSS_KEYS
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None):
+            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None, repulsion_log=None):
         """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
         `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
         them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
@@ -902,9 +997,13 @@ class PDGNTrainer:
         warm-up: iteration i of epoch e draws at (e - 1) * nb + i, whether the run was interrupted or not.  The clock is derived,
         not stored: checkpoints are what they were.  With ADAPTIVE augmentation (section 7i) `aug_log` (a path; default: aug.csv beside a
         log given as a path, else none) gets one row -- epoch, clock, p, updates, last_r, r_D1 .. r_D4 (the last update's (pos - neg) / n
-        per discriminator) -- wherever lr.csv would get one.  Rank 0 only; without adaptive augmentation, no file."""
+        per discriminator) -- wherever lr.csv would get one.  Rank 0 only; without adaptive augmentation, no file.
+
+        With the repulsion term `repulsion_log` (a path; default: repulsion.csv beside a log given as a path, else
+        none) gets one row per EPOCH -- epoch, weight, radius, total, level1 .. level4: `repulsion_state()` after the epoch's last
+        iteration, one synchronise per epoch.  Rank 0 only; without the term, no file and no synchronise."""
         return _fit.fit(self, feeder, epochs, start_epoch, snapshot, checkpoint_dir, category, issue, log, on_epoch, guard_max_skips,
-                        grad_norms, lr_log, aug_log)
+                        grad_norms, lr_log, aug_log, repulsion_log)
 
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()
