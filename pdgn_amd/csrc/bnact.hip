@@ -116,6 +116,19 @@ __device__ __forceinline__ double fin_reduce(const float *__restrict__ part, int
     return red[0][cl];
 }
 
+// The LDS tree over the part lanes for two values per (part lane, channel) at once: the sums end in red[0][cl], red2[0][cl].
+__device__ __forceinline__ void fin_tree2(double (*red)[FIN_CH], double (*red2)[FIN_CH]) {
+    const int cl = threadIdx.x % FIN_CH, pl = threadIdx.x / FIN_CH;
+    __syncthreads();
+    for (int h = FIN_PL / 2; h > 0; h >>= 1) {
+        if (pl < h) {
+            red[pl][cl] += red[pl + h][cl];
+            red2[pl][cl] += red2[pl + h][cl];
+        }
+        __syncthreads();
+    }
+}
+
 // Both column sums of a channel (slots c and C + c) in ONE pass: the loads of the two reductions are in flight together
 // and the LDS tree carries both values -- these finalize kernels are ~150 launches per step, each a pure latency chain.
 __device__ __forceinline__ void fin_reduce2(const float *__restrict__ part, int nparts, size_t ld, int c, int C, bool ok,
@@ -138,16 +151,32 @@ __device__ __forceinline__ void fin_reduce2(const float *__restrict__ part, int 
     }
     red[pl][cl] = a;
     red2[pl][cl] = b;
-    __syncthreads();
-    for (int h = FIN_PL / 2; h > 0; h >>= 1) {
-        if (pl < h) {
-            red[pl][cl] += red[pl + h][cl];
-            red2[pl][cl] += red2[pl + h][cl];
-        }
-        __syncthreads();
-    }
+    fin_tree2(red, red2);
     s1 = red[0][cl];
     s2 = red2[0][cl];
+}
+
+// The tail of every finalising kernel, from the mean and the (unclamped) biased variance of channel c over R rows: the four stats
+// rows and, with running buffers, their update with the unbiased variance.
+__device__ __forceinline__ void fin_write(int c, int C, long long R, double mean, double var, float eps, float momentum,
+                                          const float *__restrict__ gamma, const float *__restrict__ beta,
+                                          const float *__restrict__ pre_bias, float *__restrict__ running_mean,
+                                          float *__restrict__ running_var, float *__restrict__ stats) {
+    var = var < 0 ? 0 : var;
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float g = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
+    const float scale = g * invstd;
+    stats[c] = scale;
+    stats[C + c] = be - (float)mean * scale;
+    stats[2 * C + c] = (float)mean;
+    stats[3 * C + c] = invstd;
+    if (running_mean) {
+        const double unbiased = R > 1 ? var * (double)R / (double)(R - 1) : var;
+        // pre_bias: the producer's bias, left out of x (BatchNorm(x + b) = BatchNorm(x)); only the running mean sees it
+        const float mb = (float)mean + (pre_bias ? pre_bias[c] : 0.f);
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mb;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
 }
 
 __global__ __launch_bounds__(FIN_CH * FIN_PL) void cl_finalize_kernel(
@@ -162,29 +191,27 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void cl_finalize_kernel(
     fin_reduce2(part, nparts, (size_t)2 * C, c, C, ok, red, red2, s1, s2);
     if (!ok || threadIdx.x >= FIN_CH) return;
     const double ms = s1 / (double)R;                       // mean of the (shifted) values
-    double var = s2 / (double)R - ms * ms;
-    var = var < 0 ? 0 : var;
+    const double var = s2 / (double)R - ms * ms;            // (of the shifted values: the pivot cancels)
     const double mean = ms + (pivot ? (double)pivot[c] : 0.0);
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    const float scale = g * invstd;
-    stats[c] = scale;
-    stats[C + c] = b - (float)mean * scale;
-    stats[2 * C + c] = (float)mean;
-    stats[3 * C + c] = invstd;
-    if (running_mean) {
-        const double unbiased = R > 1 ? var * (double)R / (double)(R - 1) : var;
-        // pre_bias: the producer's bias, left out of x (BatchNorm(x + b) = BatchNorm(x)); only the running mean sees it
-        const float mb = (float)mean + (pre_bias ? pre_bias[c] : 0.f);
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mb;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    fin_write(c, C, R, mean, var, eps, momentum, gamma, beta, pre_bias, running_mean, running_var, stats);
 }
 
 // The same finalisation from BLOCK-SHIFTED partials (the epilogues of pdgn_gemm_nt / pdgn_gemm_nn / pdgn_thin_nt): partial
 // row b covers rows b*rpp .. of x and holds [sum (x - pv_b) | sum (x - pv_b)^2 | pv_b] with pv_b the block's own first row.
 // Per block: mean_b = pv_b + s/n, M2_b = q - s^2/n (no cancellation: |x - pv_b| ~ std); the blocks are combined in fp64:
 // mean = sum n_b mean_b / R, var = (sum M2_b + sum n_b mean_b^2) / R - mean^2.
+__device__ __forceinline__ void fin_block_terms(const float *__restrict__ part, int p, int rpp, long long R, int C, int c,
+                                                double inv_full, double &a, double &b) {       // block p's share of the two sums
+    const long long left = R - (long long)p * rpp;
+    const bool full = left >= rpp;
+    const double n = (double)(full ? rpp : left), inv = full ? inv_full : 1.0 / (double)left;
+    const float *q = part + (size_t)p * 3 * C + c;
+    const double s = (double)q[0], sq = (double)q[C], pv = (double)q[2 * C];
+    const double mb = pv + s * inv;
+    a += n * mb;
+    b += (sq - s * s * inv) + n * mb * mb;
+}
+
 __global__ __launch_bounds__(FIN_CH * FIN_PL) void cl_finalize_blocks_kernel(
     long long R, int C, int nparts, int rpp, float eps, float momentum, const float *__restrict__ part,
     const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ pre_bias,
@@ -199,42 +226,14 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void cl_finalize_blocks_kernel(
     if (ok)
 #pragma unroll 4
         for (int p = pl; p < pmax; p += FIN_PL) {                 // (no exit inside: the loads of four blocks go out together)
-            const long long left = R - (long long)p * rpp;
-            const bool full = left >= rpp;
-            const double n = (double)(full ? rpp : left), inv = full ? inv_full : 1.0 / (double)left;
-            const float *q = part + (size_t)p * 3 * C + c;
-            const double s = (double)q[0], sq = (double)q[C], pv = (double)q[2 * C];
-            const double mb = pv + s * inv;
-            a += n * mb;
-            b += (sq - s * s * inv) + n * mb * mb;
+            fin_block_terms(part, p, rpp, R, C, c, inv_full, a, b);
         }
     red[pl][cl] = a;
     red2[pl][cl] = b;
-    __syncthreads();
-    for (int h = FIN_PL / 2; h > 0; h >>= 1) {
-        if (pl < h) {
-            red[pl][cl] += red[pl + h][cl];
-            red2[pl][cl] += red2[pl + h][cl];
-        }
-        __syncthreads();
-    }
+    fin_tree2(red, red2);
     if (!ok || threadIdx.x >= FIN_CH) return;
-    const double mean = red[0][cl] / (double)R;
-    double var = red2[0][cl] / (double)R - mean * mean;
-    var = var < 0 ? 0 : var;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-    const float scale = g * invstd;
-    stats[c] = scale;
-    stats[C + c] = be - (float)mean * scale;
-    stats[2 * C + c] = (float)mean;
-    stats[3 * C + c] = invstd;
-    if (running_mean) {
-        const double unbiased = R > 1 ? var * (double)R / (double)(R - 1) : var;
-        const float mb = (float)mean + (pre_bias ? pre_bias[c] : 0.f);
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mb;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    const double mean = red[0][cl] / (double)R, var = red2[0][cl] / (double)R - mean * mean;
+    fin_write(c, C, R, mean, var, eps, momentum, gamma, beta, pre_bias, running_mean, running_var, stats);
 }
 
 // The same in two launches for long partial lists (a 358400-row GEMM leaves 2800-5600 partial rows; one workgroup per four
@@ -254,25 +253,11 @@ __global__ __launch_bounds__(FIN_CH * FIN_PL) void cl_finalize_blocks_slice_kern
     if (ok)
 #pragma unroll 4
         for (int p = p0 + pl; p < pmax; p += FIN_PL) {
-            const long long left = R - (long long)p * rpp;
-            const bool full = left >= rpp;
-            const double n = (double)(full ? rpp : left), inv = full ? inv_full : 1.0 / (double)left;
-            const float *q = part + (size_t)p * 3 * C + c;
-            const double s = (double)q[0], sq = (double)q[C], pv = (double)q[2 * C];
-            const double mb = pv + s * inv;
-            a += n * mb;
-            b += (sq - s * s * inv) + n * mb * mb;
+            fin_block_terms(part, p, rpp, R, C, c, inv_full, a, b);
         }
     red[pl][cl] = a;
     red2[pl][cl] = b;
-    __syncthreads();
-    for (int h = FIN_PL / 2; h > 0; h >>= 1) {
-        if (pl < h) {
-            red[pl][cl] += red[pl + h][cl];
-            red2[pl][cl] += red2[pl + h][cl];
-        }
-        __syncthreads();
-    }
+    fin_tree2(red, red2);
     if (!ok || threadIdx.x >= FIN_CH) return;
     scratch[((size_t)blockIdx.y * 2) * C + c] = red[0][cl];
     scratch[((size_t)blockIdx.y * 2 + 1) * C + c] = red2[0][cl];
@@ -293,14 +278,7 @@ __global__ __launch_bounds__(256) void cl_finalize_blocks_slice64_kernel(
     const int p0 = blockIdx.y * per_slice, pmax = min(pmax_all, p0 + per_slice);
 #pragma unroll 4
     for (int p = p0 + pl; p < pmax; p += 4) {
-        const long long left = R - (long long)p * rpp;
-        const bool full = left >= rpp;
-        const double n = (double)(full ? rpp : left), inv = full ? inv_full : 1.0 / (double)left;
-        const float *q = part + (size_t)p * 3 * C + c;
-        const double s = (double)q[0], sq = (double)q[C], pv = (double)q[2 * C];
-        const double mb = pv + s * inv;
-        a += n * mb;
-        b += (sq - s * s * inv) + n * mb * mb;
+        fin_block_terms(part, p, rpp, R, C, c, inv_full, a, b);
     }
     red[pl][cl] = a;
     red2[pl][cl] = b;
@@ -333,22 +311,8 @@ __global__ void cl_finalize_blocks_join_kernel(long long R, int C, int slices, f
     if (pl != 0 || c >= C) return;
     a = ((ra[0][cl] + ra[1][cl]) + ra[2][cl]) + ra[3][cl];
     b = ((rb[0][cl] + rb[1][cl]) + rb[2][cl]) + rb[3][cl];
-    const double mean = a / (double)R;
-    double var = b / (double)R - mean * mean;
-    var = var < 0 ? 0 : var;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-    const float scale = g * invstd;
-    stats[c] = scale;
-    stats[C + c] = be - (float)mean * scale;
-    stats[2 * C + c] = (float)mean;
-    stats[3 * C + c] = invstd;
-    if (running_mean) {
-        const double unbiased = R > 1 ? var * (double)R / (double)(R - 1) : var;
-        const float mb = (float)mean + (pre_bias ? pre_bias[c] : 0.f);
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mb;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    const double mean = a / (double)R, var = b / (double)R - mean * mean;
+    fin_write(c, C, R, mean, var, eps, momentum, gamma, beta, pre_bias, running_mean, running_var, stats);
 }
 
 static inline int fb_slices(int c, long long nparts) {           // 0: the one-launch form

@@ -28,7 +28,7 @@ from ._fn import Function
 from . import _lib
 from . import streams as _streams
 from ._lib import check, ptr, require, stream_of
-from .fused import (Planes, split_planes, skinny_linear, _zeros, bilateral_weighting, bn_act,  # noqa: F401
+from .fused import (Planes, split_planes, skinny_linear, _zeros, _scratch_floats, bilateral_weighting, bn_act,  # noqa: F401
                     small_sequential, bn_act_maxpool, bn_softmax_slots_permute, flush_bn_counters,  # noqa: F401
                     has_zero_colsum, linear_cl, softmax_slots_permute, DenseInput, group_colsum, mark_maxima, row_maxima_buffer)
 from .fused import _STATS_MAX as STATS_MAX  # noqa: F401
@@ -132,7 +132,7 @@ class EdgeGatherSum(Function):
                 bstride = C if (bias is not None and bias.dim() == 2) else 0
             if len(spec) > 5 and spec[5]:
                 # the consumer is a training-mode BatchNorm over (b*n*P, C): emit its partial statistics here
-                scr = torch.empty(L.pdgn_bn_scratch_floats(b * n * P, C), dtype=F32, device=Y.device)
+                scr = torch.empty(_scratch_floats(L, b * n * P, C), dtype=F32, device=Y.device)
                 check(L.pdgn_window_gather_sum_stats(b, n, k, ldy, T, P, C, off, offc, ptr(Y), ptr(idx), ptr(bias_c),
                                                      bstride, ptr(out), ptr(scr), stream_of(Y)),
                       "pdgn_window_gather_sum_stats")

@@ -177,11 +177,31 @@ def group_colsum(x2d, group_rows=None):
     return out
 
 
-def _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps, partials=None):
+class BNState(NamedTuple):
+    """What a BatchNorm op takes from its module and does not differentiate: ONE non-tensor argument of its apply (not gamma / beta / pre_bias)."""
+    running_mean: object        # None (both): no running statistics to read or update
+    running_var: object
+    training: bool              # batch statistics (and, with buffers, their update); False: the running statistics
+    momentum: float
+    eps: float
+
+
+def bn_state(bn, training):
+    """The record of an nn.BatchNorm* module; track_running_stats=False: no buffers, batch statistics in eval too (torch's rule)."""
+    if not bn.track_running_stats:
+        return BNState(None, None, True, bn.momentum, bn.eps)
+    return BNState(bn.running_mean, bn.running_var, bool(training), bn.momentum, bn.eps)
+
+
+def _params(gamma, beta, pre_bias=None):                         # as the kernels read them: detached, contiguous; None stays None
+    return [t.detach().contiguous() if t is not None else None for t in (gamma, beta, pre_bias)]
+
+
+def _bn_stats(L, x, rows, C, g, b, pb, st, partials=None):
     """[scale|shift|mean|invstd] of a BatchNorm over x (rows, C) -- batch statistics (+ running-stat update) in
-    training, running statistics in eval.  pre_bias: see include/pdgn_hip.h (the producer's bias, left out of x)."""
+    training, running statistics in eval.  g, b, pb: _params'; pb: see include/pdgn_hip.h (the producer's bias, left out of x)."""
     stats = torch.empty(4 * C, dtype=F32, device=x.device)
-    pb = pre_bias.detach().contiguous() if pre_bias is not None else None
+    running_mean, running_var, training, momentum, eps = st
     block = None
     if isinstance(partials, tuple):                             # (tensor (nparts, 3C), rows per block): a GEMM / thin-layer epilogue's
         partials, block = partials                              # block-shifted rows, with the block size linear_cl attached
@@ -227,38 +247,41 @@ class BNActCL(Function):
     bilateral product ``inte_x * w`` of models/PDGNet_v2.py:642)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, act, mul, pre_bias=None,
-                partials=None, interleave_n=0):
+    def forward(ctx, x, gamma, beta, st, act, mul, pre_bias=None, partials=None, interleave_n=0):
         rows, C = x.shape
         x = x.contiguous()
         L = _lib.lib()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        stats = _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps, partials)
+        stats = _bn_stats(L, x, rows, C, *_params(gamma, beta, pre_bias), st, partials)
         ctx.has_pre_bias = pre_bias is not None
         mul_c = mul.contiguous() if mul is not None else None
         # interleave_n = N: y is (rows * 2, C / 2), x row b*N + n / channel 2c + j at y row b*2N + j*N + n / channel c
         y = torch.empty((rows * 2, C // 2), dtype=F32, device=x.device) if interleave_n else torch.empty_like(x)
         check(L.pdgn_bn_act_forward(rows, C, act, ptr(x), ptr(stats), ptr(mul_c), ptr(y), int(interleave_n), stream_of(x)), "pdgn_bn_act_forward")
         ctx.save_for_backward(x, stats, mul_c)
-        ctx.cfg = (rows, C, act, bool(training), mul is not None and mul.requires_grad, int(interleave_n))
+        ctx.cfg = (rows, C, act, st.training, mul is not None and mul.requires_grad, int(interleave_n))
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, stats, mul = ctx.saved_tensors
         rows, C, act, training, need_dmul, inter = ctx.cfg
-        dy = dy.contiguous()
-        L = _lib.lib()
-        scratch = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
-        bs = torch.empty(2 * C, dtype=F32, device=x.device)
-        dx = torch.empty_like(x)
-        dmul = torch.empty_like(x) if need_dmul else None
-        check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dy), ptr(mul),
-                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(dmul), inter, stream_of(x)), "pdgn_bn_act_backward")
-        if training:
-            mark_zero_colsum(dx)
-        return (dx, bs[C:], bs[:C], None, None, None, None, None, None, dmul, _pre_bias_grad(ctx.has_pre_bias, C, x.device),
-                None, None)
+        dx, dg, db, dmul = _bn_act_adjoint(_lib.lib(), x, dy.contiguous(), stats, act, training, rows, C, mul, need_dmul, inter)
+        # x, gamma, beta, st, act, mul, pre_bias, partials, interleave_n
+        return dx, dg, db, None, None, dmul, _pre_bias_grad(ctx.has_pre_bias, C, x.device), None, None
+
+
+def _bn_act_adjoint(L, x, dz, stats, act, training, rows, C, mul=None, want_dmul=False, interleave_n=0):
+    """The streaming adjoint of z = act(BatchNorm(x)) [* mul] over x (rows, C), from dz: (dx, dgamma, dbeta, dmul or None).  Owns the
+    scratch and the [dbeta | dgamma] row of pdgn_bn_act_backward; under batch statistics dx is marked (mark_zero_colsum)."""
+    scratch = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
+    bs = torch.empty(2 * C, dtype=F32, device=x.device)
+    dx = torch.empty_like(x)
+    dmul = torch.empty_like(x) if want_dmul else None
+    check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dz), ptr(mul), ptr(stats), ptr(scratch), ptr(bs), ptr(dx),
+                                 ptr(dmul), interleave_n, stream_of(x)), "pdgn_bn_act_backward")
+    if training:
+        mark_zero_colsum(dx)
+    return dx, bs[C:], bs[:C], dmul
 
 
 # nn.BatchNorm's num_batches_tracked bookkeeping: one tiny int64 add per layer per forward would be
@@ -280,30 +303,33 @@ def flush_bn_counters():
     if _HOLD_COUNTS[0]:
         return
     if _PENDING_COUNTS:
-        tensors = list(_PENDING_COUNTS.keys())
-        torch._foreach_add_(tensors, [int(v) for v in _PENDING_COUNTS.values()])
+        torch._foreach_add_(list(_PENDING_COUNTS.keys()), [int(v) for v in _PENDING_COUNTS.values()])
         _PENDING_COUNTS.clear()
+
+
+def _tick(bn, training):
+    """One forward of `bn` on batch statistics: every wrapper below calls this once, behind its fall-back decisions (a wrapper that
+    hands the whole BatchNorm to another wrapper leaves the tick to it)."""
+    if training and bn.track_running_stats:
+        _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
 
 
 def bn_act(x2d, bn, training, act="leaky_relu", mul=None, pre_bias=None, partials=None, interleave_n=0):
     """Apply an nn.BatchNorm{1,2}d module's parameters/buffers to a channels-last (rows, C) view,
     followed by `act` (and an optional elementwise product).  `pre_bias`: the bias of the layer that produced
     x2d, when the caller did not add it (it cancels inside the BatchNorm; only the running mean sees it)."""
-    if training and bn.track_running_stats:
-        _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
     x2d, pre_bias = _fold_pre_bias(x2d, pre_bias, training)
+    if interleave_n and (x2d.shape[1] % 4 or mul is not None or not x2d.is_cuda):      # only the plain fused store interleaves
+        return interleave_rows(bn_act(x2d, bn, training, act, mul, pre_bias, partials), interleave_n)
+    _tick(bn, training)
+    st = bn_state(bn, training)
     if x2d.shape[1] % 4:                      # odd channel counts: library path
         if pre_bias is not None:
             x2d = x2d + pre_bias
-        y = torch.nn.functional.batch_norm(x2d, bn.running_mean, bn.running_var, bn.weight, bn.bias, training,
-                                           bn.momentum, bn.eps)
+        y = torch.nn.functional.batch_norm(x2d, st.running_mean, st.running_var, bn.weight, bn.bias, st.training, st.momentum, st.eps)
         y = {"none": lambda t: t, "relu": torch.relu, "leaky_relu": torch.nn.functional.leaky_relu}[act](y)
-        y = y * mul if mul is not None else y
-        return interleave_rows(y, interleave_n) if interleave_n else y
-    if interleave_n and (mul is not None or not x2d.is_cuda):
-        return interleave_rows(bn_act(x2d, bn, training, act, mul, pre_bias, partials), interleave_n)
-    return BNActCL.apply(x2d, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps,
-                         ACT[act], mul, pre_bias, partials, interleave_n)
+        return y * mul if mul is not None else y
+    return BNActCL.apply(x2d, bn.weight, bn.bias, st, ACT[act], mul, pre_bias, partials, interleave_n)
 
 
 def interleave_rows(y2d, n):
@@ -945,18 +971,17 @@ class BNSoftmaxSlotsPermute(Function):
     activated logits never exist in HBM.  Backward: softmax adjoint, then the BatchNorm+act adjoint on x."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, act, k, pre_bias=None):
+    def forward(ctx, x, gamma, beta, st, act, k, pre_bias=None):
         rows, C = x.shape
         m = rows // k
         x = x.contiguous()
         L = _lib.lib()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        stats = _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps)
+        stats = _bn_stats(L, x, rows, C, *_params(gamma, beta, pre_bias), st)
         ctx.has_pre_bias = pre_bias is not None
         w = torch.empty((m, k // 2, 2 * C), dtype=F32, device=x.device)
         check(L.pdgn_bn_softmax_slots_permute(m, k, C, act, ptr(x), ptr(stats), ptr(w), stream_of(x)), "pdgn_bn_softmax_slots_permute")
         ctx.save_for_backward(x, stats, w)
-        ctx.cfg = (rows, C, act, bool(training), k)
+        ctx.cfg = (rows, C, act, st.training, k)
         return w
 
     @staticmethod
@@ -967,14 +992,9 @@ class BNSoftmaxSlotsPermute(Function):
         dw = dw.contiguous()
         dh = torch.empty((rows, C), dtype=F32, device=x.device)
         check(L.pdgn_softmax_slots_permute_backward(rows // k, k, C, ptr(w), ptr(dw), ptr(dh), stream_of(w)), "pdgn_softmax_slots_permute_backward")
-        scratch = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
-        bs = torch.empty(2 * C, dtype=F32, device=x.device)
-        dx = torch.empty_like(x)
-        check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dh), ptr(None),
-                                     ptr(stats), ptr(scratch), ptr(bs), ptr(dx), ptr(None), 0, stream_of(x)), "pdgn_bn_act_backward")
-        if training:
-            mark_zero_colsum(dx)
-        return dx, bs[C:], bs[:C], None, None, None, None, None, None, None, _pre_bias_grad(ctx.has_pre_bias, C, x.device)
+        dx, dg, db, _ = _bn_act_adjoint(L, x, dh, stats, act, training, rows, C)
+        # x, gamma, beta, st, act, k, pre_bias
+        return dx, dg, db, None, None, None, _pre_bias_grad(ctx.has_pre_bias, C, x.device)
 
 
 def bn_softmax_slots_permute(x2d, bn, training, k, act="leaky_relu", pre_bias=None):
@@ -982,10 +1002,8 @@ def bn_softmax_slots_permute(x2d, bn, training, k, act="leaky_relu", pre_bias=No
     x2d, pre_bias = _fold_pre_bias(x2d, pre_bias, training)
     if x2d.shape[1] % 4:
         return softmax_slots_permute(bn_act(x2d, bn, training, act=act, pre_bias=pre_bias).view(-1, k, x2d.shape[1]))
-    if training and bn.track_running_stats:
-        _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
-    return BNSoftmaxSlotsPermute.apply(x2d, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum,
-                                       bn.eps, ACT[act], k, pre_bias)
+    _tick(bn, training)
+    return BNSoftmaxSlotsPermute.apply(x2d, bn.weight, bn.bias, bn_state(bn, training), ACT[act], k, pre_bias)
 
 
 class BilateralWeighting(Function):
@@ -995,16 +1013,14 @@ class BilateralWeighting(Function):
     the softmax weights w are recomputed from x by the fused adjoint (k = 4, 10) and never reach HBM."""
 
     @staticmethod
-    def forward(ctx, x, u, gx, bx, rmx, rvx, pbx, gu, bu, rmu, rvu, pbu, training, momentum_x, eps_x, momentum_u, eps_u,
-                act, k, partials_u=None, partials_x=None, want_max=False):
+    def forward(ctx, x, u, gx, bx, pbx, st_x, gu, bu, pbu, st_u, act, k, partials_u=None, partials_x=None, want_max=False):
         rows, C = x.shape
         m = rows // k
         x, u = x.contiguous(), u.contiguous()
         L = _lib.lib()
-        stats_x = _bn_stats(L, x, rows, C, gx.detach().contiguous(), bx.detach().contiguous(), pbx, rmx, rvx, training,
-                            momentum_x, eps_x, partials_x)
-        stats_u = _bn_stats(L, u, u.shape[0], 2 * C, gu.detach().contiguous(), bu.detach().contiguous(), pbu, rmu, rvu,
-                            training, momentum_u, eps_u, partials_u)
+        stats_x = _bn_stats(L, x, rows, C, *_params(gx, bx, pbx), st_x, partials_x)
+        g_u, b_u, pb_u = _params(gu, bu, pbu)
+        stats_u = _bn_stats(L, u, u.shape[0], 2 * C, g_u, b_u, pb_u, st_u, partials_u)
         # the fused adjoint (k = 4, 10) recomputes w from x; only the generic chain of separate adjoint kernels reads it back
         need_w = any(ctx.needs_input_grad) and k not in (4, 10)
         w = torch.empty((m, k // 2, 2 * C), dtype=F32, device=x.device) if need_w else None
@@ -1019,17 +1035,16 @@ class BilateralWeighting(Function):
         # accumulation's (gemm_x3.hip).  Measured against the alternatives: a scan of y is 176 us at stage 4, exact maxima from
         # this kernel (threads walking several points) made it 130 us slower per launch.
         # (the bound is written by the same launch: computed with tensor expressions it was four launches per block and pass on the
-        # issuing stream)
-        ycmax, g_u, b_u, bound = None, None, None, 0.0
-        if want_max and training and any(ctx.needs_input_grad):
+        # issuing stream; it reads gamma and beta only then)
+        ycmax, bound = None, 0.0
+        if want_max and st_u.training and any(ctx.needs_input_grad):
             ycmax = torch.empty((k // 2 * 2 * C,), dtype=torch.int32, device=x.device)
-            g_u, b_u = gu.detach().contiguous(), bu.detach().contiguous()
             bound = max(float(u.shape[0]) - 1.0, 1.0) ** 0.5
         check(L.pdgn_bn_softmax_slots_permute_mul(m, k, C, act, ptr(x), ptr(stats_x), act, ptr(u),
                                                   ptr(stats_u), ptr(w), ptr(y), ptr(ymax), ptr(g_u), ptr(b_u), bound, ptr(ycmax), stream_of(x)),
               "pdgn_bn_softmax_slots_permute_mul")
         ctx.save_for_backward(x, u, w, stats_x, stats_u)
-        ctx.cfg = (rows, C, act, bool(training), k, pbx is not None, pbu is not None)
+        ctx.cfg = (rows, C, act, st_x.training, k, pbx is not None, pbu is not None)       # (the wrapper: st_u.training is the same)
         if want_max:
             ctx.mark_non_differentiable(ymax)
             if ycmax is not None:
@@ -1054,27 +1069,20 @@ class BilateralWeighting(Function):
             check(L.pdgn_bilateral_weighting_backward(rows // k, k, C, act, int(training), ptr(x),
                                                       ptr(stats_x), ptr(u), ptr(stats_u), ptr(w), ptr(dy), ptr(scr), ptr(bsx),
                                                       ptr(bsu), ptr(dx), ptr(du), stream_of(x)), "pdgn_bilateral_weighting_backward")
+            if training:
+                mark_zero_colsum(du)
+                mark_zero_colsum(dx)
+            dgx, dbx, dgu, dbu = bsx[C:], bsx[:C], bsu[Cu:], bsu[:Cu]
         else:
             # y = act(BN(u)) * w: adjoint wrt u, the BatchNorm parameters and w
-            scr = torch.empty(_scratch_floats(L, rows_u, Cu), dtype=F32, device=x.device)
-            bsu = torch.empty(2 * Cu, dtype=F32, device=x.device)
-            du, dw = torch.empty_like(u), torch.empty_like(u)
-            check(L.pdgn_bn_act_backward(rows_u, Cu, act, int(training), ptr(u), ptr(dy), ptr(w),
-                                         ptr(stats_u), ptr(scr), ptr(bsu), ptr(du), ptr(dw), 0, stream_of(x)), "pdgn_bn_act_backward")
+            du, dgu, dbu, dw = _bn_act_adjoint(L, u, dy, stats_u, act, training, rows_u, Cu, w, True)
             # w = softmax_slots_permute(act(BN(x)))
             dh = torch.empty((rows, C), dtype=F32, device=x.device)
             check(L.pdgn_softmax_slots_permute_backward(rows // k, k, C, ptr(w), ptr(dw), ptr(dh),
                                                         stream_of(x)), "pdgn_softmax_slots_permute_backward")
-            scr = torch.empty(_scratch_floats(L, rows, C), dtype=F32, device=x.device)
-            bsx = torch.empty(2 * C, dtype=F32, device=x.device)
-            dx = torch.empty_like(x)
-            check(L.pdgn_bn_act_backward(rows, C, act, int(training), ptr(x), ptr(dh), ptr(None),
-                                         ptr(stats_x), ptr(scr), ptr(bsx), ptr(dx), ptr(None), 0, stream_of(x)), "pdgn_bn_act_backward")
-        if training:
-            mark_zero_colsum(du)
-            mark_zero_colsum(dx)
-        return (dx, du, bsx[C:], bsx[:C], None, None, _pre_bias_grad(has_pbx, C, x.device), bsu[Cu:], bsu[:Cu], None, None,
-                _pre_bias_grad(has_pbu, Cu, x.device), None, None, None, None, None, None, None, None, None, None)
+            dx, dgx, dbx, _ = _bn_act_adjoint(L, x, dh, stats_x, act, training, rows, C)
+        # x, u, gx, bx, pbx, st_x, gu, bu, pbu, st_u, act, k, partials_u, partials_x, want_max
+        return (dx, du, dgx, dbx, _pre_bias_grad(has_pbx, C, x.device), None, dgu, dbu, _pre_bias_grad(has_pbu, Cu, x.device)) + (None,) * 6
 
 
 def bilateral_weighting(x2d, bn_x, u2d, bn_u, training, k, act="leaky_relu", pre_bias_x=None, pre_bias_u=None,
@@ -1085,17 +1093,15 @@ def bilateral_weighting(x2d, bn_x, u2d, bn_u, training, k, act="leaky_relu", pre
     scales y row by row, its weight gradient column by column); either is None when this path did not produce it."""
     x2d, pre_bias_x = _fold_pre_bias(x2d, pre_bias_x, training)
     u2d, pre_bias_u = _fold_pre_bias(u2d, pre_bias_u, training)
-    if x2d.shape[1] % 4 or k > 16:           # (the fused adjoint holds all k slots of a channel pair in registers: k <= 16)
+    st_x, st_u = bn_state(bn_x, training), bn_state(bn_u, training)
+    if x2d.shape[1] % 4 or k > 16 or st_x.training != st_u.training:   # (the fused adjoint: k slots in registers, one kind of statistics)
         w = bn_softmax_slots_permute(x2d, bn_x, training, k, act=act, pre_bias=pre_bias_x)
         y = bn_act(u2d, bn_u, training, act=act, mul=w.view(u2d.shape), pre_bias=pre_bias_u, partials=partials_u)
         return (y, None, None) if want_max else y
-    if training:
-        for bn in (bn_x, bn_u):
-            if bn.track_running_stats:
-                _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
-    return BilateralWeighting.apply(x2d, u2d, bn_x.weight, bn_x.bias, bn_x.running_mean, bn_x.running_var, pre_bias_x,
-                                    bn_u.weight, bn_u.bias, bn_u.running_mean, bn_u.running_var, pre_bias_u, training,
-                                    bn_x.momentum, bn_x.eps, bn_u.momentum, bn_u.eps, ACT[act], k, partials_u, partials_x, want_max)
+    _tick(bn_x, training)
+    _tick(bn_u, training)
+    return BilateralWeighting.apply(x2d, u2d, bn_x.weight, bn_x.bias, pre_bias_x, st_x, bn_u.weight, bn_u.bias, pre_bias_u, st_u,
+                                    ACT[act], k, partials_u, partials_x, want_max)
 
 
 class SmallLinearBNAct(Function):
@@ -1103,18 +1109,18 @@ class SmallLinearBNAct(Function):
     (+ one small GEMM for dx): the generator's per-sample layers (csrc/small_mlp.hip)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, bn_mode, momentum, eps, act):
+    def forward(ctx, x, weight, bias, gamma, beta, st, act):
         x, weight = x.contiguous(), weight.contiguous()
         R, K = x.shape
         N = weight.shape[0]
         dev = x.device
         need = any(ctx.needs_input_grad)
+        running_mean, running_var, training, momentum, eps = st if st is not None else (None, None, False, 0.0, 0.0)
+        bn_mode = 0 if st is None else (1 if training else 2)      # no BatchNorm / batch statistics / the running ones
         y = torch.empty((R, N), dtype=F32, device=dev)
         pre = torch.empty((R, N), dtype=F32, device=dev) if need else None
         stat = torch.empty(2 * N, dtype=F32, device=dev) if (need and bn_mode) else None
-        g = gamma.detach().contiguous() if gamma is not None else None
-        b = beta.detach().contiguous() if beta is not None else None
-        bi = bias.detach().contiguous() if bias is not None else None
+        g, b, bi = _params(gamma, beta, bias)
         check(_lib.lib().pdgn_small_mlp_forward(R, K, N, act, bn_mode, eps, momentum, ptr(x),
                                                 ptr(weight), ptr(bi), ptr(g), ptr(b), ptr(running_mean), ptr(running_var),
                                                 ptr(y), ptr(pre), ptr(stat), stream_of(x)), "pdgn_small_mlp_forward")
@@ -1132,9 +1138,9 @@ class SmallLinearBNAct(Function):
             # frozen Linear (+ activation), no BatchNorm (bn_mode, not gamma: affine=False normalises too): only the input gradient
             # is wanted -- one launch (no dpre, no second product)
             if not ctx.needs_input_grad[0]:
-                return (None,) * 11
+                return (None,) * 7
             dx = skinny_nn_masked(dy, pre, act, weight) if act else dy.matmul(weight)
-            return (dx,) + (None,) * 10
+            return (dx,) + (None,) * 6
         dpre = torch.empty((R, N), dtype=F32, device=dev)
         dW = torch.empty((N, K), dtype=F32, device=dev) if ctx.needs_input_grad[1] else None
         dbias = torch.empty(N, dtype=F32, device=dev) if has_bias and ctx.needs_input_grad[2] else None
@@ -1144,7 +1150,7 @@ class SmallLinearBNAct(Function):
                                                  ptr(dpre), ptr(dg), ptr(db), ptr(dbias), ptr(dW), stream_of(dy)),
               "pdgn_small_mlp_backward")
         dx = skinny_nn(dpre, weight) if ctx.needs_input_grad[0] else None
-        return dx, dW, dbias, dg, db, None, None, None, None, None, None
+        return dx, dW, dbias, dg, db, None, None                 # x, weight, bias, gamma, beta, st, act
 
 
 class SkinnyLinearAct(Function):
@@ -1221,17 +1227,12 @@ def small_sequential(seq, x, training):
             act = 1
             i += 1
         if bn is not None:
-            use_batch = training or not bn.track_running_stats
-            if training and bn.track_running_stats:
-                _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
-            x = SmallLinearBNAct.apply(x, lin.weight, lin.bias, bn.weight, bn.bias,
-                                       bn.running_mean if bn.track_running_stats else None,
-                                       bn.running_var if bn.track_running_stats else None, 1 if use_batch else 2,
-                                       bn.momentum, bn.eps, act)
+            _tick(bn, training)
+            x = SmallLinearBNAct.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, bn_state(bn, training), act)
         elif _SKINNY_HEAD and _sk_ok(x, lin.weight) and lin.in_features % 4 == 0:
             x = SkinnyLinearAct.apply(x, lin.weight, lin.bias, act)
         else:
-            x = SmallLinearBNAct.apply(x, lin.weight, lin.bias, None, None, None, None, 0, 0.0, 0.0, act)
+            x = SmallLinearBNAct.apply(x, lin.weight, lin.bias, None, None, None, act)
     return x
 
 
@@ -1241,33 +1242,31 @@ class BNActMaxPool(Function):
     tensor; the backward is one streaming pass."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, act, B, N, pre_bias=None,
-                partials=None, dense=None):
+    def forward(ctx, x, gamma, beta, st, act, B, N, pre_bias=None, partials=None, dense=None):
         x = x.contiguous()
         rows, C = x.shape
         dev = x.device
         L = _lib.lib()
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        g, b, pb = _params(gamma, beta, pre_bias)
         ctx.has_pre_bias = pre_bias is not None
         ymax = torch.empty((B, C), dtype=F32, device=dev)
         yarg = torch.empty((B, C), dtype=torch.int32, device=dev)
-        if training and partials is None and _STATS_MAX:
+        if st.training and partials is None and _STATS_MAX:
             # no statistics from the producer: ONE pass over x for the statistics and the extremes (the sign of the scale picks later)
             stats = torch.empty(4 * C, dtype=F32, device=dev)
-            pb = pre_bias.detach().contiguous() if pre_bias is not None else None
             scr = torch.empty(L.pdgn_bn_stats_maxpool_scratch_floats(B, C), dtype=F32, device=dev)
-            check(L.pdgn_bn_stats_act_maxpool(B, N, C, act, eps, momentum, ptr(x), ptr(g), ptr(b), ptr(pb),
-                                              ptr(running_mean), ptr(running_var), ptr(scr), ptr(stats), ptr(ymax), ptr(yarg),
+            check(L.pdgn_bn_stats_act_maxpool(B, N, C, act, st.eps, st.momentum, ptr(x), ptr(g), ptr(b), ptr(pb),
+                                              ptr(st.running_mean), ptr(st.running_var), ptr(scr), ptr(stats), ptr(ymax), ptr(yarg),
                                               stream_of(x)), "pdgn_bn_stats_act_maxpool")
         else:
-            stats = _bn_stats(L, x, rows, C, g, b, pre_bias, running_mean, running_var, training, momentum, eps, partials)
+            stats = _bn_stats(L, x, rows, C, g, b, pb, st, partials)
             scr = torch.empty(L.pdgn_bn_maxpool_scratch_floats(B, C), dtype=F32, device=dev)
             check(L.pdgn_bn_act_maxpool(B, N, C, act, ptr(x), ptr(stats), ptr(scr), ptr(ymax), ptr(yarg), stream_of(x)),
                   "pdgn_bn_act_maxpool")
         ctx.save_for_backward(x, stats, yarg)
-        ctx.cfg = (B, N, C, act, bool(training))
+        ctx.cfg = (B, N, C, act, st.training)
         # dense layer in front known: the backward goes straight to that layer's input (and weight) gradient
-        ctx.dense = dense if (dense is not None and _CLOSED_TAIL and training
+        ctx.dense = dense if (dense is not None and _CLOSED_TAIL and st.training
                               and not (pre_bias is not None and pre_bias.requires_grad and not _CLOSED_DW)
                               and _dense_input_ok(dense, x, rows, C, N)) else None
         return ymax
@@ -1290,7 +1289,8 @@ class BNActMaxPool(Function):
                                                    ptr(w), w.stride(0), ptr(scr), ptr(dh), ptr(dw), K, ptr(bs), stream_of(x)),
                   "pdgn_dense_bn_maxpool_backward")
             tok = _placeholder_with_input_grad(B * N, C, dh, dw, x.device)
-            return (tok, bs[C:] if want_bn else None, bs[:C] if want_bn else None, None, None, None, None, None, None, None, None,
+            # x, gamma, beta, st, act, B, N, pre_bias, partials, dense
+            return (tok, bs[C:] if want_bn else None, bs[:C] if want_bn else None, None, None, None, None,
                     _pre_bias_grad(ctx.has_pre_bias, C, x.device), None, None)
         scr = torch.empty(B * C + 2 * C, dtype=F32, device=x.device)
         bs = torch.empty(2 * C, dtype=F32, device=x.device)
@@ -1300,8 +1300,8 @@ class BNActMaxPool(Function):
               "pdgn_bn_act_maxpool_backward")
         if training:
             mark_zero_colsum(dx)
-        return (dx, bs[C:], bs[:C], None, None, None, None, None, None, None, None,
-                _pre_bias_grad(ctx.has_pre_bias, C, x.device), None, None)
+        # x, gamma, beta, st, act, B, N, pre_bias, partials, dense
+        return dx, bs[C:], bs[:C], None, None, None, None, _pre_bias_grad(ctx.has_pre_bias, C, x.device), None, None
 
 
 def _is_plain_linear_output(y2d, dense):
@@ -1333,10 +1333,8 @@ def bn_act_maxpool(x2d, bn, training, B, N, act="leaky_relu", pre_bias=None, par
         dense = None                         # the closed tail needs x2d to BE h W^T: the unmodified output of that LinearCL
     if x2d.shape[1] % 4:
         return bn_act(x2d, bn, training, act=act, pre_bias=pre_bias).view(B, N, -1).max(dim=1)[0]
-    if training and bn.track_running_stats:
-        _PENDING_COUNTS[bn.num_batches_tracked] = _PENDING_COUNTS.get(bn.num_batches_tracked, 0) + 1
-    return BNActMaxPool.apply(x2d, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps,
-                              ACT[act], B, N, pre_bias, partials, dense)
+    _tick(bn, training)
+    return BNActMaxPool.apply(x2d, bn.weight, bn.bias, bn_state(bn, training), ACT[act], B, N, pre_bias, partials, dense)
 
 
 class PointMax(Function):
