@@ -32,20 +32,6 @@ __device__ __forceinline__ void wave_sort_di(float &d, int &i, int lane) {
     }
 }
 
-// Wave-wide bitonic sort (ascending) of one float per lane.
-__device__ __forceinline__ float wave_sort_f(float d, int lane) {
-#pragma unroll
-    for (int k2 = 2; k2 <= 64; k2 <<= 1) {
-#pragma unroll
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            float pd = __shfl_xor(d, j, 64);
-            bool keep_min = ((lane & j) == 0) == ((lane & k2) == 0);
-            d = keep_min ? fminf(d, pd) : fmaxf(d, pd);
-        }
-    }
-    return d;
-}
-
 // Merge the queued survivors q[0..cnt) into the running best-K (lanes 0..K-1 hold it, sorted).
 __device__ __forceinline__ void knn_flush(const DI *q, int cnt, int K, float &rd, int &ri, int lane) {
     const int take = 64 - K;
@@ -67,45 +53,9 @@ __device__ __forceinline__ void knn_flush(const DI *q, int cnt, int K, float &rd
     __builtin_amdgcn_wave_barrier();
 }
 
-
-#define WSEL_QCAP 256   // survivor queue entries per wave
-
-__device__ __forceinline__ float wave_kth_smallest(float v, int K);
-
-// One wave scans `tn` candidates (candidate c has distance dist(c), c in [0, tn), global index
-// t0 + c) and merges the K best into the running list (rd, ri) held by lanes 0..K-1.
-//   pass A: per-lane minimum; tau = K-th smallest lane minimum (>= the K-th nearest distance);
-//   pass B: survivors d <= tau are compacted into the wave's LDS queue `q` and merged.
-// +inf distances never enter (the reference's `d2 < best` against 1e40 never accepts them).
-template <class DistFn>
-__device__ __forceinline__ void wave_topk_scan(DistFn dist, int tn, int t0, DI *q, int K, float &rd,
-                                               int &ri, int lane) {
-    float lmin = INFINITY;
-    for (int c = lane; c < tn; c += 64) lmin = fminf(lmin, dist(c));
-    float tau = fminf(wave_kth_smallest(lmin, K), __shfl(rd, K - 1, 64));   // ballot bisection, no LDS
-    int cnt = 0;                                    // wave-uniform
-    for (int c0 = 0; c0 < tn; c0 += 64) {
-        int c = c0 + lane;
-        float d = c < tn ? dist(c) : INFINITY;
-        bool keep = d <= tau && d < INFINITY;
-        unsigned long long mask = __ballot(keep);
-        if (mask) {
-            int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            if (keep) { q[pos].d = d; q[pos].i = t0 + c; }
-            cnt += __popcll(mask);
-            if (cnt > WSEL_QCAP - 64) {
-                knn_flush(q, cnt, K, rd, ri, lane);
-                cnt = 0;
-                tau = fminf(tau, __shfl(rd, K - 1, 64));
-            }
-        }
-    }
-    knn_flush(q, cnt, K, rd, ri, lane);
-}
-
 // K-th smallest (1-based) of the 64 lane values, exact, by bisection on the order-preserving
 // integer image of the floats: 32 ballot/popcount steps on scalar registers, no LDS traffic
-// (the bitonic wave_sort_f costs 21 dependent ds_bpermute round trips).
+// (a bitonic sort of the lane values costs 21 dependent ds_bpermute round trips).
 __device__ __forceinline__ float wave_kth_smallest(float v, int K) {
     const unsigned bits = __float_as_uint(v);
     const unsigned key = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
@@ -120,26 +70,13 @@ __device__ __forceinline__ float wave_kth_smallest(float v, int K) {
     return __uint_as_float(b);
 }
 
-// Upper bound of the K-th smallest lane value: the bisection stops after the top 16 bits of the order-preserving
-// image and rounds the rest up (within 0.8 % of the exact value for the distances selected here -- as good a filter
-// threshold as the exact one at half the dependent steps).  Any sign; never past +inf.
-__device__ __forceinline__ float wave_kth_smallest_ub16_any(float v, int K) {
-    const unsigned bits = __float_as_uint(v);
-    const unsigned key = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
-    unsigned prefix = 0;
-#pragma unroll
-    for (int bit = 31; bit >= 16; --bit) {
-        const unsigned cand = prefix | (1u << bit);
-        const int below = __popcll(__ballot(key < cand));
-        prefix = below < K ? cand : prefix;
-    }
-    const unsigned ub = min(prefix | 0xffffu, 0xff800000u);
-    return __uint_as_float((ub & 0x80000000u) ? (ub ^ 0x80000000u) : ~ub);
-}
-
-// Variant of wave_topk_scan with a per-query survivor queue that persists across candidate
-// chunks: survivors are only appended here (threshold from this chunk's lane minima and the
-// running list); the (distance, index) sort runs when the queue is half full or at the end.
+// One wave scans `tn` candidates (candidate c has distance dist(c), c in [0, tn), global index
+// t0 + c) into a per-query survivor queue that persists across candidate chunks:
+//   pass A: per-lane minimum; tau = K-th smallest lane minimum (>= the K-th nearest distance),
+//           capped by the running list's K-th (rd, ri: lanes 0..K-1, sorted);
+//   pass B: survivors d <= tau are compacted into the LDS queue `q`.
+// Survivors are only appended here; the (distance, index) sort (knn_flush) runs when the queue is
+// half full or, by the caller, at the end.  +inf distances never enter.
 #define WSEL_PQCAP 128
 template <class DistFn>
 __device__ __forceinline__ void wave_topk_append(DistFn dist, int tn, int t0, DI *q, int &cnt, int K,
@@ -165,38 +102,14 @@ __device__ __forceinline__ void wave_topk_append(DistFn dist, int tn, int t0, DI
     }
 }
 
-// As wave_topk_append, for a queue of `cap` >= 64 entries: the queue is merged into the running list
-// only when the next 64-candidate step would not fit (wave-uniform test on the exact count).
-template <class DistFn>
-__device__ __forceinline__ void wave_topk_append_cap(DistFn dist, int tn, int t0, DI *q, int &cnt, int cap, int K,
-                                                     float &rd, int &ri, int lane) {
-    float lmin = INFINITY;
-    for (int c = lane; c < tn; c += 64) lmin = fminf(lmin, dist(c));
-    float tau = fminf(wave_kth_smallest_ub16_any(lmin, K), __shfl(rd, K - 1, 64));
-    for (int c0 = 0; c0 < tn; c0 += 64) {
-        int c = c0 + lane;
-        float d = c < tn ? dist(c) : INFINITY;
-        bool keep = d <= tau && d < INFINITY;
-        unsigned long long mask = __ballot(keep);
-        if (mask) {
-            const int add = __popcll(mask);
-            if (cnt + add > cap) {
-                knn_flush(q, cnt, K, rd, ri, lane);
-                cnt = 0;
-                tau = fminf(tau, __shfl(rd, K - 1, 64));
-                keep = keep && d <= tau;                      // tightened threshold: re-filter this step
-                mask = __ballot(keep);
-            }
-            int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-            if (keep) { q[pos].d = d; q[pos].i = t0 + c; }
-            cnt += __popcll(mask);
-        }
-    }
-}
-
-// wave_topk_append_cap for Q queries at once (rows[t] = LDS row of query t, tn a multiple of 64): the LDS reads, the
-// threshold bisections and the ballots of the Q queries are independent chains the hardware overlaps -- one query at a
-// time the pass is a sequence of exposed LDS / VALU->SALU latencies.  `flush(t)` merges query t's full queue into its
+// wave_topk_append for Q queries at once and queues of `cap` >= 64 entries (rows[t] = LDS row of query t, tn a multiple of
+// 64).  Differences to the single-query form: the threshold is the 16-bit UPPER BOUND of the K-th smallest lane minimum (the
+// bisection stops after the top 16 bits of the order-preserving image and rounds the rest up: within 0.8 % of the exact
+// value, as good a filter at half the dependent steps; any sign, never past +inf), and a queue is merged into its running
+// list only when the next 64-candidate step would not fit (wave-uniform test on the exact count), the step then being
+// re-filtered with the tightened threshold.  The LDS reads, the threshold bisections and the ballots of the Q queries are
+// independent chains the hardware overlaps -- one query at a time the pass is a sequence of exposed LDS / VALU->SALU
+// latencies.  `flush(t)` merges query t's full queue into its
 // running list (rd[t], ri[t]) and empties it.  Bit t of `active` clear: slot t has no query (its row pointer must still
 // be readable); nothing is queued for it.
 template <int Q, class FlushFn>
@@ -340,75 +253,20 @@ __device__ __forceinline__ void knn_flush_ranked(DI *q, int cnt, int K, float &r
     __builtin_amdgcn_wave_barrier();
 }
 
-// Final merge by selection instead of ranking everything: fp32 MFMA and the vector ALU share a SIMD's issue slots on
-// gfx950 (the matrix path IS the vector rate), so next to a Gram producer every VALU instruction of the selection waves is
-// time taken from the matrix pipe -- knn_flush_ranked spends ~4 VALU instructions per (entry, entry) pair of the queue.
-// Here the exact K-th smallest distance is bisected over the (<= 128) queued entries by ballots (2 compares per bit, the
-// counting is scalar), the entries up to it -- K of them unless distances tie at the threshold -- are compacted into
-// `win`, and only those are ranked in the (distance, index) order.  More than 32 entries at or below the K-th distance
-// (mass ties) or more than 128 queued entries: the ranked merge does it.
-__device__ __forceinline__ void knn_flush_select(DI *q, int cnt, int K, float &rd, int &ri, int lane, DI *win) {
-    __builtin_amdgcn_wave_barrier();
-    const bool have = lane < K && rd < INFINITY;
-    const unsigned long long hm = __ballot(have);
-    const int total = cnt + __popcll(hm);
-    if (total > 128) {
-        knn_flush_ranked(q, cnt, K, rd, ri, lane, win);
-        return;
-    }
-    if (have) {
-        const int pos = cnt + __popcll(hm & ((1ull << lane) - 1ull));
-        q[pos].d = rd; q[pos].i = ri;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const bool ok0 = lane < total, ok1 = lane + 64 < total;
-    const float d0 = ok0 ? q[lane].d : INFINITY, d1 = ok1 ? q[lane + 64].d : INFINITY;
-    const int i0 = ok0 ? q[lane].i : 0x7fffffff, i1 = ok1 ? q[lane + 64].i : 0x7fffffff;
-    const unsigned b0 = __float_as_uint(d0), b1 = __float_as_uint(d1);
-    const unsigned k0 = b0 ^ ((b0 >> 31) ? 0xffffffffu : 0x80000000u), k1 = b1 ^ ((b1 >> 31) ? 0xffffffffu : 0x80000000u);
-    unsigned prefix = 0;
-#pragma unroll
-    for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = prefix | (1u << bit);
-        const int below = __popcll(__ballot(k0 < cand)) + __popcll(__ballot(k1 < cand));
-        prefix = below < K ? cand : prefix;
-    }
-    // prefix = key of the K-th smallest distance (of +inf when fewer than K entries are finite)
-    const bool in0 = k0 <= prefix && d0 < INFINITY, in1 = k1 <= prefix && d1 < INFINITY;
-    const unsigned long long m0 = __ballot(in0), m1 = __ballot(in1);
-    const int n0 = __popcll(m0), m = n0 + __popcll(m1);
-    if (m > 32) {                                   // wave-uniform: mass ties at the threshold
-        knn_flush_ranked(q, total, K, rd = INFINITY, ri = 0x7fffffff, lane, win);
-        return;
-    }
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    if (in0) { const int p = __popcll(m0 & lt); win[p].d = d0; win[p].i = i0; }
-    if (in1) { const int p = n0 + __popcll(m1 & lt); win[p].d = d1; win[p].i = i1; }
-    __builtin_amdgcn_wave_barrier();
-    int r0 = 0, r1 = 0;
-    for (int j = 0; j < m; ++j) {
-        const float dj = win[j].d;
-        const int ij = win[j].i;
-        r0 += (dj < d0 || (dj == d0 && ij < i0)) ? 1 : 0;
-        r1 += (dj < d1 || (dj == d1 && ij < i1)) ? 1 : 0;
-    }
-    __builtin_amdgcn_wave_barrier();                // every lane has read win before q (its alias in some callers) is rewritten
-    if (in0 && r0 < K) { q[r0].d = d0; q[r0].i = i0; }
-    if (in1 && r1 < K) { q[r1].d = d1; q[r1].i = i1; }
-    __builtin_amdgcn_wave_barrier();
-    const bool out = lane < K && lane < m;
-    rd = out ? q[lane].d : INFINITY;
-    ri = out ? q[lane].i : 0x7fffffff;
-    __builtin_amdgcn_wave_barrier();
-}
-
-// knn_flush_select for Q queries at once: the same steps with the Q dependency chains (LDS round trips, VALU -> SALU ->
-// VALU bisection steps) interleaved stage by stage; queries that need the general path (see above) are finished one by
-// one afterwards.  Differences to the single-query form, all for fewer dependent steps: the threshold is the 16-bit upper
-// bound of the K-th smallest distance (a few entries more than K pass it; the ranking sorts that out exactly), and the
-// compacted survivors are read back one per lane so that the ranking loop broadcasts them with v_readlane instead of LDS
-// reads.  The entries are in registers before anything is overwritten, so the compaction reuses the head of each queue;
-// `scratch` (32 entries) only serves the general path.
+// Final merge of Q queries at once by selection instead of ranking everything: fp32 MFMA and the vector ALU share a SIMD's
+// issue slots on gfx950 (the matrix path IS the vector rate), so next to a Gram producer every VALU instruction of the
+// selection waves is time taken from the matrix pipe -- knn_flush_ranked spends ~4 VALU instructions per (entry, entry)
+// pair of the queue.  Here the running list joins the queue, the 16-bit upper bound of the K-th smallest distance is
+// bisected over the queued entries by ballots (2 compares per bit, the counting is scalar; the Q dependency chains -- LDS
+// round trips, VALU -> SALU -> VALU bisection steps -- interleaved stage by stage), the entries up to it -- K and a few
+// more; the ranking sorts that out exactly -- are compacted and read back one per lane, so that the ranking loop broadcasts
+// them with v_readlane instead of LDS reads, and only those are ranked in the (distance, index) order.  The entries are in
+// registers before anything is overwritten, so the compaction reuses the head of each queue.  A query with more than 32
+// entries at or below the threshold (mass ties, or K = 32 with anything else inside the 16-bit bound) is finished
+// afterwards, one by one, by knn_flush_ranked on its untouched queue; `scratch` (32 entries) only serves that path.
+// Both callers (feat_knn.hip, knn3.hip) merge in-scan at 64 queued entries and keep at most 32 in the list, so `total` never
+// exceeds 96 here (tests/knn_cases.py models it): the "more than 128 queued entries" branch, which two entries per lane
+// cannot hold, is a guard no caller reaches.
 template <int Q>
 __device__ __forceinline__ void knn_flush_select_multi(DI *const (&q)[Q], int (&cnt)[Q], int K, float (&rd)[Q], int (&ri)[Q],
                                                        int lane, DI *scratch) {
