@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 42
+#define PDGN_ABI_VERSION 43
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1156,6 +1156,20 @@ int pdgn_augment_tick_ada(unsigned long long *clock, pdgn_ada_state *state, int3
 long long pdgn_render_workspace_bytes(int rows, int cols, int cell);
 int pdgn_render_sheet(int rows, int cols, const float *const *clouds, const int *npoints, int channel_major, const float *view,
                       int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
+/* pdgn_render_sheet_lit: the same sheet, shaded by surface normals where a column has them.  Every argument of
+ * pdgn_render_sheet means what it means there; two more:
+ *   normals  HOST array of `cols` device pointers: normals[c] is (rows, npoints[c], 3) fp32, POINT-major whatever cloud c's layout is
+ *            (what pdgn_estimate_normals writes), or NULL
+ *   light    HOST, 3 floats: the direction of the light, unit length is the caller's to guarantee
+ * A column whose entry is NULL is shaded exactly as pdgn_render_sheet shades it, byte for byte.  A column with normals gets two-sided
+ * headlight shading:  c = |(nx lx + ny ly) + nz lz|, every operation rounded on its own; c = 0 where !(c >= 0) (a NaN normal: the darkest
+ * shade); c = 1 where c > 1; shade = 48 + (uint32)(207 c), truncating: 48 (edge on) .. 255 (facing the light).  key = q << 8 | shade under
+ * the same integer minimum and the same resolve, so the nearest point still wins the pixel and the image stays bitwise repeatable; being
+ * two-sided, the shading needs no consistently oriented normals.  Three launches on `stream` (pdgn_render_sheet's clear and resolve
+ * kernels, a splat kernel of its own).  PDGN_ERR_INVALID: whatever pdgn_render_sheet refuses, a null `normals` array or `light`, a
+ * normals[c] that is not 4-byte aligned; all checked before anything is launched. */
+int pdgn_render_sheet_lit(int rows, int cols, const float *const *clouds, const float *const *normals, const int *npoints, int channel_major,
+                          const float *view, const float *light, int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ exact EMD (csrc/auction.hip)
  * The assignment problem between two clouds of n points each, cost |a_i - b_j| (Euclidean, what pdgn_matchcost sums), solved in
@@ -1242,6 +1256,33 @@ int pdgn_repulsion_chunk(void);
 int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, float coef, float *s, float *loss, float *per_cloud, float *grad,
                    float *nn2, pdgn_stream_t stream);
 int pdgn_repulsion_backward(long long count, const float *grad, const float *g, float *dxyz, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ surface normals (csrc/normals.hip)
+ * Per point, the eigen-decomposition of the covariance of its k neighbours: the normal (the eigenvector of the smallest eigenvalue) and
+ * the three eigenvalues, what the lit preview sheets, evaluation.surface_stats (surface variation, Pauly et al. 2002) and the PLY export
+ * read.  The header block of csrc/normals.hip is the normative statement of the operation order (mean, covariance, PDGN_NORMALS_SWEEPS
+ * cyclic Jacobi sweeps with no convergence test, selection, sign, poison); tests/normals_mirror.py spells it in numpy and the two agree bit
+ * for bit.  No reference counterpart.
+ *   xyz      (b,n,3)
+ *   idx      (b,n,k) int32: for every point k indices into its own cloud, any (repeats allowed); what pdgn_knnquery(b, n, n, k, xyz, xyz)
+ *            writes has the point itself first.  Taken in slot order.
+ *   orient   0: the component of largest magnitude (lowest index on ties) is made non-negative; 1: n . o >= 0 (along the direction o);
+ *            2: n . (o - x_i) >= 0 (towards the position o); 3: n . (x_i - o) >= 0 (away from it).  o = (ox, oy, oz), ignored under 0.
+ *   normals  (b,n,3): V's column of the smallest eigenvalue as the iteration leaves it (unit length to a few ulp, not renormalised)
+ *   eig      (b,n,3) or NULL: lambda0 <= lambda1 <= lambda2 as computed (a tiny negative lambda0 from rounding is not clamped; equal
+ *            values keep the lower column first, so k = 1, or k equal points whose fp32 mean is exact, give the normal (1, 0, 0) and
+ *            three zeros)
+ * A point with an index outside [0, n) -- which is never dereferenced -- or with an eigenvalue that is not finite (a NaN or infinite
+ * coordinate among its neighbours) gets six NaNs; no other point is affected.  Results do not depend on the launch geometry, nor on
+ * whether the launch copies the clouds into LDS first (256-thread workgroups and n <= PDGN_NORMALS_STAGE_MAX_N: tests put n on either side).
+ * One launch on `stream`, no atomics, nothing allocated: 11.1 us for 35 x 2048 points at k = 16 (pdgn_knnquery at that shape: 117 us; profiles/normals_cost.txt).
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1, k outside [1, PDGN_NORMALS_MAX_K], b n beyond 2^28, orient
+ * outside 0 .. 3, a non-finite ox / oy / oz where orient != 0, a null pointer (eig excepted) or one not 4-byte aligned. */
+#define PDGN_NORMALS_MAX_K 64
+#define PDGN_NORMALS_SWEEPS 5
+#define PDGN_NORMALS_STAGE_MAX_N 4096
+int pdgn_estimate_normals(int b, int n, int k, const float *xyz, const int32_t *idx, int orient, float ox, float oy, float oz,
+                          float *normals, float *eig, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

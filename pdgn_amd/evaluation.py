@@ -218,6 +218,30 @@ def spacing_stats(clouds, batch=64):
             "duplicates": int((nn2 == 0).sum())}
 
 
+# ---------------------------------------------------------------------------- surface variation (no reference counterpart)
+@torch.no_grad()
+def surface_stats(clouds, k=16, batch=64):
+    """How thin the sheet is that the points of each cloud lie on: the surface variation sigma_i = max(lambda0, 0) / (lambda0 + lambda1 +
+    lambda2) of every point's k-neighbourhood covariance (Pauly et al. 2002; pointops.estimate_normals' eigenvalues, `batch` clouds per
+    launch): 0 on a plane, up to 1/3 where the neighbourhood has no direction, and what noise ACROSS the surface raises.  clouds (S,N,3),
+    N >= 2, k <= N -> {"sv_mean": the mean over clouds of the per-cloud mean of sigma, "sv_p90": the mean over clouds of the per-cloud
+    90th percentile, "degenerate": the number of points left out of both -- zero trace (all k neighbours equal) or non-finite eigenvalues},
+    Python numbers; a cloud with no point left counts 0 towards both means.  The reductions are fp64 torch ops on the device."""
+    from .pointops import estimate_normals
+    require(clouds, "clouds", F32, 3)
+    S, N, _ = clouds.shape
+    if S < 1 or N < 2 or int(batch) < 1:
+        raise ValueError("surface_stats takes at least one cloud of at least two points and a positive batch, got %s, batch %r" % (tuple(clouds.shape), batch))
+    eig = torch.cat([estimate_normals(clouds[lo:lo + int(batch)], k, return_eig=True)[1] for lo in range(0, S, int(batch))]).double()
+    trace = (eig[..., 0] + eig[..., 1]) + eig[..., 2]
+    live = torch.isfinite(trace) & (trace > 0)
+    sigma = torch.where(live, eig[..., 0].clamp_min(0.0) / torch.where(live, trace, torch.ones_like(trace)), torch.full_like(trace, float("nan")))
+    count = live.sum(dim=1)
+    mean = torch.where(count > 0, torch.nan_to_num(sigma).sum(dim=1) / count.clamp_min(1), torch.zeros_like(trace[:, 0]))
+    p90 = torch.nan_to_num(torch.nanquantile(sigma, 0.9, dim=1))
+    return {"sv_mean": float(mean.mean()), "sv_p90": float(p90.mean()), "degenerate": int((~live).sum())}
+
+
 # ---------------------------------------------------------------------------- JSD (evaluation_metrics.py:206-321)
 def unit_cube_grid_point_cloud(resolution, clip_sphere=False, device="cpu"):
     """Cell centres of a resolution^3 grid over the unit cube (:206-224); clip_sphere keeps |c| <= 0.5."""

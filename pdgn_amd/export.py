@@ -1,0 +1,94 @@
+"""Point clouds out of the project in a form mesh tools read: binary little-endian PLY, with per-point normals where wanted (what Poisson
+reconstruction, MeshLab and Blender take).
+
+    write_ply("chair.ply", xyz, normals)
+    python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient outward
+
+The writer is struct and numpy only, as report.write_png is; only the command line's --normals touches the device (pointops.estimate_normals,
+DESIGN.md section 7q)."""
+import argparse
+import os
+import struct
+import sys
+
+import numpy as np
+
+PLY_PROPERTIES = ("x", "y", "z", "nx", "ny", "nz")
+
+
+def write_ply(path, xyz, normals=None):
+    """One cloud as a binary little-endian PLY: xyz (N,3), normals (N,3) or None (numpy arrays, or tensors on any device) -> a vertex
+    element of N records `float x y z` (with normals: `float x y z nx ny nz`), the values' fp32 bits as they are (NaNs included).  No faces."""
+    def host(a, name):
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1 or a.dtype.kind != "f":
+            raise ValueError("write_ply: %s must be a non-empty (N,3) float array, got %s %s" % (name, a.dtype, a.shape))
+        return a.astype("<f4")
+    rows = host(xyz, "xyz")
+    if normals is not None:
+        nrm = host(normals, "normals")
+        if nrm.shape != rows.shape:
+            raise ValueError("write_ply: %d points and %d normals" % (rows.shape[0], nrm.shape[0]))
+        rows = np.concatenate([rows, nrm], axis=1)
+    header = ["ply", "format binary_little_endian 1.0", "comment pdgn_amd.export", "element vertex %d" % rows.shape[0]]
+    header += ["property float %s" % name for name in PLY_PROPERTIES[:rows.shape[1]]]
+    header.append("end_header")
+    payload = np.ascontiguousarray(rows).tobytes()
+    assert len(payload) == struct.calcsize("<%df" % rows.size)
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii") + payload)
+    return path
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m pdgn_amd.export", description="write clouds of a saved (S, N, 3) array (the test phase's "
+                                "out.npy) as PLY files, one per cloud")
+    p.add_argument("clouds", help=".npy file holding (S, N, 3) or (S, 3, N) clouds")
+    p.add_argument("-o", "--output", required=True, metavar="DIR", help="directory for cloud_<index>.ply (created)")
+    p.add_argument("--first", type=int, default=0, help="index of the first cloud written")
+    p.add_argument("--count", type=int, default=None, help="clouds written (default: all from --first on)")
+    p.add_argument("--normals", type=int, default=None, metavar="K", help="add per-point normals estimated from the K nearest neighbours "
+                   "(pointops.estimate_normals; needs the device)")
+    p.add_argument("--orient", choices=["outward", "none"], default="outward", help="--normals: outward (default) turns every normal away from "
+                   "its cloud's centroid -- a heuristic that is right for roughly convex shapes and wrong inside concavities; none leaves the "
+                   "sign convention of the estimate (largest component non-negative)")
+    p.add_argument("--device", default="cuda")
+    return p
+
+
+def main(argv=None):
+    """`outward` is ("away", centroid): a heuristic for roughly convex shapes, not a globally consistent orientation."""
+    p = build_parser()
+    args = p.parse_args(argv)
+    pcs = np.load(args.clouds)
+    if pcs.ndim != 3 or 3 not in pcs.shape[1:]:
+        raise SystemExit("%s: expected (S, N, 3) or (S, 3, N), got %s" % (args.clouds, pcs.shape))
+    if pcs.shape[2] != 3:
+        pcs = pcs.transpose(0, 2, 1)
+    if not 0 <= args.first < pcs.shape[0] or (args.count is not None and args.count < 1):
+        p.error("--first %d --count %r: the file holds %d clouds" % (args.first, args.count, pcs.shape[0]))
+    if args.normals is not None and not 1 <= args.normals <= pcs.shape[1]:
+        p.error("--normals %d: between 1 and the clouds' %d points" % (args.normals, pcs.shape[1]))
+    stop = pcs.shape[0] if args.count is None else min(pcs.shape[0], args.first + args.count)
+    pcs = np.ascontiguousarray(pcs[args.first:stop], dtype=np.float32)
+    normals = [None] * pcs.shape[0]
+    if args.normals is not None:
+        import torch
+        from .pointops import estimate_normals
+        dev = torch.device(args.device)
+        for i in range(pcs.shape[0]):                            # (a cloud at a time: the centroid is an argument of the launch)
+            x = torch.from_numpy(pcs[i:i + 1]).to(dev)
+            orient = ("away", x[0].double().mean(dim=0).tolist()) if args.orient == "outward" else None
+            normals[i] = estimate_normals(x, args.normals, orient=orient)[0].cpu().numpy()
+    os.makedirs(args.output, exist_ok=True)
+    for i in range(pcs.shape[0]):
+        write_ply(os.path.join(args.output, "cloud_%d.ply" % (args.first + i)), pcs[i], normals[i])
+    print("%s: %d clouds%s" % (args.output, pcs.shape[0], "" if args.normals is None else ", normals from %d neighbours" % args.normals))
+    return args.output
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

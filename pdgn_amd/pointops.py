@@ -65,6 +65,46 @@ def knnquery_with_dist(nsample, xyz, new_xyz=None):
     return idx, dist2
 
 
+_ORIENT = {"direction": 1, "towards": 2, "away": 3}
+
+
+@torch.no_grad()
+def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
+    """Per-point surface normals from the covariance of each point's k nearest neighbours (pdgn_estimate_normals, csrc/normals.hip,
+    DESIGN.md section 7q; no reference counterpart).  xyz (B,N,3) fp32 on the device -> normals (B,N,3); with return_eig=True
+    (normals, eig (B,N,3)), the neighbourhood covariance's eigenvalues ascending.  idx: (B,N,k') int32 neighbour lists of the caller's
+    (`k` is then ignored); None: knnquery(k, xyz, xyz), which needs k <= N.  orient: None (the component of largest magnitude is made
+    non-negative), ("direction", v) (n . v >= 0), ("towards", p) (n . (p - x) >= 0) or ("away", p) (n . (x - p) >= 0), v / p three
+    numbers.  A point with an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no
+    graph (a flatness loss is a request of its own)."""
+    require(xyz, "xyz", F32, 3)
+    if xyz.shape[2] != 3:
+        raise ValueError("xyz must be (B,N,3), got %s" % (tuple(xyz.shape),))
+    b, n, _ = xyz.shape
+    if idx is None:
+        if not 1 <= int(k) <= n:
+            raise ValueError("estimate_normals: k = %r neighbours of a cloud of %d points" % (k, n))
+        idx = knnquery(int(k), xyz, xyz)
+    else:
+        require(idx, "idx", I32, 3)
+        if tuple(idx.shape[:2]) != (b, n) or idx.device != xyz.device:
+            raise ValueError("idx must be (B,N,k) on xyz's device, got %s for xyz %s" % (tuple(idx.shape), tuple(xyz.shape)))
+    mode, o = 0, (0.0, 0.0, 0.0)
+    if orient is not None:
+        try:
+            kind, o = orient
+            mode, o = _ORIENT[kind], tuple(float(v) for v in o)
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("orient must be None or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,)) from None
+        if len(o) != 3:
+            raise ValueError("orient must be None or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,))
+    normals = torch.empty((b, n, 3), dtype=F32, device=xyz.device)
+    eig = torch.empty((b, n, 3), dtype=F32, device=xyz.device) if return_eig else None
+    check(_lib.lib().pdgn_estimate_normals(b, n, idx.shape[2], ptr(xyz), ptr(idx), mode, o[0], o[1], o[2], ptr(normals), ptr(eig),
+                                           stream_of(xyz)), "pdgn_estimate_normals")
+    return (normals, eig) if return_eig else normals
+
+
 class Grouping(Function):
     """pointops.py:122-151.  features (b,c,n), idx (b,m,nsample) -> (b,c,m,nsample);
     backward = scatter-add into (b,c,n)."""

@@ -5,7 +5,7 @@ all four resolutions (csrc/render.hip, pdgn_render_sheet -> an 8-bit grey PNG) a
     reporter = SnapshotReporter(trainer, val_clouds, out_dir, every=20, batch_size=35, normalize="shape_bbox", seed=9999)
     trainer.fit(feeder, epochs, on_epoch=reporter)
     python -m pdgn_amd.train ... --report_every 20
-    python -m pdgn_amd.report results/GEN_Ours_chair_<time>/out.npy -o sheet.png
+    python -m pdgn_amd.report results/GEN_Ours_chair_<time>/out.npy -o sheet.png [--lit]
 
 A report does not touch training: it runs under no_grad in eval mode after a device synchronise, draws from generators of its
 own (torch's global RNG state is left alone), and leaves every parameter, buffer and optimizer state as it found them
@@ -79,22 +79,78 @@ def _column(t, name, fit):
     return t.contiguous(), n, not point_major
 
 
-def render_sheet(clouds, view=None, cell=128, radius=1, fit=False):
+def _normals_form(normals, ncols, k):
+    """The form of render_sheet's `normals` argument, checked before anything touches the device -> a list of `ncols` entries."""
+    if isinstance(normals, str):
+        normals = [normals] * ncols
+    if isinstance(normals, torch.Tensor) or not isinstance(normals, (list, tuple)) or len(normals) != ncols:
+        raise ValueError("normals must be None, \"estimate\" or a list with one entry per cloud list (%d)" % ncols)
+    for i, entry in enumerate(normals):
+        if isinstance(entry, str) and entry != "estimate":
+            raise ValueError("normals[%d]: %r is not \"estimate\"" % (i, entry))
+        if entry is not None and not isinstance(entry, (str, torch.Tensor)):
+            raise TypeError("normals[%d] must be a torch.Tensor, \"estimate\" or None" % i)
+    if int(k) < 1:
+        raise ValueError("normals_k must be at least 1, got %r" % (k,))
+    return list(normals)
+
+
+def _normals(normals, held, k, B, dev):
+    """render_sheet's `normals` argument (a list: _normals_form) -> one (B,N,3) contiguous fp32 tensor or None per column."""
+    from .pointops import estimate_normals
+    out = []
+    for i, (entry, (t, n, cm)) in enumerate(zip(normals, held)):
+        if entry is None:
+            out.append(None)
+        elif isinstance(entry, str):
+            pts = (t if t.shape[2] == 3 else t.transpose(1, 2)).contiguous()     # point-major, as _column reads the shape
+            out.append(estimate_normals(pts, min(int(k), n)))
+        else:
+            if not entry.is_cuda:
+                raise _lib.PdgnHipError("normals[%d] must live on a ROCm device (pdgn_amd has no CPU path)" % i)
+            if entry.dtype != torch.float32 or tuple(entry.shape) != (B, n, 3) or entry.device != dev:
+                raise ValueError("normals[%d] must be fp32 (%d,%d,3) on the clouds' device, got %s %s" % (i, B, n, entry.dtype, tuple(entry.shape)))
+            out.append(entry.contiguous())
+    return out
+
+
+def _light(v, from_view):
+    """The light's direction as the kernel takes it: three fp32 numbers of unit length (from_view: v is the 3 x 4 view, whose depth row
+    is the viewing direction)."""
+    v = np.asarray(v, dtype=np.float32)
+    v = v[2, :3] if from_view else v.reshape(-1)
+    if v.shape != (3,) or not np.isfinite(v).all() or not np.any(v != 0):
+        raise ValueError("light must be three finite numbers, not all zero, got %r" % (v,))
+    return np.ascontiguousarray(v / np.sqrt((v * v).sum(dtype=np.float32)), dtype=np.float32)
+
+
+def render_sheet(clouds, view=None, cell=128, radius=1, fit=False, normals=None, normals_k=16, light=None):
     """A contact sheet of clouds: one row per sample, one column per entry of `clouds` (a tensor, or a list of up to 8; each
     (B,3,N) -- the reference's layout, the generator's outputs as they are -- or point-major (B,N,3), fp32 on the device, the
     same B) -> (B * cell, len(clouds) * cell) uint8 device tensor.  view: 3 x 4 fp32 (default `default_view(cell)`); radius: the
     splat's radius in pixels; fit: centre and scale every cloud into the unit sphere first.  One launch sequence on the current
-    stream; bitwise repeatable."""
+    stream; bitwise repeatable.
+    normals: None -- every column shaded by depth, pdgn_render_sheet, what this function always did -- or, for sheets lit by their surface
+    normals (pdgn_render_sheet_lit, DESIGN.md section 7q: two-sided, so the normals need no consistent orientation), "estimate" (every
+    column: pointops.estimate_normals of the cloud as it is drawn, from its `normals_k` nearest neighbours) or a list with one entry per
+    column: a (B,N,3) fp32 tensor of the column's normals, point-major whatever the cloud's layout, "estimate", or None (that column stays
+    shaded by depth).  light: three numbers, the direction of the light, normalised here in fp32; default: the viewing direction, `view`
+    row 2's first three entries."""
     cols = [clouds] if isinstance(clouds, torch.Tensor) else list(clouds)
     if not 1 <= len(cols) <= MAX_COLUMNS:
         raise ValueError("render_sheet takes 1 to %d cloud lists, got %d" % (MAX_COLUMNS, len(cols)))
     view = np.ascontiguousarray(np.asarray(default_view(cell) if view is None else view, dtype=np.float32))
     if view.shape != (3, 4):
         raise ValueError("view must be 3 x 4, got %s" % (view.shape,))
+    if normals is not None:
+        normals = _normals_form(normals, len(cols), normals_k)
+        light = _light(view if light is None else light, light is None)
     held = [_column(t, "clouds[%d]" % i, fit) for i, t in enumerate(cols)]
     B, dev = cols[0].shape[0], cols[0].device
     if any(t.shape[0] != B or t.device != dev for t in cols):
         raise ValueError("every cloud list must hold the same number of clouds on the same device")
+    if normals is not None:
+        normals = _normals(normals, held, normals_k, B, dev)
     L = _lib.lib()
     nbytes = L.pdgn_render_workspace_bytes(B, len(cols), int(cell))
     if nbytes < 0:
@@ -105,6 +161,12 @@ def render_sheet(clouds, view=None, cell=128, radius=1, fit=False):
         ptrs = (ctypes.c_void_p * len(cols))(*[t.data_ptr() for t, _, _ in held])
         counts = (ctypes.c_int * len(cols))(*[n for _, n, _ in held])
         mask = sum(1 << i for i, (_, _, cm) in enumerate(held) if cm)
+        if normals is not None:
+            nptrs = (ctypes.c_void_p * len(cols))(*[None if t is None else t.data_ptr() for t in normals])
+            _lib.check(L.pdgn_render_sheet_lit(B, len(cols), ptrs, nptrs, counts, mask, view.ctypes.data_as(ctypes.c_void_p),
+                                               light.ctypes.data_as(ctypes.c_void_p), int(cell), int(radius), _lib.ptr(ws), _lib.ptr(image),
+                                               _lib.stream_of(image)), "pdgn_render_sheet_lit")
+            return image
         _lib.check(L.pdgn_render_sheet(B, len(cols), ptrs, counts, mask, view.ctypes.data_as(ctypes.c_void_p), int(cell), int(radius),
                                        _lib.ptr(ws), _lib.ptr(image), _lib.stream_of(image)), "pdgn_render_sheet")
     return image
@@ -172,12 +234,16 @@ class SnapshotReporter:
     state is left as found; the generator's train / eval flag is put back.  spacing=True: every report also appends epoch, gen nn_mean,
     gen nn_cv, val nn_mean, val nn_cv, gen duplicates -- evaluation.spacing_stats of as many generated clouds as there are reference clouds
     (the metrics' noise stream, normalised like them) and of the reference clouds -- to `<out_dir>/spacing.csv` (DESIGN.md section 7p);
-    metrics.csv is what it was."""
+    metrics.csv is what it was.  lit=True: the sheet's columns are shaded by surface normals estimated from each cloud's 16 nearest
+    neighbours (render_sheet(normals="estimate")) instead of by depth.  surface=True: every report also appends epoch,
+    gen sv_mean, gen sv_p90, val sv_mean, val sv_p90, gen degenerate -- evaluation.surface_stats of the same generated clouds and of the
+    reference clouds -- to `<out_dir>/surface.csv`.  With neither, every file is what it was."""
 
     SPACING_HEADER = ("epoch", "gen nn_mean", "gen nn_cv", "val nn_mean", "val nn_cv", "gen duplicates")
+    SURFACE_HEADER = ("epoch", "gen sv_mean", "gen sv_p90", "val sv_mean", "val sv_p90", "gen degenerate")
 
     def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1, emd="approx",
-                 spacing=False):
+                 spacing=False, lit=False, surface=False):
         _lib.require(ref_pcs, "ref_pcs", torch.float32, 3)
         self.trainer, self.ref, self.out_dir = trainer, ref_pcs, str(out_dir)
         self.every, self.batch_size, self.normalize, self.seed = int(every), int(batch_size), normalize, int(seed)
@@ -195,6 +261,8 @@ class SnapshotReporter:
         self.last = None                                         # (epoch, {key: float}, seconds) of the latest report
         self.spacing = bool(spacing)
         self.last_spacing = None                                 # (epoch, generated clouds' stats, reference clouds' stats)
+        self.lit, self.surface = bool(lit), bool(surface)
+        self.last_surface = None                                 # (epoch, generated clouds' stats, reference clouds' stats)
 
     def _generator(self, offset):
         return torch.Generator(device=self.ref.device).manual_seed(self.seed + offset)
@@ -217,18 +285,24 @@ class SnapshotReporter:
         try:
             with averaged:
                 z = torch.randn(self.rows, 128, generator=self._generator(0), device=dev)
-                sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True)
+                sheet = render_sheet(list(G(z)) + [self.ref[:self.rows]], cell=self.cell, radius=self.radius, fit=True,
+                                     **({"normals": "estimate"} if self.lit else {}))
                 if self.full:
                     _, results = ev.generate_and_evaluate(G, self.ref, self.batch_size, self.normalize, self._generator(1), emd=self.emd)
                 else:
                     results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
                 results = {k: float(results[k]) for k in self.keys}
                 image = sheet.cpu().numpy()
+                if self.spacing or self.surface:
+                    gen_pcs, _ = ev.generate_clouds(G, self.ref.shape[0], self.batch_size, self.normalize, self._generator(1), dev)
                 if self.spacing:
                     if "val_spacing" not in self.cache:          # (the reference set does not change between reports)
                         self.cache["val_spacing"] = ev.spacing_stats(self.ref, self.batch_size)
-                    gen_pcs, _ = ev.generate_clouds(G, self.ref.shape[0], self.batch_size, self.normalize, self._generator(1), dev)
                     spacing = (ev.spacing_stats(gen_pcs, self.batch_size), self.cache["val_spacing"])
+                if self.surface:
+                    if "val_surface" not in self.cache:
+                        self.cache["val_surface"] = ev.surface_stats(self.ref, batch=self.batch_size)
+                    surface = (ev.surface_stats(gen_pcs, batch=self.batch_size), self.cache["val_surface"])
         finally:
             G.train(was_training)
             G.restore_forward_hints(hints)
@@ -252,6 +326,16 @@ class SnapshotReporter:
                 f.write(",".join([str(epoch)] + ["%.9g" % v for v in (gen["nn_mean"], gen["nn_cv"], val["nn_mean"], val["nn_cv"])]
                                  + ["%d" % gen["duplicates"]]) + "\n")
             self.last_spacing = (epoch, gen, val)
+        if self.surface:
+            gen, val = surface
+            path = os.path.join(self.out_dir, "surface.csv")
+            fresh = not os.path.exists(path) or os.path.getsize(path) == 0
+            with open(path, "a") as f:
+                if fresh:
+                    f.write(",".join(self.SURFACE_HEADER) + "\n")
+                f.write(",".join([str(epoch)] + ["%.9g" % v for v in (gen["sv_mean"], gen["sv_p90"], val["sv_mean"], val["sv_p90"])]
+                                 + ["%d" % gen["degenerate"]]) + "\n")
+            self.last_surface = (epoch, gen, val)
         return self.last
 
 
@@ -266,6 +350,8 @@ def build_parser():
     p.add_argument("--cell", type=int, default=128, help="pixels per cell side")
     p.add_argument("--radius", type=int, default=1, help="splat radius in pixels")
     p.add_argument("--device", default="cuda")
+    p.add_argument("--lit", action="store_true", help="shade by surface normals estimated from each cloud's 16 nearest neighbours (two-sided "
+                   "headlight shading) instead of by depth")
     return p
 
 
@@ -280,7 +366,8 @@ def main(argv=None):
     cols = max(1, min(args.cols, MAX_COLUMNS, pcs.shape[0] // rows))
     dev = torch.device(args.device)
     pcs = torch.from_numpy(np.ascontiguousarray(pcs[:rows * cols], dtype=np.float32)).to(dev)
-    sheet = render_sheet([pcs[j * rows:(j + 1) * rows] for j in range(cols)], cell=args.cell, radius=args.radius, fit=True)
+    sheet = render_sheet([pcs[j * rows:(j + 1) * rows] for j in range(cols)], cell=args.cell, radius=args.radius, fit=True,
+                         **({"normals": "estimate"} if args.lit else {}))
     write_png(args.output, sheet)
     print("%s: %d clouds, %d x %d pixels" % (args.output, rows * cols, sheet.shape[1], sheet.shape[0]))
     return args.output

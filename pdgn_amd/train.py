@@ -41,7 +41,9 @@ evenly spread duplicates where it stores fewer (data.RaggedFeeder, pdgn_feed_bat
 is zero when no two points of a cloud are closer than the level's radius (losses.repulsion); --repulsion_radius H is the radius at
 --num_point points -- without it the radius is calibrated once before training, --repulsion_radius_factor (1) times the mean nearest-neighbour distance
 of up to 64 clouds the feeder itself produces, and printed; repulsion.csv beside the log.  --report_spacing (needs --report_every): the reports also
-append nearest-neighbour spacing statistics of the generated and the val clouds to report/spacing.csv.
+append nearest-neighbour spacing statistics of the generated and the val clouds to report/spacing.csv.  --report_lit: the preview sheets are shaded by
+surface normals estimated from each cloud's 16 nearest neighbours; --report_surface: the reports also append the surface
+variation of the generated and the val clouds to report/surface.csv (both need --report_every).
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -139,6 +141,11 @@ def build_parser():
                    "coarsest) .. 4 (--num_point points), comma separated (default 1,2,3,4)")
     p.add_argument("--report_spacing", action="store_true", default=argparse.SUPPRESS, help="reports also append the nearest-neighbour spacing statistics of "
                    "the generated and of the val clouds to report/spacing.csv (evaluation.spacing_stats); needs --report_every")
+    p.add_argument("--report_lit", action="store_true", default=argparse.SUPPRESS, help="preview sheets shaded by surface normals (two-sided headlight "
+                   "shading, normals from the 16 nearest neighbours: pointops.estimate_normals) instead of by depth; needs --report_every")
+    p.add_argument("--report_surface", action="store_true", default=argparse.SUPPRESS, help="reports also append the surface variation "
+                   "lambda0 / (lambda0 + lambda1 + lambda2) of the generated and of the val clouds to report/surface.csv (evaluation.surface_stats); "
+                   "needs --report_every")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
     p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
@@ -199,6 +206,8 @@ class Args(argparse.Namespace):
     repulsion_radius_factor = 1.0
     repulsion_levels = "1,2,3,4"
     report_spacing = False
+    report_lit = False
+    report_surface = False
 
 
 def parse_args(argv=None):
@@ -296,6 +305,9 @@ def parse_args(argv=None):
             p.error("--repulsion: --num_point %d, the all-pairs kernel holds at most 8192 points" % args.num_point)
     if args.report_spacing and not args.report_every:
         p.error("--report_spacing needs --report_every")
+    for flag in ("report_lit", "report_surface"):
+        if getattr(args, flag) and not args.report_every:
+            p.error("--%s needs --report_every" % flag)
     if args.d_augment_target is None:
         for flag in ("ada_interval", "ada_span", "ada_p_min", "ada_p_max"):
             if flag in given:
@@ -676,7 +688,8 @@ def train(args):
         val = reference_clouds(args, "val", device, mesh_root, ragged_root)
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd,
-                                    **({"spacing": True} if args.report_spacing else {}))
+                                    **({"spacing": True} if args.report_spacing else {}), **({"lit": True} if args.report_lit else {}),
+                                    **({"surface": True} if args.report_surface else {}))
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
                        grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
