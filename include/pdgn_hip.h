@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 43
+#define PDGN_ABI_VERSION 44
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1283,6 +1283,33 @@ int pdgn_repulsion_backward(long long count, const float *grad, const float *g, 
 #define PDGN_NORMALS_STAGE_MAX_N 4096
 int pdgn_estimate_normals(int b, int n, int k, const float *xyz, const int32_t *idx, int orient, float ox, float oy, float oz,
                           float *normals, float *eig, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ consistent normal orientation (csrc/orient.hip)
+ * pdgn_orient_normals gives the normals of every cloud one consistent sign: a minimum spanning tree of the symmetrised neighbour graph
+ * under the weight 1 - |n_u . n_v| (Prim, Hoppe et al. 1992), grown from the highest point of each connected component, whose normal is
+ * turned upwards; every other point takes the sign that agrees with its tree parent.  The header block of csrc/orient.hip is the
+ * normative statement of the rules (live points, edges, weight, rounds, ties); tests/orient_mirror.py spells them in numpy and the two
+ * agree bit for bit: every decision is a comparison of integers.  No reference counterpart.
+ *   xyz         (b,n,3)
+ *   idx         (b,n,k) int32: neighbour lists (pdgn_knnquery's, or any: slot order and repeats change nothing; an index outside
+ *               [0, n) is never dereferenced, it and a self index are ignored)
+ *   normals_in  (b,n,3): unoriented normals (pdgn_estimate_normals, orient 0)
+ *   normals_out (b,n,3): normals_in with the sign bit of all three components flipped or kept; may be normals_in itself
+ *   parent      (b,n) int32 or NULL: the tree parent, -1 for the root of a component, -2 for a dead point (a coordinate or a normal
+ *               component that is not finite: it keeps its input bits and takes no part in the graph)
+ *   stats       (b,4) int32 or NULL: components, normals flipped, weak tree edges (weight above 0.5: more than 60 degrees between the
+ *               two lines, the sign across it is a guess), dead points
+ *   workspace   pdgn_orient_workspace_ints(b, n, k) int32 of the caller's: the reverse adjacency; contents undefined on return
+ * One workgroup per cloud, one launch on `stream`, integer LDS atomics only, nothing allocated; repeatable bit for bit.  n is at most
+ * PDGN_ORIENT_MAX_N (what one workgroup's LDS holds); a larger n is PDGN_ERR_INVALID, not a slower path.  The rounds are sequential:
+ * about n of them per cloud (profiles/orient_cost.txt).
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1 or > PDGN_ORIENT_MAX_N, k outside [1, PDGN_NORMALS_MAX_K],
+ * b n beyond 2^28, a null xyz / idx / normals_in / normals_out / workspace, any pointer not 4-byte aligned.
+ * pdgn_orient_workspace_ints: host only; the number of int32 the workspace must hold, PDGN_ERR_INVALID for a shape the entry point refuses. */
+#define PDGN_ORIENT_MAX_N 4096
+long long pdgn_orient_workspace_ints(int b, int n, int k);
+int pdgn_orient_normals(int b, int n, int k, const float *xyz, const int32_t *idx, const float *normals_in, float *normals_out,
+                        int32_t *parent, int32_t *stats, int32_t *workspace, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

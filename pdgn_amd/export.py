@@ -3,9 +3,10 @@ reconstruction, MeshLab and Blender take).
 
     write_ply("chair.ply", xyz, normals)
     python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient outward
+    python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient consistent
 
 The writer is struct and numpy only, as report.write_png is; only the command line's --normals touches the device (pointops.estimate_normals,
-DESIGN.md section 7q)."""
+DESIGN.md section 7q; --orient consistent: pointops.orient_normals, section 7r)."""
 import argparse
 import os
 import struct
@@ -14,6 +15,7 @@ import sys
 import numpy as np
 
 PLY_PROPERTIES = ("x", "y", "z", "nx", "ny", "nz")
+CONSISTENT_MAX_POINTS = 4096                                       # PDGN_ORIENT_MAX_N
 
 
 def write_ply(path, xyz, normals=None):
@@ -51,15 +53,18 @@ def build_parser():
     p.add_argument("--count", type=int, default=None, help="clouds written (default: all from --first on)")
     p.add_argument("--normals", type=int, default=None, metavar="K", help="add per-point normals estimated from the K nearest neighbours "
                    "(pointops.estimate_normals; needs the device)")
-    p.add_argument("--orient", choices=["outward", "none"], default="outward", help="--normals: outward (default) turns every normal away from "
-                   "its cloud's centroid -- a heuristic that is right for roughly convex shapes and wrong inside concavities; none leaves the "
-                   "sign convention of the estimate (largest component non-negative)")
+    p.add_argument("--orient", choices=["outward", "consistent", "none"], default="outward", help="--normals: outward (default) turns every "
+                   "normal away from its cloud's centroid -- a heuristic that is right for roughly convex shapes and wrong inside concavities; "
+                   "consistent propagates the sign along a minimum spanning tree of the neighbour graph from each component's highest point "
+                   "(what Poisson reconstruction needs; clouds of at most %d points); none leaves the sign convention of the estimate "
+                   "(largest component non-negative)" % CONSISTENT_MAX_POINTS)
     p.add_argument("--device", default="cuda")
     return p
 
 
 def main(argv=None):
-    """`outward` is ("away", centroid): a heuristic for roughly convex shapes, not a globally consistent orientation."""
+    """`outward` is ("away", centroid): a heuristic for roughly convex shapes, not a globally consistent orientation.  `consistent` is
+    spanning-tree propagation (pointops.orient_normals), all selected clouds in one batched call."""
     p = build_parser()
     args = p.parse_args(argv)
     pcs = np.load(args.clouds)
@@ -71,21 +76,35 @@ def main(argv=None):
         p.error("--first %d --count %r: the file holds %d clouds" % (args.first, args.count, pcs.shape[0]))
     if args.normals is not None and not 1 <= args.normals <= pcs.shape[1]:
         p.error("--normals %d: between 1 and the clouds' %d points" % (args.normals, pcs.shape[1]))
+    if args.normals is not None and args.orient == "consistent":
+        if pcs.shape[1] > CONSISTENT_MAX_POINTS:
+            p.error("--orient consistent: clouds of at most %d points, the file's have %d" % (CONSISTENT_MAX_POINTS, pcs.shape[1]))
+        if args.normals > 64:
+            p.error("--orient consistent: --normals at most 64, got %d" % args.normals)
     stop = pcs.shape[0] if args.count is None else min(pcs.shape[0], args.first + args.count)
     pcs = np.ascontiguousarray(pcs[args.first:stop], dtype=np.float32)
     normals = [None] * pcs.shape[0]
+    tree = ""
     if args.normals is not None:
         import torch
         from .pointops import estimate_normals
         dev = torch.device(args.device)
-        for i in range(pcs.shape[0]):                            # (a cloud at a time: the centroid is an argument of the launch)
-            x = torch.from_numpy(pcs[i:i + 1]).to(dev)
-            orient = ("away", x[0].double().mean(dim=0).tolist()) if args.orient == "outward" else None
-            normals[i] = estimate_normals(x, args.normals, orient=orient)[0].cpu().numpy()
+        if args.orient == "consistent":                          # (no centroid argument: every cloud in one batched call)
+            from .pointops import knnquery, orient_normals
+            x = torch.from_numpy(pcs).to(dev)
+            idx = knnquery(args.normals, x, x)
+            oriented, _, stats = orient_normals(x, estimate_normals(x, idx=idx), idx=idx, return_tree=True)
+            normals = list(oriented.cpu().numpy())
+            tree = " (%d components, %d weak tree edges)" % tuple(stats[:, [0, 2]].sum(dim=0).tolist())
+        else:
+            for i in range(pcs.shape[0]):                        # (a cloud at a time: the centroid is an argument of the launch)
+                x = torch.from_numpy(pcs[i:i + 1]).to(dev)
+                orient = ("away", x[0].double().mean(dim=0).tolist()) if args.orient == "outward" else None
+                normals[i] = estimate_normals(x, args.normals, orient=orient)[0].cpu().numpy()
     os.makedirs(args.output, exist_ok=True)
     for i in range(pcs.shape[0]):
         write_ply(os.path.join(args.output, "cloud_%d.ply" % (args.first + i)), pcs[i], normals[i])
-    print("%s: %d clouds%s" % (args.output, pcs.shape[0], "" if args.normals is None else ", normals from %d neighbours" % args.normals))
+    print("%s: %d clouds%s" % (args.output, pcs.shape[0], "" if args.normals is None else ", normals from %d neighbours" % args.normals) + tree)
     return args.output
 
 

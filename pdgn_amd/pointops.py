@@ -75,8 +75,9 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
     (normals, eig (B,N,3)), the neighbourhood covariance's eigenvalues ascending.  idx: (B,N,k') int32 neighbour lists of the caller's
     (`k` is then ignored); None: knnquery(k, xyz, xyz), which needs k <= N.  orient: None (the component of largest magnitude is made
     non-negative), ("direction", v) (n . v >= 0), ("towards", p) (n . (p - x) >= 0) or ("away", p) (n . (x - p) >= 0), v / p three
-    numbers.  A point with an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no
-    graph (a flatness loss is a request of its own)."""
+    numbers, or "consistent" (the estimate with orient=None, then orient_normals with the same lists: N <= 4096, k <= 64).  A point with
+    an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no graph (a flatness loss is
+    a request of its own)."""
     require(xyz, "xyz", F32, 3)
     if xyz.shape[2] != 3:
         raise ValueError("xyz must be (B,N,3), got %s" % (tuple(xyz.shape),))
@@ -90,19 +91,67 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
         if tuple(idx.shape[:2]) != (b, n) or idx.device != xyz.device:
             raise ValueError("idx must be (B,N,k) on xyz's device, got %s for xyz %s" % (tuple(idx.shape), tuple(xyz.shape)))
     mode, o = 0, (0.0, 0.0, 0.0)
-    if orient is not None:
+    consistent = isinstance(orient, str) and orient == "consistent"
+    if orient is not None and not consistent:
+        bad = "orient must be None, \"consistent\" or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,)
         try:
             kind, o = orient
             mode, o = _ORIENT[kind], tuple(float(v) for v in o)
         except (KeyError, TypeError, ValueError):
-            raise ValueError("orient must be None or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,)) from None
+            raise ValueError(bad) from None
         if len(o) != 3:
-            raise ValueError("orient must be None or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,))
+            raise ValueError(bad)
+    if consistent and n > ORIENT_MAX_N:
+        raise ValueError("estimate_normals: orient=\"consistent\" takes clouds of at most %d points, got %d" % (ORIENT_MAX_N, n))
     normals = torch.empty((b, n, 3), dtype=F32, device=xyz.device)
     eig = torch.empty((b, n, 3), dtype=F32, device=xyz.device) if return_eig else None
     check(_lib.lib().pdgn_estimate_normals(b, n, idx.shape[2], ptr(xyz), ptr(idx), mode, o[0], o[1], o[2], ptr(normals), ptr(eig),
                                            stream_of(xyz)), "pdgn_estimate_normals")
+    if consistent:
+        normals = orient_normals(xyz, normals, idx=idx)
     return (normals, eig) if return_eig else normals
+
+
+ORIENT_MAX_N = 4096                                                # PDGN_ORIENT_MAX_N
+ORIENT_MAX_K = 64                                                  # PDGN_NORMALS_MAX_K
+
+
+@torch.no_grad()
+def orient_normals(xyz, normals, k=16, idx=None, return_tree=False):
+    """A consistent sign for the normals of every cloud (pdgn_orient_normals, csrc/orient.hip; no reference
+    counterpart): the sign is propagated along a minimum spanning tree of the symmetrised neighbour graph under the weight 1 - |n_u . n_v|,
+    from the highest point of each connected component, whose normal is turned upwards.  xyz (B,N,3), normals (B,N,3) fp32 on the device
+    (estimate_normals' with orient=None) -> normals (B,N,3), a new tensor that differs from the input in sign bits alone; with
+    return_tree=True (normals, parent (B,N) int32: the tree parent, -1 a component's root, -2 a point with a non-finite coordinate or normal,
+    stats (B,4) int32: components, normals flipped, tree edges across more than 60 degrees, dead points).  idx as in estimate_normals: (B,N,k')
+    int32 lists of the caller's (`k` is then ignored), or None: knnquery(k, xyz, xyz).  N <= 4096, k' <= 64.  NOT differentiable."""
+    require(xyz, "xyz", F32, 3)
+    if xyz.shape[2] != 3:
+        raise ValueError("xyz must be (B,N,3), got %s" % (tuple(xyz.shape),))
+    require(normals, "normals", F32, 3)
+    if normals.shape != xyz.shape or normals.device != xyz.device:
+        raise ValueError("normals must be (B,N,3) on xyz's device, got %s for xyz %s" % (tuple(normals.shape), tuple(xyz.shape)))
+    b, n, _ = xyz.shape
+    if not 1 <= n <= ORIENT_MAX_N or b < 1:
+        raise ValueError("orient_normals: clouds of 1 .. %d points, got %s" % (ORIENT_MAX_N, tuple(xyz.shape)))
+    if idx is None:
+        if not 1 <= int(k) <= min(n, ORIENT_MAX_K):
+            raise ValueError("orient_normals: k = %r neighbours of a cloud of %d points (at most %d)" % (k, n, ORIENT_MAX_K))
+        idx = knnquery(int(k), xyz, xyz)
+    else:
+        require(idx, "idx", I32, 3)
+        if tuple(idx.shape[:2]) != (b, n) or idx.device != xyz.device:
+            raise ValueError("idx must be (B,N,k) on xyz's device, got %s for xyz %s" % (tuple(idx.shape), tuple(xyz.shape)))
+        if not 1 <= idx.shape[2] <= ORIENT_MAX_K:
+            raise ValueError("orient_normals: lists of 1 .. %d neighbours, got %d" % (ORIENT_MAX_K, idx.shape[2]))
+    L = _lib.lib()
+    out = torch.empty_like(normals)
+    parent = torch.empty((b, n), dtype=I32, device=xyz.device) if return_tree else None
+    stats = torch.empty((b, 4), dtype=I32, device=xyz.device) if return_tree else None
+    work = torch.empty((int(L.pdgn_orient_workspace_ints(b, n, idx.shape[2])),), dtype=I32, device=xyz.device)
+    check(L.pdgn_orient_normals(b, n, idx.shape[2], ptr(xyz), ptr(idx), ptr(normals), ptr(out), ptr(parent), ptr(stats), ptr(work),
+                                stream_of(xyz)), "pdgn_orient_normals")
+    return (out, parent, stats) if return_tree else out
 
 
 class Grouping(Function):
