@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 44
+#define PDGN_ABI_VERSION 45
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1310,6 +1310,50 @@ int pdgn_estimate_normals(int b, int n, int k, const float *xyz, const int32_t *
 long long pdgn_orient_workspace_ints(int b, int n, int k);
 int pdgn_orient_normals(int b, int n, int k, const float *xyz, const int32_t *idx, const float *normals_in, float *normals_out,
                         int32_t *parent, int32_t *stats, int32_t *workspace, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ surface reconstruction (csrc/reconstruct.hip)
+ * From oriented points to a triangle mesh: a signed-distance field on a regular grid by implicit moving least squares with the compact
+ * weight (1 - d^2 / h^2)^2, then its iso-surface by surface nets.  The header block of csrc/reconstruct.hip is the normative statement of
+ * the operation order and of the mesh's rules (live points, nodes, active cells, vertices, quads, winding, output order);
+ * tests/reconstruct_mirror.py spells them in numpy and the two agree bit for bit.  No reference counterpart.  R nodes per axis, node
+ * (i,j,k) at (i R + j) R + k; a cloud's grid is origin (3), voxel, and for the field inv = 1 / h^2.
+ *
+ * pdgn_imls_grid: field (b, R^3) from xyz (b,n,3) and oriented normals (b,n,3).
+ *   grid       (b,5) on the device: origin x y z, voxel, inv per cloud
+ *   grid_host  the caller's HOST copy of the same (b,5) values: what is checked here (the device record is not read on the host)
+ *   field      (b, R^3): negative inside; NaN (0x7FC00000) at a node with no live point within h.  A point with a non-finite coordinate
+ *              or normal component is skipped.
+ *   cull       1: per brick of 4 x 4 x 4 nodes the points that provably cannot reach it are left out, which changes no bit; 0: every
+ *              point is visited at every node (measurement and tests)
+ * One launch on `stream` per 2^22 workgroups (one for every cube of 8 x 8 x 8 nodes, R rounded up: a single launch for anything but
+ * huge batches), no atomics, nothing allocated.  pdgn_imls_chunk(): the points staged in LDS at a time (tests put n on either side).
+ * Results do not depend on the launch geometry.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1, R outside [PDGN_RECON_MIN_R, PDGN_RECON_MAX_R], b R^3 >= 2^31,
+ * cull outside 0 .. 1, a null pointer or one not 4-byte aligned, a value of grid_host that is not finite, a voxel or inv that is not positive.
+ *
+ * pdgn_surface_nets_count: field (b, R^3) -> vflag (b, R^3) int32, 1 at the node that is the lowest corner of an active cell (ascending
+ * node id is ascending cell id), qcnt (b, R^3) int32, the quads (0 .. 3) of the node's three edges, and stats (b,4) int32: vertices, faces,
+ * open edges, invalid nodes.  Launches on `stream`: one that clears stats, then per 65535 clouds the cells and the quads; integer atomics
+ * for the counters only.  PDGN_ERR_INVALID as above (shape, pointers), nothing launched, nothing written.
+ *
+ * pdgn_surface_nets_emit: the vertices and faces at their ranks.  vscan / qscan (b, R^3) int32: the INCLUSIVE prefix sums of vflag / qcnt
+ * within each cloud (torch.cumsum along the node axis); vert_off / face_off (b+1) int32 on the device: exclusive prefix sums of the clouds'
+ * vertex / face counts; total_verts / total_faces: their last entries as the caller read them from stats; vert_capacity / face_capacity:
+ * the rows verts (.,3) fp32 / faces (.,3) int32 hold.  grid (b,4) on the device: origin, voxel; grid_host: the host copy, checked here.
+ * Face entries are indices into the cloud's own vertices.  Nothing is written past the totals whatever the scans hold.  One launch per
+ * 65535 clouds, no atomics.  PDGN_ERR_INVALID, nothing launched, nothing written: the shape cases above, a null or misaligned pointer
+ * (verts / faces may be null where their total is 0), a total below 0 or above (2^31 - 1) / 3, a capacity below its total, a value of
+ * grid_host that is not finite or a voxel that is not positive. */
+#define PDGN_RECON_MIN_R 2
+#define PDGN_RECON_MAX_R 256
+int pdgn_imls_chunk(void);
+int pdgn_imls_grid(int b, int n, int R, const float *xyz, const float *normals, const float *grid, const float *grid_host, int cull,
+                   float *field, pdgn_stream_t stream);
+int pdgn_surface_nets_count(int b, int R, const float *field, int32_t *vflag, int32_t *qcnt, int32_t *stats, pdgn_stream_t stream);
+int pdgn_surface_nets_emit(int b, int R, const float *field, const float *grid, const float *grid_host, const int32_t *vflag,
+                           const int32_t *vscan, const int32_t *qcnt, const int32_t *qscan, const int32_t *vert_off,
+                           const int32_t *face_off, long long total_verts, long long total_faces, long long vert_capacity,
+                           long long face_capacity, float *verts, int32_t *faces, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }
