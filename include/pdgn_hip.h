@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 45
+#define PDGN_ABI_VERSION 46
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1354,6 +1354,49 @@ int pdgn_surface_nets_emit(int b, int R, const float *field, const float *grid, 
                            const int32_t *vscan, const int32_t *qcnt, const int32_t *qscan, const int32_t *vert_off,
                            const int32_t *face_off, long long total_verts, long long total_faces, long long vert_capacity,
                            long long face_capacity, float *verts, int32_t *faces, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ point-to-surface distance (csrc/meshdist.hip)
+ * The closest point of a triangle set: for every point of xyz (b,n,3) the live faces of shape shape[c] of a mesh set are searched.  Per
+ * point the result is the lexicographic minimum of (d2_f, f) over those faces -- one unsigned 64-bit compare on bits(d2_f) << 32 | f, d2_f
+ * being non-negative -- where d2_f is the per-face value whose fp32 operation order the header block of csrc/meshdist.hip states
+ * (tests/p2m_mirror.py spells it in numpy; the two agree bit for bit) and f the face's index in the caller's face array.  A NaN d2_f never
+ * wins.  The order in which faces are visited, the record order, the launch geometry and `cull` change no bit.  Unsigned distances; not
+ * differentiable in the mesh.  No reference counterpart.
+ *
+ * pdgn_mesh_dist_prepare: once per mesh set (and per set of live faces): the face records and the boxes of their groups.
+ *   verts (V,3), faces (F,3) int32 global vertex indices, face_off (S+1) int32: the mesh set's arrays
+ *   group_off  (S+1) int32: exclusive prefix sums of ceil(F_s / pdgn_mesh_dist_group()) over the shapes; G = group_off[S], at most
+ *              F / group + S
+ *   live       (F) int32: 0 = the face is never visited (area zero, hidden, ...), indexed by the face's own index
+ *   order      (F) int32 or NULL: slot -> face, a permutation that keeps every shape's faces inside the shape's own range
+ *              [face_off[s], face_off[s+1]) (any order gives the same bits; DESIGN.md section 7t has what each costs); NULL: slot i holds face i
+ *   records    (F,12) fp32, 16-byte aligned: per slot (a.x a.y a.z bits(f) | b.x b.y b.z 0 | c.x c.y c.z 0), f = -1 for a dead slot (a
+ *              face that is not live, or one that names a vertex outside [0, V))
+ *   groups     (G,8) fp32, 16-byte aligned: per group of slots (lo.x lo.y lo.z 0 | hi.x hi.y hi.z 0), the box of its live faces
+ *              (+inf / -inf where it has none)
+ * pdgn_mesh_dist_workspace_floats(S, F): host only; 12 F + 8 (F / group + S), what records and groups take together at most;
+ * PDGN_ERR_INVALID for a shape the entry points refuse.  One launch on `stream`, no atomics, nothing allocated.
+ *
+ * pdgn_point_mesh_distance:
+ *   shape      (b) int32: the shape of each cloud; repeats and any order are fine; an index outside [0, S) counts as a shape with no
+ *              live face
+ *   d2         (b,n): the least squared distance;  face (b,n) int32: the face that attains it;  closest (b,n,3) or NULL: the closest
+ *              point.  NaN (0x7FC00000), -1, NaN for a point with a non-finite coordinate and where no live face gave a value
+ *   cull       1: faces and groups of faces whose box provably lies farther than the best so far are left out, which changes no bit;
+ *              0: every live face is visited at every point (measurement and tests)
+ * One launch on `stream`, one thread per point, a workgroup per run of pdgn_mesh_dist_chunk() points of a cloud, the shape's records
+ * through LDS that many at a time; no atomics, nothing allocated.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: S, V, F, G, b or n < 1, 3 V or 3 F or b n >= 2^31, b ceil(n / chunk) > 2^23, G > F / group + S, cull
+ * outside 0 .. 1, a null pointer other than order / closest, a pointer not 4-byte aligned (records, groups: 16-byte). */
+int pdgn_mesh_dist_group(void);
+int pdgn_mesh_dist_chunk(void);
+long long pdgn_mesh_dist_workspace_floats(int S, int F);
+int pdgn_mesh_dist_prepare(int S, int V, int F, int G, const float *verts, const int32_t *faces, const int32_t *face_off,
+                           const int32_t *group_off, const int32_t *live, const int32_t *order, float *records, float *groups,
+                           pdgn_stream_t stream);
+int pdgn_point_mesh_distance(int b, int n, int S, int F, int G, const float *xyz, const int32_t *shape, const int32_t *face_off,
+                             const int32_t *group_off, const float *records, const float *groups, int cull, float *d2, int32_t *face,
+                             float *closest, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

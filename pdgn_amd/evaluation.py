@@ -242,6 +242,69 @@ def surface_stats(clouds, k=16, batch=64):
     return {"sv_mean": float(mean.mean()), "sv_p90": float(p90.mean()), "degenerate": int((~live).sum())}
 
 
+# ---------------------------------------------------------------------------- distance to the surface (no reference counterpart)
+def _distance_summary(d, prefix, out):
+    """mean, RMS and max over dim 1 of distances d (B,n) fp64, NaN entries left out (NaN where a row has none)."""
+    valid = ~torch.isnan(d)
+    count = valid.sum(dim=1)
+    z = torch.where(valid, d, torch.zeros_like(d))
+    none = torch.full_like(z[:, 0], float("nan"))
+    out[prefix + "_mean"] = torch.where(count > 0, z.sum(dim=1) / count.clamp_min(1), none)
+    out[prefix + "_rms"] = torch.where(count > 0, ((z * z).sum(dim=1) / count.clamp_min(1)).sqrt(), none)
+    out[prefix + "_max"] = torch.where(count > 0, torch.where(valid, d, torch.full_like(d, float("-inf"))).amax(dim=1), none)
+    return valid, count
+
+
+SURFACE_SAMPLE_SEED = 0x5F1D                                      # the seed of surface_fidelity's draw of the surface (draw 0)
+
+
+@torch.no_grad()
+def surface_fidelity(clouds, meshset, shape=None, samples=None, thresholds=(0.01, 0.02), visible_only=False):
+    """How well clouds (B,N,3) lie on, and cover, the surfaces of shape[c] of a meshes.MeshSet (PU-Net's P2F and the precision / recall of
+    Tatarchenko et al. 2019).  A dict of (B) fp64 tensors on the clouds' device:
+      accuracy_mean / _rms / _max      the distance (NOT squared) of the cloud's points to the surface (meshes.point_to_mesh: exact to the
+                                       triangles, no sampling floor)
+      completeness_mean / _rms / _max  the distance from `samples` points of the surface (MeshSet.sample, draw 0; default N) to the nearest
+                                       point of the cloud (the nn_distance kernel)
+      precision@t, recall@t, fscore@t  per threshold t: the share of the cloud's points within t of the surface, of the surface samples
+                                       within t of the cloud, and their harmonic mean (0 where both are 0)
+    and under "mean", a dict of the batch means of all of them as Python numbers.  Points that are not finite are left out of every
+    statistic."""
+    from .meshes import MeshSet, _shape_argument, point_to_mesh
+    from .structural_losses import nn_distance
+    if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.shape[2] != 3 or clouds.dtype != F32:
+        raise ValueError("surface_fidelity: clouds is a (B,N,3) float32 tensor")
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("surface_fidelity: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    B, N, _ = clouds.shape
+    samples = N if samples is None else int(samples)
+    if samples < 1:
+        raise ValueError("surface_fidelity: samples is a positive count, got %r" % (samples,))
+    thresholds = tuple(float(t) for t in thresholds)
+    if any(not (t > 0.0 and t < float("inf")) for t in thresholds):
+        raise ValueError("surface_fidelity: thresholds are positive and finite, got %r" % (thresholds,))
+    shape_h = _shape_argument(shape, B, meshset.S, "surface_fidelity")
+    if visible_only and meshset.visible is None:
+        raise ValueError("surface_fidelity: visible_only needs a mesh set built with visibility masks")
+    out = {}
+    d2, _ = point_to_mesh(clouds, meshset, shape_h, visible_only)
+    acc = d2.double().sqrt()
+    acc_valid, acc_count = _distance_summary(acc, "accuracy", out)
+    surface = meshset.sample(samples, SURFACE_SAMPLE_SEED, 0)[torch.from_numpy(shape_h).to(clouds.device)].contiguous()
+    finite = torch.isfinite(clouds).all(dim=2, keepdim=True)
+    far = torch.where(finite, clouds, torch.full_like(clouds, 1e18)).contiguous()          # a point that is not finite is nobody's neighbour
+    comp = nn_distance(surface, far)[0].double().sqrt()
+    _distance_summary(comp, "completeness", out)
+    for t in thresholds:
+        precision = (acc_valid & (acc <= t)).sum(dim=1).double() / acc_count.clamp_min(1)
+        recall = (comp <= t).sum(dim=1).double() / samples
+        both = precision + recall
+        out["precision@%g" % t], out["recall@%g" % t] = precision, recall
+        out["fscore@%g" % t] = torch.where(both > 0, 2 * precision * recall / both.clamp_min(1e-300), torch.zeros_like(both))
+    out["mean"] = {k: float(torch.nanmean(v)) for k, v in out.items()}
+    return out
+
+
 # ---------------------------------------------------------------------------- JSD (evaluation_metrics.py:206-321)
 def unit_cube_grid_point_cloud(resolution, clip_sphere=False, device="cpu"):
     """Cell centres of a resolution^3 grid over the unit cube (:206-224); clip_sphere keeps |c| <= 0.5."""

@@ -275,6 +275,41 @@ def repulsion_radii(radius, sizes):
     return [radius * (float(finest) / float(n)) ** 0.5 for n in sizes]
 
 
+class SurfaceDistance(Function):
+    """xyz (B,N,3) -> d2 (B,N), the squared distance of every point to the surface of its shape, as ONE autograd node over
+    meshes.point_to_mesh (csrc/meshdist.hip): the forward launch returns the closest points and saves them, the backward is the tensor
+    expression 2 g (p - closest), zero where d2 is NaN.  Nothing flows to the mesh."""
+
+    @staticmethod
+    def forward(ctx, xyz, meshset, shape, visible_only):
+        from .meshes import point_to_mesh
+        d2, face, closest = point_to_mesh(xyz, meshset, shape, visible_only, return_closest=True)
+        ctx.save_for_backward(xyz, closest, d2)
+        ctx.mark_non_differentiable(face)
+        return d2, face
+
+    @staticmethod
+    def backward(ctx, g, _):
+        xyz, closest, d2 = ctx.saved_tensors
+        dx = (2.0 * g)[..., None] * (xyz - closest)
+        return torch.where(torch.isnan(d2)[..., None], torch.zeros_like(dx), dx), None, None, None
+
+
+def surface_distance(xyz, meshset, shape=None, reduction="mean", visible_only=False):
+    """The squared distance of the points of xyz (B,N,3) to the surface of shape[c] of a meshes.MeshSet,
+    differentiable in xyz: d d2 / d p = 2 (p - closest point), exact wherever the closest point is unique (away from the medial axis).
+    reduction: "none" -> (B,N) with NaN at a point that is not finite; "sum" / "mean" -> over the points whose d2 is not NaN (0 where
+    there is none).  Unsigned, and not differentiable in the mesh."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError("surface_distance: reduction is 'none', 'sum' or 'mean', got %r" % (reduction,))
+    d2, _ = SurfaceDistance.apply(xyz, meshset, shape, bool(visible_only))
+    if reduction == "none":
+        return d2
+    valid = ~torch.isnan(d2)
+    total = torch.where(valid, d2, torch.zeros_like(d2)).sum()
+    return total if reduction == "sum" else total / valid.sum().clamp_min(1)
+
+
 def chamfer_sum(x, y, scale=1.0):
     """scale * ChamferLoss-style sum of both directions' minima (utils/chamfer_loss.py:16-20)."""
     return ChamferSum.apply(x, y, scale)

@@ -316,6 +316,25 @@ class MeshSet:
         return MeshSet(*(getattr(self, k).to(device).contiguous() for k in self._FIELDS), normalize=self.normalize,
                        visible=None if self.visible is None else self.visible.to(device).contiguous())
 
+    def in_frame(self, shift, scale):
+        """The same shapes with every vertex v of shape s at (v - shift[s]) / scale[s], in fp32 as data.normalize_clouds moves points:
+        shift (S,3), scale (S) tensors.  The frame of clouds that were drawn from this set and then normalised one by one (the reports'
+        reference clouds): a point drawn on a face stays within a few ulps of the moved face.  Faces, tables and masks are shared."""
+        import torch
+        shift = torch.as_tensor(shift, dtype=torch.float32, device=self.verts.device).reshape(self.S, 3)
+        scale = torch.as_tensor(scale, dtype=torch.float32, device=self.verts.device).reshape(self.S)
+        if not (torch.isfinite(shift).all() and torch.isfinite(scale).all() and (scale > 0).all()):
+            raise ValueError("MeshSet.in_frame: shifts are finite, scales finite and positive")
+        counts = (self.face_off[1:] - self.face_off[:-1]).long()
+        shape_of = torch.repeat_interleave(torch.arange(self.S, device=self.verts.device), counts)
+        owner = torch.full((self.V,), -1, dtype=torch.long, device=self.verts.device)
+        owner[self.faces.long().reshape(-1)] = shape_of.repeat_interleave(3)
+        used = owner >= 0
+        own = owner.clamp_min(0)
+        verts = torch.where(used[:, None], (self.verts - shift[own]) / scale[own][:, None], self.verts).contiguous()
+        return MeshSet(verts, self.faces, self.face_off, self.alias, self.shift + self.scale[:, None] * shift, self.scale * scale,
+                       normalize=self.normalize, visible=self.visible)
+
     def visible_stats(self):
         """What the masks leave out: {"faces", "hidden" (S) int64, "kept" (S) the share of every shape's area that is still drawn from,
         "total_faces", "total_hidden", "total_kept" (of the summed area)}; without masks nothing is hidden."""
@@ -345,6 +364,126 @@ class MeshSet:
                                                   _lib.ptr(self.alias), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF,
                                                   _lib.ptr(out), _lib.ptr(rec), _lib.stream_of(self.verts)), "pdgn_sample_surface")
         return (out, rec) if return_faces else out
+
+
+# ---------------------------------------------------------------------------- point-to-surface distance (csrc/meshdist.hip)
+SORT_POINTS = True                                               # the coherence options' defaults, each what measured faster at 10 k faces
+SORT_FACES = False                                               # (profiles/p2m_cost.txt): points in Morton order, faces as given
+
+
+def _morton30(x, lo, hi):
+    """int64 Morton codes of 10 bits per axis of x (...,3) inside the box [lo, hi] (broadcasting); a coordinate that is not finite counts
+    as the box's low side.  Only the ORDER the codes give is used, and no result depends on it."""
+    import torch
+    span = (hi - lo).clamp_min(1e-30)
+    q = (torch.nan_to_num((x - lo) / span, nan=0.0, posinf=0.0, neginf=0.0).clamp(0.0, 1.0) * 1023.0).to(torch.int64)
+    q = (q | (q << 16)) & 0x030000FF
+    q = (q | (q << 8)) & 0x0300F00F
+    q = (q | (q << 4)) & 0x030C30C3
+    q = (q | (q << 2)) & 0x09249249
+    return (q[..., 0] << 2) | (q[..., 1] << 1) | q[..., 2]
+
+
+def mesh_dist_records(meshset, visible_only=False, sort_faces=None):
+    """The prepared form of a mesh set for `point_to_mesh` (pdgn_mesh_dist_prepare), cached on the object per (visible_only, sort_faces):
+    {"records", "groups", "group_off", "G", "live"}.  live = face_areas > 0 in fp64, and under visible_only the set's masks != 0."""
+    import torch
+    from . import _lib
+    sort_faces = SORT_FACES if sort_faces is None else bool(sort_faces)
+    if visible_only and meshset.visible is None:
+        raise ValueError("point_to_mesh: visible_only needs a mesh set built with visibility masks")
+    cache = meshset.__dict__.setdefault("_mesh_dist", {})
+    key = (bool(visible_only), sort_faces)
+    if key in cache:
+        return cache[key]
+    L = _lib.lib()
+    group = L.pdgn_mesh_dist_group()
+    _lib.require(meshset.verts, "the mesh set's vertices", torch.float32, 2)
+    dev = meshset.verts.device
+    S, V, F = meshset.S, meshset.V, meshset.F
+    faces_h, off_h = meshset.faces.cpu().numpy().astype(np.int64), meshset.face_off.cpu().numpy().astype(np.int64)
+    live = face_areas(meshset.verts.cpu().numpy(), faces_h) > 0.0
+    if visible_only:
+        live &= meshset.visible.cpu().numpy() != 0
+    group_off = np.concatenate([[0], np.cumsum(-(-np.diff(off_h) // group))]).astype(np.int32)
+    G = int(group_off[-1])
+    order = None
+    if sort_faces:
+        centre = meshset.verts[meshset.faces.long()].mean(dim=1)                           # (F,3)
+        shape_of = torch.repeat_interleave(torch.arange(S, device=dev), torch.from_numpy(np.diff(off_h)).to(dev))
+        lo = torch.full((S, 3), float("inf"), device=dev).scatter_reduce(0, shape_of[:, None].expand(-1, 3), centre, "amin")
+        hi = torch.full((S, 3), float("-inf"), device=dev).scatter_reduce(0, shape_of[:, None].expand(-1, 3), centre, "amax")
+        code = (shape_of << 30) | _morton30(centre, lo[shape_of], hi[shape_of])
+        order = torch.argsort(code, stable=True).to(torch.int32).contiguous()
+    space = torch.empty(int(L.pdgn_mesh_dist_workspace_floats(S, F)), dtype=torch.float32, device=dev)
+    records, groups = space[:12 * F], space[12 * F:12 * F + 8 * G]
+    d_live, d_goff = torch.from_numpy(live.astype(np.int32)).to(dev), torch.from_numpy(group_off).to(dev)
+    _lib.check(L.pdgn_mesh_dist_prepare(S, V, F, G, _lib.ptr(meshset.verts), _lib.ptr(meshset.faces), _lib.ptr(meshset.face_off),
+                                        _lib.ptr(d_goff), _lib.ptr(d_live), _lib.ptr(order), _lib.ptr(records), _lib.ptr(groups),
+                                        _lib.stream_of(meshset.verts)), "pdgn_mesh_dist_prepare")
+    cache[key] = {"records": records, "groups": groups, "group_off": d_goff, "G": G, "live": live, "space": space}
+    return cache[key]
+
+
+def _shape_argument(shape, B, S, what):
+    """`shape` of point_to_mesh and its callers as a (B) int64 numpy array, checked."""
+    if shape is None:
+        if B != S:
+            raise ValueError("%s: %d clouds and %d shapes -- say which shape each cloud is measured against (shape=...)" % (what, B, S))
+        return np.arange(B, dtype=np.int64)
+    host = shape.detach().cpu().numpy() if hasattr(shape, "detach") else np.asarray(shape)
+    if host.ndim != 1 or host.shape[0] != B or host.dtype.kind not in "iu":
+        raise ValueError("%s: shape is (B) = (%d) integers, got %s %s" % (what, B, host.dtype, host.shape))
+    if host.size and (host.min() < 0 or host.max() >= S):
+        raise ValueError("%s: shape index %d, the mesh set has %d shapes" % (what, int(host.max() if host.max() >= S else host.min()), S))
+    return host.astype(np.int64)
+
+
+def point_to_mesh(xyz, meshset, shape=None, visible_only=False, cull=True, return_closest=False, sort_points=None, sort_faces=None):
+    """The closest point of a triangle set (pdgn_point_mesh_distance; the definition is the header block of csrc/meshdist.hip): xyz (B,N,3)
+    fp32 on the mesh set's device; shape (B) integers, the shape each cloud is measured against (repeats and any order; None: cloud c
+    against shape c, B == S) -> d2 (B,N) the least squared distance to a live face, face (B,N) int32 the global index of the face that
+    attains it (the lowest on ties)[, closest (B,N,3)]; NaN, -1, NaN for a point that is not finite.  Live: positive area and, under
+    visible_only, a visibility mask that is not 0 (the distance to the visible surface).  cull, sort_points (the points go to the kernel
+    in Morton order and the results are scattered back) and sort_faces (the records are in Morton order of the centroids) change no bit;
+    None: the module's defaults.  Unsigned; no autograd (losses.surface_distance is the differentiable form)."""
+    import torch
+    from . import _lib
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
+        raise ValueError("point_to_mesh: xyz is a (B,N,3) float32 tensor, got %s" % (
+            "%s %s" % (xyz.dtype, tuple(xyz.shape)) if isinstance(xyz, torch.Tensor) else type(xyz).__name__,))
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("point_to_mesh: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    B, N, _ = xyz.shape
+    if B < 1 or N < 1 or B * N > 0x7FFFFFFF:
+        raise ValueError("point_to_mesh: %d clouds of %d points; at least one point, and B N below 2^31" % (B, N))
+    shape_h = _shape_argument(shape, B, meshset.S, "point_to_mesh")
+    if visible_only and meshset.visible is None:
+        raise ValueError("point_to_mesh: visible_only needs a mesh set built with visibility masks")
+    if xyz.device != meshset.verts.device:
+        raise ValueError("point_to_mesh: xyz is on %s, the mesh set on %s" % (xyz.device, meshset.verts.device))
+    sort_points = SORT_POINTS if sort_points is None else bool(sort_points)
+    rec = mesh_dist_records(meshset, visible_only, sort_faces)
+    xyz = _lib.require(xyz.detach().contiguous(), "xyz", torch.float32, 3)
+    dev = xyz.device
+    perm = None
+    if sort_points and N > 1:
+        finite = torch.nan_to_num(xyz, nan=0.0, posinf=0.0, neginf=0.0)
+        perm = torch.argsort(_morton30(xyz, finite.amin(dim=1, keepdim=True), finite.amax(dim=1, keepdim=True)), dim=1, stable=True)
+        xyz = torch.gather(xyz, 1, perm[..., None].expand(-1, -1, 3)).contiguous()
+    d_shape = torch.from_numpy(shape_h.astype(np.int32)).to(dev)
+    d2 = torch.empty(B, N, dtype=torch.float32, device=dev)
+    face = torch.empty(B, N, dtype=torch.int32, device=dev)
+    closest = torch.empty(B, N, 3, dtype=torch.float32, device=dev) if return_closest else None
+    _lib.check(_lib.lib().pdgn_point_mesh_distance(B, N, meshset.S, meshset.F, rec["G"], _lib.ptr(xyz), _lib.ptr(d_shape),
+                                                   _lib.ptr(meshset.face_off), _lib.ptr(rec["group_off"]), _lib.ptr(rec["records"]),
+                                                   _lib.ptr(rec["groups"]), 1 if cull else 0, _lib.ptr(d2), _lib.ptr(face),
+                                                   _lib.ptr(closest), _lib.stream_of(xyz)), "pdgn_point_mesh_distance")
+    if perm is not None:
+        d2, face = torch.empty_like(d2).scatter_(1, perm, d2), torch.empty_like(face).scatter_(1, perm, face)
+        if return_closest:
+            closest = torch.empty_like(closest).scatter_(1, perm[..., None].expand(-1, -1, 3), closest)
+    return (d2, face, closest) if return_closest else (d2, face)
 
 
 # ---------------------------------------------------------------------------- directories and packed files
@@ -475,11 +614,71 @@ def split_meshset(root, split, normalize=None, visible=None):
     return MeshSet.from_arrays(verts, faces, face_off, normalize, visible=mask)
 
 
-USAGE = "usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]"
+USAGE = ("usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]\n"
+         "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--split val] [--device cuda]")
+
+
+def distance_table(result):
+    """The `surface_fidelity` dict as the lines `distance` prints: one row per cloud, then the batch means."""
+    cols = [k for k in result if k != "mean"]
+    lines = ["cloud " + " ".join("%22s" % k for k in cols)]
+    B = int(result[cols[0]].shape[0])
+    for c in range(B):
+        lines.append("%5d " % c + " ".join("%22.9g" % float(result[k][c]) for k in cols))
+    lines.append(" mean " + " ".join("%22.9g" % result["mean"][k] for k in cols))
+    return lines
+
+
+def _distance_main(argv):
+    """distance CLOUDS.npy MESHES.npz: CLOUDS (S,N,3) or (S,3,N); MESHES a file `pack` wrote (one split of it, raw geometry: the clouds
+    are in the meshes' frame) or one `MeshSet.save` wrote."""
+    import torch
+    from .evaluation import surface_fidelity
+    opts, rest = {"shape": None, "visible": False, "split": "val", "device": "cuda"}, list(argv[2:])
+    while rest:
+        flag = rest.pop(0)
+        if flag == "--visible":
+            opts["visible"] = True
+        elif flag in ("--shape", "--split", "--device") and rest:
+            opts[flag[2:]] = rest.pop(0)
+        else:
+            raise SystemExit(USAGE)
+    clouds = np.load(argv[0])
+    if clouds.ndim != 3 or 3 not in clouds.shape[1:]:
+        raise SystemExit("%s: clouds are (S,N,3) or (S,3,N), got %s" % (argv[0], clouds.shape))
+    if clouds.shape[2] != 3:
+        clouds = clouds.transpose(0, 2, 1)
+    shape = None
+    if opts["shape"] is not None:
+        try:
+            shape = np.asarray([int(s) for s in opts["shape"].split(",")], dtype=np.int64)
+        except ValueError:
+            raise SystemExit("--shape takes integers separated by commas\n" + USAGE) from None
+    with np.load(argv[1]) as f:
+        packed = any(k.count("/") == 2 for k in f.files)
+    if packed:
+        root = open_mesh_root(argv[1])
+        if opts["visible"] and not has_stored_visible(root, opts["split"]):
+            raise SystemExit("--visible: %s holds no visibility masks for its %r split (pack --visible writes them)" % (argv[1], opts["split"]))
+        try:
+            ms = split_meshset(root, opts["split"], visible="stored" if opts["visible"] else None)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+    else:
+        ms = MeshSet.load(argv[1])
+    dev = torch.device(opts["device"])
+    try:
+        result = surface_fidelity(torch.from_numpy(np.ascontiguousarray(clouds, dtype=np.float32)).to(dev), ms.to(dev), shape,
+                                  visible_only=opts["visible"])
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    print("\n".join(distance_table(result)))
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) >= 3 and argv[0] == "distance":
+        return _distance_main(argv[1:])
     if len(argv) < 3 or argv[0] != "pack":
         raise SystemExit(USAGE)
     opts, rest, given = {"views": 26, "resolution": 128}, argv[3:], False

@@ -203,3 +203,32 @@ def to_meshset(verts, faces, vert_off, face_off, normalize=None):
     f = _host(faces).astype(np.int64).reshape(-1, 3)
     voff, foff = _host(vert_off).astype(np.int64), _host(face_off).astype(np.int64)
     return MeshSet.from_arrays(_host(verts), f + np.repeat(voff[:-1], np.diff(foff))[:, None], foff, normalize)
+
+
+MESH_ERROR_SEED = 0x3E5E                                          # the seed of mesh_error's two draws (draw 0 of each set)
+
+
+@torch.no_grad()
+def mesh_error(verts, faces, vert_off, face_off, meshset, shape=None, samples=4096):
+    """The two-sided sampled distance between reconstructed meshes (surface_nets' verts, faces, vert_off, face_off: B meshes) and the
+    surfaces they came from (shape[c] of `meshset`, on the device; None: mesh c against shape c): `samples` points of each surface are
+    measured against the other (MeshSet.sample, then meshes.point_to_mesh).  -> a dict of (B) fp64 tensors, distances (not squared):
+    to_reference_mean / _rms / _max (from the reconstruction to the reference surface) and to_reconstruction_mean / _rms / _max."""
+    from .evaluation import _distance_summary
+    from .meshes import MeshSet, _shape_argument, point_to_mesh
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("mesh_error: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    B = int(_host(face_off).shape[0]) - 1
+    if B < 1 or int(_host(vert_off).shape[0]) != B + 1:
+        raise ValueError("mesh_error: vert_off and face_off are (B+1) prefix sums over at least one mesh")
+    if int(samples) < 1:
+        raise ValueError("mesh_error: samples is a positive count, got %r" % (samples,))
+    shape_h = _shape_argument(shape, B, meshset.S, "mesh_error")
+    dev = meshset.verts.device
+    ours = to_meshset(verts, faces, vert_off, face_off).to(dev)
+    out = {}
+    mine = ours.sample(int(samples), MESH_ERROR_SEED, 0)
+    _distance_summary(point_to_mesh(mine, meshset, shape_h)[0].double().sqrt(), "to_reference", out)
+    theirs = meshset.sample(int(samples), MESH_ERROR_SEED, 0)[torch.from_numpy(shape_h).to(dev)].contiguous()
+    _distance_summary(point_to_mesh(theirs, ours)[0].double().sqrt(), "to_reconstruction", out)
+    return out

@@ -218,6 +218,7 @@ def quick_metrics(generator, ref_pcs, batch_size, normalize=None, rng=None, cach
         generator.train(was_training)
     M_rs = ev.pairwise_cd(gen_pcs, ref_pcs)
     M_ss = ev.pairwise_cd(gen_pcs, gen_pcs)
+    cache["generated"] = (gen_pcs, M_rs)                         # (for SnapshotReporter(fidelity=...): the clouds and their Chamfer matrix)
     results = ev.reduce_metrics(M_rs.t(), cache["M_rr"], M_rs, M_ss, "CD")
     results["jsd"] = ev.jensen_shannon_divergence(ev.entropy_of_occupancy_grid(gen_pcs, 28, True)[1], cache["ref_counters"])
     return results
@@ -237,13 +238,21 @@ class SnapshotReporter:
     metrics.csv is what it was.  lit=True: the sheet's columns are shaded by surface normals estimated from each cloud's 16 nearest
     neighbours (render_sheet(normals="estimate")) instead of by depth.  surface=True: every report also appends epoch,
     gen sv_mean, gen sv_p90, val sv_mean, val sv_p90, gen degenerate -- evaluation.surface_stats of the same generated clouds and of the
-    reference clouds -- to `<out_dir>/surface.csv`.  With neither, every file is what it was."""
+    reference clouds -- to `<out_dir>/surface.csv`.  With neither, every file is what it was.  fidelity=meshset: a
+    meshes.MeshSet on the reference clouds' device whose shape c is the surface reference cloud c was drawn from, in the clouds' own frame
+    (MeshSet.in_frame) -- the constructor measures the reference clouds against it and refuses a set they do not lie on.  Every report then
+    appends epoch, gen acc_mean, gen acc_rms, gen acc_max, val acc_mean, val acc_rms, val acc_max to `<out_dir>/fidelity.csv`: the distance
+    of every generated cloud's points to the surface of the validation shape nearest to it in the Chamfer matrix the report computes anyway
+    (meshes.point_to_mesh; per cloud, then averaged over the clouds), and the same of the reference clouds against their own shapes -- the
+    floor, a few ulps of the coordinates."""
+    FIDELITY_HEADER = ("epoch", "gen acc_mean", "gen acc_rms", "gen acc_max", "val acc_mean", "val acc_rms", "val acc_max")
+    FIDELITY_FLOOR_ULPS = 256.0                                  # the kernel's own bound (64) and the roundings of the sampler and of the frame
 
     SPACING_HEADER = ("epoch", "gen nn_mean", "gen nn_cv", "val nn_mean", "val nn_cv", "gen duplicates")
     SURFACE_HEADER = ("epoch", "gen sv_mean", "gen sv_p90", "val sv_mean", "val sv_p90", "gen degenerate")
 
     def __init__(self, trainer, ref_pcs, out_dir, every, batch_size, normalize, seed, rows=8, full=False, rank=0, cell=128, radius=1, emd="approx",
-                 spacing=False, lit=False, surface=False):
+                 spacing=False, lit=False, surface=False, fidelity=None):
         _lib.require(ref_pcs, "ref_pcs", torch.float32, 3)
         self.trainer, self.ref, self.out_dir = trainer, ref_pcs, str(out_dir)
         self.every, self.batch_size, self.normalize, self.seed = int(every), int(batch_size), normalize, int(seed)
@@ -263,6 +272,29 @@ class SnapshotReporter:
         self.last_spacing = None                                 # (epoch, generated clouds' stats, reference clouds' stats)
         self.lit, self.surface = bool(lit), bool(surface)
         self.last_surface = None                                 # (epoch, generated clouds' stats, reference clouds' stats)
+        self.fidelity, self.last_fidelity = fidelity, None       # last: (epoch, generated clouds' (mean, rms, max), reference clouds')
+        if fidelity is not None:
+            self.fidelity_floor = self._check_fidelity(fidelity)
+
+    def _accuracy(self, clouds, shape=None):
+        """(mean, rms, max) of the clouds' distance to their shapes of self.fidelity, per cloud and then averaged over the clouds."""
+        from .evaluation import _distance_summary
+        from .meshes import point_to_mesh
+        out = {}
+        d2, _ = point_to_mesh(clouds.contiguous(), self.fidelity, shape, visible_only=self.fidelity.visible is not None)
+        _distance_summary(d2.double().sqrt(), "acc", out)
+        return tuple(float(torch.nanmean(out[k])) for k in ("acc_mean", "acc_rms", "acc_max"))
+
+    def _check_fidelity(self, fidelity):
+        from .meshes import MeshSet
+        if not isinstance(fidelity, MeshSet) or fidelity.S != self.ref.shape[0] or fidelity.verts.device != self.ref.device:
+            raise ValueError("fidelity must be a MeshSet of the %d reference clouds' shapes on their device" % self.ref.shape[0])
+        floor = self._accuracy(self.ref)
+        most = max(float(self.ref.abs().max()), float(fidelity.verts[fidelity.faces.long().reshape(-1)].abs().max()))
+        if not floor[2] <= self.FIDELITY_FLOOR_ULPS * 2.0 ** -24 * most:
+            raise ValueError("fidelity: the reference clouds do not lie on the mesh set's shapes (largest distance %.3g, coordinates up to %.3g): "
+                             "it must hold the shapes the clouds are draw 0 of, in the clouds' frame (MeshSet.in_frame)" % (floor[2], most))
+        return floor
 
     def _generator(self, offset):
         return torch.Generator(device=self.ref.device).manual_seed(self.seed + offset)
@@ -293,8 +325,12 @@ class SnapshotReporter:
                     results = quick_metrics(G, self.ref, self.batch_size, self.normalize, self._generator(1), self.cache)
                 results = {k: float(results[k]) for k in self.keys}
                 image = sheet.cpu().numpy()
-                if self.spacing or self.surface:
+                if self.spacing or self.surface or (self.fidelity is not None and self.full):
                     gen_pcs, _ = ev.generate_clouds(G, self.ref.shape[0], self.batch_size, self.normalize, self._generator(1), dev)
+                if self.fidelity is not None:
+                    # the clouds the metrics were computed on and their Chamfer matrix (the quick metrics keep both; the full ones do not)
+                    clouds, M_rs = (gen_pcs, ev.pairwise_cd(gen_pcs, self.ref)) if self.full else self.cache["generated"]
+                    fidelity = (self._accuracy(clouds, M_rs.argmin(dim=1)), self.fidelity_floor)
                 if self.spacing:
                     if "val_spacing" not in self.cache:          # (the reference set does not change between reports)
                         self.cache["val_spacing"] = ev.spacing_stats(self.ref, self.batch_size)
@@ -336,6 +372,15 @@ class SnapshotReporter:
                 f.write(",".join([str(epoch)] + ["%.9g" % v for v in (gen["sv_mean"], gen["sv_p90"], val["sv_mean"], val["sv_p90"])]
                                  + ["%d" % gen["degenerate"]]) + "\n")
             self.last_surface = (epoch, gen, val)
+        if self.fidelity is not None:
+            gen, val = fidelity
+            path = os.path.join(self.out_dir, "fidelity.csv")
+            fresh = not os.path.exists(path) or os.path.getsize(path) == 0
+            with open(path, "a") as f:
+                if fresh:
+                    f.write(",".join(self.FIDELITY_HEADER) + "\n")
+                f.write(",".join([str(epoch)] + ["%.9g" % v for v in gen + val]) + "\n")
+            self.last_fidelity = (epoch, gen, val)
         return self.last
 
 

@@ -44,6 +44,8 @@ of up to 64 clouds the feeder itself produces, and printed; repulsion.csv beside
 append nearest-neighbour spacing statistics of the generated and the val clouds to report/spacing.csv.  --report_lit: the preview sheets are shaded by
 surface normals estimated from each cloud's 16 nearest neighbours; --report_surface: the reports also append the surface
 variation of the generated and the val clouds to report/surface.csv (both need --report_every).
+--report_fidelity (needs --report_every and a mesh --data_root): the reports also append to report/fidelity.csv the distance of the generated
+clouds' points to the surface of the nearest val shape, and of the val clouds to their own shapes (meshes.point_to_mesh).
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -143,6 +145,9 @@ def build_parser():
                    "the generated and of the val clouds to report/spacing.csv (evaluation.spacing_stats); needs --report_every")
     p.add_argument("--report_lit", action="store_true", default=argparse.SUPPRESS, help="preview sheets shaded by surface normals (two-sided headlight "
                    "shading, normals from the 16 nearest neighbours: pointops.estimate_normals) instead of by depth; needs --report_every")
+    p.add_argument("--report_fidelity", action="store_true", default=argparse.SUPPRESS, help="reports also append the distance of the generated "
+                   "clouds' points to the surface of the nearest val shape, and of the val clouds to their own, to report/fidelity.csv "
+                   "(meshes.point_to_mesh); needs --report_every and a mesh --data_root")
     p.add_argument("--report_surface", action="store_true", default=argparse.SUPPRESS, help="reports also append the surface variation "
                    "lambda0 / (lambda0 + lambda1 + lambda2) of the generated and of the val clouds to report/surface.csv (evaluation.surface_stats); "
                    "needs --report_every")
@@ -208,6 +213,7 @@ class Args(argparse.Namespace):
     report_spacing = False
     report_lit = False
     report_surface = False
+    report_fidelity = False
 
 
 def parse_args(argv=None):
@@ -305,7 +311,7 @@ def parse_args(argv=None):
             p.error("--repulsion: --num_point %d, the all-pairs kernel holds at most 8192 points" % args.num_point)
     if args.report_spacing and not args.report_every:
         p.error("--report_spacing needs --report_every")
-    for flag in ("report_lit", "report_surface"):
+    for flag in ("report_lit", "report_surface", "report_fidelity"):
         if getattr(args, flag) and not args.report_every:
             p.error("--%s needs --report_every" % flag)
     if args.d_augment_target is None:
@@ -554,6 +560,18 @@ def reference_clouds(args, split, device, mesh_root=None, ragged_root=None):
     return normalize_point_clouds(_visible_meshset(args, mesh_root, split, None, device).to(device).sample(args.num_point, args.seed, draw=0), args.normalize).contiguous()
 
 
+def reference_clouds_and_meshset(args, split, device, mesh_root):
+    """`reference_clouds` of a mesh root and the split's MeshSet in those clouds' frame (MeshSet.in_frame with the shift and scale the
+    normalisation gave every cloud): what SnapshotReporter(fidelity=...) takes.  The clouds are the same bits."""
+    from .data import normalize_clouds
+    ms = _visible_meshset(args, mesh_root, split, None, device).to(device)
+    raw = ms.sample(args.num_point, args.seed, draw=0)
+    if args.normalize is None:
+        return raw.contiguous(), ms
+    clouds, shift, scale = normalize_clouds(raw, args.normalize)
+    return clouds.contiguous(), ms.in_frame(shift.reshape(-1, 3), scale.reshape(-1))
+
+
 def init_dist(device):
     """(rank, world): from the process group under torch.distributed.run, else (0, 1)."""
     import torch.distributed as dist
@@ -685,11 +703,19 @@ def train(args):
     reporter = None
     if args.report_every > 0 and rank == 0:
         from .report import SnapshotReporter
-        val = reference_clouds(args, "val", device, mesh_root, ragged_root)
+        val_meshset = None
+        if args.report_fidelity:
+            if mesh_root is None:
+                raise SystemExit("--report_fidelity: %s holds point clouds -- the distance is measured to the faces of the val meshes; give a "
+                                 "mesh --data_root or drop the flag" % args.data_root)
+            val, val_meshset = reference_clouds_and_meshset(args, "val", device, mesh_root)
+        else:
+            val = reference_clouds(args, "val", device, mesh_root, ragged_root)
         reporter = SnapshotReporter(trainer, val, os.path.join(run_dir, "report"), args.report_every, args.batch_size, args.normalize,
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd,
                                     **({"spacing": True} if args.report_spacing else {}), **({"lit": True} if args.report_lit else {}),
-                                    **({"surface": True} if args.report_surface else {}))
+                                    **({"surface": True} if args.report_surface else {}),
+                                    **({"fidelity": val_meshset} if val_meshset is not None else {}))
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
                        grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
