@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 46
+#define PDGN_ABI_VERSION 47
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1397,6 +1397,38 @@ int pdgn_mesh_dist_prepare(int S, int V, int F, int G, const float *verts, const
 int pdgn_point_mesh_distance(int b, int n, int S, int F, int G, const float *xyz, const int32_t *shape, const int32_t *face_off,
                              const int32_t *group_off, const float *records, const float *groups, int cull, float *d2, int32_t *face,
                              float *closest, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ generalized winding numbers (csrc/winding.hip)
+ * Inside / outside of a triangle set (Jacobson et al. 2013): for every point of xyz (b,n,3) the solid angles that the live faces of shape
+ * shape[c] subtend at it are summed.  Per face, h_f is half the signed solid angle by the van Oosterom-Strackee formula in the fp32
+ * operation order that the header block of csrc/winding.hip states (tests/winding_mirror.py spells it in numpy; the two agree bit for
+ * bit), t_f = llrint((double)h_f 2^32), and per point
+ *   T       (b,n) int64: the sum of t_f;  INT64_MIN for a point with a non-finite coordinate and where any face gave a non-finite h_f;
+ *           0 for a shape with no live face
+ *   w       (b,n) fp32: (float)((double)T K), K the double nearest 1 / (2^33 pi): the winding number;  NaN (0x7FC00000) where T is INT64_MIN
+ *   inside  (b,n) int32 or NULL: T >= pdgn_winding_half_turn() = llrint(pi 2^32), which is w >= 1/2
+ * A sum of integers: the record order, the split over workgroups, the point order and the launch geometry change no bit.  No reference
+ * counterpart.
+ *   records    what pdgn_mesh_dist_prepare wrote for the same S, F and face_off (the group boxes are not used); 16-byte aligned
+ *   shape      (b) int32 as for pdgn_point_mesh_distance: an index outside [0, S) counts as a shape with no live face
+ *   splits     k >= 1: the chunks of pdgn_mesh_dist_chunk() record slots of each shape are divided over exactly k workgroups per run of
+ *              points;  0: the library takes pdgn_winding_splits(b, n, F) -- F is the bound on a shape's face count that this call has; a
+ *              caller that knows the largest face count of the shapes it names asks pdgn_winding_splits with it and passes the answer
+ *   workspace  pdgn_winding_workspace_bytes(b, n, F, splits) bytes, 8-byte aligned: one int64 per point and part, each written before it is
+ *              read (nothing to zero); may be NULL where that is 0 (one part)
+ * One thread per point, a workgroup per run of 256 points of a cloud and part; one launch on `stream` for one part, a second small one
+ * that adds the parts otherwise.  No atomics, nothing allocated.
+ * pdgn_winding_splits(b, n, faces): host only; ceil(2048 / (b ceil(n / 256))) -- eight workgroups for each of 256 CUs -- at most
+ * ceil(faces / 256) / 2 and 4096, at least 1.  pdgn_winding_workspace_bytes: host only; 8 parts b n, 0 for one part.  Both PDGN_ERR_INVALID
+ * for sizes the entry point refuses.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: S, F, b or n < 1, F > 2^28, b n >= 2^31, splits outside 0 .. 4096,
+ * b ceil(n / 256) parts > 2^23, a null pointer other than inside (and workspace for one part), a pointer not 4-byte aligned (records:
+ * 16-byte; workspace, T: 8-byte). */
+long long pdgn_winding_half_turn(void);
+int pdgn_winding_splits(int b, int n, int faces);
+long long pdgn_winding_workspace_bytes(int b, int n, int F, int splits);
+int pdgn_winding_number(int b, int n, int S, int F, const float *xyz, const int32_t *shape, const int32_t *face_off, const float *records,
+                        int splits, long long *workspace, long long *T, float *w, int32_t *inside, pdgn_stream_t stream);
 
 #ifdef __cplusplus
 }

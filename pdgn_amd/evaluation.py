@@ -9,6 +9,7 @@ temporaries, tens of thousands of pairs per launch.  MMD / COV / 1-NNA are the r
 torch reductions over those matrices.
 """
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -259,7 +260,7 @@ SURFACE_SAMPLE_SEED = 0x5F1D                                      # the seed of 
 
 
 @torch.no_grad()
-def surface_fidelity(clouds, meshset, shape=None, samples=None, thresholds=(0.01, 0.02), visible_only=False):
+def surface_fidelity(clouds, meshset, shape=None, samples=None, thresholds=(0.01, 0.02), visible_only=False, signed=False):
     """How well clouds (B,N,3) lie on, and cover, the surfaces of shape[c] of a meshes.MeshSet (PU-Net's P2F and the precision / recall of
     Tatarchenko et al. 2019).  A dict of (B) fp64 tensors on the clouds' device:
       accuracy_mean / _rms / _max      the distance (NOT squared) of the cloud's points to the surface (meshes.point_to_mesh: exact to the
@@ -269,8 +270,11 @@ def surface_fidelity(clouds, meshset, shape=None, samples=None, thresholds=(0.01
       precision@t, recall@t, fscore@t  per threshold t: the share of the cloud's points within t of the surface, of the surface samples
                                        within t of the cloud, and their harmonic mean (0 where both are 0)
     and under "mean", a dict of the batch means of all of them as Python numbers.  Points that are not finite are left out of every
-    statistic."""
-    from .meshes import MeshSet, _shape_argument, point_to_mesh
+    statistic.  signed=True (shapes that `meshes.winding_report` calls closed) adds
+      inside_fraction                  the share of the cloud's points whose winding number is at least one half
+      signed_mean                      the mean of the distance, negated at those points: which side of the surface the cloud errs on
+    after the other keys, which keep their values."""
+    from .meshes import MeshSet, _shape_argument, _winding, point_to_mesh
     from .structural_losses import nn_distance
     if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.shape[2] != 3 or clouds.dtype != F32:
         raise ValueError("surface_fidelity: clouds is a (B,N,3) float32 tensor")
@@ -301,8 +305,42 @@ def surface_fidelity(clouds, meshset, shape=None, samples=None, thresholds=(0.01
         both = precision + recall
         out["precision@%g" % t], out["recall@%g" % t] = precision, recall
         out["fscore@%g" % t] = torch.where(both > 0, 2 * precision * recall / both.clamp_min(1e-300), torch.zeros_like(both))
+    if signed:
+        inside = (_winding(clouds, meshset, shape_h, visible_only, None, None, "surface_fidelity")[2] != 0) & acc_valid
+        none = torch.full_like(acc[:, 0], float("nan"))
+        out["inside_fraction"] = torch.where(acc_count > 0, inside.sum(dim=1).double() / acc_count.clamp_min(1), none)
+        z = torch.where(acc_valid, torch.where(inside, -acc, acc), torch.zeros_like(acc))
+        out["signed_mean"] = torch.where(acc_count > 0, z.sum(dim=1) / acc_count.clamp_min(1), none)
     out["mean"] = {k: float(torch.nanmean(v)) for k, v in out.items()}
     return out
+
+
+# ---------------------------------------------------------------------------- volume overlap (no reference counterpart)
+@torch.no_grad()
+def volume_iou(meshset_a, meshset_b, shape_a=None, shape_b=None, resolution=64, bounds=None):
+    """Volumetric intersection over union of shape_a[c] of one meshes.MeshSet and shape_b[c] of another (None: all of a set's shapes, in
+    order): both occupancies (meshes.occupancy_grid: the winding number at the cell centres) on ONE grid of `resolution` cells per axis
+    per pair -- bounds = (lo, hi) as for occupancy_grid, or None: the union of the two shapes' boxes, grown by 5 % of its longest side
+    and made cubic.  -> {"iou" (B) fp64 = intersection / union (NaN where the union is empty), "intersection", "union", "count_a",
+    "count_b" (B) int64: counts of cells}, on the sets' device.  A ratio of integer counts: nothing in it depends on an order."""
+    from .meshes import MeshSet, _occupancy, _resolution_argument, _shape_list, bounds_grid, cubic_grid, shape_boxes
+    if not isinstance(meshset_a, MeshSet) or not isinstance(meshset_b, MeshSet):
+        raise ValueError("volume_iou: both sets are MeshSets, got %s and %s" % (type(meshset_a).__name__, type(meshset_b).__name__))
+    R = _resolution_argument(resolution, "volume_iou")
+    sa, sb = _shape_list(shape_a, meshset_a.S, "volume_iou"), _shape_list(shape_b, meshset_b.S, "volume_iou")
+    if sa.shape[0] != sb.shape[0] or sa.shape[0] < 1:
+        raise ValueError("volume_iou: %d shapes against %d -- the pairs are shape_a[c] with shape_b[c]" % (sa.shape[0], sb.shape[0]))
+    if meshset_a.verts.device != meshset_b.verts.device:
+        raise ValueError("volume_iou: the sets are on %s and %s" % (meshset_a.verts.device, meshset_b.verts.device))
+    if bounds is None:
+        (alo, ahi), (blo, bhi) = shape_boxes(meshset_a, sa), shape_boxes(meshset_b, sb)
+        origin, voxel = cubic_grid(np.minimum(alo, blo), np.maximum(ahi, bhi), R, 0.05)
+    else:
+        origin, voxel = bounds_grid(bounds, sa.shape[0], R)
+    a, b = _occupancy(meshset_a, sa, R, origin, voxel).flatten(1), _occupancy(meshset_b, sb, R, origin, voxel).flatten(1)
+    inter, union = (a & b).sum(dim=1), (a | b).sum(dim=1)
+    iou = torch.where(union > 0, inter.double() / union.clamp_min(1).double(), torch.full_like(inter, float("nan"), dtype=torch.float64))
+    return {"iou": iou, "intersection": inter, "union": union, "count_a": a.sum(dim=1), "count_b": b.sum(dim=1)}
 
 
 # ---------------------------------------------------------------------------- JSD (evaluation_metrics.py:206-321)

@@ -9,6 +9,10 @@ proportional to its area from one 8-byte load -- normalised in closed form over 
 Visible-surface sampling: `face_visibility` asks the device which faces some view of a ring can see
 (csrc/visible.hip: pdgn_mesh_visibility); a `MeshSet` built with `visible=mask` gives the others weight zero wherever the area is used,
 so they are never drawn.  `pack --visible` stores the masks beside the meshes.
+
+Distances and sides (DESIGN.md sections 7t and 7u): `point_to_mesh` is the closest point of a shape's faces (csrc/meshdist.hip),
+`winding_number` the generalized winding number about them (csrc/winding.hip) -- 1 inside a closed, consistently oriented shape, 0
+outside -- and on the two `signed_distance`, `occupancy_grid` and `winding_report`; the commands `distance`, `occupancy` and `check`.
 """
 import os
 import sys
@@ -486,6 +490,197 @@ def point_to_mesh(xyz, meshset, shape=None, visible_only=False, cull=True, retur
     return (d2, face, closest) if return_closest else (d2, face)
 
 
+# ---------------------------------------------------------------------------- generalized winding numbers (csrc/winding.hip)
+def _winding(xyz, meshset, shape, visible_only, sort_points, splits, what):
+    """The checks and the launch of `winding_number` -> (T (B,N) int64, w (B,N) fp32, inside (B,N) int32), all from the kernel."""
+    import torch
+    from . import _lib
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
+        raise ValueError("%s: xyz is a (B,N,3) float32 tensor, got %s" % (
+            what, "%s %s" % (xyz.dtype, tuple(xyz.shape)) if isinstance(xyz, torch.Tensor) else type(xyz).__name__))
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("%s: meshset is a MeshSet, got %s" % (what, type(meshset).__name__))
+    B, N, _ = xyz.shape
+    if B < 1 or N < 1 or B * N > 0x7FFFFFFF:
+        raise ValueError("%s: %d clouds of %d points; at least one point, and B N below 2^31" % (what, B, N))
+    shape_h = _shape_argument(shape, B, meshset.S, what)
+    if visible_only and meshset.visible is None:
+        raise ValueError("%s: visible_only needs a mesh set built with visibility masks" % what)
+    if xyz.device != meshset.verts.device:
+        raise ValueError("%s: xyz is on %s, the mesh set on %s" % (what, xyz.device, meshset.verts.device))
+    splits = 0 if splits is None else int(splits)
+    if splits < 0:
+        raise ValueError("%s: splits is None or 0 (the library chooses) or a count of parts, got %d" % (what, splits))
+    sort_points = SORT_POINTS if sort_points is None else bool(sort_points)
+    rec = mesh_dist_records(meshset, visible_only)
+    L = _lib.lib()
+    if splits == 0:                                              # from the largest face count among the shapes named, which the host knows
+        counts = meshset.__dict__.get("_face_counts")
+        if counts is None:
+            counts = meshset.__dict__["_face_counts"] = np.diff(meshset.face_off.cpu().numpy().astype(np.int64))
+        splits = L.pdgn_winding_splits(B, N, max(1, int(counts[shape_h].max())))
+        _lib.check(min(splits, 0), "pdgn_winding_splits")
+    xyz = _lib.require(xyz.detach().contiguous(), "xyz", torch.float32, 3)
+    dev = xyz.device
+    perm = None
+    if sort_points and N > 1:
+        finite = torch.nan_to_num(xyz, nan=0.0, posinf=0.0, neginf=0.0)
+        perm = torch.argsort(_morton30(xyz, finite.amin(dim=1, keepdim=True), finite.amax(dim=1, keepdim=True)), dim=1, stable=True)
+        xyz = torch.gather(xyz, 1, perm[..., None].expand(-1, -1, 3)).contiguous()
+    d_shape = torch.from_numpy(shape_h.astype(np.int32)).to(dev)
+    nbytes = L.pdgn_winding_workspace_bytes(B, N, meshset.F, splits)
+    _lib.check(min(nbytes, 0), "pdgn_winding_workspace_bytes")
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev) if nbytes else None
+    T = torch.empty(B, N, dtype=torch.int64, device=dev)
+    w = torch.empty(B, N, dtype=torch.float32, device=dev)
+    inside = torch.empty(B, N, dtype=torch.int32, device=dev)
+    _lib.check(L.pdgn_winding_number(B, N, meshset.S, meshset.F, _lib.ptr(xyz), _lib.ptr(d_shape), _lib.ptr(meshset.face_off),
+                                     _lib.ptr(rec["records"]), splits, _lib.ptr(work), _lib.ptr(T), _lib.ptr(w), _lib.ptr(inside),
+                                     _lib.stream_of(xyz)), "pdgn_winding_number")
+    if perm is not None:
+        T, w, inside = (torch.empty_like(t).scatter_(1, perm, t) for t in (T, w, inside))
+    return T, w, inside
+
+
+def winding_number(xyz, meshset, shape=None, visible_only=False, sort_points=None, splits=None, return_sum=False):
+    """The generalized winding number (pdgn_winding_number; the definition is the header block of csrc/winding.hip): xyz (B,N,3) fp32 on
+    the mesh set's device; shape, visible_only and sort_points as for `point_to_mesh` -> w (B,N) fp32: 1 inside a closed, consistently
+    oriented shape, 0 outside, NaN for a point that is not finite[, T (B,N) int64: the sum of the faces' half solid angles in units of
+    2^-32, of which w is a rounding; INT64_MIN where w is NaN].  splits: None / 0, the library divides a shape's faces over as many
+    workgroups as cover the chip; k: exactly k parts.  Neither it nor sort_points changes a bit.  No autograd."""
+    T, w, _ = _winding(xyz, meshset, shape, visible_only, sort_points, splits, "winding_number")
+    return (w, T) if return_sum else w
+
+
+def signed_distance(xyz, meshset, shape=None, visible_only=False):
+    """(sd (B,N) fp32, face (B,N) int32, inside (B,N) bool): sqrt(d2) of `point_to_mesh`, negated where the winding number is at least
+    one half (the kernel's integer comparison); NaN, -1, False for a point that is not finite.  The sign means something on shapes whose
+    faces are consistently oriented (`winding_report`)."""
+    import torch
+    d2, face = point_to_mesh(xyz, meshset, shape, visible_only)
+    inside = _winding(xyz, meshset, shape, visible_only, None, None, "signed_distance")[2] != 0
+    d = torch.sqrt(d2)
+    return torch.where(inside, -d, d), face, inside
+
+
+def _shape_list(shape, S, what):
+    """A list of shapes to work on (None: all S of them) as an int64 numpy array, checked like `_shape_argument`."""
+    if shape is None:
+        return np.arange(S, dtype=np.int64)
+    host = shape.detach().cpu().numpy() if hasattr(shape, "detach") else np.asarray(shape)
+    if host.size < 1:
+        raise ValueError("%s: shape names at least one shape" % what)
+    return _shape_argument(host.reshape(-1) if host.ndim == 0 else host, int(host.size), S, what)
+
+
+def shape_boxes(meshset, shape=None, visible_only=False):
+    """(lo, hi) float64 numpy (S',3): the boxes of the vertices of the live faces of the shapes `shape` (None: all of them)."""
+    shape_h = _shape_list(shape, meshset.S, "shape_boxes")
+    live = mesh_dist_records(meshset, visible_only)["live"]
+    verts, faces = meshset.verts.cpu().numpy().astype(np.float64), meshset.faces.cpu().numpy().astype(np.int64)
+    off = meshset.face_off.cpu().numpy().astype(np.int64)
+    lo, hi = np.zeros((shape_h.shape[0], 3)), np.zeros((shape_h.shape[0], 3))
+    for k, s in enumerate(shape_h):
+        f = faces[off[s]:off[s + 1]][live[off[s]:off[s + 1]]]
+        if f.shape[0]:
+            lo[k], hi[k] = verts[f.reshape(-1)].min(axis=0), verts[f.reshape(-1)].max(axis=0)
+    return lo, hi
+
+
+def cubic_grid(lo, hi, resolution, pad):
+    """(origin (S',3) fp32, voxel (S') fp32) of R cells per axis over the boxes [lo, hi] (S',3) grown by `pad` of their longest side on
+    every side and made cubic about their centres, in float64, rounded at the end."""
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(-1, 3), np.asarray(hi, dtype=np.float64).reshape(-1, 3)
+    side = (hi - lo).max(axis=1) * (1.0 + 2.0 * float(pad))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (side > 0).all()):
+        raise ValueError("occupancy_grid: every box is finite and has an extent")
+    return ((lo + hi) / 2.0 - side[:, None] / 2.0).astype(np.float32), (side / int(resolution)).astype(np.float32)
+
+
+def bounds_grid(bounds, count, resolution):
+    """`cubic_grid` without padding of a caller's bounds = (lo, hi), each (3) or (count,3): the grid starts at lo."""
+    try:
+        lo, hi = (np.broadcast_to(np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64), (count, 3)) for x in bounds)
+    except (TypeError, ValueError):
+        raise ValueError("occupancy_grid: bounds is a pair (lo, hi), each (3) or (%d,3)" % count) from None
+    side = (hi - lo).max(axis=1)
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (side > 0).all()):
+        raise ValueError("occupancy_grid: every box is finite and has an extent")
+    return np.ascontiguousarray(lo, dtype=np.float32), (side / int(resolution)).astype(np.float32)
+
+
+OCCUPANCY_SLAB_POINTS = 1 << 22                                   # queries per launch of occupancy_grid, over all its shapes
+
+
+def _occupancy(meshset, shape_h, resolution, origin, voxel, visible_only=False):
+    """occ (S',R,R,R) bool on the device: T >= half a turn at the cell centres origin + (i + 0.5) voxel (the fp32 product, then the fp32
+    sum), index order (x, y, z); planes of x in slabs of at most OCCUPANCY_SLAB_POINTS queries."""
+    import torch
+    from . import _lib
+    dev = meshset.verts.device
+    R, Sq = int(resolution), int(shape_h.shape[0])
+    half = _lib.lib().pdgn_winding_half_turn()
+    o, v = torch.from_numpy(np.ascontiguousarray(origin, dtype=np.float32)).to(dev), torch.from_numpy(np.ascontiguousarray(voxel, dtype=np.float32)).to(dev)
+    axes = (torch.arange(R, dtype=torch.float32, device=dev) + 0.5)[None, :, None] * v[:, None, None] + o[:, None, :]      # (S',R,3)
+    occ = torch.empty(Sq, R, R, R, dtype=torch.bool, device=dev)
+    planes = max(1, min(R, OCCUPANCY_SLAB_POINTS // (Sq * R * R)))
+    for x0 in range(0, R, planes):
+        k = min(planes, R - x0)
+        q = torch.stack([axes[:, x0:x0 + k, 0][:, :, None, None].expand(Sq, k, R, R), axes[:, :, 1][:, None, :, None].expand(Sq, k, R, R),
+                         axes[:, :, 2][:, None, None, :].expand(Sq, k, R, R)], dim=-1).reshape(Sq, k * R * R, 3).contiguous()
+        T = _winding(q, meshset, shape_h, visible_only, False, None, "occupancy_grid")[0]
+        occ[:, x0:x0 + k] = (T >= half).reshape(Sq, k, R, R)
+    return occ
+
+
+def _resolution_argument(resolution, what):
+    R = int(resolution)
+    if R < 1 or R > 1024:
+        raise ValueError("%s: resolution is 1 .. 1024 cells per axis, got %r" % (what, resolution))
+    return R
+
+
+def occupancy_grid(meshset, shape=None, resolution=64, bounds=None, pad=0.05, visible_only=False):
+    """Which cells of a grid lie inside a shape (the winding number at the cell centres, `winding_number`'s integer comparison):
+    -> (occ (S',R,R,R) bool indexed (shape, x, y, z), origin (S',3) fp32, voxel (S') fp32), cell (i, j, k)'s centre being
+    origin + (i + 0.5, j + 0.5, k + 0.5) voxel.  shape: the shapes to grid (None: all).  bounds: (lo, hi), each (3) or (S',3) -- the grid
+    starts at lo and its cubic cells are the longest side / R wide; None: every shape's own box, grown by `pad` of its longest side on
+    every side and made cubic.  The queries go out in slabs of planes, so the memory taken besides the result stays bounded."""
+    import torch
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("occupancy_grid: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    R = _resolution_argument(resolution, "occupancy_grid")
+    shape_h = _shape_list(shape, meshset.S, "occupancy_grid")
+    if visible_only and meshset.visible is None:
+        raise ValueError("occupancy_grid: visible_only needs a mesh set built with visibility masks")
+    if bounds is None:
+        origin, voxel = cubic_grid(*shape_boxes(meshset, shape_h, visible_only), R, pad)
+    else:
+        origin, voxel = bounds_grid(bounds, shape_h.shape[0], R)
+    occ = _occupancy(meshset, shape_h, R, origin, voxel, visible_only)
+    dev = meshset.verts.device
+    return occ, torch.from_numpy(origin).to(dev), torch.from_numpy(voxel).to(dev)
+
+
+def winding_report(meshset, samples=4096, seed=0):
+    """Whether the shapes of a set are closed and consistently oriented enough for the signed quantities to mean anything: per shape, the
+    winding number at `samples` uniform points of its box (grown by 5 % of its longest side) -> {"w_min", "w_max" (S) float64 numpy,
+    "fractional" (S): the share of the points with |w - rint(w)| > 0.05}.  A watertight, outward-oriented shape gives 0, 1 and a share
+    of 0 up to the points that fall within a hair of the surface; flipped or missing faces show as values in between."""
+    import torch
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("winding_report: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    if int(samples) < 1:
+        raise ValueError("winding_report: samples is a positive count, got %r" % (samples,))
+    lo, hi = shape_boxes(meshset)
+    grow = 0.05 * (hi - lo).max(axis=1, keepdims=True)
+    u = torch.rand(meshset.S, int(samples), 3, dtype=torch.float64, generator=torch.Generator().manual_seed(int(seed)))
+    pts = (torch.from_numpy(lo - grow)[:, None, :] + u * torch.from_numpy(hi - lo + 2 * grow)[:, None, :]).float().to(meshset.verts.device)
+    w = winding_number(pts.contiguous(), meshset).double()
+    frac = ((w - torch.round(w)).abs() > 0.05).double().mean(dim=1)
+    return {"w_min": w.amin(dim=1).cpu().numpy(), "w_max": w.amax(dim=1).cpu().numpy(), "fractional": frac.cpu().numpy()}
+
+
 # ---------------------------------------------------------------------------- directories and packed files
 def read_obj_root(root, synsetids=None):
     """A directory <synsetid>/<split>/*.obj -> {synsetid: {split: (verts, faces GLOBAL within the split, face_off)}}, the files of a
@@ -615,7 +810,9 @@ def split_meshset(root, split, normalize=None, visible=None):
 
 
 USAGE = ("usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]\n"
-         "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--split val] [--device cuda]")
+         "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--signed] [--split val] [--device cuda]\n"
+         "       python -m pdgn_amd.meshes occupancy MESHES.npz OUT.npz --resolution R [--shape I,J,...] [--visible] [--split val] [--device cuda]\n"
+         "       python -m pdgn_amd.meshes check MESHES.npz [--samples N] [--split val] [--device cuda]")
 
 
 def distance_table(result):
@@ -629,56 +826,109 @@ def distance_table(result):
     return lines
 
 
-def _distance_main(argv):
-    """distance CLOUDS.npy MESHES.npz: CLOUDS (S,N,3) or (S,3,N); MESHES a file `pack` wrote (one split of it, raw geometry: the clouds
-    are in the meshes' frame) or one `MeshSet.save` wrote."""
-    import torch
-    from .evaluation import surface_fidelity
-    opts, rest = {"shape": None, "visible": False, "split": "val", "device": "cuda"}, list(argv[2:])
+def _options(rest, opts, flags=(), valued=("--shape", "--split", "--device")):
+    """The commands' options: `flags` set opts[name] = True, `valued` take the next word."""
+    rest = list(rest)
     while rest:
         flag = rest.pop(0)
-        if flag == "--visible":
-            opts["visible"] = True
-        elif flag in ("--shape", "--split", "--device") and rest:
+        if flag in flags:
+            opts[flag[2:]] = True
+        elif flag in valued and rest:
             opts[flag[2:]] = rest.pop(0)
         else:
             raise SystemExit(USAGE)
+    return opts
+
+
+def _shape_option(text):
+    if text is None:
+        return None
+    try:
+        return np.asarray([int(s) for s in text.split(",")], dtype=np.int64)
+    except ValueError:
+        raise SystemExit("--shape takes integers separated by commas\n" + USAGE) from None
+
+
+def _open_meshset(path, split, visible):
+    """MESHES.npz of the commands: a file `pack` wrote (one split of it, raw geometry) or one `MeshSet.save` wrote."""
+    with np.load(path) as f:
+        packed = any(k.count("/") == 2 for k in f.files)
+    if not packed:
+        return MeshSet.load(path)
+    root = open_mesh_root(path)
+    if visible and not has_stored_visible(root, split):
+        raise SystemExit("--visible: %s holds no visibility masks for its %r split (pack --visible writes them)" % (path, split))
+    try:
+        return split_meshset(root, split, visible="stored" if visible else None)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+
+
+def _distance_main(argv):
+    """distance CLOUDS.npy MESHES.npz: CLOUDS (S,N,3) or (S,3,N), in the meshes' frame."""
+    import torch
+    from .evaluation import surface_fidelity
+    opts = _options(argv[2:], {"shape": None, "visible": False, "signed": False, "split": "val", "device": "cuda"}, ("--visible", "--signed"))
     clouds = np.load(argv[0])
     if clouds.ndim != 3 or 3 not in clouds.shape[1:]:
         raise SystemExit("%s: clouds are (S,N,3) or (S,3,N), got %s" % (argv[0], clouds.shape))
     if clouds.shape[2] != 3:
         clouds = clouds.transpose(0, 2, 1)
-    shape = None
-    if opts["shape"] is not None:
-        try:
-            shape = np.asarray([int(s) for s in opts["shape"].split(",")], dtype=np.int64)
-        except ValueError:
-            raise SystemExit("--shape takes integers separated by commas\n" + USAGE) from None
-    with np.load(argv[1]) as f:
-        packed = any(k.count("/") == 2 for k in f.files)
-    if packed:
-        root = open_mesh_root(argv[1])
-        if opts["visible"] and not has_stored_visible(root, opts["split"]):
-            raise SystemExit("--visible: %s holds no visibility masks for its %r split (pack --visible writes them)" % (argv[1], opts["split"]))
-        try:
-            ms = split_meshset(root, opts["split"], visible="stored" if opts["visible"] else None)
-        except ValueError as e:
-            raise SystemExit(str(e)) from None
-    else:
-        ms = MeshSet.load(argv[1])
+    shape = _shape_option(opts["shape"])
+    ms = _open_meshset(argv[1], opts["split"], opts["visible"])
     dev = torch.device(opts["device"])
     try:
         result = surface_fidelity(torch.from_numpy(np.ascontiguousarray(clouds, dtype=np.float32)).to(dev), ms.to(dev), shape,
-                                  visible_only=opts["visible"])
+                                  visible_only=opts["visible"], **({"signed": True} if opts["signed"] else {}))
     except ValueError as e:
         raise SystemExit(str(e)) from None
     print("\n".join(distance_table(result)))
+
+
+def _occupancy_main(argv):
+    """occupancy MESHES.npz OUT.npz --resolution R: OUT holds "occupancy" (S',ceil(R^3 / 8)) uint8 -- np.packbits of every shape's (R,R,R)
+    grid in (x, y, z) order -- with "resolution", "origin" (S',3), "voxel" (S') and "shape" (S')."""
+    import torch
+    opts = _options(argv[2:], {"shape": None, "visible": False, "resolution": None, "split": "val", "device": "cuda"}, ("--visible",),
+                    ("--shape", "--split", "--device", "--resolution"))
+    if opts["resolution"] is None or not opts["resolution"].isdigit():
+        raise SystemExit("occupancy takes --resolution R\n" + USAGE)
+    shape = _shape_option(opts["shape"])
+    ms = _open_meshset(argv[0], opts["split"], opts["visible"]).to(torch.device(opts["device"]))
+    try:
+        occ, origin, voxel = occupancy_grid(ms, shape, int(opts["resolution"]), visible_only=opts["visible"])
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    occ = occ.cpu().numpy()
+    np.savez(argv[1], occupancy=np.packbits(occ.reshape(occ.shape[0], -1), axis=1), resolution=np.asarray(occ.shape[1]),
+             origin=origin.cpu().numpy(), voxel=voxel.cpu().numpy(), shape=np.arange(ms.S) if shape is None else shape)
+    print("%d grids of %d^3 cells into %s; cells inside: %s" % (occ.shape[0], occ.shape[1], argv[1],
+                                                              " ".join(str(int(c)) for c in occ.reshape(occ.shape[0], -1).sum(axis=1))))
+
+
+def _check_main(argv):
+    """check MESHES.npz: `winding_report`, one row per shape."""
+    import torch
+    opts = _options(argv[1:], {"samples": "4096", "split": "val", "device": "cuda"}, (), ("--samples", "--split", "--device"))
+    if not opts["samples"].isdigit():
+        raise SystemExit(USAGE)
+    ms = _open_meshset(argv[0], opts["split"], False).to(torch.device(opts["device"]))
+    rep = winding_report(ms, int(opts["samples"]))
+    print("shape %12s %12s %12s" % ("w_min", "w_max", "fractional"))
+    for c in range(ms.S):
+        print("%5d %12.6f %12.6f %12.4f" % (c, rep["w_min"][c], rep["w_max"][c], rep["fractional"][c]))
+    print("worst fractional share %.4f: %s" % (rep["fractional"].max(), "closed and consistently oriented" if rep["fractional"].max() <= 0.01
+                                               else "open, self-intersecting or inconsistently oriented shapes: signs are not to be trusted"))
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if len(argv) >= 3 and argv[0] == "distance":
         return _distance_main(argv[1:])
+    if len(argv) >= 3 and argv[0] == "occupancy":
+        return _occupancy_main(argv[1:])
+    if len(argv) >= 2 and argv[0] == "check":
+        return _check_main(argv[1:])
     if len(argv) < 3 or argv[0] != "pack":
         raise SystemExit(USAGE)
     opts, rest, given = {"views": 26, "resolution": 128}, argv[3:], False

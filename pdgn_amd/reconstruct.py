@@ -209,13 +209,16 @@ MESH_ERROR_SEED = 0x3E5E                                          # the seed of 
 
 
 @torch.no_grad()
-def mesh_error(verts, faces, vert_off, face_off, meshset, shape=None, samples=4096):
+def mesh_error(verts, faces, vert_off, face_off, meshset, shape=None, samples=4096, signed=False, iou_resolution=64):
     """The two-sided sampled distance between reconstructed meshes (surface_nets' verts, faces, vert_off, face_off: B meshes) and the
     surfaces they came from (shape[c] of `meshset`, on the device; None: mesh c against shape c): `samples` points of each surface are
     measured against the other (MeshSet.sample, then meshes.point_to_mesh).  -> a dict of (B) fp64 tensors, distances (not squared):
-    to_reference_mean / _rms / _max (from the reconstruction to the reference surface) and to_reconstruction_mean / _rms / _max."""
-    from .evaluation import _distance_summary
-    from .meshes import MeshSet, _shape_argument, point_to_mesh
+    to_reference_mean / _rms / _max (from the reconstruction to the reference surface) and to_reconstruction_mean / _rms / _max.
+    signed=True (the reference shapes closed and consistently oriented) adds to_reference_signed_mean -- the same
+    distances as to_reference_mean, negated where the sample lies inside the reference: positive means the reconstruction lies outside
+    -- and iou, evaluation.volume_iou of the two on iou_resolution cells per axis."""
+    from .evaluation import _distance_summary, volume_iou
+    from .meshes import MeshSet, _shape_argument, _winding, point_to_mesh
     if not isinstance(meshset, MeshSet):
         raise ValueError("mesh_error: meshset is a MeshSet, got %s" % type(meshset).__name__)
     B = int(_host(face_off).shape[0]) - 1
@@ -228,7 +231,13 @@ def mesh_error(verts, faces, vert_off, face_off, meshset, shape=None, samples=40
     ours = to_meshset(verts, faces, vert_off, face_off).to(dev)
     out = {}
     mine = ours.sample(int(samples), MESH_ERROR_SEED, 0)
-    _distance_summary(point_to_mesh(mine, meshset, shape_h)[0].double().sqrt(), "to_reference", out)
+    to_reference = point_to_mesh(mine, meshset, shape_h)[0].double().sqrt()
+    _distance_summary(to_reference, "to_reference", out)
     theirs = meshset.sample(int(samples), MESH_ERROR_SEED, 0)[torch.from_numpy(shape_h).to(dev)].contiguous()
     _distance_summary(point_to_mesh(theirs, ours)[0].double().sqrt(), "to_reconstruction", out)
+    if signed:
+        inside = _winding(mine, meshset, shape_h, False, None, None, "mesh_error")[2] != 0
+        _distance_summary(torch.where(inside, -to_reference, to_reference), "to_reference_signed", out)
+        del out["to_reference_signed_rms"], out["to_reference_signed_max"]
+        out["iou"] = volume_iou(ours, meshset, None, shape_h, iou_resolution)["iou"]
     return out
