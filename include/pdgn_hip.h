@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 47
+#define PDGN_ABI_VERSION 48
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1170,6 +1170,30 @@ int pdgn_render_sheet(int rows, int cols, const float *const *clouds, const int 
  * normals[c] that is not 4-byte aligned; all checked before anything is launched. */
 int pdgn_render_sheet_lit(int rows, int cols, const float *const *clouds, const float *const *normals, const int *npoints, int channel_major,
                           const float *view, const float *light, int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
+/* pdgn_render_sheet_mesh: a sheet whose columns are each a cloud list or a list of TRIANGLE MESHES (csrc/render_mesh.hip, DESIGN.md
+ * section 7v; no reference counterpart).  Column c is a mesh column where mesh_verts[c] is not NULL; every other column is a cloud column
+ * and clouds[c], normals[c], npoints[c], channel_major bit c and radius mean what they mean in pdgn_render_sheet_lit (of a mesh column
+ * they are not read).  All the mesh_* arguments are HOST arrays of `cols` entries, per column:
+ *   mesh_verts   device (mesh_nverts[c], 3) fp32
+ *   mesh_faces   device (mesh_nfaces[c], 3) int32
+ *   mesh_range   device (rows, 3) int32: (first face, face count, vertex base) of the row's mesh.  The faces first .. first + count - 1,
+ *                clipped to [0, mesh_nfaces[c]), are drawn; the base is added to each of their indices (surface-nets output: indices
+ *                local to their cloud, base = vert_off[row]; a packed mesh set: global indices, base 0).  A count <= 0 draws nothing.
+ *   mesh_mask    device (mesh_nfaces[c]) int32 or NULL: a face whose word is 0 is skipped
+ *   mesh_shade   0: flat-lit, one shade per face from its fp32 normal and `light`; 1: depth, 255 - (q >> 17) of the pixel's own depth
+ * The triangles are rasterised exactly, in integers, after a snap to 4 sub-pixel bits (the definition: the head of csrc/render_mesh.hip;
+ * tests/mesh_render_mirror.py spells it in numpy) into the same key buffer under the same key q << 8 | shade and the same integer minimum
+ * as the points: a vertex and a point at the same place land on the same pixel with the same q, and the image is bitwise repeatable
+ * and independent of the order of the faces.  Launches on `stream`: pdgn_render_sheet's clear, pdgn_render_sheet_lit's splat over the
+ * cloud columns (skipped where there are none), the triangle kernel over the mesh columns, pdgn_render_sheet's resolve.  workspace and
+ * image as in pdgn_render_sheet.  PDGN_ERR_INVALID: whatever pdgn_render_sheet_lit refuses of the sheet and of a cloud column, a null
+ * mesh_* array other than mesh_mask, no mesh column at all, and of a mesh column a null range pointer, a null faces pointer beside a
+ * face count above 0, a misaligned verts, faces, range or mask pointer, a vertex count outside [1, 2^28], a face count outside
+ * [0, 2^28] or a shade that is not 0 or 1; all checked before anything is launched. */
+int pdgn_render_sheet_mesh(int rows, int cols, const float *const *clouds, const float *const *normals, const int *npoints, int channel_major,
+                           const float *const *mesh_verts, const int32_t *const *mesh_faces, const int32_t *const *mesh_range,
+                           const int32_t *const *mesh_mask, const int *mesh_nverts, const int *mesh_nfaces, const int *mesh_shade,
+                           const float *view, const float *light, int cell, int radius, void *workspace, uint8_t *image, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ exact EMD (csrc/auction.hip)
  * The assignment problem between two clouds of n points each, cost |a_i - b_j| (Euclidean, what pdgn_matchcost sums), solved in

@@ -13,6 +13,9 @@
 // two-sided headlight shading, c = |n . l| as (nx lx + ny ly) + nz lz with every operation rounded on its own, 0 where !(c >= 0), 1 where
 // c > 1, shade = 48 + (unsigned)(207 c) -- under the same key, the same atomicMin and the same clear and resolve kernels; a column without
 // normals takes the depth shade above, byte for byte.  tests/normals_mirror.py spells it.
+//
+// pdgn_render_sheet_mesh (the second half of this file): columns of triangle meshes beside the columns of clouds, rasterised exactly in
+// integers into the same keys.  Its definition heads that half; tests/mesh_render_mirror.py spells it.
 #include "common.h"
 
 #define RENDER_THREADS 256
@@ -194,6 +197,259 @@ extern "C" int pdgn_render_sheet_lit(int rows, int cols, const float *const *clo
     const int quads = cdiv(cdiv(total, 4), RENDER_THREADS);
     hipLaunchKernelGGL(render_clear_kernel, dim3(quads), dim3(RENDER_THREADS), 0, (hipStream_t)stream, a.key, total);
     hipLaunchKernelGGL(render_splat_lit_kernel, dim3(cdiv(nmax, RENDER_THREADS), rows, cols), dim3(RENDER_THREADS), 0, (hipStream_t)stream, la);
+    hipLaunchKernelGGL(render_resolve_kernel, dim3(quads), dim3(RENDER_THREADS), 0, (hipStream_t)stream, a.key, image, total);
+    return pdgn_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// pdgn_render_sheet_mesh: the same sheet with columns of TRIANGLE MESHES beside the columns of clouds.  The launch
+// sequence is the clear above, render_splat_lit_kernel over the cloud columns (skipped where there are none), render_mesh_kernel over the
+// mesh columns, the resolve above: one key buffer, one key, one integer minimum; a column is one kind or the other.
+//
+// THE DEFINITION (normative; tests/mesh_render_mirror.py spells the same function in numpy).  A mesh column has verts (V,3) fp32, faces
+// (F,3) int32, range (rows,3) int32 = (first, count, base) per row, an optional mask (F) int32 and a shade mode.  Row b draws the faces
+// f in [max(first, 0), min(first + count, F)); a count <= 0 draws nothing.
+//   Dead.   Face f is skipped where mask[f] == 0, or where one of i_k + base (k = 0, 1, 2; the sum taken in 64 bits) lies outside [0, V).
+//   Snap.   Per vertex p = verts[i_k + base]: u, v, d from the 3 x 4 view by exactly the __fmaf_rn chain of render_splat_kernel.  A
+//           u, v or d that is not finite kills the face.  With s = 16 cell (exact in fp32):
+//             X = (int) clamp(rintf(u * 16), -s, 2 s)    pixel units with 4 sub-pixel bits, a guard band of one cell either side
+//             Y likewise from v;     Z = min((unsigned)(clamp(d, 0, 1) * 16777216.f), 0xffffff)      the splat's q
+//           (rintf rounds halves to even; u * 16 is one fp32 product, +-inf where it overflows, which the clamp takes.)  After the snap
+//           nothing is floating point but the flat shade.
+//   Cover.  With edge(A, B, P) = (B.x - A.x)(P.y - A.y) - (B.y - A.y)(P.x - A.x) in int64:  A2 = edge(P0, P1, P2); where A2 < 0, P1 and
+//           P2 (and their Z) change places and A2 its sign; A2 = 0 draws nothing.  The pixel centres C = ((2 px + 1) 8, (2 py + 1) 8) of
+//           the face's bounding box, clipped to 0 <= px, py < cell of the face's OWN cell, are COVERED where w0 = edge(P1, P2, C), w1 =
+//           edge(P2, P0, C) and w2 = edge(P0, P1, C) are all >= 0: edges inclusive, faces two-sided, exactly as csrc/visible.hip, so two
+//           faces on a shared edge leave no hole and the minimum decides.  There
+//             q = floor((w0 Z0 + w1 Z1 + w2 Z2) / A2),   key = q << 8 | shade,   key buffer <- min(key buffer, key).
+//           BOUND: coordinates span at most 48 cell <= 3 * 2^16 (cell <= 4096), so every edge function is below 2^37 in magnitude, A2 < 2^37
+//           and the numerator below 2^37 2^24 = 2^61; the quotient is at most 2^24 - 1.  The division is exact: an fp64 estimate (off by
+//           less than one) corrected by the integer remainder, as vis_div of csrc/visible.hip.
+//   Shade.  Depth (mode 1): 255 - (q >> 17) from the pixel's own q.  Flat-lit (mode 0), one value per face from the fp32 vertices as
+//           handed in, before any swap: e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 (nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz =
+//           e1x e2y - e1y e2x), every subtraction, product and sum rounded on its own, never contracted; len = sqrtf((nx nx + ny ny) + nz nz),
+//           correctly rounded; c = fabsf((nx lx + ny ly) + nz lz) / len (the correctly rounded quotient); c = 0 where !(c >= 0), c = 1
+//           where c > 1; shade = 48 + (unsigned)(207 c): the lit splat's constants and light vector.  A len that is 0 or not finite kills
+//           the face (flat-lit columns only).  Equal depths from two faces resolve to the smaller key, the darker shade: still
+//           independent of the order of the faces.
+// LIMITS.  A face with a vertex on the guard band's clamp is drawn distorted (the vertex is moved onto the band's edge).  A face that
+// covers no pixel centre draws nothing: no wireframe, no anti-aliasing.  The normal of a face whose edge products underflow in fp32 is
+// lost (len = 0: the face is not drawn in a flat-lit column).
+//
+// THE KERNEL.  Grid (chunks, rows, cols), 256 threads; a workgroup takes the faces of its row 256 at a time, striding by the grid, a lane
+// per face.  A face whose clipped box holds at most MESH_SMALL_BOX pixels is rasterised by its lane (a surface-nets face at R = 64 in a
+// 128-pixel cell covers a handful); a larger one goes to an LDS list that, after a barrier, whole waves sweep with their lanes striding
+// over the box (one face of a CAD mesh can cover the cell: 16 384 centres, 256 per lane).  The keys go to the key buffer in global memory
+// with atomicMin, as the splat's do.  No float atomics: two runs agree bit for bit.
+#define MESH_THREADS 256
+#define MESH_WAVES (MESH_THREADS / PDGN_WAVE)
+#define MESH_SMALL_BOX 32
+#define MESH_MAX_CHUNKS 64
+
+struct RenderMeshArgs {
+    const float *verts[RENDER_MAX_COLS];                         // null: not a mesh column
+    const int32_t *faces[RENDER_MAX_COLS], *range[RENDER_MAX_COLS], *mask[RENDER_MAX_COLS];
+    int V[RENDER_MAX_COLS], F[RENDER_MAX_COLS];
+    int depth_shade;                                             // bit c: column c is shaded by depth
+    int rows, cols, cell;
+    float m[12], l[3];
+    unsigned *key;
+};
+
+struct MeshFace {
+    int x0, y0, z0, x1, y1, z1, x2, y2, z2;
+    int bx, by, bw, bh;                                          // the clipped pixel box; bw * bh = 0: no centre to look at
+    long long a2;
+    double ra2;
+    unsigned shade;
+};
+
+__device__ __forceinline__ long long mesh_edge(int ax, int ay, int bx, int by, int px, int py) {
+    return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
+}
+
+// Project and snap one vertex.  False: u, v or d is not finite.
+__device__ __forceinline__ bool mesh_snap(const float *m, float s, const float *p, int &X, int &Y, int &Z) {
+    const float x = p[0], y = p[1], z = p[2];
+    const float u = __fmaf_rn(m[2], z, __fmaf_rn(m[1], y, __fmaf_rn(m[0], x, m[3])));
+    const float v = __fmaf_rn(m[6], z, __fmaf_rn(m[5], y, __fmaf_rn(m[4], x, m[7])));
+    const float d = __fmaf_rn(m[10], z, __fmaf_rn(m[9], y, __fmaf_rn(m[8], x, m[11])));
+    if (!(fabsf(u) <= 3.4028234e38f && fabsf(v) <= 3.4028234e38f && fabsf(d) <= 3.4028234e38f)) return false;
+    X = (int)fminf(fmaxf(rintf(__fmul_rn(u, 16.f)), -s), 2.f * s);
+    Y = (int)fminf(fmaxf(rintf(__fmul_rn(v, 16.f)), -s), 2.f * s);
+    const float dc = fminf(fmaxf(d, 0.f), 1.f);
+    Z = (int)min((unsigned)(dc * 16777216.f), 0xffffffu);
+    return true;
+}
+
+// Gather, snap and shade face f of column c.  False: the face is dead.
+__device__ __forceinline__ bool mesh_load(const RenderMeshArgs &a, int c, int base, int f, MeshFace &t) {
+    if (a.mask[c] && a.mask[c][f] == 0) return false;
+    const int32_t *fi = a.faces[c] + 3 * (size_t)f;
+    const long long i0 = (long long)fi[0] + base, i1 = (long long)fi[1] + base, i2 = (long long)fi[2] + base;
+    const long long V = a.V[c];
+    if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) return false;
+    const float *q0 = a.verts[c] + 3 * (size_t)i0, *q1 = a.verts[c] + 3 * (size_t)i1, *q2 = a.verts[c] + 3 * (size_t)i2;
+    const float p0[3] = {q0[0], q0[1], q0[2]}, p1[3] = {q1[0], q1[1], q1[2]}, p2[3] = {q2[0], q2[1], q2[2]};
+    const float s = (float)(a.cell << 4);
+    if (!mesh_snap(a.m, s, p0, t.x0, t.y0, t.z0) || !mesh_snap(a.m, s, p1, t.x1, t.y1, t.z1) || !mesh_snap(a.m, s, p2, t.x2, t.y2, t.z2))
+        return false;
+    t.shade = 0;
+    if (!((a.depth_shade >> c) & 1)) {
+        const float ux = __fsub_rn(p1[0], p0[0]), uy = __fsub_rn(p1[1], p0[1]), uz = __fsub_rn(p1[2], p0[2]);
+        const float vx = __fsub_rn(p2[0], p0[0]), vy = __fsub_rn(p2[1], p0[1]), vz = __fsub_rn(p2[2], p0[2]);
+        const float nx = __fsub_rn(__fmul_rn(uy, vz), __fmul_rn(uz, vy));
+        const float ny = __fsub_rn(__fmul_rn(uz, vx), __fmul_rn(ux, vz));
+        const float nz = __fsub_rn(__fmul_rn(ux, vy), __fmul_rn(uy, vx));
+        const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+        if (!(len > 0.f && len <= 3.4028234e38f)) return false;                      // (false for a NaN too)
+        float lit = __fdiv_rn(fabsf(__fadd_rn(__fadd_rn(__fmul_rn(nx, a.l[0]), __fmul_rn(ny, a.l[1])), __fmul_rn(nz, a.l[2]))), len);
+        lit = lit >= 0.f ? lit : 0.f;
+        lit = lit > 1.f ? 1.f : lit;
+        t.shade = 48u + (unsigned)__fmul_rn(207.f, lit);
+    }
+    t.a2 = mesh_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+    if (t.a2 < 0) {
+        int w;
+        w = t.x1, t.x1 = t.x2, t.x2 = w;
+        w = t.y1, t.y1 = t.y2, t.y2 = w;
+        w = t.z1, t.z1 = t.z2, t.z2 = w;
+        t.a2 = -t.a2;
+    }
+    t.bw = t.bh = 0, t.bx = t.by = 0, t.ra2 = 0.0;
+    if (t.a2 != 0) {
+        // the centres (2 p + 1) 8 inside [lo, hi]: p from ceil((lo - 8) / 16) to floor((hi - 8) / 16), clipped to the cell
+        const int xlo = min(t.x0, min(t.x1, t.x2)), xhi = max(t.x0, max(t.x1, t.x2));
+        const int ylo = min(t.y0, min(t.y1, t.y2)), yhi = max(t.y0, max(t.y1, t.y2));
+        const int px0 = max((xlo + 7) >> 4, 0), px1 = min((xhi - 8) >> 4, a.cell - 1);
+        const int py0 = max((ylo + 7) >> 4, 0), py1 = min((yhi - 8) >> 4, a.cell - 1);
+        if (px1 >= px0 && py1 >= py0) t.bx = px0, t.by = py0, t.bw = px1 - px0 + 1, t.bh = py1 - py0 + 1;
+        t.ra2 = 1.0 / (double)t.a2;
+    }
+    return true;
+}
+
+// floor(num / den) for 0 <= num < 2^61, 0 < den < 2^37 and a quotient below 2^24: the fp64 estimate is off by less than one
+__device__ __forceinline__ long long mesh_div(long long num, long long den, double rden) {
+    long long q = (long long)((double)num * rden);
+    long long r = num - q * den;
+    if (r < 0) --q, r += den;
+    if (r >= den) ++q;
+    return q;
+}
+
+// The pixels start, start + step, ... (row-major in the box) of face t, minima into the cell's keys (cellkey: the cell's first pixel).
+__device__ __forceinline__ void mesh_scan(const MeshFace &t, unsigned *cellkey, size_t width, bool depth, int start, int step) {
+    const int n = t.bw * t.bh;
+    const int qy = step / t.bw, qx = step - qy * t.bw;
+    int iy = start / t.bw, ix = start - iy * t.bw;
+    for (int k = start; k < n; k += step) {
+        const int px = t.bx + ix, py = t.by + iy;
+        const int cx = (2 * px + 1) << 3, cy = (2 * py + 1) << 3;
+        const long long w0 = mesh_edge(t.x1, t.y1, t.x2, t.y2, cx, cy);
+        const long long w1 = mesh_edge(t.x2, t.y2, t.x0, t.y0, cx, cy);
+        const long long w2 = t.a2 - w0 - w1;                     // = edge(P0, P1, C): the three sum to A2 identically
+        if ((w0 | w1 | w2) >= 0) {
+            const unsigned q = (unsigned)mesh_div(w0 * t.z0 + w1 * t.z1 + w2 * t.z2, t.a2, t.ra2);
+            atomicMin(cellkey + (size_t)py * width + px, (q << 8) | (depth ? 255u - (q >> 17) : t.shade));
+        }
+        ix += qx, iy += qy;
+        if (ix >= t.bw) ix -= t.bw, ++iy;
+    }
+}
+
+__global__ __launch_bounds__(MESH_THREADS) void render_mesh_kernel(RenderMeshArgs a) {
+    __shared__ int s_list[MESH_THREADS];
+    __shared__ int s_cnt[2];
+    const int c = blockIdx.z, b = blockIdx.y;
+    if (!a.verts[c]) return;                                     // a cloud column (the whole workgroup leaves)
+    const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int32_t *rg = a.range[c] + 3 * (size_t)b;
+    const int first = rg[0], count = rg[1], vbase = rg[2];
+    const long long f0 = max(first, 0), f1 = min((long long)first + max(count, 0), (long long)a.F[c]);
+    const bool depth = (a.depth_shade >> c) & 1;
+    const size_t width = (size_t)a.cols * a.cell;
+    unsigned *cellkey = a.key + ((size_t)b * a.cell) * width + (size_t)c * a.cell;
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    int par = 0;
+    for (long long base = f0 + (long long)blockIdx.x * MESH_THREADS; base < f1; base += (long long)gridDim.x * MESH_THREADS, par ^= 1) {
+        // ---- a lane per face: the small ones here, the large ones onto the list
+        const long long f = base + tid;
+        MeshFace t;
+        if (f < f1 && mesh_load(a, c, vbase, (int)f, t)) {
+            const int n = t.bw * t.bh;
+            if (n > MESH_SMALL_BOX) s_list[atomicAdd(&s_cnt[par], 1)] = (int)f;
+            else if (n > 0) mesh_scan(t, cellkey, width, depth, 0, 1);
+        }
+        __syncthreads();
+        // ---- a wave per large face
+        const int cnt = s_cnt[par];
+        if (tid == 0) s_cnt[par ^ 1] = 0;                        // (last read before the barrier that ended the previous sweep)
+        for (int e = wave; e < cnt; e += MESH_WAVES) {
+            const int g = __builtin_amdgcn_readfirstlane(s_list[e]);
+            mesh_load(a, c, vbase, g, t);                        // (it was alive when it was listed)
+            mesh_scan(t, cellkey, width, depth, lane, PDGN_WAVE);
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" int pdgn_render_sheet_mesh(int rows, int cols, const float *const *clouds, const float *const *normals, const int *npoints,
+                                      int channel_major, const float *const *mesh_verts, const int32_t *const *mesh_faces,
+                                      const int32_t *const *mesh_range, const int32_t *const *mesh_mask, const int *mesh_nverts,
+                                      const int *mesh_nfaces, const int *mesh_shade, const float *view, const float *light, int cell, int radius,
+                                      void *workspace, uint8_t *image, pdgn_stream_t stream) {
+    // host-side checks only: nothing here touches the device
+    if (!render_shape_ok(rows, cols, cell) || radius < 0 || radius > RENDER_MAX_RADIUS) return PDGN_ERR_INVALID;
+    if (!clouds || !normals || !npoints || !view || !light || !workspace || !image) return PDGN_ERR_INVALID;
+    if (!mesh_verts || !mesh_faces || !mesh_range || !mesh_nverts || !mesh_nfaces || !mesh_shade) return PDGN_ERR_INVALID;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)image & 3)) return PDGN_ERR_INVALID;
+    RenderLitArgs la;
+    RenderArgs &a = la.r;
+    RenderMeshArgs ma;
+    int nmax = 0, fmax = 0, nmesh = 0;
+    ma.depth_shade = 0;
+    for (int c = 0; c < RENDER_MAX_COLS; ++c) {
+        const bool mesh = c < cols && mesh_verts[c];
+        const bool cloud = c < cols && !mesh;
+        a.cloud[c] = cloud ? clouds[c] : nullptr;
+        la.normal[c] = cloud ? normals[c] : nullptr;
+        a.n[c] = cloud ? npoints[c] : 0;                         // (a mesh column: the splat's threads all leave at once)
+        if (cloud && (!clouds[c] || ((uintptr_t)clouds[c] & 3) || ((uintptr_t)normals[c] & 3) || npoints[c] <= 0 || npoints[c] > (1 << 24)))
+            return PDGN_ERR_INVALID;
+        nmax = a.n[c] > nmax ? a.n[c] : nmax;
+        ma.verts[c] = mesh ? mesh_verts[c] : nullptr;
+        ma.faces[c] = mesh ? mesh_faces[c] : nullptr;
+        ma.range[c] = mesh ? mesh_range[c] : nullptr;
+        ma.mask[c] = mesh && mesh_mask ? mesh_mask[c] : nullptr;
+        ma.V[c] = mesh ? mesh_nverts[c] : 0;
+        ma.F[c] = mesh ? mesh_nfaces[c] : 0;
+        if (mesh) {
+            if (!ma.range[c] || (((uintptr_t)ma.verts[c] | (uintptr_t)ma.faces[c] | (uintptr_t)ma.range[c] | (uintptr_t)ma.mask[c]) & 3))
+                return PDGN_ERR_INVALID;
+            if (ma.V[c] < 1 || ma.V[c] > (1 << 28) || ma.F[c] < 0 || ma.F[c] > (1 << 28) || (ma.F[c] > 0 && !ma.faces[c])) return PDGN_ERR_INVALID;
+            if (mesh_shade[c] != 0 && mesh_shade[c] != 1) return PDGN_ERR_INVALID;
+            ma.depth_shade |= mesh_shade[c] << c;
+            fmax = ma.F[c] > fmax ? ma.F[c] : fmax;
+            ++nmesh;
+        }
+    }
+    if (!nmesh) return PDGN_ERR_INVALID;
+    a.channel_major = channel_major, a.rows = rows, a.cols = cols, a.cell = cell, a.radius = radius;
+    ma.rows = rows, ma.cols = cols, ma.cell = cell;
+    for (int i = 0; i < 12; ++i) a.m[i] = ma.m[i] = view[i];
+    for (int i = 0; i < 3; ++i) la.l[i] = ma.l[i] = light[i];
+    a.key = ma.key = (unsigned *)workspace;
+    const long long total = (long long)rows * cell * cols * cell;
+    const int quads = cdiv(cdiv(total, 4), RENDER_THREADS);
+    hipLaunchKernelGGL(render_clear_kernel, dim3(quads), dim3(RENDER_THREADS), 0, (hipStream_t)stream, a.key, total);
+    if (nmax > 0)
+        hipLaunchKernelGGL(render_splat_lit_kernel, dim3(cdiv(nmax, RENDER_THREADS), rows, cols), dim3(RENDER_THREADS), 0, (hipStream_t)stream, la);
+    if (fmax > 0) {
+        const int chunks = cdiv(fmax, MESH_THREADS) < MESH_MAX_CHUNKS ? cdiv(fmax, MESH_THREADS) : MESH_MAX_CHUNKS;
+        hipLaunchKernelGGL(render_mesh_kernel, dim3(chunks, rows, cols), dim3(MESH_THREADS), 0, (hipStream_t)stream, ma);
+    }
     hipLaunchKernelGGL(render_resolve_kernel, dim3(quads), dim3(RENDER_THREADS), 0, (hipStream_t)stream, a.key, image, total);
     return pdgn_launch_status();
 }

@@ -13,6 +13,9 @@ so they are never drawn.  `pack --visible` stores the masks beside the meshes.
 Distances and sides (DESIGN.md sections 7t and 7u): `point_to_mesh` is the closest point of a shape's faces (csrc/meshdist.hip),
 `winding_number` the generalized winding number about them (csrc/winding.hip) -- 1 inside a closed, consistently oriented shape, 0
 outside -- and on the two `signed_distance`, `occupancy_grid` and `winding_report`; the commands `distance`, `occupancy` and `check`.
+
+Looking at a set: the command `render` draws its shapes as shaded triangles into a preview sheet
+(report.MeshColumn, csrc/render.hip: pdgn_render_sheet_mesh), with --visible only the faces the sampler would draw from.
 """
 import os
 import sys
@@ -812,7 +815,9 @@ def split_meshset(root, split, normalize=None, visible=None):
 USAGE = ("usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]\n"
          "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--signed] [--split val] [--device cuda]\n"
          "       python -m pdgn_amd.meshes occupancy MESHES.npz OUT.npz --resolution R [--shape I,J,...] [--visible] [--split val] [--device cuda]\n"
-         "       python -m pdgn_amd.meshes check MESHES.npz [--samples N] [--split val] [--device cuda]")
+         "       python -m pdgn_amd.meshes check MESHES.npz [--samples N] [--split val] [--device cuda]\n"
+         "       python -m pdgn_amd.meshes render MESHES.npz -o sheet.png [--split val] [--shape I,J,...] [--rows N] [--cols N] [--cell C] "
+         "[--visible] [--shade flat|depth] [--device cuda]")
 
 
 def distance_table(result):
@@ -921,8 +926,45 @@ def _check_main(argv):
                                                else "open, self-intersecting or inconsistently oriented shapes: signs are not to be trusted"))
 
 
+def _render_main(argv):
+    """render MESHES.npz -o sheet.png: the shapes as flat-lit (or depth-shaded) triangles, `rows` down and up to `cols` across, column by
+    column (report.MeshColumn, csrc/render.hip: pdgn_render_sheet_mesh); --visible: only the faces the sampler would draw from."""
+    import torch
+    from .report import MAX_COLUMNS, MESH_SHADES, MeshColumn, render_sheet, write_png
+    opts = _options(argv[1:], {"o": "sheet.png", "shape": None, "visible": False, "split": "val", "device": "cuda", "rows": "8",
+                               "cols": str(MAX_COLUMNS), "cell": "128", "shade": "flat"}, ("--visible",),
+                    ("--shape", "--split", "--device", "--rows", "--cols", "--cell", "--shade", "--o"))
+    if not all(opts[k].isdigit() and int(opts[k]) > 0 for k in ("rows", "cols", "cell")) or opts["shade"] not in MESH_SHADES:
+        raise SystemExit(USAGE)
+    ms = _open_meshset(argv[0], opts["split"], opts["visible"])
+    if opts["visible"] and ms.visible is None:
+        raise SystemExit("--visible: %s holds no visibility masks" % argv[0])
+    try:
+        picks = _shape_list(_shape_option(opts["shape"]), ms.S, "render")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    rows = min(int(opts["rows"]), len(picks))
+    cols = min(int(opts["cols"]), MAX_COLUMNS, -(-len(picks) // rows))
+    picks = np.asarray(picks, dtype=np.int64)[:rows * cols]
+    ms = ms.to(torch.device(opts["device"]))
+    off = ms.face_off.cpu().numpy().astype(np.int64)
+    columns = []
+    for j in range(cols):
+        sub = picks[j * rows:(j + 1) * rows]
+        begin, count = np.zeros(rows, np.int64), np.zeros(rows, np.int64)          # (the last column may end early: empty cells)
+        begin[:len(sub)], count[:len(sub)] = off[sub], off[sub + 1] - off[sub]
+        columns.append(MeshColumn(ms.verts, ms.faces, begin, count, np.zeros(rows, np.int64), ms.visible if opts["visible"] else None,
+                                  opts["shade"]))
+    sheet = render_sheet(columns, cell=int(opts["cell"]), fit=True)
+    write_png(opts["o"], sheet)
+    print("%s: %d shapes, %d x %d pixels" % (opts["o"], len(picks), sheet.shape[1], sheet.shape[0]))
+    return opts["o"]
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) >= 2 and argv[0] == "render":
+        return _render_main([a if a != "-o" else "--o" for a in argv[1:]])
     if len(argv) >= 3 and argv[0] == "distance":
         return _distance_main(argv[1:])
     if len(argv) >= 3 and argv[0] == "occupancy":

@@ -46,6 +46,8 @@ surface normals estimated from each cloud's 16 nearest neighbours (DESIGN.md sec
 variation of the generated and the val clouds to report/surface.csv (both need --report_every).
 --report_fidelity (needs --report_every and a mesh --data_root): the reports also append to report/fidelity.csv the distance of the generated
 clouds' points to the surface of the nearest val shape, and of the val clouds to their own shapes (meshes.point_to_mesh).
+--report_mesh [R] (needs --report_every): the preview sheets get one more column, the surface reconstructed from the finest generated clouds at grid
+resolution R (default 64) drawn as flat-lit triangles, and with --report_fidelity another one, the val meshes themselves.
 Under torch.distributed.run every rank trains on its own slice of each global batch."""
 import argparse
 import os
@@ -151,6 +153,10 @@ def build_parser():
     p.add_argument("--report_surface", action="store_true", default=argparse.SUPPRESS, help="reports also append the surface variation "
                    "lambda0 / (lambda0 + lambda1 + lambda2) of the generated and of the val clouds to report/surface.csv (evaluation.surface_stats); "
                    "needs --report_every")
+    p.add_argument("--report_mesh", type=int, nargs="?", const=64, default=argparse.SUPPRESS, metavar="R", help="preview sheets get one more column: "
+                   "the surface reconstructed from the finest generated clouds at grid resolution R (default 64; reconstruct.reconstruct), drawn "
+                   "as flat-lit triangles in those clouds' frames, and with --report_fidelity a column of the val meshes themselves; needs "
+                   "--report_every")
     p.add_argument("--resample_pool", type=int, default=argparse.SUPPRESS, metavar="P", help="clouds stored with more than --num_point points: draw "
                    "each visit's points from the leading P points of a cloud (default: all stored points)")
     p.add_argument("--subsample", choices=["random", "fps"], default=argparse.SUPPRESS, help="the three coarse real resolutions: random (default: "
@@ -214,6 +220,7 @@ class Args(argparse.Namespace):
     report_lit = False
     report_surface = False
     report_fidelity = False
+    report_mesh = None
 
 
 def parse_args(argv=None):
@@ -314,6 +321,10 @@ def parse_args(argv=None):
     for flag in ("report_lit", "report_surface", "report_fidelity"):
         if getattr(args, flag) and not args.report_every:
             p.error("--%s needs --report_every" % flag)
+    if args.report_mesh is not None and not args.report_every:
+        p.error("--report_mesh needs --report_every")
+    if args.report_mesh is not None and args.report_mesh < 2:
+        p.error("--report_mesh takes a grid resolution of at least 2")
     if args.d_augment_target is None:
         for flag in ("ada_interval", "ada_span", "ada_p_min", "ada_p_max"):
             if flag in given:
@@ -715,6 +726,7 @@ def train(args):
                                     args.seed, rows=args.report_rows, full=args.report_full, rank=rank, emd=args.emd,
                                     **({"spacing": True} if args.report_spacing else {}), **({"lit": True} if args.report_lit else {}),
                                     **({"surface": True} if args.report_surface else {}),
+                                    **({"mesh": args.report_mesh} if args.report_mesh is not None else {}),
                                     **({"fidelity": val_meshset} if val_meshset is not None else {}))
     last = trainer.fit(feeder, args.max_epoch, start_epoch=start, snapshot=args.snapshot, checkpoint_dir=ckpt,
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
