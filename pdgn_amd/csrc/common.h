@@ -22,4 +22,13 @@ __device__ __forceinline__ float sqdist3(float qx, float qy, float qz, float px,
     return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
 }
 
+// dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, every product and sum rounded on its own: the dot product of every geometry kernel whose
+// result is pinned bit for bit (normals, orient, reconstruct, meshdist, winding)
+__device__ __forceinline__ float dot3_rn(float ax, float ay, float az, float bx, float by, float bz) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
+}
+
+// Whether a pointer an entry point was handed sits on a multiple of `to` bytes (a power of two); a null pointer does
+static inline bool pdgn_aligned(const void *p, uintptr_t to) { return !((uintptr_t)p & (to - 1)); }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (PDGN_WAVE - 1); }

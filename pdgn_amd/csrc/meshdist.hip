@@ -10,8 +10,9 @@
 // set does not depend on the order of its members: slot order, chunking, culling and launch geometry change no bit.
 //
 // NORMATIVE ORDER of d2_f and its closest point q_f (tests/p2m_mirror.py restates it in numpy; every fp32 operation below is one rounding --
-// __fadd_rn / __fsub_rn / __fmul_rn / __fdiv_rn -- nothing contracted; dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z as in csrc/normals.hip and
-// csrc/reconstruct.hip; cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), two products and one difference each).
+// __fadd_rn / __fsub_rn / __fmul_rn / __fdiv_rn -- nothing contracted; dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z: dot3_rn of csrc/common.h, as in
+// csrc/normals.hip and csrc/reconstruct.hip; cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x), two products and one
+// difference each).
 // CLAMPS are fminf(fmaxf(x, lo), hi): fmaxf / fminf return the other operand where one is NaN (the mirror: np.fmax / np.fmin, never
 // np.maximum), so a clamped value is never NaN where lo and hi are finite.
 //     face (a, b, c);  lo = min(min(a, b), c),  hi = max(max(a, b), c) per component
@@ -29,15 +30,8 @@
 // of that routine are differences of nearly equal products and pick a far vertex; here every candidate is a point of the face's box and a
 // wrong "counts" costs at most the gap between the plane candidate and the nearest edge (DESIGN.md section 7t has the measured errors).
 //
-// RECORDS (pdgn_mesh_dist_prepare).  Slot i of the record array holds face order[i] (order = NULL: face i): three 16-byte words
-// (a, bits(f)), (b, 0), (c, 0), f = -1 for a dead slot.  Slots keep inside their shape's range; a group is MD_GROUP = 64 consecutive slots
-// counted from the start of the shape's range, group_off[s] the index of shape s's first group, and per group two 16-byte words hold the
-// box of its live faces (+inf / -inf for none).  One wave writes one group: lane l gathers slot l, the box is reduced across the lanes.
-//
-// SHAPE OF THE DISTANCE KERNEL.  One thread per point; a workgroup of MD_THREADS = 256 owns a run of 256 points of one cloud.  The shape's
-// records pass through LDS in chunks of MD_CHUNK = 256 slots, thread t staging slot j0 + t.  A wave takes the chunk one group at a time:
-// lane l decides whether slot l of the group is to be visited by this wave, a ballot collects the decisions, and the wave walks the set
-// bits, reading each surviving face's three words at a uniform address (broadcasts).
+// RECORDS and THE WALK: csrc/meshrec.h, which csrc/winding.hip shares.  The distance kernel adds the boxes of the groups to the walk: thread
+// t < 4 stages the box of group t of the chunk beside the records, and the three levels of culling below decide what is visited.
 //
 // CULLING, exact under rounding (the pattern of imls_skips in csrc/reconstruct.hip).  For a box [flo, fhi] that holds the boxes of a set
 // of faces and a box [plo, phi] that holds a set of points:
@@ -52,22 +46,9 @@
 // against the wave's point box and the largest best of its live lanes (recomputed per group), a face against the same, and in the walk a
 // face against the lane's own point and best.  A lane without a live point carries best = -1, so it takes no part and is never evaluated.
 // cull = 0 visits every live face at every point.
-#include "common.h"
+#include "meshrec.h"
 
-#include <math.h>
-
-#define MD_THREADS 256
-#define MD_CHUNK 256
-#define MD_GROUP 64
-#define MD_NAN_BITS 0x7FC00000u
 #define MD_MAX_BLOCKS (1 << 23)                                  // workgroups per launch: 2^31 threads
-static_assert(MD_CHUNK == MD_THREADS, "thread t stages slot j0 + t");
-static_assert(MD_GROUP == PDGN_WAVE, "lane l of a wave holds slot l of a group");
-static_assert(MD_CHUNK % MD_GROUP == 0, "a chunk is whole groups");
-
-__device__ __forceinline__ float md_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
 
 __device__ __forceinline__ float md_clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
@@ -92,21 +73,8 @@ __device__ __forceinline__ float md_lower(float flx, float fly, float flz, float
     const float mx = fmaxf(fmaxf(__fsub_rn(flx, phx), __fsub_rn(plx, fhx)), 0.f);
     const float my = fmaxf(fmaxf(__fsub_rn(fly, phy), __fsub_rn(ply, fhy)), 0.f);
     const float mz = fmaxf(fmaxf(__fsub_rn(flz, phz), __fsub_rn(plz, fhz)), 0.f);
-    return md_dot(mx, my, mz, mx, my, mz);
+    return dot3_rn(mx, my, mz, mx, my, mz);
 }
-
-struct MdVec {
-    float x, y, z;
-};
-
-__device__ __forceinline__ MdVec md_sub(MdVec a, MdVec b) { return {__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y), __fsub_rn(a.z, b.z)}; }
-
-__device__ __forceinline__ MdVec md_cross(MdVec u, MdVec v) {
-    return {__fsub_rn(__fmul_rn(u.y, v.z), __fmul_rn(u.z, v.y)), __fsub_rn(__fmul_rn(u.z, v.x), __fmul_rn(u.x, v.z)),
-            __fsub_rn(__fmul_rn(u.x, v.y), __fmul_rn(u.y, v.x))};
-}
-
-__device__ __forceinline__ float md_dotv(MdVec a, MdVec b) { return md_dot(a.x, a.y, a.z, b.x, b.y, b.z); }
 
 __device__ __forceinline__ MdVec md_clampv(MdVec q, MdVec lo, MdVec hi) {
     return {md_clamp(q.x, lo.x, hi.x), md_clamp(q.y, lo.y, hi.y), md_clamp(q.z, lo.z, hi.z)};
@@ -145,13 +113,13 @@ __device__ __forceinline__ float md_face(MdVec p, MdVec a, MdVec b, MdVec c, MdV
 }
 
 // RECORDS above.  One wave per group.
-__global__ __launch_bounds__(MD_THREADS) void md_prepare_kernel(int S, int V, int F, int G, const float *__restrict__ verts,
+__global__ __launch_bounds__(MESHREC_THREADS) void md_prepare_kernel(int S, int V, int F, int G, const float *__restrict__ verts,
                                                                 const int32_t *__restrict__ faces, const int32_t *__restrict__ face_off,
                                                                 const int32_t *__restrict__ group_off, const int32_t *__restrict__ live,
                                                                 const int32_t *__restrict__ order, float4 *__restrict__ rec,
                                                                 float4 *__restrict__ grp) {
     const int lane = threadIdx.x & (PDGN_WAVE - 1);
-    const int g = blockIdx.x * (MD_THREADS / PDGN_WAVE) + (threadIdx.x >> 6);
+    const int g = blockIdx.x * (MESHREC_THREADS / PDGN_WAVE) + (threadIdx.x >> 6);
     if (g >= G) return;                                            // (uniform per wave; no barrier in this kernel)
     int lo = 0, hi = S - 1;                                        // the shape whose groups hold g: the first s with group_off[s + 1] > g
     while (lo < hi) {
@@ -160,7 +128,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_prepare_kernel(int S, int V, in
         else lo = mid + 1;
     }
     const int s = lo;
-    const long long slot = (long long)face_off[s] + (long long)(g - group_off[s]) * MD_GROUP + lane;
+    const long long slot = (long long)face_off[s] + (long long)(g - group_off[s]) * MESHREC_GROUP + lane;
     const bool in = slot >= face_off[s] && slot < face_off[s + 1] && slot < F;
     const float inf = __builtin_inff();
     float blx = inf, bly = inf, blz = inf, bhx = -inf, bhy = -inf, bhz = -inf;
@@ -187,70 +155,55 @@ __global__ __launch_bounds__(MD_THREADS) void md_prepare_kernel(int S, int V, in
     if (lane == 0) grp[(size_t)g * 2] = make_float4(blx, bly, blz, 0.f), grp[(size_t)g * 2 + 1] = make_float4(bhx, bhy, bhz, 0.f);
 }
 
-__global__ __launch_bounds__(MD_THREADS) void md_distance_kernel(int n, int S, int F, int G, int runs, const float *__restrict__ xyz,
-                                                                 const int32_t *__restrict__ shape, const int32_t *__restrict__ face_off,
-                                                                 const int32_t *__restrict__ group_off, const float4 *__restrict__ rec,
-                                                                 const float4 *__restrict__ grp, int cull, float *__restrict__ out_d2,
-                                                                 int32_t *__restrict__ out_face, float *__restrict__ out_q) {
-    __shared__ float4 s_rec[3 * MD_CHUNK];
-    __shared__ float4 s_grp[2 * (MD_CHUNK / MD_GROUP)];
+__global__ __launch_bounds__(MESHREC_THREADS) void md_distance_kernel(int n, int S, int F, int G, int runs, const float *__restrict__ xyz,
+                                                                      const int32_t *__restrict__ shape,
+                                                                      const int32_t *__restrict__ face_off,
+                                                                      const int32_t *__restrict__ group_off,
+                                                                      const float4 *__restrict__ rec, const float4 *__restrict__ grp,
+                                                                      int cull, float *__restrict__ out_d2,
+                                                                      int32_t *__restrict__ out_face, float *__restrict__ out_q) {
+    __shared__ float4 s_rec[3 * MESHREC_CHUNK];
+    __shared__ float4 s_grp[2 * (MESHREC_CHUNK / MESHREC_GROUP)];
     const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1);
-    const int c = blockIdx.x / runs, i = (blockIdx.x % runs) * MD_THREADS + tid;
+    const int c = blockIdx.x / runs, i = (blockIdx.x % runs) * MESHREC_THREADS + tid;
     const bool mine = i < n;
-    const float inf = __builtin_inff(), nan = __uint_as_float(MD_NAN_BITS);
-    MdVec p = {nan, nan, nan};
-    if (mine) {
-        const size_t at = ((size_t)c * n + i) * 3;
-        p = {xyz[at], xyz[at + 1], xyz[at + 2]};
-    }
+    const float inf = __builtin_inff(), nan = __uint_as_float(MESHREC_NAN_BITS);
+    const MdVec p = meshrec_point(xyz, c, n, i);
     const bool live = mine && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    // the shape's slots and groups (uniform per workgroup); anything out of range is a shape without faces
-    const int s = shape[c];
-    int f0 = 0, f1 = 0, g0 = 0;
-    if (s >= 0 && s < S) {
-        f0 = face_off[s], f1 = face_off[s + 1], g0 = group_off[s];
-        if (f0 < 0 || f1 > F || f1 < f0 || g0 < 0) f0 = f1 = 0;
-    }
-    const int slots = f1 - f0;
+    const MeshrecRange r = meshrec_range<true>(shape, face_off, group_off, c, S, F);
+    const int f0 = r.f0, g0 = r.g0, slots = r.f1 - r.f0;
     // the box of the wave's live points
     const float plx = md_wave_min(live ? p.x : inf), ply = md_wave_min(live ? p.y : inf), plz = md_wave_min(live ? p.z : inf);
     const float phx = md_wave_max(live ? p.x : -inf), phy = md_wave_max(live ? p.y : -inf), phz = md_wave_max(live ? p.z : -inf);
     unsigned long long key = ~0ULL;
     float best = live ? inf : -1.f;
     MdVec best_q = {nan, nan, nan};
-    for (int j0 = 0; j0 < slots; j0 += MD_CHUNK) {
-        const int cnt = min(MD_CHUNK, slots - j0);
+    for (int j0 = 0; j0 < slots; j0 += MESHREC_CHUNK) {
+        const int cnt = min(MESHREC_CHUNK, slots - j0);
         if (j0) __syncthreads();                                   // everyone is done reading the previous chunk
-        {
-            float4 a = make_float4(0.f, 0.f, 0.f, __int_as_float(-1)), b = make_float4(0.f, 0.f, 0.f, 0.f), cc = b;
-            if (tid < cnt) {
-                const size_t at = (size_t)(f0 + j0 + tid) * 3;
-                a = rec[at], b = rec[at + 1], cc = rec[at + 2];
-            }
-            s_rec[3 * tid] = a, s_rec[3 * tid + 1] = b, s_rec[3 * tid + 2] = cc;
-            if (tid < MD_CHUNK / MD_GROUP) {
-                const long long g = (long long)g0 + j0 / MD_GROUP + tid;
-                float4 glo = make_float4(inf, inf, inf, 0.f), ghi = make_float4(-inf, -inf, -inf, 0.f);
-                if (tid * MD_GROUP < cnt && g < G) glo = grp[g * 2], ghi = grp[g * 2 + 1];
-                s_grp[2 * tid] = glo, s_grp[2 * tid + 1] = ghi;
-            }
+        meshrec_stage(rec, f0 + j0, cnt, s_rec);
+        if (tid < MESHREC_CHUNK / MESHREC_GROUP) {
+            const long long g = (long long)g0 + j0 / MESHREC_GROUP + tid;
+            float4 glo = make_float4(inf, inf, inf, 0.f), ghi = make_float4(-inf, -inf, -inf, 0.f);
+            if (tid * MESHREC_GROUP < cnt && g < G) glo = grp[g * 2], ghi = grp[g * 2 + 1];
+            s_grp[2 * tid] = glo, s_grp[2 * tid + 1] = ghi;
         }
         __syncthreads();
-        for (int s0 = 0; s0 < cnt; s0 += MD_GROUP) {
+        for (int s0 = 0; s0 < cnt; s0 += MESHREC_GROUP) {
             float wmax = 0.f;
             if (cull) {
                 wmax = md_wave_max(best);
-                const float4 glo = s_grp[2 * (s0 / MD_GROUP)], ghi = s_grp[2 * (s0 / MD_GROUP) + 1];
+                const float4 glo = s_grp[2 * (s0 / MESHREC_GROUP)], ghi = s_grp[2 * (s0 / MESHREC_GROUP) + 1];
                 if (md_lower(glo.x, glo.y, glo.z, ghi.x, ghi.y, ghi.z, plx, ply, plz, phx, phy, phz) > wmax) continue;      // (uniform)
             }
-            const float4 ra = s_rec[3 * (s0 + lane)];               // (s0 + lane < MD_CHUNK: a staged record, dead past cnt)
-            bool visit = __float_as_int(ra.w) >= 0;
+            const float4 ra = s_rec[3 * (s0 + lane)];               // (s0 + lane < MESHREC_CHUNK: a staged record, dead past cnt)
+            bool visit = meshrec_face(ra) >= 0;
             if (cull && visit) {
                 const float4 rb = s_rec[3 * (s0 + lane) + 1], rc = s_rec[3 * (s0 + lane) + 2];
                 visit = !(md_lower(md_min3(ra.x, rb.x, rc.x), md_min3(ra.y, rb.y, rc.y), md_min3(ra.z, rb.z, rc.z), md_max3(ra.x, rb.x, rc.x),
                                    md_max3(ra.y, rb.y, rc.y), md_max3(ra.z, rb.z, rc.z), plx, ply, plz, phx, phy, phz) > wmax);
             }
-            unsigned long long todo = __ballot(visit);
+            unsigned long long todo = __ballot(visit);             // meshrec_walk's loop, spelled out (csrc/meshrec.h says why)
             while (todo) {
                 const int jj = s0 + __builtin_ctzll(todo);         // uniform: the lowest slot still to visit
                 todo &= todo - 1;
@@ -261,7 +214,7 @@ __global__ __launch_bounds__(MD_THREADS) void md_distance_kernel(int n, int S, i
                 if (cull && md_lower(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, p.x, p.y, p.z, p.x, p.y, p.z) > best) continue;
                 MdVec q;
                 const float d2 = md_face(p, a, b, cc, lo, hi, q);
-                const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(fa.w);
+                const unsigned long long k = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)meshrec_face(fa);
                 if (d2 == d2 && k < key) key = k, best = d2, best_q = q;
             }
         }
@@ -280,19 +233,17 @@ __global__ __launch_bounds__(MD_THREADS) void md_distance_kernel(int n, int S, i
 }
 
 // ---------------------------------------------------------------------------- entry points (host-side checks only before any launch)
-static bool md_aligned(const void *p, uintptr_t to) { return !((uintptr_t)p & (to - 1)); }
-
 static bool md_mesh_ok(int S, int F, int G) {
-    return S >= 1 && F >= 1 && G >= 1 && 3LL * F < (1LL << 31) && (long long)G <= (long long)F / MD_GROUP + S;
+    return S >= 1 && F >= 1 && G >= 1 && 3LL * F < (1LL << 31) && (long long)G <= (long long)F / MESHREC_GROUP + S;
 }
 
-extern "C" int pdgn_mesh_dist_group(void) { return MD_GROUP; }
+extern "C" int pdgn_mesh_dist_group(void) { return MESHREC_GROUP; }
 
-extern "C" int pdgn_mesh_dist_chunk(void) { return MD_CHUNK; }
+extern "C" int pdgn_mesh_dist_chunk(void) { return MESHREC_CHUNK; }
 
 extern "C" long long pdgn_mesh_dist_workspace_floats(int S, int F) {
     if (S < 1 || F < 1 || 3LL * F >= (1LL << 31)) return PDGN_ERR_INVALID;
-    return 12LL * F + 8LL * ((long long)F / MD_GROUP + S);
+    return 12LL * F + 8LL * ((long long)F / MESHREC_GROUP + S);
 }
 
 extern "C" int pdgn_mesh_dist_prepare(int S, int V, int F, int G, const float *verts, const int32_t *faces, const int32_t *face_off,
@@ -300,10 +251,10 @@ extern "C" int pdgn_mesh_dist_prepare(int S, int V, int F, int G, const float *v
                                       pdgn_stream_t stream) {
     if (!md_mesh_ok(S, F, G) || V < 1 || 3LL * V >= (1LL << 31)) return PDGN_ERR_INVALID;
     if (!verts || !faces || !face_off || !group_off || !live || !records || !groups) return PDGN_ERR_INVALID;
-    if (!md_aligned(verts, 4) || !md_aligned(faces, 4) || !md_aligned(face_off, 4) || !md_aligned(group_off, 4) || !md_aligned(live, 4) ||
-        !md_aligned(order, 4) || !md_aligned(records, 16) || !md_aligned(groups, 16))
+    if (!pdgn_aligned(verts, 4) || !pdgn_aligned(faces, 4) || !pdgn_aligned(face_off, 4) || !pdgn_aligned(group_off, 4) || !pdgn_aligned(live, 4) ||
+        !pdgn_aligned(order, 4) || !pdgn_aligned(records, 16) || !pdgn_aligned(groups, 16))
         return PDGN_ERR_INVALID;
-    hipLaunchKernelGGL(md_prepare_kernel, dim3(cdiv(G, MD_THREADS / PDGN_WAVE)), dim3(MD_THREADS), 0, (hipStream_t)stream, S, V, F, G, verts,
+    hipLaunchKernelGGL(md_prepare_kernel, dim3(cdiv(G, MESHREC_THREADS / PDGN_WAVE)), dim3(MESHREC_THREADS), 0, (hipStream_t)stream, S, V, F, G, verts,
                        faces, face_off, group_off, live, order, (float4 *)records, (float4 *)groups);
     return pdgn_launch_status();
 }
@@ -312,13 +263,13 @@ extern "C" int pdgn_point_mesh_distance(int b, int n, int S, int F, int G, const
                                         const int32_t *group_off, const float *records, const float *groups, int cull, float *d2,
                                         int32_t *face, float *closest, pdgn_stream_t stream) {
     if (!md_mesh_ok(S, F, G) || b < 1 || n < 1 || (long long)b * n >= (1LL << 31) || cull < 0 || cull > 1) return PDGN_ERR_INVALID;
-    if ((long long)b * cdiv(n, MD_THREADS) > MD_MAX_BLOCKS) return PDGN_ERR_INVALID;
+    if ((long long)b * cdiv(n, MESHREC_THREADS) > MD_MAX_BLOCKS) return PDGN_ERR_INVALID;
     if (!xyz || !shape || !face_off || !group_off || !records || !groups || !d2 || !face) return PDGN_ERR_INVALID;
-    if (!md_aligned(xyz, 4) || !md_aligned(shape, 4) || !md_aligned(face_off, 4) || !md_aligned(group_off, 4) || !md_aligned(records, 16) ||
-        !md_aligned(groups, 16) || !md_aligned(d2, 4) || !md_aligned(face, 4) || !md_aligned(closest, 4))
+    if (!pdgn_aligned(xyz, 4) || !pdgn_aligned(shape, 4) || !pdgn_aligned(face_off, 4) || !pdgn_aligned(group_off, 4) || !pdgn_aligned(records, 16) ||
+        !pdgn_aligned(groups, 16) || !pdgn_aligned(d2, 4) || !pdgn_aligned(face, 4) || !pdgn_aligned(closest, 4))
         return PDGN_ERR_INVALID;
-    const int runs = cdiv(n, MD_THREADS);
-    hipLaunchKernelGGL(md_distance_kernel, dim3((unsigned)((long long)b * runs)), dim3(MD_THREADS), 0, (hipStream_t)stream, n, S, F, G, runs,
+    const int runs = cdiv(n, MESHREC_THREADS);
+    hipLaunchKernelGGL(md_distance_kernel, dim3((unsigned)((long long)b * runs)), dim3(MESHREC_THREADS), 0, (hipStream_t)stream, n, S, F, G, runs,
                        xyz, shape, face_off, group_off, (const float4 *)records, (const float4 *)groups, cull, d2, face, closest);
     return pdgn_launch_status();
 }

@@ -61,10 +61,6 @@ __device__ __forceinline__ void nrm_rotate(float &app, float &aqq, float &apq, f
     v2p = __fsub_rn(__fmul_rn(c, a2), __fmul_rn(s, b2)), v2q = __fadd_rn(__fmul_rn(s, a2), __fmul_rn(c, b2));
 }
 
-__device__ __forceinline__ float nrm_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-
 // compare-and-swap of the selection: (la, ca) <-> (lb, cb) where lb < la
 __device__ __forceinline__ void nrm_cas(float &la, int &ca, float &lb, int &cb) {
     const bool sw = lb < la;
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(BLOCK) void normals_kernel(int n, int k, int per, c
         const float wx = orient == 1 ? ox : orient == 2 ? __fsub_rn(ox, xi) : __fsub_rn(xi, ox);
         const float wy = orient == 1 ? oy : orient == 2 ? __fsub_rn(oy, yi) : __fsub_rn(yi, oy);
         const float wz = orient == 1 ? oz : orient == 2 ? __fsub_rn(oz, zi) : __fsub_rn(zi, oz);
-        flip = nrm_dot(nx, ny, nz, wx, wy, wz) < 0.f;
+        flip = dot3_rn(nx, ny, nz, wx, wy, wz) < 0.f;
     }
     if (flip) nx = -nx, ny = -ny, nz = -nz;
     // 6: poison
@@ -156,14 +152,13 @@ __global__ __launch_bounds__(BLOCK) void normals_kernel(int n, int k, int per, c
     if (eig) eig[3 * at] = l0, eig[3 * at + 1] = l1, eig[3 * at + 2] = l2;
 }
 
-static bool nrm_aligned(const void *p) { return !((uintptr_t)p & 3); }
 
 extern "C" int pdgn_estimate_normals(int b, int n, int k, const float *xyz, const int32_t *idx, int orient, float ox, float oy, float oz,
                                      float *normals, float *eig, pdgn_stream_t stream) {
     if (b < 1 || n < 1 || k < 1 || k > PDGN_NORMALS_MAX_K || (long long)b * n > (1LL << 28)) return PDGN_ERR_INVALID;
     if (orient < 0 || orient > 3 || (orient != 0 && !(isfinite(ox) && isfinite(oy) && isfinite(oz)))) return PDGN_ERR_INVALID;
     if (!xyz || !idx || !normals) return PDGN_ERR_INVALID;
-    if (!nrm_aligned(xyz) || !nrm_aligned(idx) || !nrm_aligned(normals) || !nrm_aligned(eig)) return PDGN_ERR_INVALID;
+    if (!pdgn_aligned(xyz, 4) || !pdgn_aligned(idx, 4) || !pdgn_aligned(normals, 4) || !pdgn_aligned(eig, 4)) return PDGN_ERR_INVALID;
     // the largest workgroup that still leaves one per CU (256 of them); 64 where even that does not
     const int block = (long long)b * cdiv(n, 256) >= 256 ? 256 : (long long)b * cdiv(n, 128) >= 256 ? 128 : 64;
     // one launch whatever b is: grid.x carries (cloud, workgroup of the cloud), at most 2^28 of them (grid.y would end at 65535 clouds)

@@ -114,10 +114,6 @@ __device__ __forceinline__ u64 ori_block_min(u64 v, u64 *slot) {
     return ((u64)hi << 32) | lo;
 }
 
-__device__ __forceinline__ float ori_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-
 __device__ __forceinline__ bool ori_bit(const unsigned *words, int i) { return (words[i >> 5] >> (i & 31)) & 1u; }
 
 // bytes of dynamic LDS for a cloud of n points (the kernel's carve-up below)
@@ -247,7 +243,7 @@ __global__ __launch_bounds__(ORI_THREADS) void orient_kernel(OriArgs a) {
             const u64 b = best[u];
             par = (int)(unsigned)b;
             const unsigned sp = ori_bit(flipw, par) ? 0x80000000u : 0u;
-            const float d = ori_dot(__uint_as_float(g[3 * u]), __uint_as_float(g[3 * u + 1]), __uint_as_float(g[3 * u + 2]),
+            const float d = dot3_rn(__uint_as_float(g[3 * u]), __uint_as_float(g[3 * u + 1]), __uint_as_float(g[3 * u + 2]),
                                     __uint_as_float(g[3 * par] ^ sp), __uint_as_float(g[3 * par + 1] ^ sp),
                                     __uint_as_float(g[3 * par + 2] ^ sp));
             flip = d < 0.f;
@@ -271,7 +267,7 @@ __global__ __launch_bounds__(ORI_THREADS) void orient_kernel(OriArgs a) {
                 t = rev[r0 + (e - k)];
             }
             // (a t inside the tree takes the minimum too: its key is never read again)
-            float w = __fsub_rn(1.0f, fabsf(ori_dot(ux, uy, uz, __uint_as_float(g[3 * t]), __uint_as_float(g[3 * t + 1]),
+            float w = __fsub_rn(1.0f, fabsf(dot3_rn(ux, uy, uz, __uint_as_float(g[3 * t]), __uint_as_float(g[3 * t + 1]),
                                                     __uint_as_float(g[3 * t + 2]))));
             w = w > 0.f ? w : 0.f;
             atomicMin(&best[t], ((u64)__float_as_uint(w) << 32) | (unsigned)u);

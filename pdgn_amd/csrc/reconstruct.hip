@@ -69,10 +69,6 @@
 static_assert(IMLS_CHUNK == IMLS_THREADS, "thread t stages point j0 + t");
 static_assert(IMLS_CHUNK % PDGN_WAVE == 0, "a wave takes the chunk 64 points at a time");
 
-__device__ __forceinline__ float rc_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-
 __device__ __forceinline__ float rc_pos(float o, int i, float v) { return __fadd_rn(o, __fmul_rn((float)i, v)); }
 
 // CULLING above: true where t <= 0 is proven for every node of the box [lo, hi]
@@ -81,7 +77,7 @@ __device__ __forceinline__ bool imls_skips(float x, float y, float z, float lox,
     const float mx = fmaxf(fmaxf(__fsub_rn(lox, x), __fsub_rn(x, hix)), 0.f);
     const float my = fmaxf(fmaxf(__fsub_rn(loy, y), __fsub_rn(y, hiy)), 0.f);
     const float mz = fmaxf(fmaxf(__fsub_rn(loz, z), __fsub_rn(z, hiz)), 0.f);
-    const float T = __fsub_rn(1.0f, __fmul_rn(rc_dot(mx, my, mz, mx, my, mz), inv));
+    const float T = __fsub_rn(1.0f, __fmul_rn(dot3_rn(mx, my, mz, mx, my, mz), inv));
     return !(T > 0.f);
 }
 
@@ -134,10 +130,10 @@ __global__ __launch_bounds__(IMLS_THREADS) void imls_kernel(int n, int R, int pe
                 todo &= todo - 1;
                 const float4 p = rec[2 * jj], gn = rec[2 * jj + 1];
                 const float dx = __fsub_rn(px, p.x), dy = __fsub_rn(py, p.y), dz = __fsub_rn(pz, p.z);
-                const float d2 = rc_dot(dx, dy, dz, dx, dy, dz);
+                const float d2 = dot3_rn(dx, dy, dz, dx, dy, dz);
                 const float t = __fsub_rn(1.0f, __fmul_rn(d2, inv));
                 const float w = __fmul_rn(t, t);
-                const float term = __fmul_rn(w, rc_dot(dx, dy, dz, gn.x, gn.y, gn.z));
+                const float term = __fmul_rn(w, dot3_rn(dx, dy, dz, gn.x, gn.y, gn.z));
                 const bool in = t > 0.f;
                 sw = in ? __fadd_rn(sw, w) : sw;
                 sf = in ? __fadd_rn(sf, term) : sf;
@@ -323,7 +319,6 @@ __global__ __launch_bounds__(SN_THREADS) void sn_emit_kernel(SnEmitArgs a) {
 }
 
 // ---------------------------------------------------------------------------- entry points (host-side checks only before any launch)
-static bool rc_aligned(const void *p) { return !((uintptr_t)p & 3); }
 
 static bool rc_shape_ok(int b, int R) {
     return b >= 1 && R >= PDGN_RECON_MIN_R && R <= PDGN_RECON_MAX_R && (long long)b * R * R * R < (1LL << 31);
@@ -344,7 +339,8 @@ extern "C" int pdgn_imls_grid(int b, int n, int R, const float *xyz, const float
                               int cull, float *field, pdgn_stream_t stream) {
     if (!rc_shape_ok(b, R) || n < 1 || cull < 0 || cull > 1) return PDGN_ERR_INVALID;
     if (!xyz || !normals || !grid || !grid_host || !field) return PDGN_ERR_INVALID;
-    if (!rc_aligned(xyz) || !rc_aligned(normals) || !rc_aligned(grid) || !rc_aligned(grid_host) || !rc_aligned(field)) return PDGN_ERR_INVALID;
+    if (!pdgn_aligned(xyz, 4) || !pdgn_aligned(normals, 4) || !pdgn_aligned(grid, 4) || !pdgn_aligned(grid_host, 4) || !pdgn_aligned(field, 4))
+        return PDGN_ERR_INVALID;
     if (!rc_grid_ok(b, grid_host, 5)) return PDGN_ERR_INVALID;
     const int per_axis = cdiv(R, IMLS_EDGE);
     const int per_cloud = per_axis * per_axis * per_axis;           // (at most 32^3)
@@ -363,7 +359,7 @@ extern "C" int pdgn_surface_nets_count(int b, int R, const float *field, int32_t
                                        pdgn_stream_t stream) {
     if (!rc_shape_ok(b, R)) return PDGN_ERR_INVALID;
     if (!field || !vflag || !qcnt || !stats) return PDGN_ERR_INVALID;
-    if (!rc_aligned(field) || !rc_aligned(vflag) || !rc_aligned(qcnt) || !rc_aligned(stats)) return PDGN_ERR_INVALID;
+    if (!pdgn_aligned(field, 4) || !pdgn_aligned(vflag, 4) || !pdgn_aligned(qcnt, 4) || !pdgn_aligned(stats, 4)) return PDGN_ERR_INVALID;
     const int nodes = R * R * R;
     hipLaunchKernelGGL(sn_clear_kernel, dim3(cdiv(4LL * b, SN_THREADS)), dim3(SN_THREADS), 0, (hipStream_t)stream, 4LL * b, stats);
     // grid.y carries the cloud: at most 65535 of them per launch
@@ -384,8 +380,9 @@ extern "C" int pdgn_surface_nets_emit(int b, int R, const float *field, const fl
                                       long long face_capacity, float *verts, int32_t *faces, pdgn_stream_t stream) {
     if (!rc_shape_ok(b, R)) return PDGN_ERR_INVALID;
     if (!field || !grid || !grid_host || !vflag || !vscan || !qcnt || !qscan || !vert_off || !face_off) return PDGN_ERR_INVALID;
-    if (!rc_aligned(field) || !rc_aligned(grid) || !rc_aligned(grid_host) || !rc_aligned(vflag) || !rc_aligned(vscan) || !rc_aligned(qcnt) ||
-        !rc_aligned(qscan) || !rc_aligned(vert_off) || !rc_aligned(face_off) || !rc_aligned(verts) || !rc_aligned(faces))
+    if (!pdgn_aligned(field, 4) || !pdgn_aligned(grid, 4) || !pdgn_aligned(grid_host, 4) || !pdgn_aligned(vflag, 4) || !pdgn_aligned(vscan, 4) ||
+        !pdgn_aligned(qcnt, 4) || !pdgn_aligned(qscan, 4) || !pdgn_aligned(vert_off, 4) || !pdgn_aligned(face_off, 4) ||
+        !pdgn_aligned(verts, 4) || !pdgn_aligned(faces, 4))
         return PDGN_ERR_INVALID;
     const long long most = 0x7FFFFFFFLL / 3;
     if (total_verts < 0 || total_faces < 0 || total_verts > most || total_faces > most) return PDGN_ERR_INVALID;

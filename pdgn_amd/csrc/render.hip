@@ -16,7 +16,7 @@
 //
 // pdgn_render_sheet_mesh (the second half of this file): columns of triangle meshes beside the columns of clouds, rasterised exactly in
 // integers into the same keys.  Its definition heads that half; tests/mesh_render_mirror.py spells it.
-#include "common.h"
+#include "raster.h"
 
 #define RENDER_THREADS 256
 #define RENDER_MAX_COLS 8
@@ -219,12 +219,12 @@ extern "C" int pdgn_render_sheet_lit(int rows, int cols, const float *const *clo
 //   Cover.  With edge(A, B, P) = (B.x - A.x)(P.y - A.y) - (B.y - A.y)(P.x - A.x) in int64:  A2 = edge(P0, P1, P2); where A2 < 0, P1 and
 //           P2 (and their Z) change places and A2 its sign; A2 = 0 draws nothing.  The pixel centres C = ((2 px + 1) 8, (2 py + 1) 8) of
 //           the face's bounding box, clipped to 0 <= px, py < cell of the face's OWN cell, are COVERED where w0 = edge(P1, P2, C), w1 =
-//           edge(P2, P0, C) and w2 = edge(P0, P1, C) are all >= 0: edges inclusive, faces two-sided, exactly as csrc/visible.hip, so two
+//           edge(P2, P0, C) and w2 = edge(P0, P1, C) are all >= 0: edges inclusive, faces two-sided, exactly as csrc/raster.h, so two
 //           faces on a shared edge leave no hole and the minimum decides.  There
 //             q = floor((w0 Z0 + w1 Z1 + w2 Z2) / A2),   key = q << 8 | shade,   key buffer <- min(key buffer, key).
 //           BOUND: coordinates span at most 48 cell <= 3 * 2^16 (cell <= 4096), so every edge function is below 2^37 in magnitude, A2 < 2^37
 //           and the numerator below 2^37 2^24 = 2^61; the quotient is at most 2^24 - 1.  The division is exact: an fp64 estimate (off by
-//           less than one) corrected by the integer remainder, as vis_div of csrc/visible.hip.
+//           less than one) corrected by the integer remainder, as raster_div of csrc/raster.h.
 //   Shade.  Depth (mode 1): 255 - (q >> 17) from the pixel's own q.  Flat-lit (mode 0), one value per face from the fp32 vertices as
 //           handed in, before any swap: e1 = p1 - p0, e2 = p2 - p0, n = e1 x e2 (nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz =
 //           e1x e2y - e1y e2x), every subtraction, product and sum rounded on its own, never contracted; len = sqrtf((nx nx + ny ny) + nz nz),
@@ -236,14 +236,10 @@ extern "C" int pdgn_render_sheet_lit(int rows, int cols, const float *const *clo
 // covers no pixel centre draws nothing: no wireframe, no anti-aliasing.  The normal of a face whose edge products underflow in fp32 is
 // lost (len = 0: the face is not drawn in a flat-lit column).
 //
-// THE KERNEL.  Grid (chunks, rows, cols), 256 threads; a workgroup takes the faces of its row 256 at a time, striding by the grid, a lane
-// per face.  A face whose clipped box holds at most MESH_SMALL_BOX pixels is rasterised by its lane (a surface-nets face at R = 64 in a
-// 128-pixel cell covers a handful); a larger one goes to an LDS list that, after a barrier, whole waves sweep with their lanes striding
-// over the box (one face of a CAD mesh can cover the cell: 16 384 centres, 256 per lane).  The keys go to the key buffer in global memory
-// with atomicMin, as the splat's do.  No float atomics: two runs agree bit for bit.
-#define MESH_THREADS 256
-#define MESH_WAVES (MESH_THREADS / PDGN_WAVE)
-#define MESH_SMALL_BOX 32
+// THE KERNEL.  Grid (chunks, rows, cols), 256 threads; a workgroup sweeps the faces of its row 256 at a time, striding by the grid
+// (csrc/raster.h, THE SWEEP: a lane per small face, a wave per large one; 1 KB of static LDS).  The keys go to the key buffer in global
+// memory with atomicMin, as the splat's do.  No float atomics: two runs agree bit for bit.
+#define MESH_THREADS RASTER_THREADS
 #define MESH_MAX_CHUNKS 64
 
 struct RenderMeshArgs {
@@ -255,18 +251,6 @@ struct RenderMeshArgs {
     float m[12], l[3];
     unsigned *key;
 };
-
-struct MeshFace {
-    int x0, y0, z0, x1, y1, z1, x2, y2, z2;
-    int bx, by, bw, bh;                                          // the clipped pixel box; bw * bh = 0: no centre to look at
-    long long a2;
-    double ra2;
-    unsigned shade;
-};
-
-__device__ __forceinline__ long long mesh_edge(int ax, int ay, int bx, int by, int px, int py) {
-    return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
 
 // Project and snap one vertex.  False: u, v or d is not finite.
 __device__ __forceinline__ bool mesh_snap(const float *m, float s, const float *p, int &X, int &Y, int &Z) {
@@ -282,8 +266,8 @@ __device__ __forceinline__ bool mesh_snap(const float *m, float s, const float *
     return true;
 }
 
-// Gather, snap and shade face f of column c.  False: the face is dead.
-__device__ __forceinline__ bool mesh_load(const RenderMeshArgs &a, int c, int base, int f, MeshFace &t) {
+// Gather, snap and shade face f of column c (shade: the flat shade, 0 in a column shaded by depth).  False: the face is dead.
+__device__ __forceinline__ bool mesh_load(const RenderMeshArgs &a, int c, int base, int f, RasterFace &t, unsigned &shade) {
     if (a.mask[c] && a.mask[c][f] == 0) return false;
     const int32_t *fi = a.faces[c] + 3 * (size_t)f;
     const long long i0 = (long long)fi[0] + base, i1 = (long long)fi[1] + base, i2 = (long long)fi[2] + base;
@@ -294,7 +278,7 @@ __device__ __forceinline__ bool mesh_load(const RenderMeshArgs &a, int c, int ba
     const float s = (float)(a.cell << 4);
     if (!mesh_snap(a.m, s, p0, t.x0, t.y0, t.z0) || !mesh_snap(a.m, s, p1, t.x1, t.y1, t.z1) || !mesh_snap(a.m, s, p2, t.x2, t.y2, t.z2))
         return false;
-    t.shade = 0;
+    shade = 0;
     if (!((a.depth_shade >> c) & 1)) {
         const float ux = __fsub_rn(p1[0], p0[0]), uy = __fsub_rn(p1[1], p0[1]), uz = __fsub_rn(p1[2], p0[2]);
         const float vx = __fsub_rn(p2[0], p0[0]), vy = __fsub_rn(p2[1], p0[1]), vz = __fsub_rn(p2[2], p0[2]);
@@ -306,56 +290,10 @@ __device__ __forceinline__ bool mesh_load(const RenderMeshArgs &a, int c, int ba
         float lit = __fdiv_rn(fabsf(__fadd_rn(__fadd_rn(__fmul_rn(nx, a.l[0]), __fmul_rn(ny, a.l[1])), __fmul_rn(nz, a.l[2]))), len);
         lit = lit >= 0.f ? lit : 0.f;
         lit = lit > 1.f ? 1.f : lit;
-        t.shade = 48u + (unsigned)__fmul_rn(207.f, lit);
+        shade = 48u + (unsigned)__fmul_rn(207.f, lit);
     }
-    t.a2 = mesh_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
-    if (t.a2 < 0) {
-        int w;
-        w = t.x1, t.x1 = t.x2, t.x2 = w;
-        w = t.y1, t.y1 = t.y2, t.y2 = w;
-        w = t.z1, t.z1 = t.z2, t.z2 = w;
-        t.a2 = -t.a2;
-    }
-    t.bw = t.bh = 0, t.bx = t.by = 0, t.ra2 = 0.0;
-    if (t.a2 != 0) {
-        // the centres (2 p + 1) 8 inside [lo, hi]: p from ceil((lo - 8) / 16) to floor((hi - 8) / 16), clipped to the cell
-        const int xlo = min(t.x0, min(t.x1, t.x2)), xhi = max(t.x0, max(t.x1, t.x2));
-        const int ylo = min(t.y0, min(t.y1, t.y2)), yhi = max(t.y0, max(t.y1, t.y2));
-        const int px0 = max((xlo + 7) >> 4, 0), px1 = min((xhi - 8) >> 4, a.cell - 1);
-        const int py0 = max((ylo + 7) >> 4, 0), py1 = min((yhi - 8) >> 4, a.cell - 1);
-        if (px1 >= px0 && py1 >= py0) t.bx = px0, t.by = py0, t.bw = px1 - px0 + 1, t.bh = py1 - py0 + 1;
-        t.ra2 = 1.0 / (double)t.a2;
-    }
+    raster_setup<4>(t, 0, a.cell - 1);
     return true;
-}
-
-// floor(num / den) for 0 <= num < 2^61, 0 < den < 2^37 and a quotient below 2^24: the fp64 estimate is off by less than one
-__device__ __forceinline__ long long mesh_div(long long num, long long den, double rden) {
-    long long q = (long long)((double)num * rden);
-    long long r = num - q * den;
-    if (r < 0) --q, r += den;
-    if (r >= den) ++q;
-    return q;
-}
-
-// The pixels start, start + step, ... (row-major in the box) of face t, minima into the cell's keys (cellkey: the cell's first pixel).
-__device__ __forceinline__ void mesh_scan(const MeshFace &t, unsigned *cellkey, size_t width, bool depth, int start, int step) {
-    const int n = t.bw * t.bh;
-    const int qy = step / t.bw, qx = step - qy * t.bw;
-    int iy = start / t.bw, ix = start - iy * t.bw;
-    for (int k = start; k < n; k += step) {
-        const int px = t.bx + ix, py = t.by + iy;
-        const int cx = (2 * px + 1) << 3, cy = (2 * py + 1) << 3;
-        const long long w0 = mesh_edge(t.x1, t.y1, t.x2, t.y2, cx, cy);
-        const long long w1 = mesh_edge(t.x2, t.y2, t.x0, t.y0, cx, cy);
-        const long long w2 = t.a2 - w0 - w1;                     // = edge(P0, P1, C): the three sum to A2 identically
-        if ((w0 | w1 | w2) >= 0) {
-            const unsigned q = (unsigned)mesh_div(w0 * t.z0 + w1 * t.z1 + w2 * t.z2, t.a2, t.ra2);
-            atomicMin(cellkey + (size_t)py * width + px, (q << 8) | (depth ? 255u - (q >> 17) : t.shade));
-        }
-        ix += qx, iy += qy;
-        if (ix >= t.bw) ix -= t.bw, ++iy;
-    }
 }
 
 __global__ __launch_bounds__(MESH_THREADS) void render_mesh_kernel(RenderMeshArgs a) {
@@ -363,36 +301,24 @@ __global__ __launch_bounds__(MESH_THREADS) void render_mesh_kernel(RenderMeshArg
     __shared__ int s_cnt[2];
     const int c = blockIdx.z, b = blockIdx.y;
     if (!a.verts[c]) return;                                     // a cloud column (the whole workgroup leaves)
-    const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t *rg = a.range[c] + 3 * (size_t)b;
     const int first = rg[0], count = rg[1], vbase = rg[2];
     const long long f0 = max(first, 0), f1 = min((long long)first + max(count, 0), (long long)a.F[c]);
     const bool depth = (a.depth_shade >> c) & 1;
     const size_t width = (size_t)a.cols * a.cell;
-    unsigned *cellkey = a.key + ((size_t)b * a.cell) * width + (size_t)c * a.cell;
-    if (tid < 2) s_cnt[tid] = 0;
+    unsigned *cellkey = a.key + ((size_t)b * a.cell) * width + (size_t)c * a.cell;      // the cell's first pixel
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    int par = 0;
-    for (long long base = f0 + (long long)blockIdx.x * MESH_THREADS; base < f1; base += (long long)gridDim.x * MESH_THREADS, par ^= 1) {
-        // ---- a lane per face: the small ones here, the large ones onto the list
-        const long long f = base + tid;
-        MeshFace t;
-        if (f < f1 && mesh_load(a, c, vbase, (int)f, t)) {
-            const int n = t.bw * t.bh;
-            if (n > MESH_SMALL_BOX) s_list[atomicAdd(&s_cnt[par], 1)] = (int)f;
-            else if (n > 0) mesh_scan(t, cellkey, width, depth, 0, 1);
-        }
-        __syncthreads();
-        // ---- a wave per large face
-        const int cnt = s_cnt[par];
-        if (tid == 0) s_cnt[par ^ 1] = 0;                        // (last read before the barrier that ended the previous sweep)
-        for (int e = wave; e < cnt; e += MESH_WAVES) {
-            const int g = __builtin_amdgcn_readfirstlane(s_list[e]);
-            mesh_load(a, c, vbase, g, t);                        // (it was alive when it was listed)
-            mesh_scan(t, cellkey, width, depth, lane, PDGN_WAVE);
-        }
-        __syncthreads();
-    }
+    unsigned shade;                                              // of the face this thread last loaded
+    raster_sweep<4>(
+        f0 + (long long)blockIdx.x * MESH_THREADS, f1, (long long)gridDim.x * MESH_THREADS, s_list, s_cnt,
+        [&](int f, RasterFace &t) { return mesh_load(a, c, vbase, f, t, shade); },
+        [&](int px, int py, long long z) {
+            const unsigned q = (unsigned)z;
+            atomicMin(cellkey + (size_t)py * width + px, (q << 8) | (depth ? 255u - (q >> 17) : shade));
+            return false;
+        },
+        [](int, const RasterFace &, bool, bool) {});
 }
 
 extern "C" int pdgn_render_sheet_mesh(int rows, int cols, const float *const *clouds, const float *const *normals, const int *npoints,

@@ -120,7 +120,6 @@ __global__ __launch_bounds__(256) void repulsion_bwd_kernel(long long count, con
         dxyz[k] = __fmul_rn(up, grad[k]);
 }
 
-static bool rp_aligned(const void *p) { return !((uintptr_t)p & 3); }
 
 extern "C" int pdgn_repulsion_chunk(void) { return RP_CHUNK; }
 
@@ -129,7 +128,8 @@ extern "C" int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, floa
     if (b < 1 || n < 1 || n > PDGN_REPULSION_MAX_N || (long long)b * n > (1LL << 28)) return PDGN_ERR_INVALID;
     if (!isfinite(inv_h2) || !(inv_h2 > 0.f) || !isfinite(coef)) return PDGN_ERR_INVALID;
     if (!xyz || !s || !loss) return PDGN_ERR_INVALID;
-    if (!rp_aligned(xyz) || !rp_aligned(s) || !rp_aligned(loss) || !rp_aligned(per_cloud) || !rp_aligned(grad) || !rp_aligned(nn2))
+    if (!pdgn_aligned(xyz, 4) || !pdgn_aligned(s, 4) || !pdgn_aligned(loss, 4) || !pdgn_aligned(per_cloud, 4) || !pdgn_aligned(grad, 4) ||
+        !pdgn_aligned(nn2, 4))
         return PDGN_ERR_INVALID;
     // the largest workgroup that still leaves one per CU (256 of them); 64 where even that does not
     const int block = (long long)b * cdiv(n, 256) >= 256 ? 256 : (long long)b * cdiv(n, 128) >= 256 ? 128 : 64;
@@ -153,7 +153,7 @@ extern "C" int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, floa
 
 extern "C" int pdgn_repulsion_backward(long long count, const float *grad, const float *g, float *dxyz, pdgn_stream_t stream) {
     if (count < 1 || !grad || !g || !dxyz) return PDGN_ERR_INVALID;
-    if (!rp_aligned(grad) || !rp_aligned(g) || !rp_aligned(dxyz)) return PDGN_ERR_INVALID;
+    if (!pdgn_aligned(grad, 4) || !pdgn_aligned(g, 4) || !pdgn_aligned(dxyz, 4)) return PDGN_ERR_INVALID;
     const int grid = (int)(count < 256LL * 1024 ? cdiv(count, 256) : 1024);
     hipLaunchKernelGGL(repulsion_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, count, grad, g, dxyz);
     return pdgn_launch_status();

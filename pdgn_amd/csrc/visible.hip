@@ -30,16 +30,12 @@
 //
 // THE KERNEL.  One workgroup of 256 threads per (shape, view), view fastest in the grid, so that the NV workgroups that gather the same
 // vertices run next to each other and hit in L2.  The depth buffer is dynamic LDS, 4 R^2 bytes (64 KB at R = 128: two workgroups per
-// CU; 144 KB at R = 192: one).  Faces are taken 256 at a time, a lane per face: a face whose clipped bounding box holds at most
-// VIS_SMALL_BOX pixels is rasterised by its lane; a larger one is appended to an LDS list and, after a barrier, taken by a whole wave
-// whose lanes stride over the pixels of its box (a face as large as the image is 16 384 centres at R = 128: 256 per lane).  The two
-// passes are the same sweep with atomicMin (ds_min_u32) in the first and a compare in the second.  The division by A2 is an fp64
-// estimate corrected by one step either way with the integer remainder: exact.
-#include "common.h"
+// CU; 144 KB at R = 192: one), beside the sweep's static 1 KB.  The two passes are the same sweep of the shape's faces (csrc/raster.h,
+// THE SWEEP: a lane per small face, a wave per large one, the exact division) with atomicMin (ds_min_u32) in the first and a compare in
+// the second.
+#include "raster.h"
 
-#define VIS_THREADS 256
-#define VIS_WAVES (VIS_THREADS / PDGN_WAVE)
-#define VIS_SMALL_BOX 32
+#define VIS_THREADS RASTER_THREADS
 #define VIS_EMPTY 0xffffffffu
 
 struct VisArgs {
@@ -48,13 +44,6 @@ struct VisArgs {
     const float *frame, *views;
     uint32_t *mask;
     int V, F, NV, R, bias_small;
-};
-
-struct VisFace {
-    int x0, y0, z0, x1, y1, z1, x2, y2, z2;
-    int bx, by, bw, bh;                                          // the clipped pixel box; bw * bh = 0: no centre to look at
-    long long a2;
-    double ra2;
 };
 
 struct VisView {
@@ -79,12 +68,8 @@ __device__ __forceinline__ void vis_snap(const VisView &w, const float *p, int &
     Z = vis_quant(vis_dot(w.ez, d0, d1, d2), w.rho, 1048576.f);
 }
 
-__device__ __forceinline__ long long vis_edge(int ax, int ay, int bx, int by, int px, int py) {
-    return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-
 // Gather and snap face f.  False: the face is dead (zero area in 3D, or an index outside the vertices).
-__device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int f, VisFace &t) {
+__device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int f, RasterFace &t) {
     const int i0 = a.faces[3 * (size_t)f], i1 = a.faces[3 * (size_t)f + 1], i2 = a.faces[3 * (size_t)f + 2];
     if ((unsigned)i0 >= (unsigned)a.V || (unsigned)i1 >= (unsigned)a.V || (unsigned)i2 >= (unsigned)a.V) return false;
     const float *q0 = a.verts + 3 * (size_t)i0, *q1 = a.verts + 3 * (size_t)i1, *q2 = a.verts + 3 * (size_t)i2;
@@ -100,112 +85,32 @@ __device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int
     vis_snap(w, p0, t.x0, t.y0, t.z0);
     vis_snap(w, p1, t.x1, t.y1, t.z1);
     vis_snap(w, p2, t.x2, t.y2, t.z2);
-    t.a2 = vis_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
-    if (t.a2 < 0) {
-        int s;
-        s = t.x1, t.x1 = t.x2, t.x2 = s;
-        s = t.y1, t.y1 = t.y2, t.y2 = s;
-        s = t.z1, t.z1 = t.z2, t.z2 = s;
-        t.a2 = -t.a2;
-    }
-    t.bw = t.bh = 0, t.bx = t.by = 0, t.ra2 = 0.0;
-    if (t.a2 != 0) {
-        // the centres (2 p + 1) 2^7 inside [lo, hi]: p from ceil((lo - 128) / 256) to floor((hi - 128) / 256), clipped to the image
-        const int xlo = min(t.x0, min(t.x1, t.x2)), xhi = max(t.x0, max(t.x1, t.x2));
-        const int ylo = min(t.y0, min(t.y1, t.y2)), yhi = max(t.y0, max(t.y1, t.y2));
-        const int px0 = (xlo + 127) >> 8, px1 = min((xhi - 128) >> 8, w.R - 1);
-        const int py0 = (ylo + 127) >> 8, py1 = min((yhi - 128) >> 8, w.R - 1);
-        if (px1 >= px0 && py1 >= py0) t.bx = px0, t.by = py0, t.bw = px1 - px0 + 1, t.bh = py1 - py0 + 1;
-        t.ra2 = 1.0 / (double)t.a2;
-    }
+    raster_setup<8>(t, 0, w.R - 1);
     return true;
 }
 
-// floor(num / den) for 0 <= num < 2^55, 0 < den < 2^34 and a quotient of at most 2^21: the fp64 estimate is off by less than one
-__device__ __forceinline__ long long vis_div(long long num, long long den, double rden) {
-    long long q = (long long)((double)num * rden);
-    long long r = num - q * den;
-    if (r < 0) --q, r += den;
-    if (r >= den) ++q;
-    return q;
-}
-
-// The pixels start, start + step, ... (row-major in the box) of face t.  TEST false: pass 1, minima into buf.  TEST true: pass 2; returns
-// whether the face passed at one of these pixels, covered whether one of them was covered.
-template <bool TEST>
-__device__ __forceinline__ bool vis_scan(const VisFace &t, unsigned *buf, int R, int start, int step, bool &covered) {
-    const int n = t.bw * t.bh;
-    const int qy = step / t.bw, qx = step - qy * t.bw;
-    int iy = start / t.bw, ix = start - iy * t.bw;
-    bool pass = false;
-    for (int k = start; k < n; k += step) {
-        const int px = t.bx + ix, py = t.by + iy;
-        const int cx = (2 * px + 1) << 7, cy = (2 * py + 1) << 7;
-        const long long w0 = vis_edge(t.x1, t.y1, t.x2, t.y2, cx, cy);
-        const long long w1 = vis_edge(t.x2, t.y2, t.x0, t.y0, cx, cy);
-        const long long w2 = t.a2 - w0 - w1;                     // = edge(P0, P1, C): the three sum to A2 identically
-        if ((w0 | w1 | w2) >= 0) {
-            const long long zp = vis_div(w0 * t.z0 + w1 * t.z1 + w2 * t.z2, t.a2, t.ra2);
-            if (TEST) {
-                covered = true;
-                if (zp <= (long long)buf[py * R + px] + PDGN_VISIBLE_BIAS_COVER) {
-                    pass = true;
-                    break;
-                }
-            } else {
-                atomicMin(buf + py * R + px, (unsigned)zp);
-            }
-        }
-        ix += qx, iy += qy;
-        if (ix >= t.bw) ix -= t.bw, ++iy;
-    }
-    return pass;
-}
-
-__device__ __forceinline__ bool vis_fallback(const VisFace &t, const unsigned *buf, int R, int bias_small) {
+__device__ __forceinline__ bool vis_fallback(const RasterFace &t, const unsigned *buf, int R, int bias_small) {
     const int px = min((t.x0 + t.x1 + t.x2) / 3 >> 8, R - 1), py = min((t.y0 + t.y1 + t.y2) / 3 >> 8, R - 1);
     return (long long)((t.z0 + t.z1 + t.z2) / 3) <= (long long)buf[py * R + px] + bias_small;
 }
 
 extern __shared__ unsigned vis_buf[];
 
+// One pass over the faces [f0, f1).  TEST false: pass 1, minima into the buffer.  TEST true: pass 2, the depth test; a face that passes
+// at one of its covered centres (the scan stops there), or at its fallback pixel where it covers none, ORs `bit` into its mask.
 template <bool TEST>
 __device__ __forceinline__ void vis_pass(const VisArgs &a, const VisView &w, int f0, int f1, unsigned bit, int *s_list, int *s_cnt) {
-    const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int par = 0;
-    for (int base = f0; base < f1; base += VIS_THREADS, par ^= 1) {
-        // ---- a lane per face: the small ones here, the large ones onto the list
-        const int f = base + tid;
-        VisFace t;
-        if (f < f1 && vis_load(a, w, f, t)) {
-            const int n = t.bw * t.bh;
-            if (n > VIS_SMALL_BOX) {
-                s_list[atomicAdd(&s_cnt[par], 1)] = f;
-            } else {
-                bool covered = false, pass = false;
-                if (n > 0) pass = vis_scan<TEST>(t, vis_buf, w.R, 0, 1, covered);
-                if (TEST) {
-                    if (!covered) pass = vis_fallback(t, vis_buf, w.R, a.bias_small);
-                    if (pass) atomicOr(a.mask + f, bit);
-                }
-            }
-        }
-        __syncthreads();
-        // ---- a wave per large face
-        const int cnt = s_cnt[par];
-        if (tid == 0) s_cnt[par ^ 1] = 0;                        // (last read before the barrier that ended the previous sweep)
-        for (int e = wave; e < cnt; e += VIS_WAVES) {
-            const int g = __builtin_amdgcn_readfirstlane(s_list[e]);
-            vis_load(a, w, g, t);                                // (it was alive when it was listed)
-            bool covered = false;
-            const bool pass = vis_scan<TEST>(t, vis_buf, w.R, lane, PDGN_WAVE, covered);
-            if (TEST) {
-                const bool any_pass = __any(pass), any_cov = __any(covered);
-                if (lane == 0 && (any_cov ? any_pass : vis_fallback(t, vis_buf, w.R, a.bias_small))) atomicOr(a.mask + g, bit);
-            }
-        }
-        __syncthreads();
-    }
+    const int R = w.R;
+    raster_sweep<8>(
+        f0, f1, VIS_THREADS, s_list, s_cnt, [&](int f, RasterFace &t) { return vis_load(a, w, f, t); },
+        [&](int px, int py, long long zp) {
+            if (TEST) return zp <= (long long)vis_buf[py * R + px] + PDGN_VISIBLE_BIAS_COVER;
+            atomicMin(vis_buf + py * R + px, (unsigned)zp);
+            return false;
+        },
+        [&](int f, const RasterFace &t, bool covered, bool passed) {
+            if (TEST && (covered ? passed : vis_fallback(t, vis_buf, R, a.bias_small))) atomicOr(a.mask + f, bit);
+        });
     if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;                 // (the next pass starts from parity 0 again)
     __syncthreads();
 }

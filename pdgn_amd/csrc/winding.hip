@@ -1,6 +1,6 @@
 // winding.hip -- generalized winding numbers (Jacobson, Kavan, Sorkine-Hornung 2013): pdgn_winding_number sums, for every point of a cloud,
 // the solid angles that the live faces of one shape subtend at it, over 4 pi: 1 inside a closed, consistently oriented surface, 0 outside
-// (include/pdgn_hip.h).  The faces are the records of pdgn_mesh_dist_prepare (csrc/meshdist.hip), unchanged.  No
+// (include/pdgn_hip.h).  The faces are the records of pdgn_mesh_dist_prepare (csrc/meshrec.h), unchanged.  No
 // inline assembly, no atomics of any kind, plain vector stores, nothing allocated.
 //
 // THE RESULT.  Per point p, over the live faces f of the shape:
@@ -33,23 +33,16 @@
 //     if x or y is NaN: v = NaN   (0x7FC00000; and r = inf / inf is NaN by itself: coordinates whose products overflow mark the point bad)
 // Its largest error against float64 arctan2 is 1.13 * 2^-22 over the sweeps of tests/test_winding_host.py (numpy's float32 arctan2: 1.32).
 //
-// SHAPE OF THE LAUNCH.  One thread per point; a workgroup of WN_THREADS = 256 owns a run of 256 points of one cloud and one PART of the
-// shape's chunks.  A chunk is WN_CHUNK = 256 record slots counted from the start of the shape's range; with nchunks of them and `parts`
-// parts, part k owns the chunks [k nchunks / parts, (k + 1) nchunks / parts) -- possibly none.  The chunks pass through LDS, thread t staging
-// slot j0 + t; a wave takes a chunk 64 slots at a time, a ballot collects which of them are live, and the wave walks the set bits reading
-// each face's three words at a uniform address (broadcasts).  Nothing can be culled: every live face is evaluated at every point.
+// SHAPE OF THE LAUNCH.  THE WALK of csrc/meshrec.h, with one thing added: a workgroup owns a run of 256 points of one cloud and one PART
+// of the shape's chunks.  With nchunks of them and `parts` parts, part k owns the chunks [k nchunks / parts, (k + 1) nchunks / parts) --
+// possibly none.  Nothing can be culled: every live face is evaluated at every point.
 //   parts = 1: the workgroup writes T, w and inside itself.  One launch.
 //   parts > 1: it writes its partial sum (INT64_MIN where bad -- no sum of fewer than 2^28 terms reaches it) to workspace[part][point], and a
 //   second launch of one thread per point adds the parts and writes T, w and inside.  Every workspace entry is written by exactly one
 //   workgroup before it is read, so nothing is zeroed beforehand and there are no atomics.
-#include "common.h"
+#include "meshrec.h"
 
-#include <math.h>
-
-#define WN_THREADS 256
-#define WN_CHUNK 256
-#define WN_GROUP 64
-#define WN_NAN_BITS 0x7FC00000u
+#define WN_THREADS MESHREC_THREADS                               // (wn_finish_kernel's too)
 #define WN_MAX_BLOCKS (1 << 23)                                  // workgroups per launch: 2^31 threads
 #define WN_MAX_FACES (1 << 28)
 #define WN_MAX_SPLITS 4096
@@ -57,13 +50,6 @@
 #define WN_T_HALF 13493037705LL                                  // llrint(pi 2^32)
 #define WN_T_BAD INT64_MIN
 #define WN_K 0x1.45f306dc9c883p-35                               // the double nearest 1 / (2^33 pi)
-static_assert(WN_CHUNK == WN_THREADS, "thread t stages slot j0 + t");
-static_assert(WN_GROUP == PDGN_WAVE, "lane l of a wave looks at slot l of a group");
-static_assert(WN_CHUNK % WN_GROUP == 0, "a chunk is whole groups");
-
-__device__ __forceinline__ float wn_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
 
 // NORMATIVE ORDER: natan2
 __device__ __forceinline__ float wn_atan2(float y, float x) {
@@ -83,20 +69,22 @@ __device__ __forceinline__ float wn_atan2(float y, float x) {
     if (x < 0.f) v = __fsub_rn(PI, v);
     if (y < 0.f) v = -v;
     if (y == 0.f) v = 0.f;
-    if (x != x || y != y) v = __uint_as_float(WN_NAN_BITS);
+    if (x != x || y != y) v = __uint_as_float(MESHREC_NAN_BITS);
     return v;
 }
 
 // NORMATIVE ORDER: h_f of the face (a, b, c) at p
+// (spelled in scalars: through MdVec and md_sub / md_cross / md_dotv of csrc/meshrec.h, the same operations, the compiler pairs them
+// differently into packed instructions and the walk's loop is one instruction in 200 longer, 0.4 % of the kernel's time, measured)
 __device__ __forceinline__ float wn_half_angle(float px, float py, float pz, float4 a, float4 b, float4 c) {
     const float Ax = __fsub_rn(a.x, px), Ay = __fsub_rn(a.y, py), Az = __fsub_rn(a.z, pz);
     const float Bx = __fsub_rn(b.x, px), By = __fsub_rn(b.y, py), Bz = __fsub_rn(b.z, pz);
     const float Cx = __fsub_rn(c.x, px), Cy = __fsub_rn(c.y, py), Cz = __fsub_rn(c.z, pz);
-    const float la = sqrtf(wn_dot(Ax, Ay, Az, Ax, Ay, Az)), lb = sqrtf(wn_dot(Bx, By, Bz, Bx, By, Bz)), lc = sqrtf(wn_dot(Cx, Cy, Cz, Cx, Cy, Cz));
+    const float la = sqrtf(dot3_rn(Ax, Ay, Az, Ax, Ay, Az)), lb = sqrtf(dot3_rn(Bx, By, Bz, Bx, By, Bz)), lc = sqrtf(dot3_rn(Cx, Cy, Cz, Cx, Cy, Cz));
     const float nx = __fsub_rn(__fmul_rn(By, Cz), __fmul_rn(Bz, Cy)), ny = __fsub_rn(__fmul_rn(Bz, Cx), __fmul_rn(Bx, Cz)),
                 nz = __fsub_rn(__fmul_rn(Bx, Cy), __fmul_rn(By, Cx));
-    const float num = wn_dot(Ax, Ay, Az, nx, ny, nz);
-    const float ab = wn_dot(Ax, Ay, Az, Bx, By, Bz), bc = wn_dot(Bx, By, Bz, Cx, Cy, Cz), ca = wn_dot(Cx, Cy, Cz, Ax, Ay, Az);
+    const float num = dot3_rn(Ax, Ay, Az, nx, ny, nz);
+    const float ab = dot3_rn(Ax, Ay, Az, Bx, By, Bz), bc = dot3_rn(Bx, By, Bz, Cx, Cy, Cz), ca = dot3_rn(Cx, Cy, Cz, Ax, Ay, Az);
     const float den = __fadd_rn(__fadd_rn(__fmul_rn(__fmul_rn(la, lb), lc), __fmul_rn(ab, lc)), __fadd_rn(__fmul_rn(bc, la), __fmul_rn(ca, lb)));
     return wn_atan2(num, den);
 }
@@ -105,7 +93,7 @@ __device__ __forceinline__ float wn_half_angle(float px, float py, float pz, flo
 __device__ __forceinline__ void wn_store(long long T, size_t at, long long *__restrict__ out_T, float *__restrict__ out_w,
                                          int32_t *__restrict__ out_in) {
     out_T[at] = T;
-    out_w[at] = T == WN_T_BAD ? __uint_as_float(WN_NAN_BITS) : (float)((double)T * WN_K);
+    out_w[at] = T == WN_T_BAD ? __uint_as_float(MESHREC_NAN_BITS) : (float)((double)T * WN_K);
     if (out_in) out_in[at] = T >= WN_T_HALF ? 1 : 0;
 }
 
@@ -115,50 +103,30 @@ __global__ __launch_bounds__(WN_THREADS) void wn_sum_kernel(int n, int S, int F,
                                                             const float4 *__restrict__ rec, long long *__restrict__ partial,
                                                             long long *__restrict__ out_T, float *__restrict__ out_w,
                                                             int32_t *__restrict__ out_in) {
-    __shared__ float4 s_rec[3 * WN_CHUNK];
+    __shared__ float4 s_rec[3 * MESHREC_CHUNK];
     const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1);
     const int part = blockIdx.x % parts, cr = blockIdx.x / parts;
     const int c = cr / runs, i = (cr % runs) * WN_THREADS + tid;
     const bool mine = i < n;
-    const float nan = __uint_as_float(WN_NAN_BITS);
-    float px = nan, py = nan, pz = nan;
-    if (mine) {
-        const size_t at = ((size_t)c * n + i) * 3;
-        px = xyz[at], py = xyz[at + 1], pz = xyz[at + 2];
-    }
-    bool bad = !(isfinite(px) && isfinite(py) && isfinite(pz));
-    // the shape's slots (uniform per workgroup); anything out of range is a shape without faces
-    const int s = shape[c];
-    int f0 = 0, f1 = 0;
-    if (s >= 0 && s < S) {
-        f0 = face_off[s], f1 = face_off[s + 1];
-        if (f0 < 0 || f1 > F || f1 < f0) f0 = f1 = 0;
-    }
-    const int slots = f1 - f0, nchunks = (slots + WN_CHUNK - 1) / WN_CHUNK;
+    const MdVec p = meshrec_point(xyz, c, n, i);
+    bool bad = !(isfinite(p.x) && isfinite(p.y) && isfinite(p.z));
+    const MeshrecRange r = meshrec_range<false>(shape, face_off, nullptr, c, S, F);
+    const int f0 = r.f0, slots = r.f1 - r.f0, nchunks = (slots + MESHREC_CHUNK - 1) / MESHREC_CHUNK;
     const int k0 = (int)((long long)part * nchunks / parts), k1 = (int)((long long)(part + 1) * nchunks / parts);
     long long T = 0;
     for (int k = k0; k < k1; ++k) {
-        const int j0 = k * WN_CHUNK, cnt = min(WN_CHUNK, slots - j0);
+        const int j0 = k * MESHREC_CHUNK, cnt = min(MESHREC_CHUNK, slots - j0);
         if (k > k0) __syncthreads();                               // everyone is done reading the previous chunk
-        {
-            float4 a = make_float4(0.f, 0.f, 0.f, __int_as_float(-1)), b = make_float4(0.f, 0.f, 0.f, 0.f), cc = b;
-            if (tid < cnt) {
-                const size_t at = (size_t)(f0 + j0 + tid) * 3;
-                a = rec[at], b = rec[at + 1], cc = rec[at + 2];
-            }
-            s_rec[3 * tid] = a, s_rec[3 * tid + 1] = b, s_rec[3 * tid + 2] = cc;
-        }
+        meshrec_stage(rec, f0 + j0, cnt, s_rec);
         __syncthreads();
-        for (int s0 = 0; s0 < cnt; s0 += WN_GROUP) {
-            unsigned long long todo = __ballot(__float_as_int(s_rec[3 * (s0 + lane)].w) >= 0);      // (s0 + lane < WN_CHUNK: a staged record, dead past cnt)
-            while (todo) {
-                const int jj = s0 + __builtin_ctzll(todo);         // uniform: the lowest live slot still to visit
-                todo &= todo - 1;
-                const float h = wn_half_angle(px, py, pz, s_rec[3 * jj], s_rec[3 * jj + 1], s_rec[3 * jj + 2]);
+        for (int s0 = 0; s0 < cnt; s0 += MESHREC_GROUP) {
+            // (s0 + lane < MESHREC_CHUNK: a staged record, dead past cnt)
+            meshrec_walk(s_rec, s0, __ballot(meshrec_face(s_rec[3 * (s0 + lane)]) >= 0), [&](const float4 *f) {
+                const float h = wn_half_angle(p.x, p.y, p.z, f[0], f[1], f[2]);
                 const bool ok = isfinite(h);
                 bad |= !ok;
                 T += ok ? __double2ll_rn((double)h * 4294967296.0) : 0LL;
-            }
+            });
         }
     }
     if (mine) {
@@ -186,8 +154,6 @@ __global__ __launch_bounds__(WN_THREADS) void wn_finish_kernel(long long total, 
 }
 
 // ---------------------------------------------------------------------------- entry points (host-side checks only before any launch)
-static bool wn_aligned(const void *p, uintptr_t to) { return !((uintptr_t)p & (to - 1)); }
-
 static bool wn_sizes_ok(int b, int n, int faces) {
     return b >= 1 && n >= 1 && faces >= 1 && faces <= WN_MAX_FACES && (long long)b * n < (1LL << 31);
 }
@@ -196,7 +162,7 @@ extern "C" long long pdgn_winding_half_turn(void) { return WN_T_HALF; }
 
 extern "C" int pdgn_winding_splits(int b, int n, int faces) {
     if (!wn_sizes_ok(b, n, faces)) return PDGN_ERR_INVALID;
-    const long long blocks = (long long)b * cdiv(n, WN_THREADS), chunks = cdiv(faces, WN_CHUNK);
+    const long long blocks = (long long)b * cdiv(n, WN_THREADS), chunks = cdiv(faces, MESHREC_CHUNK);
     long long parts = (WN_TARGET_BLOCKS + blocks - 1) / blocks;
     if (parts > chunks / 2) parts = chunks / 2;                    // a part has at least two chunks: single chunks divide unevenly
     if (parts > WN_MAX_SPLITS) parts = WN_MAX_SPLITS;
@@ -217,8 +183,8 @@ extern "C" int pdgn_winding_number(int b, int n, int S, int F, const float *xyz,
     const int runs = cdiv(n, WN_THREADS);
     if ((long long)b * runs * parts > WN_MAX_BLOCKS) return PDGN_ERR_INVALID;
     if (!xyz || !shape || !face_off || !records || !T || !w || (parts > 1 && !workspace)) return PDGN_ERR_INVALID;
-    if (!wn_aligned(xyz, 4) || !wn_aligned(shape, 4) || !wn_aligned(face_off, 4) || !wn_aligned(records, 16) || !wn_aligned(workspace, 8) ||
-        !wn_aligned(T, 8) || !wn_aligned(w, 4) || !wn_aligned(inside, 4))
+    if (!pdgn_aligned(xyz, 4) || !pdgn_aligned(shape, 4) || !pdgn_aligned(face_off, 4) || !pdgn_aligned(records, 16) || !pdgn_aligned(workspace, 8) ||
+        !pdgn_aligned(T, 8) || !pdgn_aligned(w, 4) || !pdgn_aligned(inside, 4))
         return PDGN_ERR_INVALID;
     hipLaunchKernelGGL(wn_sum_kernel, dim3((unsigned)((long long)b * runs * parts)), dim3(WN_THREADS), 0, (hipStream_t)stream, n, S, F, runs,
                        parts, (long long)b * n, xyz, shape, face_off, (const float4 *)records, workspace, T, w, inside);

@@ -446,6 +446,49 @@ def _shape_argument(shape, B, S, what):
     return host.astype(np.int64)
 
 
+def _meshset_argument(meshset, visible_only, what):
+    if not isinstance(meshset, MeshSet):
+        raise ValueError("%s: meshset is a MeshSet, got %s" % (what, type(meshset).__name__))
+    if visible_only and meshset.visible is None:
+        raise ValueError("%s: visible_only needs a mesh set built with visibility masks" % what)
+
+
+def _query_arguments(xyz, meshset, shape, visible_only, what):
+    """The checks every query of points against a mesh set opens with -> (B, N, shape (B) int64 numpy)."""
+    import torch
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
+        raise ValueError("%s: xyz is a (B,N,3) float32 tensor, got %s" % (
+            what, "%s %s" % (xyz.dtype, tuple(xyz.shape)) if isinstance(xyz, torch.Tensor) else type(xyz).__name__))
+    _meshset_argument(meshset, False, what)
+    B, N, _ = xyz.shape
+    if B < 1 or N < 1 or B * N > 0x7FFFFFFF:
+        raise ValueError("%s: %d clouds of %d points; at least one point, and B N below 2^31" % (what, B, N))
+    shape_h = _shape_argument(shape, B, meshset.S, what)
+    _meshset_argument(meshset, visible_only, what)
+    if xyz.device != meshset.verts.device:
+        raise ValueError("%s: xyz is on %s, the mesh set on %s" % (what, xyz.device, meshset.verts.device))
+    return B, N, shape_h
+
+
+def _sorted_points(xyz, sort_points):
+    """(xyz as the kernels take it, perm): every cloud's points in Morton order; perm None: as given (sort_points off, or one point)."""
+    import torch
+    from . import _lib
+    xyz = _lib.require(xyz.detach().contiguous(), "xyz", torch.float32, 3)
+    if not (SORT_POINTS if sort_points is None else bool(sort_points)) or xyz.shape[1] <= 1:
+        return xyz, None
+    finite = torch.nan_to_num(xyz, nan=0.0, posinf=0.0, neginf=0.0)
+    perm = torch.argsort(_morton30(xyz, finite.amin(dim=1, keepdim=True), finite.amax(dim=1, keepdim=True)), dim=1, stable=True)
+    return torch.gather(xyz, 1, perm[..., None].expand(-1, -1, 3)).contiguous(), perm
+
+
+def _unsorted(perm, *tensors):
+    """The kernel's results (B,N) or (B,N,3) back in the caller's point order; None stays None."""
+    if perm is None:
+        return tensors
+    return tuple(t if t is None else t.new_empty(t.shape).scatter_(1, perm if t.dim() == 2 else perm[..., None].expand_as(t), t) for t in tensors)
+
+
 def point_to_mesh(xyz, meshset, shape=None, visible_only=False, cull=True, return_closest=False, sort_points=None, sort_faces=None):
     """The closest point of a triangle set (pdgn_point_mesh_distance; the definition is the header block of csrc/meshdist.hip): xyz (B,N,3)
     fp32 on the mesh set's device; shape (B) integers, the shape each cloud is measured against (repeats and any order; None: cloud c
@@ -456,28 +499,10 @@ def point_to_mesh(xyz, meshset, shape=None, visible_only=False, cull=True, retur
     None: the module's defaults.  Unsigned; no autograd (losses.surface_distance is the differentiable form)."""
     import torch
     from . import _lib
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
-        raise ValueError("point_to_mesh: xyz is a (B,N,3) float32 tensor, got %s" % (
-            "%s %s" % (xyz.dtype, tuple(xyz.shape)) if isinstance(xyz, torch.Tensor) else type(xyz).__name__,))
-    if not isinstance(meshset, MeshSet):
-        raise ValueError("point_to_mesh: meshset is a MeshSet, got %s" % type(meshset).__name__)
-    B, N, _ = xyz.shape
-    if B < 1 or N < 1 or B * N > 0x7FFFFFFF:
-        raise ValueError("point_to_mesh: %d clouds of %d points; at least one point, and B N below 2^31" % (B, N))
-    shape_h = _shape_argument(shape, B, meshset.S, "point_to_mesh")
-    if visible_only and meshset.visible is None:
-        raise ValueError("point_to_mesh: visible_only needs a mesh set built with visibility masks")
-    if xyz.device != meshset.verts.device:
-        raise ValueError("point_to_mesh: xyz is on %s, the mesh set on %s" % (xyz.device, meshset.verts.device))
-    sort_points = SORT_POINTS if sort_points is None else bool(sort_points)
+    B, N, shape_h = _query_arguments(xyz, meshset, shape, visible_only, "point_to_mesh")
     rec = mesh_dist_records(meshset, visible_only, sort_faces)
-    xyz = _lib.require(xyz.detach().contiguous(), "xyz", torch.float32, 3)
+    xyz, perm = _sorted_points(xyz, sort_points)
     dev = xyz.device
-    perm = None
-    if sort_points and N > 1:
-        finite = torch.nan_to_num(xyz, nan=0.0, posinf=0.0, neginf=0.0)
-        perm = torch.argsort(_morton30(xyz, finite.amin(dim=1, keepdim=True), finite.amax(dim=1, keepdim=True)), dim=1, stable=True)
-        xyz = torch.gather(xyz, 1, perm[..., None].expand(-1, -1, 3)).contiguous()
     d_shape = torch.from_numpy(shape_h.astype(np.int32)).to(dev)
     d2 = torch.empty(B, N, dtype=torch.float32, device=dev)
     face = torch.empty(B, N, dtype=torch.int32, device=dev)
@@ -486,10 +511,7 @@ def point_to_mesh(xyz, meshset, shape=None, visible_only=False, cull=True, retur
                                                    _lib.ptr(meshset.face_off), _lib.ptr(rec["group_off"]), _lib.ptr(rec["records"]),
                                                    _lib.ptr(rec["groups"]), 1 if cull else 0, _lib.ptr(d2), _lib.ptr(face),
                                                    _lib.ptr(closest), _lib.stream_of(xyz)), "pdgn_point_mesh_distance")
-    if perm is not None:
-        d2, face = torch.empty_like(d2).scatter_(1, perm, d2), torch.empty_like(face).scatter_(1, perm, face)
-        if return_closest:
-            closest = torch.empty_like(closest).scatter_(1, perm[..., None].expand(-1, -1, 3), closest)
+    d2, face, closest = _unsorted(perm, d2, face, closest)
     return (d2, face, closest) if return_closest else (d2, face)
 
 
@@ -498,23 +520,10 @@ def _winding(xyz, meshset, shape, visible_only, sort_points, splits, what):
     """The checks and the launch of `winding_number` -> (T (B,N) int64, w (B,N) fp32, inside (B,N) int32), all from the kernel."""
     import torch
     from . import _lib
-    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.dtype != torch.float32:
-        raise ValueError("%s: xyz is a (B,N,3) float32 tensor, got %s" % (
-            what, "%s %s" % (xyz.dtype, tuple(xyz.shape)) if isinstance(xyz, torch.Tensor) else type(xyz).__name__))
-    if not isinstance(meshset, MeshSet):
-        raise ValueError("%s: meshset is a MeshSet, got %s" % (what, type(meshset).__name__))
-    B, N, _ = xyz.shape
-    if B < 1 or N < 1 or B * N > 0x7FFFFFFF:
-        raise ValueError("%s: %d clouds of %d points; at least one point, and B N below 2^31" % (what, B, N))
-    shape_h = _shape_argument(shape, B, meshset.S, what)
-    if visible_only and meshset.visible is None:
-        raise ValueError("%s: visible_only needs a mesh set built with visibility masks" % what)
-    if xyz.device != meshset.verts.device:
-        raise ValueError("%s: xyz is on %s, the mesh set on %s" % (what, xyz.device, meshset.verts.device))
+    B, N, shape_h = _query_arguments(xyz, meshset, shape, visible_only, what)
     splits = 0 if splits is None else int(splits)
     if splits < 0:
         raise ValueError("%s: splits is None or 0 (the library chooses) or a count of parts, got %d" % (what, splits))
-    sort_points = SORT_POINTS if sort_points is None else bool(sort_points)
     rec = mesh_dist_records(meshset, visible_only)
     L = _lib.lib()
     if splits == 0:                                              # from the largest face count among the shapes named, which the host knows
@@ -523,13 +532,8 @@ def _winding(xyz, meshset, shape, visible_only, sort_points, splits, what):
             counts = meshset.__dict__["_face_counts"] = np.diff(meshset.face_off.cpu().numpy().astype(np.int64))
         splits = L.pdgn_winding_splits(B, N, max(1, int(counts[shape_h].max())))
         _lib.check(min(splits, 0), "pdgn_winding_splits")
-    xyz = _lib.require(xyz.detach().contiguous(), "xyz", torch.float32, 3)
+    xyz, perm = _sorted_points(xyz, sort_points)
     dev = xyz.device
-    perm = None
-    if sort_points and N > 1:
-        finite = torch.nan_to_num(xyz, nan=0.0, posinf=0.0, neginf=0.0)
-        perm = torch.argsort(_morton30(xyz, finite.amin(dim=1, keepdim=True), finite.amax(dim=1, keepdim=True)), dim=1, stable=True)
-        xyz = torch.gather(xyz, 1, perm[..., None].expand(-1, -1, 3)).contiguous()
     d_shape = torch.from_numpy(shape_h.astype(np.int32)).to(dev)
     nbytes = L.pdgn_winding_workspace_bytes(B, N, meshset.F, splits)
     _lib.check(min(nbytes, 0), "pdgn_winding_workspace_bytes")
@@ -540,9 +544,7 @@ def _winding(xyz, meshset, shape, visible_only, sort_points, splits, what):
     _lib.check(L.pdgn_winding_number(B, N, meshset.S, meshset.F, _lib.ptr(xyz), _lib.ptr(d_shape), _lib.ptr(meshset.face_off),
                                      _lib.ptr(rec["records"]), splits, _lib.ptr(work), _lib.ptr(T), _lib.ptr(w), _lib.ptr(inside),
                                      _lib.stream_of(xyz)), "pdgn_winding_number")
-    if perm is not None:
-        T, w, inside = (torch.empty_like(t).scatter_(1, perm, t) for t in (T, w, inside))
-    return T, w, inside
+    return _unsorted(perm, T, w, inside)
 
 
 def winding_number(xyz, meshset, shape=None, visible_only=False, sort_points=None, splits=None, return_sum=False):
@@ -650,12 +652,10 @@ def occupancy_grid(meshset, shape=None, resolution=64, bounds=None, pad=0.05, vi
     starts at lo and its cubic cells are the longest side / R wide; None: every shape's own box, grown by `pad` of its longest side on
     every side and made cubic.  The queries go out in slabs of planes, so the memory taken besides the result stays bounded."""
     import torch
-    if not isinstance(meshset, MeshSet):
-        raise ValueError("occupancy_grid: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    _meshset_argument(meshset, False, "occupancy_grid")
     R = _resolution_argument(resolution, "occupancy_grid")
     shape_h = _shape_list(shape, meshset.S, "occupancy_grid")
-    if visible_only and meshset.visible is None:
-        raise ValueError("occupancy_grid: visible_only needs a mesh set built with visibility masks")
+    _meshset_argument(meshset, visible_only, "occupancy_grid")
     if bounds is None:
         origin, voxel = cubic_grid(*shape_boxes(meshset, shape_h, visible_only), R, pad)
     else:
@@ -671,8 +671,7 @@ def winding_report(meshset, samples=4096, seed=0):
     "fractional" (S): the share of the points with |w - rint(w)| > 0.05}.  A watertight, outward-oriented shape gives 0, 1 and a share
     of 0 up to the points that fall within a hair of the surface; flipped or missing faces show as values in between."""
     import torch
-    if not isinstance(meshset, MeshSet):
-        raise ValueError("winding_report: meshset is a MeshSet, got %s" % type(meshset).__name__)
+    _meshset_argument(meshset, False, "winding_report")
     if int(samples) < 1:
         raise ValueError("winding_report: samples is a positive count, got %r" % (samples,))
     lo, hi = shape_boxes(meshset)
