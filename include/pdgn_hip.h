@@ -354,7 +354,10 @@ int pdgn_skinny_nn_masked(int R, int N, int K, const float *A, int lda, const fl
 int pdgn_skinny_tn(int R, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, pdgn_stream_t stream);
 /* A weight matrix split ONCE into the three bf16 parts the contractions multiply (x = h + m + l, csrc/split.hip) instead of by
  * every workgroup's loader: src (rows x cols fp32, pitch ld_src) -> planes (3 x [rows][ld_planes] bf16, plane_stride elements
- * apart; may be NULL) and / or planes_t, the same for the TRANSPOSE (3 x [cols][ld_planes_t]; may be NULL).
+ * apart; may be NULL) and / or planes_t, the same for the TRANSPOSE (3 x [cols][ld_planes_t]; may be NULL).  The pad columns
+ * of EVERY row, the last row's too, are zero-filled up to cols rounded up to 32 (ld_planes beyond that stays unwritten; the
+ * contraction's 16-byte loads reach at most cols rounded up to 8): plane_stride >= rows * ld_planes (plane_stride_t >= cols *
+ * ld_planes_t, its pads filled up to rows rounded up to 32), else PDGN_ERR_INVALID.
  * pdgn_gemm_nt_ps = pdgn_gemm_nt_ex with such planes as the second operand (n x k, pitch ldw, wplane elements between planes;
  * ldw and wplane multiples of 8, the planes 16-byte aligned):
  * forward y = x W^T with W's planes, input gradient dX = dY W with the planes of W^T.  parts = 3 (these planes) or 2 (the two

@@ -67,8 +67,10 @@ extern "C" int pdgn_split_bf16x3(int rows, int cols, const float *src, int ld_sr
                                  long long plane_stride, unsigned short *planes_t, int ld_planes_t, long long plane_stride_t,
                                  pdgn_stream_t stream) {
     if (rows < 1 || cols < 1 || ld_src < cols || (!planes && !planes_t)) return PDGN_ERR_INVALID;
-    if (planes && (ld_planes < cols || plane_stride < (long long)(rows - 1) * ld_planes + cols)) return PDGN_ERR_INVALID;
-    if (planes_t && (ld_planes_t < rows || plane_stride_t < (long long)(cols - 1) * ld_planes_t + rows)) return PDGN_ERR_INVALID;
+    // (the kernel fills the pad columns of every row, the last one's too -- as in pdgn_split_f16x2: the planes must hold whole rows,
+    // or the last row's pads land in the next plane and, behind the third, outside the buffer)
+    if (planes && (ld_planes < cols || plane_stride < (long long)rows * ld_planes)) return PDGN_ERR_INVALID;
+    if (planes_t && (ld_planes_t < rows || plane_stride_t < (long long)cols * ld_planes_t)) return PDGN_ERR_INVALID;
     hipLaunchKernelGGL(split_bf16x3_kernel, dim3(cdiv(cols, 32), cdiv(rows, 32)), dim3(256), 0, (hipStream_t)stream, rows, cols, src,
                        ld_src, planes, ld_planes, plane_stride, planes_t, ld_planes_t, plane_stride_t);
     return pdgn_launch_status();
