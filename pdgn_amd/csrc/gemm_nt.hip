@@ -485,153 +485,77 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_nt_kernel(const NtArgs p
     }
 }
 
-template <int TM, int TN, int WM, int WN, int MAXWG>
+// ------------------------------------------------------------------ host side
+// What is compile-time about a tile: the kernel's template parameters and its instances.  The rest -- sizes, workgroups per CU,
+// the launch model -- is the tile's record in gemm_plan.h (FP32_TILES, in this order); the static_assert ties the two together.
+constexpr int nt_flags(bool atomic, bool wt, bool at, bool epi) { return (atomic ? 1 : 0) | (wt ? 2 : 0) | (at ? 4 : 0) | (epi ? 8 : 0); }
+// the (ATOMIC, WT, AT, EPI) combinations nt_launch can ask for; the weight gradient's (AT) not on the 160 x 64 tile
+#define NT_INSTANCES(X)                                                                                                          \
+    X(false, false, false, false) X(true, false, false, false) X(false, false, false, true) X(false, true, false, false)          \
+    X(true, true, false, false) X(false, true, false, true)
+#define NT_INSTANCES_AT(X) X(false, true, true, false) X(true, true, true, false)
+
+template <int TM, int TN, int WM, int WN, int MAXWG, bool HAS_AT>
 struct NtCfg {
     static constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
     static constexpr int LDS = 2 * (BM + BN) * NT_BK * 4;
     static constexpr int WG_PER_CU = (160 * 1024 / LDS) < MAXWG ? (160 * 1024 / LDS) : MAXWG;   // MAXWG: the register file's limit
-
-    // what the launch will do: tiles, slots, whether a stream-K tail follows the whole rounds
-    struct Plan {
-        int tiles_m, tiles_n, kchunks, grid_dp, dp_tiles, grid_sk;
-        long long sk_per_wg;
-        double cost;                                               // launch model, microseconds
-    };
-    // Launch model (calibrated on MI355X, tools/gemm_shapes.py): a CU multiplies ~0.56 Mflop/us on this loop; the w
-    // workgroups sharing a CU share that; a tile costs ~2.5 chunks on top of its own (ring fill, output); the atomics of
-    // a partial tile are added at ~1.3 TB/s chip-wide.
-    // Workgroups of the data-parallel launch: at least one per slot, and more -- each then walks fewer tiles -- so that
-    // the hardware hands them out as CUs come free (this kernel shares the chip with the step's other streams; a static
-    // assignment over exactly `slots` workgroups lets one delayed workgroup hold up the launch): enough tiles per
-    // workgroup to keep ~32 chunks of work behind one ring fill.
-    static int dp_grid(long long tiles, int slots, int kc) {
-        static int tpw_env = -1;
-        if (tpw_env < 0) { const char *e = getenv("PDGN_NT_TPW"); tpw_env = e ? atoi(e) : 0; }
-        int tpw = tpw_env > 0 ? tpw_env : (32 + kc - 1) / kc;
-        tpw = tpw < 1 ? 1 : (tpw > 8 ? 8 : tpw);
-        if (tpw_env >= 1000) return (int)(tiles < slots ? tiles : slots);          // measurement: one workgroup per slot
-        const long long g = (tiles + tpw - 1) / tpw;
-        const long long lo = tiles < slots ? tiles : slots;
-        return (int)(g < lo ? lo : g);
+    static constexpr bool matches(const GemmTile &t) {
+        return BM == t.bm && BN == t.bn && WG_PER_CU == t.wg_per_cu && WM == t.stat_div && t.rate == 0.56e6 * (TM * TN >= 16 ? 1.0 : 0.95);
     }
-    static double chunk_us(int w) { return 2.0 * BM * BN * NT_BK * w / (0.56e6 * (TM * TN >= 16 ? 1.0 : 0.95)); }
-    static Plan plan(long long m, int n, int k, bool allow_sk) {
-        Plan pl;
-        pl.tiles_m = cdiv(m, BM);
-        pl.tiles_n = cdiv(n, BN);
-        pl.kchunks = cdiv(k, NT_BK);
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        const int cus = nt_cus(), slots = cus * WG_PER_CU, KC = pl.kchunks;
-        const long long rounds = T / slots, tail = T - rounds * slots;
-        const double ov = 2.5;
-        const double full = (double)rounds * (KC + ov) * chunk_us(WG_PER_CU);
-        // data-parallel only: the last, partial round runs ceil(tail / cus) workgroups on its busiest CU
-        pl.dp_tiles = (int)T;
-        pl.grid_dp = dp_grid(T, slots, KC);
-        pl.grid_sk = 0;
-        pl.sk_per_wg = 0;
-        pl.cost = full + (tail ? (KC + ov) * chunk_us((int)((tail + cus - 1) / cus)) : 0.0);
-        if (allow_sk && tail > 0) {
-            // stream-K tail over g workgroups: every slot, one per CU, or fewer with at least 16 chunks each
-            const long long iters = tail * KC;
-            const long long cand[3] = {(long long)slots, (long long)cus, iters / 16};
-            for (int ci = 0; ci < 3; ++ci) {
-                long long g = cand[ci] < 1 ? 1 : (cand[ci] > slots ? slots : cand[ci]);
-                g = g < iters ? g : iters;
-                const long long per = (iters + g - 1) / g;
-                if (per < 8 && g > 1) continue;                    // short ranges: the atomics cost more than they balance
-                g = (iters + per - 1) / per;
-                const double zero_rows = (double)(m - (long long)((rounds * slots) / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * BM);
-                const double c = full + (per + ov) * chunk_us((int)((g + cus - 1) / cus)) + (double)(g + tail) * BM * BN * 4 / 1.3e6 +
-                                 zero_rows * n * 4 / 3.0e6 + 4.0;
-                if (c < pl.cost) {
-                    pl.cost = c;
-                    pl.dp_tiles = (int)(rounds * slots);
-                    pl.grid_dp = rounds ? dp_grid(rounds * slots, slots, KC) : 0;
-                    pl.grid_sk = (int)g;
-                    pl.sk_per_wg = per;
-                }
-            }
-        }
-        return pl;
-    }
-
-    template <bool WT, bool AT = false>
-    static int launch(long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
-                      const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
-                      const NtEpi &epi = NtEpi()) {
-        const bool allow_sk = stat_part == nullptr && ldc == n && !epi.any();
-        const Plan pl = plan(m, n, k, allow_sk);
-        NtArgs a;
-        a.Wp = nullptr; a.wplane = 0;
-        a.M = m; a.N = n; a.K = k; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldadd = ldadd;
-        a.A = A; a.W = W; a.bias = bias; a.addend = addend; a.C = C; a.stat_part = stat_part;
-        a.row_bias = epi.row_bias; a.ld_rb = epi.ld_rb; a.rows_per_group = epi.rows_per_group > 0 ? epi.rows_per_group : 1;
-        a.rpg_magic = a.rows_per_group > 1 ? (unsigned)(0x100000000ULL / (unsigned)a.rows_per_group) + 1u : 0u;
-        a.rb_bytes = epi.row_bias ? (int)((((m + a.rows_per_group - 1) / a.rows_per_group - 1) * (long long)epi.ld_rb + n) * 4) : 0;
-        a.act = epi.act; a.gate = epi.gate; a.ldgate = epi.ldgate; a.sk_split = 0; a.sk_ws = nullptr; a.sk_seg = 0; a.max_a = a.max_w = nullptr;
-        a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n; a.kchunks = pl.kchunks;
-        a.dbg = 0;
-#ifdef PDGN_NT_DEBUG
-        { const char *e = getenv("PDGN_NT_DBG"); a.dbg = e ? atoi(e) : 0; }
-#endif
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        if (pl.grid_sk) {
-            // the tail tiles start in tile-row group dp_tiles / (NT_GROUP_M tiles_n): zero its rows and all below (whole rows; the data-parallel
-            // launch overwrites its share of that tile row afterwards)
-            const long long r0 = (long long)(pl.dp_tiles / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * BM;
-            if (hipMemsetAsync(C + r0 * ldc, 0, (size_t)(m - r0) * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
-        }
-        if (pl.grid_dp) {
-            a.tile_begin = 0; a.tile_end = pl.dp_tiles; a.sk_per_wg = 0;
-            if (!AT && epi.any())
-                hipLaunchKernelGGL((gemm_nt_kernel<TM, TN, WM, WN, false, WT, false, true>), dim3(pl.grid_dp), dim3(64 * WM * WN), 0, s, a);
-            else
-                hipLaunchKernelGGL((gemm_nt_kernel<TM, TN, WM, WN, false, WT, AT>), dim3(pl.grid_dp), dim3(64 * WM * WN), 0, s, a);
-        }
-        if (pl.grid_sk) {
-            a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_per_wg = pl.sk_per_wg;
-            hipLaunchKernelGGL((gemm_nt_kernel<TM, TN, WM, WN, true, WT, AT>), dim3(pl.grid_sk), dim3(64 * WM * WN), 0, s, a);
-        }
-        return pdgn_launch_status();
+    static NtInstance instance(int flags) {
+#define NT_CASE(A_, WT_, AT_, EPI_)                                                                                               \
+    if (flags == nt_flags(A_, WT_, AT_, EPI_)) return {(const void *)gemm_nt_kernel<TM, TN, WM, WN, A_, WT_, AT_, EPI_>, 64 * WM * WN};
+        NT_INSTANCES(NT_CASE)
+        if constexpr (HAS_AT) { NT_INSTANCES_AT(NT_CASE) }
+#undef NT_CASE
+        return {nullptr, 0};
     }
 };
 
-typedef NtCfg<4, 4, 4, 2, 1> NtBig;      // 256 x 128, 8 waves (96 KB): one workgroup per CU
-typedef NtCfg<4, 4, 2, 2, 2> NtSquare;   // 128 x 128, 4 waves (64 KB): two per CU
-typedef NtCfg<5, 2, 2, 2, 2> NtTall;     // 160 x 64, 4 waves (56 KB): two per CU; 35840 = 224 x 160
-typedef NtCfg<4, 2, 2, 2, 3> NtNarrow;   // 128 x 64, 4 waves (48 KB, < 168 registers): three per CU
+typedef NtCfg<4, 4, 4, 2, 1, true> NtBig;       // 256 x 128, 8 waves (96 KB): one workgroup per CU
+typedef NtCfg<4, 4, 2, 2, 2, true> NtSquare;    // 128 x 128, 4 waves (64 KB): two per CU
+typedef NtCfg<5, 2, 2, 2, 2, false> NtTall;     // 160 x 64, 4 waves (56 KB): two per CU; 35840 = 224 x 160
+typedef NtCfg<4, 2, 2, 2, 3, true> NtNarrow;    // 128 x 64, 4 waves (48 KB, < 168 registers): three per CU
+static_assert(NtBig::matches(FP32_TILES[0]) && NtSquare::matches(FP32_TILES[1]) && NtTall::matches(FP32_TILES[2]) &&
+                  NtNarrow::matches(FP32_TILES[3]),
+              "gemm_plan.h's fp32 tile table and the kernel's template parameters disagree");
 
-// Tile configuration for a problem: PDGN_NT_CFG (0-3, measurement only), else the cheapest by the launch model.
-static int nt_pick(long long m, int n, int k, bool stats, bool no_tall = false) {
-    const int forced = nt_switches().cfg;
-    if (forced >= 0) return (no_tall && forced == 2) ? 1 : forced;
-    const bool sk = !stats;
-    const double c[4] = {NtBig::plan(m, n, k, sk).cost, NtSquare::plan(m, n, k, sk).cost, NtTall::plan(m, n, k, sk).cost,
-                         NtNarrow::plan(m, n, k, sk).cost};
-    int best = 1;
-    for (int i = 0; i < 4; ++i)
-        if (c[i] < c[best] * 0.97 && !(no_tall && i == 2)) best = i;    // the square tile unless another is clearly cheaper
-    return best;
-}
-
-static bool nt_args_ok(long long m, int n, int k, int lda, int ldw, int ldadd, int ldc, const float *addend, bool wt) {
-    return m >= 1 && n >= 4 && k >= 4 && n % 4 == 0 && k % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && ldc % 4 == 0 &&
-           lda >= k && ldw >= (wt ? n : k) && ldc >= n && (!addend || (ldadd % 4 == 0 && ldadd >= n)) && lda < (1 << 19) &&
-           ldw < (1 << 19) && ldc < (1 << 19) && (long long)cdiv(m, 128) * cdiv(n, 64) < 0x7fffffffLL &&
-           (!wt || (long long)k * ldw < (1LL << 27));
-}
-
-template <bool WT>
-static int nt_dispatch(long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
-                       const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
-                       const NtEpi &epi = NtEpi()) {
-    switch (nt_pick(m, n, k, stat_part != nullptr || epi.any())) {
-        case 0: return NtBig::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi);
-        case 2: return NtTall::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi);
-        case 3: return NtNarrow::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi);
-        default: return NtSquare::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi);
+static NtInstance nt_instance(int cfg, int flags) {
+    switch (cfg) {
+        case 0: return NtBig::instance(flags);
+        case 2: return NtTall::instance(flags);
+        case 3: return NtNarrow::instance(flags);
+        default: return NtSquare::instance(flags);
     }
+}
+
+// One product on tile cfg: the data-parallel launch over the whole rounds and, where the plan has one, the stream-K tail.
+// wt / at: the second / the first operand is given transposed.
+static int nt_launch(int cfg, bool wt, bool at, long long m, int n, int k, const float *A, int lda, const float *W, int ldw,
+                     const float *bias, const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
+                     const NtEpi &epi = NtEpi()) {
+    const GemmTile &t = FP32_TILES[cfg];
+    const bool allow_sk = stat_part == nullptr && ldc == n && !epi.any();
+    const GemmPlan pl = gemm_plan(t, m, n, k, allow_sk, nt_cus());
+    NtArgs a;
+    nt_fill_args(a, pl, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, epi);
+    const long long T = (long long)pl.tiles_m * pl.tiles_n;
+    if (pl.grid_sk) {
+        // the tail tiles start in tile-row group dp_tiles / (NT_GROUP_M tiles_n): zero its rows and all below (whole rows; the data-parallel
+        // launch overwrites its share of that tile row afterwards)
+        const long long r0 = (long long)(pl.dp_tiles / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * t.bm;
+        if (hipMemsetAsync(C + r0 * ldc, 0, (size_t)(m - r0) * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
+    }
+    if (pl.grid_dp) {
+        a.tile_begin = 0; a.tile_end = pl.dp_tiles; a.sk_per_wg = 0;
+        nt_go(nt_instance(cfg, nt_flags(false, wt, at, !at && epi.any())), pl.grid_dp, s, a);
+    }
+    if (pl.grid_sk) {
+        a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_per_wg = pl.sk_per_wg;
+        nt_go(nt_instance(cfg, nt_flags(true, wt, at, false)), pl.grid_sk, s, a);
+    }
+    return pdgn_launch_status();
 }
 
 // C (m x n, row pitch ldc) = A (m x k, pitch lda) W (n x k, pitch ldw)^T (+ bias[n]) (+ addend (m x n, pitch ldadd)).
@@ -642,7 +566,8 @@ int fp32_gemm_nt(long long m, int n, int k, const float *A, int lda, const float
                             const float *bias, const float *addend, int ldadd, float *C, int ldc, float *stat_part,
                             pdgn_stream_t stream) {
     if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, false)) return PDGN_ERR_INVALID;
-    return nt_dispatch<false>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
+    return nt_launch(nt_pick(true, m, n, k, stat_part != nullptr), false, false, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc,
+                     stat_part, (hipStream_t)stream);
 }
 
 // The same product with the second operand given transposed: C (m x n) = A (m x k) Wt (k x n, row pitch ldw) -- the
@@ -651,7 +576,8 @@ int fp32_gemm_nn(long long m, int n, int k, const float *A, int lda, const float
                             const float *bias, const float *addend, int ldadd, float *C, int ldc, float *stat_part,
                             pdgn_stream_t stream) {
     if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, true)) return PDGN_ERR_INVALID;
-    return nt_dispatch<true>(m, n, k, A, lda, Wt, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
+    return nt_launch(nt_pick(true, m, n, k, stat_part != nullptr), true, false, m, n, k, A, lda, Wt, ldw, bias, addend, ldadd, C, ldc,
+                     stat_part, (hipStream_t)stream);
 }
 
 // pdgn_gemm_nt / pdgn_gemm_nn (transposed_w != 0) with the extended epilogue:  C = act(A W^T + bias + addend +
@@ -663,15 +589,12 @@ int fp32_gemm_nt_ex(long long m, int n, int k, const float *A, int lda, const fl
                                const float *addend, int ldadd, float *C, int ldc, float *stat_part, const float *row_bias,
                                int ld_rb, int rows_per_group, int act, const float *gate, int ldgate, int transposed_w,
                                pdgn_stream_t stream) {
-    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, transposed_w != 0)) return PDGN_ERR_INVALID;
-    if ((act != 0 && act != 2) || (row_bias && (ld_rb < n || ld_rb % 4 || rows_per_group < 1)) ||
-        (gate && (ldgate < n || ldgate % 4)) || m >= (1LL << 31) || (row_bias && m * rows_per_group >= (1LL << 32)) ||
-        (row_bias && rows_per_group >= 1 && ((m + rows_per_group - 1) / rows_per_group) * (long long)ld_rb * 4 >= (long long)NT_OOB))
-        return PDGN_ERR_INVALID;
     NtEpi e;
-    e.row_bias = row_bias; e.ld_rb = ld_rb; e.rows_per_group = rows_per_group; e.act = act; e.gate = gate; e.ldgate = ldgate;
-    return transposed_w ? nt_dispatch<true>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e)
-                        : nt_dispatch<false>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e);
+    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, transposed_w != 0) ||
+        !nt_epi_ok(m, n, row_bias, ld_rb, rows_per_group, act, gate, ldgate, e))
+        return PDGN_ERR_INVALID;
+    return nt_launch(nt_pick(true, m, n, k, stat_part != nullptr || e.any()), transposed_w != 0, false, m, n, k, A, lda, W, ldw, bias,
+                     addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e);
 }
 
 // Weight gradient of a point-major dense layer, dW (n x k) = dY (m x n)^T X (m x k): the same kernel with BOTH operands
@@ -680,47 +603,9 @@ int fp32_gemm_nt_ex(long long m, int n, int k, const float *A, int lda, const fl
 // small ones.
 int fp32_gemm_tn_big(long long m, int n, int k, const float *dY, int ldy, const float *X, int ldx, float *dW,
                                 pdgn_stream_t stream) {
-    if (m < 1 || n < 4 || k < 4 || n % 4 || k % 4 || ldy % 4 || ldx % 4 || ldy < n || ldx < k || ldy >= (1 << 19) ||
-        ldx >= (1 << 19) || m > 0x7fffffffLL * 16)
-        return PDGN_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
+    if (!nt_tn_big_args_ok(m, n, k, ldy, ldx)) return PDGN_ERR_INVALID;
     // kernel roles: output rows = n (columns of dY), output columns = k (columns of X), reduction = m
-    switch (nt_pick(n, k, (int)(m > 0x7fffffff ? 0x7fffffff : m), false, true)) {
-        case 0: return NtBig::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s);
-        case 3: return NtNarrow::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s);
-        default: return NtSquare::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s);
-    }
-}
-
-// Number of [3n] partial-statistics rows pdgn_gemm_nt writes for this problem (tile rows x waves along m).
-long long fp32_gemm_nt_stat_rows(long long m, int n, int k) {
-    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    switch (nt_pick(m, n, k, true)) {
-        case 0: return (long long)cdiv(m, NtBig::BM) * 4;
-        case 2: return (long long)cdiv(m, NtTall::BM) * 2;
-        case 3: return (long long)cdiv(m, NtNarrow::BM) * 2;
-        default: return (long long)cdiv(m, NtSquare::BM) * 2;
-    }
-}
-
-// Rows of C each of those partial rows covers (partial p: rows p * block .. ; the blocks past m are empty).
-int fp32_gemm_nt_stat_block_rows(long long m, int n, int k) {
-    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    switch (nt_pick(m, n, k, true)) {
-        case 0: return NtBig::BM / 4;
-        case 2: return NtTall::BM / 2;
-        case 3: return NtNarrow::BM / 2;
-        default: return NtSquare::BM / 2;
-    }
-}
-
-// Tile configuration pdgn_gemm_nt picks for a problem (0: 256x128, 1: 128x128, 2: 160x64, 3: 128x64), + 16 when a
-// stream-K launch follows the data-parallel one; host-side only.
-int fp32_gemm_nt_config(long long m, int n, int k, int with_stats) {
-    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    const int c = nt_pick(m, n, k, with_stats != 0);
-    const bool sk = !with_stats;
-    const int g = c == 0 ? NtBig::plan(m, n, k, sk).grid_sk : c == 1 ? NtSquare::plan(m, n, k, sk).grid_sk
-                : c == 2 ? NtTall::plan(m, n, k, sk).grid_sk : NtNarrow::plan(m, n, k, sk).grid_sk;
-    return c + (g ? 16 : 0);
+    const int red = nt_tn_big_reduction(m);
+    return nt_launch(nt_pick(true, n, k, red, false, true), true, true, n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr,
+                     (hipStream_t)stream);
 }

@@ -1,16 +1,19 @@
 // gemm_shared.h -- what the two dense-contraction kernels (gemm_nt.hip: fp32 matrix instructions; gemm_x3.hip: fp32 operands
-// split into three bf16 parts) have in common: operand descriptors, the LDS-DMA instruction, the argument block.
+// split into three bf16 parts) have in common.  Device side: operand descriptors, the LDS-DMA instruction, the argument block, the
+// two-part scales.  Host side: the process-wide switches, the ARGUMENT FRONT of the public entry points (one check of the common
+// arguments, one of the extended epilogue -- which builds the NtEpi --, one of the weight gradient's), the one fill of the
+// argument block's common part, the launch of a kernel instance, and the prototypes of what one contraction file calls in another.
+// The launch model (tile tables, plan, pick rules) is gemm_plan.h, which has no HIP in it.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-#define NT_BK 32
-#define NT_GROUP_M 8
 #define NT_OOB 0x40000000u            // a byte offset past every tile descriptor (num_records < 2^30)
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -83,9 +86,6 @@ __device__ __forceinline__ float x2_scale(unsigned maxbits) { return __int_as_fl
 __device__ __forceinline__ float x2_unscale(unsigned maxbits) { return __int_as_float((254 - x2_scale_field(maxbits)) << 23); }  // 2^-e
 
 // ------------------------------------------------------------------ host side
-struct NtDev {
-    int cus;
-};
 static inline int nt_cus() {
     static int cached = 0;
     if (!cached) {
@@ -110,6 +110,27 @@ struct NtSwitches {
 };
 NtSwitches &nt_switches();
 
+// The tile configuration of a problem under the switches in force (gemm_plan.h: forced, or the launch model's pick on this device)
+// and its record.  fp32: the fp32 kernel's family (mode 0, and every call gemm_nt.hip takes).
+static inline int nt_pick(bool fp32, long long m, int n, int k, bool stats, bool no_tall = false) {
+    return fp32 ? gemm_pick_fp32(nt_switches().cfg, m, n, k, stats, no_tall, nt_cus()) : gemm_pick_x3(nt_switches().cfg, m, n, k, stats, nt_cus());
+}
+static inline const GemmTile &nt_tile(bool fp32, int cfg) { return fp32 ? FP32_TILES[cfg] : X3_TILES[cfg]; }
+
+// ---- the argument front
+static inline bool nt_args_ok(long long m, int n, int k, int lda, int ldw, int ldadd, int ldc, const float *addend, bool wt) {
+    return m >= 1 && n >= 4 && k >= 4 && n % 4 == 0 && k % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && ldc % 4 == 0 &&
+           lda >= k && ldw >= (wt ? n : k) && ldc >= n && (!addend || (ldadd % 4 == 0 && ldadd >= n)) && lda < (1 << 19) &&
+           ldw < (1 << 19) && ldc < (1 << 19) && (long long)cdiv(m, 128) * cdiv(n, 64) < 0x7fffffffLL &&
+           (!wt || (long long)k * ldw < (1LL << 27));
+}
+// weight gradient dW (n x k) = dY (m x n)^T X (m x k)
+static inline bool nt_tn_big_args_ok(long long m, int n, int k, int ldy, int ldx) {
+    return !(m < 1 || n < 4 || k < 4 || n % 4 || k % 4 || ldy % 4 || ldx % 4 || ldy < n || ldx < k || ldy >= (1 << 19) ||
+             ldx >= (1 << 19) || m > 0x7fffffffLL * 16);
+}
+static inline int nt_tn_big_reduction(long long m) { return (int)(m > 0x7fffffff ? 0x7fffffff : m); }
+
 struct NtEpi {                        // extended epilogue of pdgn_gemm_nt_ex (all optional)
     const float *row_bias = nullptr;
     int ld_rb = 0, rows_per_group = 1, act = 0;
@@ -117,9 +138,51 @@ struct NtEpi {                        // extended epilogue of pdgn_gemm_nt_ex (a
     int ldgate = 0;
     bool any() const { return row_bias || act || gate; }
 };
+// the extended epilogue's arguments checked and, when they are in range, taken into e (rows_per_group at least 1)
+static inline bool nt_epi_ok(long long m, int n, const float *row_bias, int ld_rb, int rows_per_group, int act, const float *gate,
+                             int ldgate, NtEpi &e) {
+    if ((act != 0 && act != 2) || (row_bias && (ld_rb < n || ld_rb % 4 || rows_per_group < 1)) ||
+        (gate && (ldgate < n || ldgate % 4)) || m >= (1LL << 31) || (row_bias && m * rows_per_group >= (1LL << 32)) ||
+        (row_bias && rows_per_group >= 1 && ((m + rows_per_group - 1) / rows_per_group) * (long long)ld_rb * 4 >= (long long)NT_OOB))
+        return false;
+    e.row_bias = row_bias; e.ld_rb = ld_rb; e.rows_per_group = rows_per_group > 0 ? rows_per_group : 1; e.act = act; e.gate = gate;
+    e.ldgate = ldgate;
+    return true;
+}
 
+// The part of the argument block that both families fill alike: the problem, the epilogue, the plan's tiling; what only gemm_x3
+// uses (stream-K workspace, split-K, pre-split planes, maxima) at "none".  The tile range and sk_per_wg are the launch's.
+static inline void nt_fill_args(NtArgs &a, const GemmPlan &pl, long long m, int n, int k, const float *A, int lda, const float *W, int ldw,
+                                const float *bias, const float *addend, int ldadd, float *C, int ldc, float *stat_part, const NtEpi &epi) {
+    a.M = m; a.N = n; a.K = k; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldadd = ldadd;
+    a.A = A; a.W = W; a.bias = bias; a.addend = addend; a.C = C; a.stat_part = stat_part;
+    a.row_bias = epi.row_bias; a.ld_rb = epi.ld_rb; a.rows_per_group = epi.rows_per_group;
+    a.rpg_magic = a.rows_per_group > 1 ? (unsigned)(0x100000000ULL / (unsigned)a.rows_per_group) + 1u : 0u;
+    a.rb_bytes = epi.row_bias ? (int)((((m + a.rows_per_group - 1) / a.rows_per_group - 1) * (long long)epi.ld_rb + n) * 4) : 0;
+    a.act = epi.act; a.gate = epi.gate; a.ldgate = epi.ldgate;
+    a.sk_split = 0; a.sk_ws = nullptr; a.sk_seg = 0; a.Wp = nullptr; a.wplane = 0; a.max_a = a.max_w = nullptr;
+    a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n; a.kchunks = pl.kchunks;
+    a.dbg = 0;
+#ifdef PDGN_NT_DEBUG
+    { const char *e = getenv("PDGN_NT_DBG"); a.dbg = e ? atoi(e) : 0; }
+#endif
+}
 
-// The fp32-matrix-instruction forms of the public entry points (gemm_nt.hip); gemm_x3.hip dispatches between the two.
+// A kernel instance as the launchers hand it around: its host symbol and workgroup size.  An instance that does not exist (NULL)
+// is a build error, not a run-time condition: launching it aborts.
+struct NtInstance {
+    const void *sym;
+    int threads;
+};
+static inline void nt_go(NtInstance f, int grid, hipStream_t s, const NtArgs &a) {
+    if (!f.sym) abort();
+    NtArgs args = a;
+    void *params[] = {&args};
+    (void)hipLaunchKernel(f.sym, dim3(grid), dim3(f.threads), params, 0, s);
+}
+
+// ---- what one contraction file calls in another
+// gemm_nt.hip: the fp32-matrix-instruction forms of the public entry points; gemm_x3.hip dispatches between the two
 int fp32_gemm_nt(long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
                  const float *addend, int ldadd, float *C, int ldc, float *stat_part, pdgn_stream_t stream);
 int fp32_gemm_nn(long long m, int n, int k, const float *A, int lda, const float *Wt, int ldw, const float *bias,
@@ -129,6 +192,11 @@ int fp32_gemm_nt_ex(long long m, int n, int k, const float *A, int lda, const fl
                     int rows_per_group, int act, const float *gate, int ldgate, int transposed_w, pdgn_stream_t stream);
 int fp32_gemm_tn_big(long long m, int n, int k, const float *dY, int ldy, const float *X, int ldx, float *dW,
                      pdgn_stream_t stream);
-long long fp32_gemm_nt_stat_rows(long long m, int n, int k);
-int fp32_gemm_nt_stat_block_rows(long long m, int n, int k);
-int fp32_gemm_nt_config(long long m, int n, int k, int with_stats);
+// gemm_rp.hip: the row-panel kernel of the short-reduction, wide-result products on two-part planes
+bool rp_takes(long long m, int n, int k);
+int rp_launch(long long m, int n, int k, const float *A, int lda, const unsigned short *Wp, int ldw, long long wplane, float *C, int ldc,
+              float *stat_part, hipStream_t s);
+// gemm_x3_16.hip / gemm_x3_h2.hip: instance (tile, flags: x3_flags) of gemm_x3_kernel<..., 16> / of gemm_x3_kernel<..., 32, 2> (two fp16
+// parts; the 256 x 128 tile as eight waves or four)
+NtInstance x3_instance16(int cfg, int flags);
+NtInstance x3_instance_h2(int flags, bool eight_waves);

@@ -41,6 +41,14 @@
 // Measured (MI355X, tools/x3_check.py, tools/x3_pmc.sh): 190-200 TFLOP/s on 35840 x 512 x 5120 (gemm_nt.hip: 135) with the
 // matrix pipe busy 68 % of the cycles at the 1.77 GHz the chip holds under this load (2.4 GHz nominal: the bf16 peak at
 // that clock is 1.84 PFLOP/s = 307 TFLOP/s of fp32 products).
+//
+// Where things live.  This file: the kernel; the tiles' template parameters and the list of instances (X3Cfg, X3_INSTANCES; the part
+// gemm_x3_16.hip and gemm_x3_h2.hip include under X3_KERNEL_ONLY for their arms); on the host side the hand-overs (tail workspace,
+// operand maxima), the tail's reduce and the maxima scan, the launcher (x3_launch: ordinary code over a tile index) and every public
+// entry point and query of the dense contractions, both families.  gemm_plan.h: the launch model -- tile tables, plan, tail and
+// split-K layouts, pick rules, x2_pays -- with no HIP in it.  gemm_shared.h: the argument block and its one fill, the argument checks,
+// the switches, the launch of an instance, and the prototypes between the contraction files.  gemm_nt.hip: the fp32 kernel and
+// the fp32 forms of the four launching entry points.
 #include <atomic>
 #include <type_traits>
 
@@ -1093,9 +1101,54 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void gemm_x3_kernel(const NtArgs
     }
 }
 
+// ------------------------------------------------------------------ the kernel's instances
+// What is compile-time about a tile: the kernel's template parameters and its instances.  The rest -- sizes, workgroups per CU, the
+// launch model -- is the tile's record in gemm_plan.h (X3_TILES, in the order Big, Square, Narrow).  This part is visible under
+// X3_KERNEL_ONLY: the three arms -- MS = 32 here, MS = 16 in gemm_x3_16.hip, two fp16 parts in gemm_x3_h2.hip -- map (tile, flags)
+// to their instances with the ONE list below; the launcher (x3_instance, host side) picks the arm.
+constexpr int x3_flags(bool atomic, bool wt, bool at, bool epi, bool pw) {
+    return (atomic ? 1 : 0) | (wt ? 2 : 0) | (at ? 4 : 0) | (epi ? 8 : 0) | (pw ? 16 : 0);
+}
+// exactly the (ATOMIC, WT, AT, EPI, PW) combinations x3_launch can ask for
+#define X3_INSTANCES(X)                                                                                                          \
+    X(true, false, false, false, false) X(false, false, false, true, true) X(false, false, false, false, true)                    \
+    X(true, false, false, false, true) X(false, false, false, true, false) X(false, false, false, false, false)                   \
+    X(true, true, false, false, false) X(false, true, false, true, false) X(false, true, false, false, false)                     \
+    X(true, true, true, false, false) X(false, true, true, false, false)
+
+template <int TM, int TN, int WM, int WN, int OCC>
+struct X3Cfg {
+    static constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;      // (LDS: two stages of three bf16 parts of [rows][32 k], 384 (BM + BN) bytes)
+    static constexpr bool matches(const GemmTile &t) { return BM == t.bm && BN == t.bn && OCC == t.wg_per_cu && WM == t.stat_div; }
+    template <int MS, int NP>
+    static NtInstance instance(int flags) {
+#define X3_CASE(A_, WT_, AT_, EPI_, PW_)                                                                                          \
+    if (flags == x3_flags(A_, WT_, AT_, EPI_, PW_))                                                                               \
+        return {(const void *)gemm_x3_kernel<TM, TN, WM, WN, OCC, A_, WT_, AT_, EPI_, PW_, MS, NP>, 64 * WM * WN};
+        X3_INSTANCES(X3_CASE)
+#undef X3_CASE
+        return {nullptr, 0};
+    }
+};
+typedef X3Cfg<4, 2, 2, 2, 1> X3Big;      // 256 x 128, 4 waves of 128 x 64 (144 KB of LDS): one per CU, one wave per SIMD
+// (the bf16 form as eight waves of 64 x 64 -- what the two-part form runs on, gemm_x3_h2.hip -- has no room for the result staging
+// (147 + 32 KB of LDS) and measured 1055 -> 1027 us on conv2's dense half, 860 -> 905 on the per-point product: not built)
+typedef X3Cfg<2, 2, 2, 2, 1> X3Square;   // 128 x 128, 4 waves of 64 x 64 (96 KB of LDS): one per CU
+typedef X3Cfg<2, 1, 2, 2, 2> X3Narrow;   // 128 x 64, 4 waves of 64 x 32 (72 KB of LDS): two per CU
+static_assert(X3Big::matches(X3_TILES[0]) && X3Square::matches(X3_TILES[1]) && X3Narrow::matches(X3_TILES[2]),
+              "gemm_plan.h's x3 tile table and the kernel's template parameters disagree");
+
+template <int MS>
+static NtInstance x3_tile_instance(int cfg, int flags) {
+    switch (cfg) {
+        case 0: return X3Big::instance<MS, 3>(flags);
+        case 2: return X3Narrow::instance<MS, 3>(flags);
+        default: return X3Square::instance<MS, 3>(flags);
+    }
+}
+
 #ifndef X3_KERNEL_ONLY                // (tools/x3_inst.hip compiles single instances of the kernel for ISA inspection)
 // ------------------------------------------------------------------ host side
-static bool x3_shape16(int cfg_index, bool atomic, bool epi, bool pw);
 
 // ---- stream-K tails without atomics (round 5).  A launch whose tiles do not fill the last round of workgroups used to finish with
 // a second launch that split the leftover tiles' k range over all CUs and ADDED its partial tiles into C with fp32 atomics (after
@@ -1298,7 +1351,7 @@ static unsigned *x2_arena_take(long long entries) {
 }
 // the maxima of the kernel-side rows of an operand (rows x cols in memory, pitch ld) on stream s: of its rows, or -- bycol: the
 // operand is given transposed -- of its columns.  A device pointer valid for the launches that follow on s (NULL: no arena)
-const unsigned *x2_scan(const float *X, long long rows, int cols, int ld, bool bycol, hipStream_t s) {
+static const unsigned *x2_scan(const float *X, long long rows, int cols, int ld, bool bycol, hipStream_t s) {
     unsigned *out = x2_arena_take(bycol ? cols : rows);
     if (!out) return nullptr;
     if (x2_maxima_launch(X, rows, cols, ld, bycol ? nullptr : out, bycol ? out : nullptr, s) != 0) return nullptr;
@@ -1330,248 +1383,6 @@ static int x3_reduce_split(int tiles) {
     while (tiles * y < 512 && y < 64) y *= 2;
     return y;
 }
-
-// gemm_rp.hip: the row-panel kernel of the short-reduction, wide-result products on two-part planes
-bool rp_takes(long long m, int n, int k);
-int rp_launch(long long m, int n, int k, const float *A, int lda, const unsigned short *Wp, int ldw, long long wplane, float *C, int ldc,
-              float *stat_part, hipStream_t s);
-// gemm_x3_16.hip: instance (tile cfg, flags = ATOMIC | WT << 1 | AT << 2 | EPI << 3 | PW << 4) of gemm_x3_kernel<..., 16>
-void x3_launch16(int cfg, int flags, int grid, hipStream_t s, const NtArgs &a);
-// gemm_x3_h2.hip: the same of gemm_x3_kernel<..., 32, 2> (two fp16 parts), and an instance's host symbol
-void x3_launch_h2(int flags, int grid, hipStream_t s, const NtArgs &a, bool eight_waves);
-const void *x3_symbol_h2(int flags, bool eight_waves);
-// Where the two-part form pays (measured, tools/x2_shapes.py: every contraction of an iteration alone in both forms): it halves
-// the matrix-core work of a launch and needs the operands' maxima first -- a pass over every operand that does not bring them
-// along.  On the 256 x 128 tile, with a reduction of at least 128 and >= 20 GFLOP, the products are the larger part of the
-// launch (conv2's dense half 927 -> 782 us with both scans, its input gradient 952 -> 693, the per-point product 761 -> 610);
-// the smaller tiles' launches are bound by their operand path and only pay the scans (+5 .. 100 us each).  A launch that
-// would have to read more than 4.5 bytes per kflop for the maxima keeps three parts (the per-point product's input gradient:
-// 1.8 GB of dY for 118 GFLOP).
-static bool x2_pays(int cfg, long long m, int n, int k, long long scan_bytes) {
-    if (nt_switches().mode != 2 || cfg != 0 || k < 128 || m >= (1LL << 28)) return false;
-    const double flops = 2.0 * (double)m * n * k;
-    static const double min_flops = [] { const char *e = getenv("PDGN_X2_MIN_GFLOP"); return (e && *e) ? atof(e) * 1e9 : 2e10; }();   // (measurement)
-    return flops >= min_flops && (double)scan_bytes <= 4.5e-3 * flops;
-}
-
-template <int TM, int TN, int WM, int WN, int OCC, int RATE, int CFG>      // RATE: fp32-equivalent kflop / us a CU sustains on this tile's loop
-struct X3Cfg {
-    static constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    static constexpr int LDS = 2 * 3 * (BM + BN) * 64;              // two stages of three bf16 parts of [rows][32 k]
-    static constexpr int WG_PER_CU = OCC;
-
-    struct Plan {
-        int tiles_m, tiles_n, kchunks, grid_dp, dp_tiles, grid_sk;
-        long long sk_per_wg;
-        double cost;                                               // launch model, microseconds
-    };
-    // Launch model as in gemm_nt.hip, with this loop's measured rate (tools/x3_check.py on MI355X).
-    static int dp_grid(long long tiles, int slots, int kc) {
-        int tpw = (64 + kc - 1) / kc;
-        tpw = tpw < 1 ? 1 : (tpw > 8 ? 8 : tpw);
-        const long long g = (tiles + tpw - 1) / tpw;
-        const long long lo = tiles < slots ? tiles : slots;
-        return (int)(g < lo ? lo : g);
-    }
-    static double chunk_us(int w) { return 2.0 * BM * BN * NT_BK * w / (RATE * 1e3); }
-    static Plan plan(long long m, int n, int k, bool allow_sk) {
-        Plan pl;
-        pl.tiles_m = cdiv(m, BM);
-        pl.tiles_n = cdiv(n, BN);
-        pl.kchunks = cdiv(k, NT_BK);
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        const int cus = nt_cus(), slots = cus * WG_PER_CU, KC = pl.kchunks;
-        const long long rounds = T / slots, tail = T - rounds * slots;
-        const double ov = 2.0;
-        const double full = (double)rounds * (KC + ov) * chunk_us(WG_PER_CU);
-        pl.dp_tiles = (int)T;
-        pl.grid_dp = dp_grid(T, slots, KC);
-        pl.grid_sk = 0;
-        pl.sk_per_wg = 0;
-        pl.cost = full + (tail ? (KC + ov) * chunk_us((int)((tail + cus - 1) / cus)) : 0.0);
-        if (allow_sk && tail > 0) {
-            const long long iters = tail * KC;
-            const long long cand[3] = {(long long)slots, (long long)cus, iters / 16};
-            for (int ci = 0; ci < 3; ++ci) {
-                long long g = cand[ci] < 1 ? 1 : (cand[ci] > slots ? slots : cand[ci]);
-                g = g < iters ? g : iters;
-                const long long per = (iters + g - 1) / g;
-                if (per < 8 && g > 1) continue;                    // short ranges: the atomics cost more than they balance
-                g = (iters + per - 1) / per;
-                const double zero_rows = (double)(m - (long long)((rounds * slots) / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * BM);
-                const double c = full + (per + ov) * chunk_us((int)((g + cus - 1) / cus)) + (double)(g + tail) * BM * BN * 4 / 1.3e6 +
-                                 zero_rows * n * 4 / 3.0e6 + 4.0;
-                if (c < pl.cost) {
-                    pl.cost = c;
-                    pl.dp_tiles = (int)(rounds * slots);
-                    pl.grid_dp = rounds ? dp_grid(rounds * slots, slots, KC) : 0;
-                    pl.grid_sk = (int)g;
-                    pl.sk_per_wg = per;
-                }
-            }
-        }
-        return pl;
-    }
-
-    template <bool ATOMIC, bool WT, bool AT, bool EPI, bool PW = false>
-    static void go(int grid, hipStream_t s, const NtArgs &a, bool two_part = false) {
-        // the matrix instruction is chosen per instance class (tile, atomic / extended epilogue / pre-split operand): nt_switches().shape16
-        // (the 16x16x32 instances live in their own translation unit, gemm_x3_16.hip: the two compile side by side)
-        const int flags = (ATOMIC ? 1 : 0) | (WT ? 2 : 0) | (AT ? 4 : 0) | (EPI ? 8 : 0) | (PW ? 16 : 0);
-        if (two_part) x3_launch_h2(flags, grid, s, a, a.stat_part == nullptr);      // (256 x 128 tiles only: x2_pays; eight waves unless BatchNorm partials are emitted)
-        else if (x3_shape16(CFG, ATOMIC, EPI, PW)) x3_launch16(CFG, flags, grid, s, a);
-        else hipLaunchKernelGGL((gemm_x3_kernel<TM, TN, WM, WN, OCC, ATOMIC, WT, AT, EPI, PW, 32>), dim3(grid), dim3(64 * WM * WN), 0, s, a);
-    }
-
-    // How a stream-K tail (the leftover tiles' k ranges over all CUs) is laid out when its partial tiles go to a workspace.
-    // Aligned: every tile's chunks in s_tail equal slices, workgroup v = (slice, tile): the workgroups that run together read the
-    // same chunks of different tiles.  When the tiles do not divide the CUs well (140 leftover tiles on 256 CUs: one slice each
-    // = 55 % of the chip, the per-point product's input gradient) the FLATTENED order instead: iteration ranges of equal length,
-    // a workgroup's range may span seg tiles.
-    struct Tail {
-        int t_tail, s_tail, per_tail, grid, seg;
-        long long per_flat, floats;
-    };
-    static Tail tail_layout(const Plan &pl) {
-        Tail t = {0, 0, 0, 0, 0, 0, 0};
-        if (!pl.grid_sk) return t;
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        const int slots_ = nt_cus() * WG_PER_CU;
-        t.t_tail = (int)(T - pl.dp_tiles);
-        t.s_tail = slots_ / t.t_tail < 1 ? 1 : slots_ / t.t_tail;
-        t.s_tail = t.s_tail > pl.kchunks ? pl.kchunks : t.s_tail;
-        t.per_tail = (pl.kchunks + t.s_tail - 1) / t.s_tail;
-        t.s_tail = (pl.kchunks + t.per_tail - 1) / t.per_tail;
-        t.grid = t.s_tail * t.t_tail;
-        const long long iters = (long long)t.t_tail * pl.kchunks;
-        if (t.grid * 5 < slots_ * 4 && iters >= (long long)slots_ * 8) {     // under 80 % of the chip, and ranges of >= 8 chunks to hand out
-            t.per_flat = (iters + slots_ - 1) / slots_;
-            t.grid = (int)((iters + t.per_flat - 1) / t.per_flat);
-            t.seg = (int)((t.per_flat + pl.kchunks - 2) / pl.kchunks) + 1;
-            t.floats = (long long)t.grid * t.seg * BM * BN;
-        } else {
-            t.floats = (long long)t.grid * BM * BN;
-        }
-        return t;
-    }
-    // floats of workspace the stream-K tail of (m, n, k) wants (0: no tail)
-    static long long tail_floats(long long m, int n, int k, bool allow_sk) { return tail_layout(plan(m, n, k, allow_sk)).floats; }
-    // weight gradients (split-K over few output tiles): the number of NON-EMPTY k slices per tile, and the workspace their partial
-    // tiles want (0: the launch is not a split-K one)
-    static int at_slices(const Plan &pl) {
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        const int slots = nt_cus() * WG_PER_CU;
-        const int S = (int)(slots / T) < pl.kchunks ? (int)(slots / T) : pl.kchunks;
-        const int per = (pl.kchunks + S - 1) / S;
-        return (pl.kchunks + per - 1) / per;
-    }
-    static long long at_floats(long long m, int n, int k) {
-        const Plan pl = plan(m, n, k, true);
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        if (T > nt_cus() * WG_PER_CU || !nt_switches().splitk) return 0;
-        return (long long)at_slices(pl) * T * BM * BN;
-    }
-
-    template <bool WT, bool AT = false>
-    static int launch(long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
-                      const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
-                      const NtEpi &epi = NtEpi(), bool prezeroed = false, const unsigned short *Wp = nullptr, long long wplane = 0,
-                      int parts = 3) {
-        const bool allow_sk = stat_part == nullptr && ldc == n && !epi.any();
-        const Plan pl = plan(m, n, k, allow_sk);
-        NtArgs a;
-        a.M = m; a.N = n; a.K = k; a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldadd = ldadd;
-        a.A = A; a.W = W; a.bias = bias; a.addend = addend; a.C = C; a.stat_part = stat_part;
-        a.row_bias = epi.row_bias; a.ld_rb = epi.ld_rb; a.rows_per_group = epi.rows_per_group > 0 ? epi.rows_per_group : 1;
-        a.rpg_magic = a.rows_per_group > 1 ? (unsigned)(0x100000000ULL / (unsigned)a.rows_per_group) + 1u : 0u;
-        a.rb_bytes = epi.row_bias ? (int)((((m + a.rows_per_group - 1) / a.rows_per_group - 1) * (long long)epi.ld_rb + n) * 4) : 0;
-        a.act = epi.act; a.gate = epi.gate; a.ldgate = epi.ldgate; a.sk_split = 0;
-        a.Wp = Wp; a.wplane = wplane;
-        a.sk_ws = nullptr;
-        a.sk_seg = 0;
-        a.max_a = a.max_w = nullptr;
-        // two parts or three: pre-split planes say it themselves; otherwise where it pays (x2_pays: mode 2, this tile, enough
-        // matrix-core work per byte that still has to be scanned for its maximum)
-        const unsigned *hand_a = x2_cur_max_a, *hand_w = x2_cur_max_w;
-        x2_cur_max_a = x2_cur_max_w = nullptr;
-        const bool two = Wp ? parts == 2
-                            : x2_pays(CFG, m, n, k, (hand_a ? 0 : (long long)m * k * 4) + (hand_w ? 0 : (long long)n * k * 4));
-        if (two && CFG != 0) return PDGN_ERR_INVALID;              // (two-part planes for a problem the other tiles take: x2_pays said no)
-        if (two) {
-            // per-row maxima of each operand as the kernel sees it (a transposed operand: the columns of the matrix in memory)
-            a.max_a = hand_a ? hand_a : x2_scan(A, AT ? (long long)k : m, AT ? (int)m : k, lda, AT, s);
-            if (Wp) a.max_w = reinterpret_cast<const unsigned *>(Wp + 2 * wplane);      // (behind the two planes: pdgn_split_f16x2)
-            else a.max_w = hand_w ? hand_w : x2_scan(W, WT ? k : n, WT ? n : k, ldw, WT, s);
-            if (!a.max_a || !a.max_w) return PDGN_ERR_INVALID;     // (no arena: pdgn_gemm_set_scale_slots)
-        }
-        a.tiles_m = pl.tiles_m; a.tiles_n = pl.tiles_n; a.kchunks = pl.kchunks;
-        a.dbg = 0;
-#ifdef PDGN_NT_DEBUG
-        { const char *e = getenv("PDGN_NT_DBG"); a.dbg = e ? atoi(e) : 0; }
-#endif
-        const long long T = (long long)pl.tiles_m * pl.tiles_n;
-        if (AT && T <= nt_cus() * WG_PER_CU && nt_switches().splitk) {
-            // weight gradients: few output tiles, a reduction of 10^4 .. 10^5.5 rows.  Split-K: the workgroups that run at the same
-            // time work on the SAME row range of different tiles (tile = v % T), so the XCD's L2 serves the operand panels they
-            // share; the flattened stream-K order gives neighbouring workgroups neighbouring row ranges of one tile and every
-            // panel is fetched from HBM once per tile (conv2's dense half: 4.4 GB for 0.8 GB of operands).
-            const int slots = nt_cus() * WG_PER_CU;
-            const int S = (int)(slots / T) < pl.kchunks ? (int)(slots / T) : pl.kchunks;
-            a.tile_begin = 0; a.tile_end = (int)T; a.sk_split = (int)T; a.sk_per_wg = (pl.kchunks + S - 1) / S;
-            // with a workspace (pdgn_gemm_tn_big_workspace_floats): the slices' partial tiles go there and x3_sk_reduce_kernel sums
-            // them in slice order -- no atomics, no zero-fill, the same bits every run; without one: fp32 atomics into a zeroed dW
-            const int s_ws = at_slices(pl);
-            float *ws = x3_take_workspace((size_t)s_ws * T * BM * BN);
-            if (ws) {
-                a.sk_ws = ws;
-                go<false, WT, AT, false>((int)T * s_ws, s, a, two);
-                hipLaunchKernelGGL(x3_sk_reduce_kernel, dim3((int)T, x3_reduce_split((int)T)), dim3(256), 0, s, ws, s_ws, (int)T, BM, BN, 0, pl.tiles_m, pl.tiles_n, m, n,
-                                   C, ldc, nullptr, nullptr, 0, 0, 0LL, pl.kchunks);
-                return pdgn_launch_status();
-            }
-            if (!prezeroed && hipMemsetAsync(C, 0, (size_t)m * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
-            go<true, WT, AT, false>((int)T * S, s, a, two);
-            return pdgn_launch_status();
-        }
-        // stream-K tail: the leftover tiles' k range in S slices, partial tiles to the workspace + a reduce (no atomics); the atomic
-        // form (zero-fill + fp32 atomics into C) when there is no workspace
-        const Tail tl = tail_layout(pl);
-        float *ws = (tl.t_tail > 0 && !AT) ? x3_take_workspace((size_t)tl.floats) : nullptr;
-        if (pl.grid_sk && !ws) {
-            const long long r0 = (long long)(pl.dp_tiles / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * BM;
-            if (!prezeroed && hipMemsetAsync(C + r0 * ldc, 0, (size_t)(m - r0) * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
-        }
-        constexpr bool CAN_PW = !WT && !AT;
-        if (pl.grid_dp) {
-            a.tile_begin = 0; a.tile_end = pl.dp_tiles; a.sk_per_wg = 0;
-            if (CAN_PW && Wp) {
-                if (epi.any()) go<false, false, false, true, CAN_PW>(pl.grid_dp, s, a, two);
-                else go<false, false, false, false, CAN_PW>(pl.grid_dp, s, a, two);
-            } else if (!AT && epi.any()) go<false, WT, false, true>(pl.grid_dp, s, a, two);
-            else go<false, WT, AT, false>(pl.grid_dp, s, a, two);
-        }
-        if (pl.grid_sk && ws) {
-            a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_ws = ws;
-            a.sk_split = tl.seg ? 0 : tl.t_tail; a.sk_seg = tl.seg; a.sk_per_wg = tl.seg ? tl.per_flat : tl.per_tail;
-            a.bias = nullptr; a.addend = nullptr;                  // (the reduce adds them)
-            if (CAN_PW && Wp) go<false, false, false, false, CAN_PW>(tl.grid, s, a, two);
-            else go<false, WT, AT, false>(tl.grid, s, a, two);
-            hipLaunchKernelGGL(x3_sk_reduce_kernel, dim3(tl.t_tail, x3_reduce_split(tl.t_tail)), dim3(256), 0, s, ws, tl.s_tail, tl.t_tail, BM, BN, pl.dp_tiles, pl.tiles_m,
-                               pl.tiles_n, m, n, C, ldc, bias, addend, ldadd, tl.seg, tl.per_flat, pl.kchunks);
-        } else if (pl.grid_sk) {
-            a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_per_wg = pl.sk_per_wg;
-            if (CAN_PW && Wp) go<true, false, false, false, CAN_PW>(pl.grid_sk, s, a, two);
-            else go<true, WT, AT, false>(pl.grid_sk, s, a, two);
-        }
-        return pdgn_launch_status();
-    }
-};
-
-typedef X3Cfg<2, 2, 2, 2, 1, 660, 1> X3Square;   // 128 x 128, 4 waves of 64 x 64 (96 KB of LDS): one per CU
-typedef X3Cfg<4, 2, 2, 2, 1, 760, 0> X3Big;      // 256 x 128, 4 waves of 128 x 64 (144 KB of LDS): one per CU, one wave per SIMD
-// (the bf16 form as eight waves of 64 x 64 -- what the two-part form runs on, gemm_x3_h2.hip -- has no room for the result staging
-// (147 + 32 KB of LDS) and measured 1055 -> 1027 us on conv2's dense half, 860 -> 905 on the per-point product: not built)
-typedef X3Cfg<2, 1, 2, 2, 2, 540, 2> X3Narrow;   // 128 x 64, 4 waves of 64 x 32 (72 KB of LDS): two per CU
 
 NtSwitches &nt_switches() {
     static NtSwitches sw = [] {
@@ -1656,20 +1467,103 @@ extern "C" int pdgn_gemm_set_shape(int shape) {
 }
 
 static int x3_mode() { return nt_switches().mode; }
-static bool x3_shape16(int cfg_index, bool atomic, bool epi, bool pw) {
-    const int cls = epi ? 3 : atomic ? 2 : pw ? 1 : 0;
-    return (nt_switches().shape16 >> (4 * cfg_index + cls)) & 1;
+static int x3_pick(long long m, int n, int k, bool stats) { return nt_pick(false, m, n, k, stats); }
+// the matrix instruction is chosen per instance class (tile, atomic / extended epilogue / pre-split operand): nt_switches().shape16
+static bool x3_shape16(int cfg, int flags) {
+    const int cls = (flags & 8) ? 3 : (flags & 1) ? 2 : (flags & 16) ? 1 : 0;
+    return (nt_switches().shape16 >> (4 * cfg + cls)) & 1;
+}
+// Instance (tile cfg, flags) in the arm that runs it: two fp16 parts (gemm_x3_h2.hip; the 256 x 128 tile only: x2_pays; eight waves
+// unless BatchNorm partials are emitted), else the bf16 form on the class's matrix instruction (16x16x32: gemm_x3_16.hip -- the two
+// compile side by side)
+static NtInstance x3_instance(int cfg, int flags, bool two_part, bool eight_waves) {
+    if (two_part) return x3_instance_h2(flags, eight_waves);
+    return x3_shape16(cfg, flags) ? x3_instance16(cfg, flags) : x3_tile_instance<32>(cfg, flags);
+}
+// short-reduction products on two-part planes with nothing added to them run on the row-panel kernel (gemm_rp.hip) in mode 2
+static bool x3_row_panel(long long m, int n, int k, int parts, bool plain) {
+    return x3_mode() == 2 && parts == 2 && plain && m >= 1 && rp_takes(m, n, k);
 }
 
-static int x3_pick(long long m, int n, int k, bool stats) {
-    const int forced = nt_switches().cfg;          // 0 .. 2 (3, the fp32 kernel's fourth, reads as 2)
-    if (forced >= 0) return forced > 2 ? 2 : forced;
-    const bool sk = !stats;
-    const double c[3] = {X3Big::plan(m, n, k, sk).cost, X3Square::plan(m, n, k, sk).cost, X3Narrow::plan(m, n, k, sk).cost};
-    int best = 0;
-    for (int i = 1; i < 3; ++i)
-        if (c[i] < c[best]) best = i;
-    return best;
+// One product on tile cfg.  wt / at: the second / the first operand is given transposed; Wp: the second operand pre-split into
+// `parts` planes (row-major only); prezeroed: C holds zeros already (weight gradients).
+static int x3_launch(int cfg, bool wt, bool at, long long m, int n, int k, const float *A, int lda, const float *W, int ldw,
+                     const float *bias, const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
+                     const NtEpi &epi = NtEpi(), bool prezeroed = false, const unsigned short *Wp = nullptr, long long wplane = 0,
+                     int parts = 3) {
+    const GemmTile &t = X3_TILES[cfg];
+    const int cus = nt_cus(), BM = t.bm, BN = t.bn;
+    const bool allow_sk = stat_part == nullptr && ldc == n && !epi.any();
+    const GemmPlan pl = gemm_plan(t, m, n, k, allow_sk, cus);
+    NtArgs a;
+    nt_fill_args(a, pl, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, epi);
+    a.Wp = Wp; a.wplane = wplane;
+    // two parts or three: pre-split planes say it themselves; otherwise where it pays (x2_pays: mode 2, this tile, enough
+    // matrix-core work per byte that still has to be scanned for its maximum)
+    const unsigned *hand_a = x2_cur_max_a, *hand_w = x2_cur_max_w;
+    x2_cur_max_a = x2_cur_max_w = nullptr;
+    const bool two = Wp ? parts == 2
+                        : x2_pays(x3_mode(), cfg, m, n, k, (hand_a ? 0 : (long long)m * k * 4) + (hand_w ? 0 : (long long)n * k * 4));
+    if (two && cfg != 0) return PDGN_ERR_INVALID;                  // (two-part planes for a problem the other tiles take: x2_pays said no)
+    if (two) {
+        // per-row maxima of each operand as the kernel sees it (a transposed operand: the columns of the matrix in memory)
+        a.max_a = hand_a ? hand_a : x2_scan(A, at ? (long long)k : m, at ? (int)m : k, lda, at, s);
+        if (Wp) a.max_w = reinterpret_cast<const unsigned *>(Wp + 2 * wplane);      // (behind the two planes: pdgn_split_f16x2)
+        else a.max_w = hand_w ? hand_w : x2_scan(W, wt ? k : n, wt ? n : k, ldw, wt, s);
+        if (!a.max_a || !a.max_w) return PDGN_ERR_INVALID;         // (no arena: pdgn_gemm_set_scale_slots)
+    }
+    const auto go = [&](int flags, int grid) { nt_go(x3_instance(cfg, flags, two, stat_part == nullptr), grid, s, a); };
+    const bool pw = Wp && !wt && !at;
+    const auto plain = [&](bool atomic) { return pw ? x3_flags(atomic, false, false, false, true) : x3_flags(atomic, wt, at, false, false); };
+    const long long T = (long long)pl.tiles_m * pl.tiles_n;
+    if (at && gemm_at_splits(t, pl, cus) && nt_switches().splitk) {
+        // weight gradients: few output tiles, a reduction of 10^4 .. 10^5.5 rows.  Split-K: the workgroups that run at the same
+        // time work on the SAME row range of different tiles (tile = v % T), so the XCD's L2 serves the operand panels they
+        // share; the flattened stream-K order gives neighbouring workgroups neighbouring row ranges of one tile and every
+        // panel is fetched from HBM once per tile (conv2's dense half: 4.4 GB for 0.8 GB of operands).
+        const int S = gemm_at_split(t, pl, cus);
+        a.tile_begin = 0; a.tile_end = (int)T; a.sk_split = (int)T; a.sk_per_wg = (pl.kchunks + S - 1) / S;
+        // with a workspace (pdgn_gemm_tn_big_workspace_floats): the slices' partial tiles go there and x3_sk_reduce_kernel sums
+        // them in slice order -- no atomics, no zero-fill, the same bits every run; without one: fp32 atomics into a zeroed dW
+        const int s_ws = gemm_at_slices(t, pl, cus);
+        float *ws = x3_take_workspace((size_t)s_ws * T * BM * BN);
+        if (ws) {
+            a.sk_ws = ws;
+            go(x3_flags(false, wt, at, false, false), (int)T * s_ws);
+            hipLaunchKernelGGL(x3_sk_reduce_kernel, dim3((int)T, x3_reduce_split((int)T)), dim3(256), 0, s, ws, s_ws, (int)T, BM, BN, 0, pl.tiles_m, pl.tiles_n, m, n,
+                               C, ldc, nullptr, nullptr, 0, 0, 0LL, pl.kchunks);
+            return pdgn_launch_status();
+        }
+        if (!prezeroed && hipMemsetAsync(C, 0, (size_t)m * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
+        go(x3_flags(true, wt, at, false, false), (int)T * S);
+        return pdgn_launch_status();
+    }
+    // stream-K tail: the leftover tiles' k range in S slices, partial tiles to the workspace + a reduce (no atomics); the atomic
+    // form (zero-fill + fp32 atomics into C) when there is no workspace
+    const GemmTail tl = gemm_tail_layout(t, pl, cus);
+    float *ws = (tl.t_tail > 0 && !at) ? x3_take_workspace((size_t)tl.floats) : nullptr;
+    if (pl.grid_sk && !ws) {
+        const long long r0 = (long long)(pl.dp_tiles / (NT_GROUP_M * pl.tiles_n)) * NT_GROUP_M * BM;
+        if (!prezeroed && hipMemsetAsync(C + r0 * ldc, 0, (size_t)(m - r0) * ldc * sizeof(float), s) != hipSuccess) return pdgn_launch_status();
+    }
+    if (pl.grid_dp) {
+        a.tile_begin = 0; a.tile_end = pl.dp_tiles; a.sk_per_wg = 0;
+        if (pw) go(x3_flags(false, false, false, epi.any(), true), pl.grid_dp);
+        else if (!at && epi.any()) go(x3_flags(false, wt, false, true, false), pl.grid_dp);
+        else go(plain(false), pl.grid_dp);
+    }
+    if (pl.grid_sk && ws) {
+        a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_ws = ws;
+        a.sk_split = tl.seg ? 0 : tl.t_tail; a.sk_seg = tl.seg; a.sk_per_wg = tl.seg ? tl.per_flat : tl.per_tail;
+        a.bias = nullptr; a.addend = nullptr;                      // (the reduce adds them)
+        go(plain(false), tl.grid);
+        hipLaunchKernelGGL(x3_sk_reduce_kernel, dim3(tl.t_tail, x3_reduce_split(tl.t_tail)), dim3(256), 0, s, ws, tl.s_tail, tl.t_tail, BM, BN, pl.dp_tiles, pl.tiles_m,
+                           pl.tiles_n, m, n, C, ldc, bias, addend, ldadd, tl.seg, tl.per_flat, pl.kchunks);
+    } else if (pl.grid_sk) {
+        a.tile_begin = pl.dp_tiles; a.tile_end = (int)T; a.sk_per_wg = pl.sk_per_wg;
+        go(plain(true), pl.grid_sk);
+    }
+    return pdgn_launch_status();
 }
 
 // Whether a product against PRE-SPLIT planes should use two-part ones (pdgn_split_f16x2) when scan_bytes of the activations would
@@ -1681,24 +1575,14 @@ extern "C" int pdgn_gemm_two_part_planes(long long m, int n, int k, long long sc
     const double flops = 2.0 * (double)m * n * k;
     return (flops >= 2e9 && (double)scan_bytes <= 4.5e-3 * flops) ? 1 : 0;
 }
-// The tail workspace of pdgn_gemm_nt_ps(m, n, k) for planes of `parts` parts (two-part planes always run on the 256 x 128 tile).
-extern "C" long long pdgn_gemm_nt_ps_workspace_floats(long long m, int n, int k, int parts, int with_stats);
-
 // Whether the contraction (m, n, k) runs on two parts under the switches in force when scan_bytes of its operands still have to be
 // scanned for their maxima (x2_pays): what a caller that pre-splits a weight (pdgn_split_f16x2 or _bf16x3) or hands maxima over asks first.
 extern "C" int pdgn_gemm_two_part(long long m, int n, int k, long long scan_bytes) {
     if (!x3_mode() || m < 1 || n < 4 || k < 4) return 0;
-    return x2_pays(x3_pick(m, n, k, false), m, n, k, scan_bytes) ? 1 : 0;
-}
-static bool x3_args_ok(long long m, int n, int k, int lda, int ldw, int ldadd, int ldc, const float *addend, bool wt) {
-    return m >= 1 && n >= 4 && k >= 4 && n % 4 == 0 && k % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && ldc % 4 == 0 &&
-           lda >= k && ldw >= (wt ? n : k) && ldc >= n && (!addend || (ldadd % 4 == 0 && ldadd >= n)) && lda < (1 << 19) &&
-           ldw < (1 << 19) && ldc < (1 << 19) && (long long)cdiv(m, 128) * cdiv(n, 64) < 0x7fffffffLL &&
-           (!wt || (long long)k * ldw < (1LL << 27));
+    return x2_pays(x3_mode(), x3_pick(m, n, k, false), m, n, k, scan_bytes) ? 1 : 0;
 }
 
-template <bool WT>
-static int x3_dispatch(long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
+static int x3_dispatch(bool wt, long long m, int n, int k, const float *A, int lda, const float *W, int ldw, const float *bias,
                        const float *addend, int ldadd, float *C, int ldc, float *stat_part, hipStream_t s,
                        const NtEpi &epi = NtEpi(), const unsigned short *Wp = nullptr, long long wplane = 0, int parts = 3) {
     // two-part planes run on the 256 x 128 tile whatever the launch model would pick for three parts (with the maxima handed in
@@ -1709,11 +1593,7 @@ static int x3_dispatch(long long m, int n, int k, const float *A, int lda, const
         if (stat_part && cfg != 0) return PDGN_ERR_INVALID;
         cfg = 0;
     }
-    switch (cfg) {
-        case 0: return X3Big::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi, false, Wp, wplane, parts);
-        case 2: return X3Narrow::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi, false, Wp, wplane, parts);
-        default: return X3Square::launch<WT>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi, false, Wp, wplane, parts);
-    }
+    return x3_launch(cfg, wt, false, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, s, epi, false, Wp, wplane, parts);
 }
 
 // C (m x n, row pitch ldc) = A (m x k, pitch lda) W (n x k, pitch ldw)^T (+ bias[n]) (+ addend (m x n, pitch ldadd)).
@@ -1725,8 +1605,8 @@ extern "C" int pdgn_gemm_nt(long long m, int n, int k, const float *A, int lda, 
                             pdgn_stream_t stream) {
     const X3Handover handover;                                 // (pending workspace / maxima belong to this call, even if it is refused)
     if (!x3_mode()) return fp32_gemm_nt(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, stream);
-    if (!x3_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, false)) return PDGN_ERR_INVALID;
-    return x3_dispatch<false>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
+    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, false)) return PDGN_ERR_INVALID;
+    return x3_dispatch(false, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
 }
 
 // The same product with the second operand given transposed: C (m x n) = A (m x k) Wt (k x n, row pitch ldw) -- the
@@ -1736,8 +1616,8 @@ extern "C" int pdgn_gemm_nn(long long m, int n, int k, const float *A, int lda, 
                             pdgn_stream_t stream) {
     const X3Handover handover;                                 // (pending workspace / maxima belong to this call, even if it is refused)
     if (!x3_mode()) return fp32_gemm_nn(m, n, k, A, lda, Wt, ldw, bias, addend, ldadd, C, ldc, stat_part, stream);
-    if (!x3_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, true)) return PDGN_ERR_INVALID;
-    return x3_dispatch<true>(m, n, k, A, lda, Wt, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
+    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, true)) return PDGN_ERR_INVALID;
+    return x3_dispatch(true, m, n, k, A, lda, Wt, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream);
 }
 
 // pdgn_gemm_nt / pdgn_gemm_nn (transposed_w != 0) with the extended epilogue:  C = act(A W^T + bias + addend +
@@ -1753,15 +1633,11 @@ extern "C" int pdgn_gemm_nt_ex(long long m, int n, int k, const float *A, int ld
     if (!x3_mode())
         return fp32_gemm_nt_ex(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, row_bias, ld_rb, rows_per_group,
                                act, gate, ldgate, transposed_w, stream);
-    if (!x3_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, transposed_w != 0)) return PDGN_ERR_INVALID;
-    if ((act != 0 && act != 2) || (row_bias && (ld_rb < n || ld_rb % 4 || rows_per_group < 1)) ||
-        (gate && (ldgate < n || ldgate % 4)) || m >= (1LL << 31) || (row_bias && m * rows_per_group >= (1LL << 32)) ||
-        (row_bias && rows_per_group >= 1 && ((m + rows_per_group - 1) / rows_per_group) * (long long)ld_rb * 4 >= (long long)NT_OOB))
-        return PDGN_ERR_INVALID;
     NtEpi e;
-    e.row_bias = row_bias; e.ld_rb = ld_rb; e.rows_per_group = rows_per_group; e.act = act; e.gate = gate; e.ldgate = ldgate;
-    return transposed_w ? x3_dispatch<true>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e)
-                        : x3_dispatch<false>(m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e);
+    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, transposed_w != 0) ||
+        !nt_epi_ok(m, n, row_bias, ld_rb, rows_per_group, act, gate, ldgate, e))
+        return PDGN_ERR_INVALID;
+    return x3_dispatch(transposed_w != 0, m, n, k, A, lda, W, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e);
 }
 
 // pdgn_gemm_nt / pdgn_gemm_nt_ex with the second operand PRE-SPLIT by pdgn_split_bf16x3: Wplanes = three bf16 planes [n][ldw]
@@ -1774,41 +1650,32 @@ extern "C" int pdgn_gemm_nt_ps(long long m, int n, int k, const float *A, int ld
                                int ldgate, pdgn_stream_t stream) {
     const X3Handover handover;                                 // (pending workspace / maxima belong to this call, even if it is refused)
     if (!x3_mode() || !Wplanes || (parts != 3 && parts != 2)) return PDGN_ERR_INVALID;
-    if (!x3_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, false)) return PDGN_ERR_INVALID;
+    if (!nt_args_ok(m, n, k, lda, ldw, ldadd, ldc, addend, false)) return PDGN_ERR_INVALID;
     if (wplane < (long long)(n - 1) * ldw + k || wplane >= (1LL << 28) || ldw % 8 || wplane % 8 || ((uintptr_t)Wplanes & 15))
         return PDGN_ERR_INVALID;                                  // 16-B loads of 8 bf16: rows and planes start on 16-B boundaries
-    if ((act != 0 && act != 2) || (row_bias && (ld_rb < n || ld_rb % 4 || rows_per_group < 1)) ||
-        (gate && (ldgate < n || ldgate % 4)) || m >= (1LL << 31) || (row_bias && m * rows_per_group >= (1LL << 32)) ||
-        (row_bias && rows_per_group >= 1 && ((m + rows_per_group - 1) / rows_per_group) * (long long)ld_rb * 4 >= (long long)NT_OOB))
-        return PDGN_ERR_INVALID;
-    if (parts == 2 && x3_mode() == 2 && !bias && !addend && !row_bias && !act && !gate && rp_takes(m, n, k)) {
+    NtEpi e;
+    if (!nt_epi_ok(m, n, row_bias, ld_rb, rows_per_group, act, gate, ldgate, e)) return PDGN_ERR_INVALID;
+    if (x3_row_panel(m, n, k, parts, !bias && !addend && !e.any())) {
         // a short reduction and a wide result: the row-panel kernel (gemm_rp.hip: A resident in registers, the weight tiles streamed,
         // the same two-part arithmetic bit for bit)
         // (A's row maxima: taken inside the kernel -- handed-in ones are not needed and not read)
         return rp_launch(m, n, k, A, lda, Wplanes, ldw, wplane, C, ldc, stat_part, (hipStream_t)stream);      // (stat_part: one partial row per 256-row panel, pdgn_gemm_nt_ps_stat_rows)
     }
-    NtEpi e;
-    e.row_bias = row_bias; e.ld_rb = ld_rb; e.rows_per_group = rows_per_group > 0 ? rows_per_group : 1; e.act = act; e.gate = gate;
-    e.ldgate = ldgate;
-    return x3_dispatch<false>(m, n, k, A, lda, nullptr, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e, Wplanes,
-                              wplane, parts);
+    return x3_dispatch(false, m, n, k, A, lda, nullptr, ldw, bias, addend, ldadd, C, ldc, stat_part, (hipStream_t)stream, e, Wplanes,
+                       wplane, parts);
 }
 
 // Stream-K tails without atomics: floats of workspace the tail of pdgn_gemm_nt / _nn / _nt_ps (m, n, k) wants (0: that launch has no
 // tail, or runs on the fp32 instructions), and the hand-over of a buffer to the NEXT such call of the calling thread.
 extern "C" long long pdgn_gemm_tail_workspace_floats(long long m, int n, int k, int with_stats) {
     if (!x3_mode() || m < 1 || n < 4 || k < 4) return 0;
-    const bool sk = !with_stats;
-    switch (x3_pick(m, n, k, with_stats != 0)) {
-        case 0: return X3Big::tail_floats(m, n, k, sk);
-        case 2: return X3Narrow::tail_floats(m, n, k, sk);
-        default: return X3Square::tail_floats(m, n, k, sk);
-    }
+    return gemm_tail_floats(X3_TILES[x3_pick(m, n, k, with_stats != 0)], m, n, k, !with_stats, nt_cus());
 }
+// The same for pdgn_gemm_nt_ps with planes of `parts` parts (two-part planes always run on the 256 x 128 tile).
 extern "C" long long pdgn_gemm_nt_ps_workspace_floats(long long m, int n, int k, int parts, int with_stats) {
     if (!x3_mode() || m < 1 || n < 4 || k < 4) return 0;
     if (parts == 2 && rp_takes(m, n, k)) return 0;                        // (the row-panel kernel has no tail)
-    if (parts == 2) return with_stats ? 0 : X3Big::tail_floats(m, n, k, true);
+    if (parts == 2) return with_stats ? 0 : gemm_tail_floats(X3_TILES[0], m, n, k, true, nt_cus());
     return pdgn_gemm_tail_workspace_floats(m, n, k, with_stats);
 }
 extern "C" int pdgn_gemm_set_tail_workspace(float *ws, long long floats) {
@@ -1823,22 +1690,10 @@ extern "C" int pdgn_gemm_set_tail_workspace(float *ws, long long floats) {
 // 16x16x32 arm), *grid = its grid.  Lets a measurement find that launch inside a recorded iteration (pdgn_replay_kernel_nodes).
 extern "C" int pdgn_gemm_nt_ps_launch_info(long long m, int n, int k, int parts, const void **sym, int *grid) {
     if (!x3_mode() || m < 1 || n < 4 || k < 4 || !sym || !grid) return PDGN_ERR_INVALID;
-    const int cfg = x3_pick(m, n, k, false);
-    const bool s16 = x3_shape16(cfg, false, false, true);
-    *sym = nullptr;
-    if (parts == 2) {
-        *grid = X3Big::plan(m, n, k, true).grid_dp;
-        *sym = x3_symbol_h2(16, true);
-    } else if (cfg == 0) {
-        *grid = X3Big::plan(m, n, k, true).grid_dp;
-        if (!s16) *sym = (const void *)gemm_x3_kernel<4, 2, 2, 2, 1, false, false, false, false, true, 32>;
-    } else if (cfg == 2) {
-        *grid = X3Narrow::plan(m, n, k, true).grid_dp;
-        if (!s16) *sym = (const void *)gemm_x3_kernel<2, 1, 2, 2, 2, false, false, false, false, true, 32>;
-    } else {
-        *grid = X3Square::plan(m, n, k, true).grid_dp;
-        if (!s16) *sym = (const void *)gemm_x3_kernel<2, 2, 2, 2, 1, false, false, false, false, true, 32>;
-    }
+    const bool two = parts == 2;
+    const int cfg = two ? 0 : x3_pick(m, n, k, false), flags = x3_flags(false, false, false, false, true);
+    *grid = gemm_plan(X3_TILES[cfg], m, n, k, true, nt_cus()).grid_dp;
+    *sym = (two || !x3_shape16(cfg, flags)) ? x3_instance(cfg, flags, two, true).sym : nullptr;
     return 0;
 }
 
@@ -1858,76 +1713,46 @@ extern "C" int pdgn_gemm_tn_big(long long m, int n, int k, const float *dY, int 
                                 int dw_is_zero, pdgn_stream_t stream) {
     const X3Handover handover;                                 // (pending workspace / maxima belong to this call, even if it is refused)
     if (!x3_mode()) return fp32_gemm_tn_big(m, n, k, dY, ldy, X, ldx, dW, stream);       // (zero-fills dW itself in any case)
-    if (m < 1 || n < 4 || k < 4 || n % 4 || k % 4 || ldy % 4 || ldx % 4 || ldy < n || ldx < k || ldy >= (1 << 19) ||
-        ldx >= (1 << 19) || m > 0x7fffffffLL * 16)
-        return PDGN_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
+    if (!nt_tn_big_args_ok(m, n, k, ldy, ldx)) return PDGN_ERR_INVALID;
     // kernel roles: output rows = n (columns of dY), output columns = k (columns of X), reduction = m
-    const int cfg = x3_pick(n, k, (int)(m > 0x7fffffff ? 0x7fffffff : m), false);
-    switch (cfg) {
-        case 0: return X3Big::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s, NtEpi(), dw_is_zero != 0);
-        case 2: return X3Narrow::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s, NtEpi(), dw_is_zero != 0);
-        default: return X3Square::launch<true, true>(n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k, nullptr, s, NtEpi(), dw_is_zero != 0);
-    }
+    return x3_launch(x3_pick(n, k, nt_tn_big_reduction(m), false), true, true, n, k, (int)m, dY, ldy, X, ldx, nullptr, nullptr, 0, dW, k,
+                     nullptr, (hipStream_t)stream, NtEpi(), dw_is_zero != 0);
 }
 
 // Floats of workspace with which pdgn_gemm_tn_big(m, n, k) sums its k slices without atomics (pdgn_gemm_set_tail_workspace hands the
 // buffer to the next call, as for the stream-K tails); 0: that call does not split (or runs on the fp32 instructions).
 extern "C" long long pdgn_gemm_tn_big_workspace_floats(long long m, int n, int k) {
-    if (!x3_mode() || m < 1 || n < 4 || k < 4) return 0;
-    const int red = (int)(m > 0x7fffffff ? 0x7fffffff : m);
-    switch (x3_pick(n, k, red, false)) {
-        case 0: return X3Big::at_floats(n, k, red);
-        case 2: return X3Narrow::at_floats(n, k, red);
-        default: return X3Square::at_floats(n, k, red);
-    }
+    if (!x3_mode() || m < 1 || n < 4 || k < 4 || !nt_switches().splitk) return 0;
+    const int red = nt_tn_big_reduction(m);
+    return gemm_at_floats(X3_TILES[x3_pick(n, k, red, false)], n, k, red, nt_cus());
+}
+
+// The statistics geometry of a product, both families.  Number of [3n] partial-statistics rows pdgn_gemm_nt writes for this problem
+// (tile rows x waves along m) and the rows of C each of them covers (partial p: rows p * block .. ; the blocks past m are empty).
+extern "C" long long pdgn_gemm_nt_stat_rows(long long m, int n, int k) {
+    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
+    return gemm_stat_rows(nt_tile(!x3_mode(), nt_pick(!x3_mode(), m, n, k, true)), m);
+}
+extern "C" int pdgn_gemm_nt_stat_block_rows(long long m, int n, int k) {
+    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
+    return gemm_stat_block_rows(nt_tile(!x3_mode(), nt_pick(!x3_mode(), m, n, k, true)));
 }
 
 // The same two questions for pdgn_gemm_nt_ps with `parts`-part planes, bias / addend / epilogue extras absent (`plain` != 0): a
 // short-reduction product on two-part planes runs on the row-panel kernel (gemm_rp.hip), whose partial rows cover a 256-row panel each.
-extern "C" int pdgn_gemm_nt_ps_row_panel(long long m, int n, int k, int parts, int plain) {
-    return (x3_mode() == 2 && parts == 2 && plain && m >= 1 && rp_takes(m, n, k)) ? 1 : 0;
-}
+extern "C" int pdgn_gemm_nt_ps_row_panel(long long m, int n, int k, int parts, int plain) { return x3_row_panel(m, n, k, parts, plain != 0) ? 1 : 0; }
 extern "C" long long pdgn_gemm_nt_ps_stat_rows(long long m, int n, int k, int parts, int plain) {
-    if (x3_mode() == 2 && parts == 2 && plain && m >= 1 && rp_takes(m, n, k)) return (m + 255) / 256;
-    return pdgn_gemm_nt_stat_rows(m, n, k);
+    return x3_row_panel(m, n, k, parts, plain != 0) ? (m + 255) / 256 : pdgn_gemm_nt_stat_rows(m, n, k);
 }
 extern "C" int pdgn_gemm_nt_ps_stat_block_rows(long long m, int n, int k, int parts, int plain) {
-    if (x3_mode() == 2 && parts == 2 && plain && m >= 1 && rp_takes(m, n, k)) return 256;
-    return pdgn_gemm_nt_stat_block_rows(m, n, k);
-}
-
-// Number of [3n] partial-statistics rows pdgn_gemm_nt writes for this problem (tile rows x waves along m).
-extern "C" long long pdgn_gemm_nt_stat_rows(long long m, int n, int k) {
-    if (!x3_mode()) return fp32_gemm_nt_stat_rows(m, n, k);
-    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    switch (x3_pick(m, n, k, true)) {
-        case 0: return (long long)cdiv(m, X3Big::BM) * 2;
-        case 2: return (long long)cdiv(m, X3Narrow::BM) * 2;
-        default: return (long long)cdiv(m, X3Square::BM) * 2;
-    }
-}
-
-// Rows of C each of those partial rows covers (partial p: rows p * block .. ; the blocks past m are empty).
-extern "C" int pdgn_gemm_nt_stat_block_rows(long long m, int n, int k) {
-    if (!x3_mode()) return fp32_gemm_nt_stat_block_rows(m, n, k);
-    if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    switch (x3_pick(m, n, k, true)) {
-        case 0: return X3Big::BM / 2;
-        case 2: return X3Narrow::BM / 2;
-        default: return X3Square::BM / 2;
-    }
+    return x3_row_panel(m, n, k, parts, plain != 0) ? 256 : pdgn_gemm_nt_stat_block_rows(m, n, k);
 }
 
 // Tile configuration pdgn_gemm_nt picks for a problem, + 16 when a stream-K launch follows the data-parallel one; host-side
 // only.  x3: 0: 256x128, 1: 128x128, 2: 128x64;  fp32: 0: 256x128, 1: 128x128, 2: 160x64, 3: 128x64.
 extern "C" int pdgn_gemm_nt_config(long long m, int n, int k, int with_stats) {
-    if (!x3_mode()) return fp32_gemm_nt_config(m, n, k, with_stats);
     if (m < 1 || n < 1 || k < 1) return PDGN_ERR_INVALID;
-    const int c = x3_pick(m, n, k, with_stats != 0);
-    const bool sk = !with_stats;
-    const int g = c == 0 ? X3Big::plan(m, n, k, sk).grid_sk : c == 1 ? X3Square::plan(m, n, k, sk).grid_sk
-                                                                      : X3Narrow::plan(m, n, k, sk).grid_sk;
-    return c + (g ? 16 : 0);
+    const int c = nt_pick(!x3_mode(), m, n, k, with_stats != 0);
+    return c + (gemm_plan(nt_tile(!x3_mode(), c), m, n, k, !with_stats, nt_cus()).grid_sk ? 16 : 0);
 }
 #endif  // X3_KERNEL_ONLY

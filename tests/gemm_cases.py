@@ -1,11 +1,13 @@
 """The cases of tests/test_gpu_gemm_exact.py: the dense contraction kernels (csrc/gemm_x3.hip and its two other translation units,
 csrc/gemm_nt.hip, csrc/gemm_rp.hip, csrc/split.hip) in every tile and tail regime, with their operands and references.  Shared by
-the host test (tests/test_gemm_cases_host.py: guards, regime coverage and the split mirrors, no GPU) and the GPU module.
+the host test (tests/test_gemm_cases_host.py: guards, regime coverage, the library's queries and the split mirrors, no GPU) and the
+GPU module.
 
-The launch arithmetic of the three files is restated here with the CU count as a parameter (`plan`, `dp_grid`, `tail_layout`,
-`at_slices`, `pick`, `x2_pays`, `rp_takes`, the allow_sk rule): the cost formulas are IEEE double arithmetic, evaluated in the
-order the C++ evaluates them, so the picks reproduce exactly.  `describe` turns a case into what its call launches, `reached` into
-the regime tags it enters, and REQUIRED lists the tags that at least one case must carry.
+The launch arithmetic of csrc/gemm_plan.h (`gemm_plan`, `gemm_dp_grid`, `gemm_tail_layout`, `gemm_at_slices`, the two pick rules,
+`x2_pays`) and gemm_rp.hip's `rp_takes` and the launchers' allow_sk rule are restated here with the CU count as a parameter: the
+cost formulas are IEEE double arithmetic, evaluated in the order the C++ evaluates them, so the picks reproduce exactly.
+`describe` turns a case into what its call launches, `reached` into the regime tags it enters, REQUIRED lists the tags that at
+least one case must carry, and `check_launch_model_queries` compares the built library's queries with the restatement.
 
 Four kinds of data, each with a guard that the host test checks for every case that uses it:
   "int"          float32 integers with |v| <= 7, zeros included; row r of an operand (as the kernel sees it) is capped at
@@ -49,8 +51,8 @@ def cdiv(a, b):
 
 
 # ---------------------------------------------------------------------------- the launch arithmetic, restated
-# fam "x3": gemm_x3.hip's X3Cfg (cfg 0 X3Big, 1 X3Square, 2 X3Narrow); fam "fp32": gemm_nt.hip's NtCfg (0 NtBig, 1 NtSquare,
-# 2 NtTall, 3 NtNarrow).  WG: workgroups per CU; stat_div: a statistics block is BM / stat_div rows (one per wave row).
+# fam "x3": gemm_plan.h's X3_TILES (gemm_x3.hip's X3Big, X3Square, X3Narrow); fam "fp32": FP32_TILES (gemm_nt.hip's NtBig, NtSquare,
+# NtTall, NtNarrow).  WG: workgroups per CU; stat_div: a statistics block is BM / stat_div rows (one per wave row).
 Tile = collections.namedtuple("Tile", "fam cfg BM BN WG rate stat_div")
 X3_TILES = (Tile("x3", 0, 256, 128, 1, 760, 2), Tile("x3", 1, 128, 128, 1, 660, 2), Tile("x3", 2, 128, 64, 2, 540, 2))
 FP32_TILES = (Tile("fp32", 0, 256, 128, 1, 1.0, 4), Tile("fp32", 1, 128, 128, 2, 1.0, 2), Tile("fp32", 2, 160, 64, 2, 0.95, 2),
@@ -75,7 +77,7 @@ def dp_grid(tile, tiles, slots, kc):
 
 
 def plan(tile, m, n, k, allow_sk, cus):
-    """X3Cfg::plan / NtCfg::plan."""
+    """gemm_plan.h::gemm_plan."""
     tiles_m, tiles_n, kc = cdiv(m, tile.BM), cdiv(n, tile.BN), cdiv(k, NT_BK)
     T = tiles_m * tiles_n
     slots = cus * tile.WG
@@ -105,7 +107,7 @@ def plan(tile, m, n, k, allow_sk, cus):
 
 
 def tail_layout(tile, pl, cus):
-    """X3Cfg::tail_layout: how the stream-K tail of a plan is laid out when its partial tiles go to a workspace."""
+    """gemm_plan.h::gemm_tail_layout: how the stream-K tail of a plan is laid out when its partial tiles go to a workspace."""
     if not pl.grid_sk:
         return Tail(0, 0, 0, 0, 0, 0, 0)
     T, slots = pl.tiles_m * pl.tiles_n, cus * tile.WG
@@ -125,7 +127,7 @@ def tail_layout(tile, pl, cus):
 
 
 def at_slices(tile, pl, cus):
-    """X3Cfg::at_slices: non-empty k slices per tile of a split-K weight gradient."""
+    """gemm_plan.h::gemm_at_slices: non-empty k slices per tile of a split-K weight gradient."""
     T, slots = pl.tiles_m * pl.tiles_n, cus * tile.WG
     S = min(slots // T, pl.kchunks)
     per = cdiv(pl.kchunks, S)
@@ -133,7 +135,7 @@ def at_slices(tile, pl, cus):
 
 
 def pick(fam, m, n, k, stats, cus, forced=None, no_tall=False):
-    """x3_pick / nt_pick: the tile configuration, forced or the launch model's."""
+    """gemm_plan.h::gemm_pick_x3 / gemm_pick_fp32: the tile configuration, forced or the launch model's."""
     if fam == "x3":
         if forced is not None:
             return 2 if forced > 2 else forced
@@ -277,7 +279,7 @@ def describe(c, cus):
     if c.entry == "ps2" and c.mode == "x2" and plain and rp_takes(M, N, K):
         d.update(kernel="row_panel", fam="rp", tile=None, plan=None, allow_sk=False, two=True)
         return d
-    # (a weight gradient: x3_pick(n, k, m, false) / nt_pick(..., false, no_tall))
+    # (a weight gradient: the pick over (n, k, m), no statistics; fp32: no_tall)
     cfg = pick(fam, M, N, K, stats or has_epi(c), cus, c.cfg, no_tall=(c.entry == "tn_big"))
     d["picked"] = cfg
     if c.entry == "ps2":
@@ -307,6 +309,56 @@ def tail_ways(d):
     """How the GPU module runs a described case: a call that wants a workspace (a stream-K tail or a split-K weight gradient on the
     matrix cores) runs with it ("ws"), with one a float too small ("short": must fall back to the atomics) and with none."""
     return ("ws", "short", "none") if d["ws_floats"] else ("none",)
+
+
+def check_launch_model_queries(L, c, cus):
+    """pdgn_gemm_nt_config, the three workspace queries, the launch-info grid, the row-panel and two-part questions and the statistics
+    geometry of the library L (the ctypes handle, case c's switches in force) against this module's restatement at `cus` CUs -- the
+    device's count, or the 256 the library assumes where it finds no device.  Host-side queries only: nothing is launched."""
+    import ctypes
+    M, N, K = kernel_dims(c)
+    fam = "fp32" if c.mode == "fp32" else "x3"
+    for ws in (0, 1):
+        t = pick(fam, M, N, K, bool(ws), cus, c.cfg)
+        tile = TILES[fam][t]
+        pl = plan(tile, M, N, K, not ws, cus)
+        assert L.pdgn_gemm_nt_config(M, N, K, ws) == t + (16 if pl.grid_sk else 0), (ws, t, pl)
+        floats = 0 if fam == "fp32" else tail_layout(tile, pl, cus).floats
+        assert L.pdgn_gemm_tail_workspace_floats(M, N, K, ws) == floats, (ws, t, pl)
+        assert (floats > 0) == (fam == "x3" and pl.grid_sk > 0)
+        if fam == "x3":
+            assert L.pdgn_gemm_nt_ps_workspace_floats(M, N, K, 3, ws) == floats
+            # two-part planes run on the 256 x 128 tile: its tail's floats, none with statistics.  The library answers 0 outright for a
+            # shape the row-panel kernel can take, whatever the mode and the epilogue; that is no quirk to pin, because such a shape
+            # (k <= 128: at most 4 chunks) never plans a tail on this tile -- asserted here from the restated plan, not from the rule
+            big = X3_TILES[0]
+            two = 0 if ws else tail_layout(big, plan(big, M, N, K, True, cus), cus).floats
+            assert not (rp_takes(M, N, K) and two), "a row-panel shape that plans a tail: the library's shortcut would lose it"
+            assert L.pdgn_gemm_nt_ps_workspace_floats(M, N, K, 2, ws) == two, ws
+    ts = TILES[fam][pick(fam, M, N, K, True, cus, c.cfg)]
+    assert L.pdgn_gemm_nt_stat_rows(M, N, K) == cdiv(M, ts.BM) * ts.stat_div
+    assert L.pdgn_gemm_nt_stat_block_rows(M, N, K) == ts.BM // ts.stat_div      # BM / 4 on the big fp32 tile, BM / 2 elsewhere
+    if fam == "fp32":
+        assert L.pdgn_gemm_tn_big_workspace_floats(M, N, K) == 0 and L.pdgn_gemm_two_part(M, N, K, 0) == 0
+        return
+    for parts in (3, 2):
+        sym, grid = ctypes.c_void_p(), ctypes.c_int(-1)
+        assert L.pdgn_gemm_nt_ps_launch_info(M, N, K, parts, ctypes.byref(sym), ctypes.byref(grid)) == 0
+        tile = X3_TILES[0 if parts == 2 else pick("x3", M, N, K, False, cus, c.cfg)]
+        assert grid.value == plan(tile, M, N, K, True, cus).grid_dp, (parts, tile)
+        for plain in (0, 1):
+            takes = c.mode == "x2" and parts == 2 and plain == 1 and rp_takes(M, N, K)
+            assert L.pdgn_gemm_nt_ps_row_panel(M, N, K, parts, plain) == int(takes)
+            assert L.pdgn_gemm_nt_ps_stat_block_rows(M, N, K, parts, plain) == (256 if takes else ts.BM // ts.stat_div)
+            assert L.pdgn_gemm_nt_ps_stat_rows(M, N, K, parts, plain) == (cdiv(M, 256) if takes else cdiv(M, ts.BM) * ts.stat_div)
+    for scan in (0, (M * K + N * K) * 4):
+        assert L.pdgn_gemm_two_part(M, N, K, scan) == int(x2_pays(c.mode, pick("x3", M, N, K, False, cus, c.cfg), M, N, K, scan))
+    # the weight gradient of the same kernel-side problem: dW (M x N) over K rows
+    d = describe(c._replace(entry="tn_big", m=K, n=M, k=N, epi=(), pads=NOPAD), cus)
+    assert L.pdgn_gemm_tn_big_workspace_floats(K, M, N) == d["at_floats"], d
+    d = describe(c, cus)
+    if d["kernel"] == "tile" and c.entry != "tn_big":
+        assert d["ws_floats"] == (d["tail"].floats if d["plan"].grid_sk else 0)
 
 
 def reached(c, cus):

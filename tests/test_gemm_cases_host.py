@@ -1,5 +1,6 @@
 """tests/gemm_cases.py checked on the CPU: every case passes the guard of its kind of data, every required regime tag is carried by
-some case at 256 CUs, the shapes named in the module enter the regimes they were chosen for, and the numpy mirrors of the two splits
+some case at 256 CUs, the shapes named in the module enter the regimes they were chosen for, the library's launch-model queries
+(host code: csrc/gemm_plan.h) equal the module's restatement for every case, and the numpy mirrors of the two splits
 (csrc/split.hip, csrc/gemm_x3.hip's loaders) reassemble their inputs within the bounds the kernels' headers state."""
 import numpy as np
 import pytest
@@ -90,7 +91,7 @@ def test_the_named_shapes_enter_their_regimes_at_256_cus():
 
 def test_launch_arithmetic_restated():
     big, sq, nar = gc.X3_TILES
-    assert [160 * 1024 // (2 * (t.BM + t.BN) * 32 * 4) for t in gc.FP32_TILES] == [t.WG for t in gc.FP32_TILES] == [1, 2, 2, 3]      # NtCfg::WG_PER_CU
+    assert [160 * 1024 // (2 * (t.BM + t.BN) * 32 * 4) for t in gc.FP32_TILES] == [t.WG for t in gc.FP32_TILES] == [1, 2, 2, 3]      # gemm_nt.hip: NtCfg::WG_PER_CU
     assert gc.dp_grid(big, 258, 256, 1) == 256 and gc.dp_grid(big, 1000, 256, 1) == 256 and gc.dp_grid(big, 4096, 256, 1) == 512
     assert gc.dp_grid(gc.FP32_TILES[0], 4096, 256, 8) == 1024 and gc.dp_grid(big, 4096, 256, 8) == 512
     assert gc.chunk_us(big, 1) == 2.0 * 256 * 128 * 32 / 760e3
@@ -106,6 +107,29 @@ def test_launch_arithmetic_restated():
     assert gc.rp_takes(4099, 3908, 32) and not gc.rp_takes(4095, 4100, 128) and not gc.rp_takes(4099, 3900, 64) and not gc.rp_takes(4099, 4100, 256)
     # a forced configuration: the fp32 kernel's fourth reads as the narrow x3 tile; the tall fp32 tile is not a weight-gradient tile
     assert gc.pick("x3", 100, 8, 4, False, CUS, 3) == 2 and gc.pick("fp32", 100, 8, 4, False, CUS, 2, no_tall=True) == 1
+
+
+@pytest.mark.parametrize("case", ORDERED, ids=lambda c: c.name)
+def test_launch_model_queries_equal_the_restatement_on_the_host(case):
+    """The comparison of tests/test_gpu_gemm_exact.py's query test, the same assertions, wherever the library loads: the queries are host
+    code (csrc/gemm_plan.h), which without a device plans for 256 CUs.  No device pointer is passed and nothing is launched.  The
+    switches are process-wide and tests/conftest.py resets them after gpu-marked tests only: this test puts back what it found."""
+    import torch
+    from pdgn_amd import _lib
+    L = _lib.lib()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else CUS
+    found = (L.pdgn_gemm_set_mode(-1), L.pdgn_gemm_set_config(-2), L.pdgn_gemm_set_shape(-2))      # (-1 / -2 / -2: leave, tell)
+    try:
+        L.pdgn_gemm_set_mode({"fp32": 0, "x3": 1, "x2": 2}[case.mode])
+        L.pdgn_gemm_set_config(-1 if case.cfg is None else case.cfg)
+        if case.mode != "fp32":
+            L.pdgn_gemm_set_shape(case.shape)
+        gc.check_launch_model_queries(L, case, cus)
+    finally:
+        L.pdgn_gemm_set_mode(found[0])
+        L.pdgn_gemm_set_config(found[1])
+        L.pdgn_gemm_set_shape(0x1000 | found[2])
+        assert (L.pdgn_gemm_set_mode(-1), L.pdgn_gemm_set_config(-2), L.pdgn_gemm_set_shape(-2)) == found
 
 
 # ---------------------------------------------------------------------------- the split mirrors

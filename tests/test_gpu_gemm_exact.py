@@ -82,52 +82,8 @@ def test_every_required_tag_is_carried_on_this_device():
 def test_launch_model_queries_equal_the_restatement(case):
     """pdgn_gemm_nt_config, the three workspace queries, the launch-info grid, the row-panel and two-part questions and the statistics
     geometry under the case's switches against tests/gemm_cases.py at this device's CU count."""
-    c, cus, L = case, _cus(), _L()
-    _switch(c)
-    M, N, K = gc.kernel_dims(c)
-    fam = "fp32" if c.mode == "fp32" else "x3"
-    for ws in (0, 1):
-        t = gc.pick(fam, M, N, K, bool(ws), cus, c.cfg)
-        tile = gc.TILES[fam][t]
-        pl = gc.plan(tile, M, N, K, not ws, cus)
-        assert L.pdgn_gemm_nt_config(M, N, K, ws) == t + (16 if pl.grid_sk else 0), (ws, t, pl)
-        floats = 0 if fam == "fp32" else gc.tail_layout(tile, pl, cus).floats
-        assert L.pdgn_gemm_tail_workspace_floats(M, N, K, ws) == floats, (ws, t, pl)
-        assert (floats > 0) == (fam == "x3" and pl.grid_sk > 0)
-        if fam == "x3":
-            assert L.pdgn_gemm_nt_ps_workspace_floats(M, N, K, 3, ws) == floats
-            # two-part planes run on the 256 x 128 tile: its tail's floats, none with statistics.  The library answers 0 outright for a
-            # shape the row-panel kernel can take, whatever the mode and the epilogue; that is no quirk to pin, because such a shape
-            # (k <= 128: at most 4 chunks) never plans a tail on this tile -- asserted here from the restated plan, not from the rule
-            big = gc.X3_TILES[0]
-            two = 0 if ws else gc.tail_layout(big, gc.plan(big, M, N, K, True, cus), cus).floats
-            assert not (gc.rp_takes(M, N, K) and two), "a row-panel shape that plans a tail: the library's shortcut would lose it"
-            assert L.pdgn_gemm_nt_ps_workspace_floats(M, N, K, 2, ws) == two, ws
-    ts = gc.TILES[fam][gc.pick(fam, M, N, K, True, cus, c.cfg)]
-    assert L.pdgn_gemm_nt_stat_rows(M, N, K) == gc.cdiv(M, ts.BM) * ts.stat_div
-    assert L.pdgn_gemm_nt_stat_block_rows(M, N, K) == ts.BM // ts.stat_div      # BM / 4 on the big fp32 tile, BM / 2 elsewhere
-    if fam == "fp32":
-        assert L.pdgn_gemm_tn_big_workspace_floats(M, N, K) == 0 and L.pdgn_gemm_two_part(M, N, K, 0) == 0
-        return
-    import ctypes
-    for parts in (3, 2):
-        sym, grid = ctypes.c_void_p(), ctypes.c_int(-1)
-        assert L.pdgn_gemm_nt_ps_launch_info(M, N, K, parts, ctypes.byref(sym), ctypes.byref(grid)) == 0
-        tile = gc.X3_TILES[0 if parts == 2 else gc.pick("x3", M, N, K, False, cus, c.cfg)]
-        assert grid.value == gc.plan(tile, M, N, K, True, cus).grid_dp, (parts, tile)
-        for plain in (0, 1):
-            takes = c.mode == "x2" and parts == 2 and plain == 1 and gc.rp_takes(M, N, K)
-            assert L.pdgn_gemm_nt_ps_row_panel(M, N, K, parts, plain) == int(takes)
-            assert L.pdgn_gemm_nt_ps_stat_block_rows(M, N, K, parts, plain) == (256 if takes else ts.BM // ts.stat_div)
-            assert L.pdgn_gemm_nt_ps_stat_rows(M, N, K, parts, plain) == (gc.cdiv(M, 256) if takes else gc.cdiv(M, ts.BM) * ts.stat_div)
-    for scan in (0, (M * K + N * K) * 4):
-        assert L.pdgn_gemm_two_part(M, N, K, scan) == int(gc.x2_pays(c.mode, gc.pick("x3", M, N, K, False, cus, c.cfg), M, N, K, scan))
-    # the weight gradient of the same kernel-side problem: dW (M x N) over K rows
-    d = gc.describe(c._replace(entry="tn_big", m=K, n=M, k=N, epi=(), pads=gc.NOPAD), cus)
-    assert L.pdgn_gemm_tn_big_workspace_floats(K, M, N) == d["at_floats"], d
-    d = gc.describe(c, cus)
-    if d["kernel"] == "tile" and c.entry != "tn_big":
-        assert d["ws_floats"] == (d["tail"].floats if d["plan"].grid_sk else 0)
+    _switch(case)
+    gc.check_launch_model_queries(_L(), case, _cus())
 
 
 def _planes(L, c, w_dev, N, K, ldw_pad, stream):

@@ -46,6 +46,9 @@ def kernels(src, out):
             funcs[cur] = []
         elif cur and line.strip() and not line.startswith("Disassembly"):
             funcs[cur].append(re.sub(r"<[^>]*>|//.*$", "", line).strip())
+    for body in funcs.values():                                      # "...": the zero bytes llvm-objdump skips between a function's end and
+        while body and body[-1] == "...":                            # the next one's aligned start -- there or not by the function's place
+            body.pop()                                               # in the section (the last one has none), not by its code
     return funcs
 
 

@@ -16,9 +16,9 @@ int fp32_gemm_nt(long long, int, int, const float *, int, const float *, int, co
 int fp32_gemm_nn(long long, int, int, const float *, int, const float *, int, const float *, const float *, int, float *, int, float *, pdgn_stream_t) { return -1; }
 int fp32_gemm_nt_ex(long long, int, int, const float *, int, const float *, int, const float *, const float *, int, float *, int, float *, const float *, int, int, int, const float *, int, int, pdgn_stream_t) { return -1; }
 int fp32_gemm_tn_big(long long, int, int, const float *, int, const float *, int, float *, pdgn_stream_t) { return -1; }
-long long fp32_gemm_nt_stat_rows(long long, int, int) { return -1; }
-int fp32_gemm_nt_stat_block_rows(long long, int, int) { return -1; }
-int fp32_gemm_nt_config(long long, int, int, int) { return -1; }
+// nor is the row-panel kernel (gemm_rp.hip)
+bool rp_takes(long long, int, int) { return false; }
+int rp_launch(long long, int, int, const float *, int, const unsigned short *, int, long long, float *, int, float *, hipStream_t) { return -1; }
 
 int main() {
     void *slots = nullptr;                                         // mode 2: the ring of operand-scale slots is the caller's
