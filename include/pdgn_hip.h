@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 48
+#define PDGN_ABI_VERSION 49
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1310,6 +1310,39 @@ int pdgn_repulsion_backward(long long count, const float *grad, const float *g, 
 #define PDGN_NORMALS_STAGE_MAX_N 4096
 int pdgn_estimate_normals(int b, int n, int k, const float *xyz, const int32_t *idx, int orient, float ox, float oy, float oz,
                           float *normals, float *eig, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ flatness regulariser (csrc/flatness.hip)
+ * The batch mean of Pauly's surface variation sigma_i = l0 / ((l0 + l1) + l2 + eps) of every point's k-neighbourhood, and its gradient with
+ * respect to the points: the term that pulls a generated cloud ONTO its surface (the repulsion term spreads it ALONG the surface).  The
+ * header block of csrc/flatness.hip is the normative definition; tests/flatness_mirror.py spells it in numpy and the two agree bit for
+ * bit.  The eigenvalues are pdgn_estimate_normals' on the same lists, bit for bit (csrc/pca3.h is shared).  No reference counterpart.
+ *   xyz         (b,n,3)
+ *   idx         (b,n,k) int32: for every point k indices into its own cloud, any (repeats allowed), taken in slot order.  The lists are
+ *               DATA: the neighbour choice is not differentiated.
+ *   eps         >= 0: added to the trace in the denominator (a floor under the trace of a nearly coincident neighbourhood)
+ *   coef        the factor of the gradient: 1 / (b n) for d loss / d xyz; the caller computes it in fp64 and rounds it once
+ *   sigma       (b,n), always written: sigma_i; 0 for a DEGENERATE point (!(l0 > 0) or !(trace + eps > 0): coincident points, an exactly
+ *               flat neighbourhood), NaN for a BAD one (an index outside [0, n) -- never dereferenced -- or an eigenvalue that is not finite)
+ *   loss        (1): (float)(T / (double)(b n)), T = sum_c (double)P_c, P_c = sum_i sigma_i in pdgn_repulsion's fixed fp32 order of one wave
+ *   per_cloud   (b) or NULL: (float)((double)P_c / n)
+ *   degenerate  (b) int32 or NULL: the number of degenerate points of every cloud (zeroed by the call, integer atomics)
+ *   grad        (b,n,3) or NULL: grad_j = coef * sum over the in-edges e = i k + s of j (idx[i][s] == j), in ASCENDING e, of H_i (x_j - mu_i)
+ *               with H_i = (2 / (k q)) (v v^T - sigma_i I); zero rows for a degenerate source, NaN for every target on a bad point's list.
+ *               Gathered over a CSR transpose of idx whose rows are in increasing edge id: no float atomics, bitwise repeatable.
+ *   ws          pdgn_flatness_workspace_bytes(b, n, k, 1) bytes, 16-byte aligned, or NULL where grad is NULL (not read then): the 48-byte
+ *               records (mu, H) and the transpose's integers
+ * With grad == NULL no record is written and nothing is transposed; sigma, loss, per_cloud and degenerate are the same bits either way.
+ * Results do not depend on the launch geometry, nor on whether the clouds pass through LDS (as pdgn_estimate_normals).  Kernel and memset
+ * nodes only on `stream` (the per-point launch and the reduction; with grad the transpose -- one workgroup per cloud up to 4096 points, csrc/det.hip's
+ * memset and two launches above -- and the gather), nothing
+ * allocated, no host synchronisation.  The backward of the autograd node is pdgn_repulsion_backward (dxyz = up * grad).
+ * pdgn_flatness_workspace_bytes: 0 for with_grad == 0; PDGN_ERR_INVALID for dimensions pdgn_flatness refuses.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1, k outside [1, PDGN_NORMALS_MAX_K], b n k >= 2^31, eps negative or
+ * not finite, coef not finite, a null pointer (per_cloud, degenerate, grad and ws excepted), grad without ws, a pointer not 4-byte (ws:
+ * 16-byte) aligned. */
+long long pdgn_flatness_workspace_bytes(int b, int n, int k, int with_grad);
+int pdgn_flatness(int b, int n, int k, const float *xyz, const int32_t *idx, float eps, float coef, float *sigma, float *loss,
+                  float *per_cloud, int32_t *degenerate, float *grad, void *ws, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ consistent normal orientation (csrc/orient.hip)
  * pdgn_orient_normals gives the normals of every cloud one consistent sign: a minimum spanning tree of the symmetrised neighbour graph

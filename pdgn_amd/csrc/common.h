@@ -32,3 +32,11 @@ __device__ __forceinline__ float dot3_rn(float ax, float ay, float az, float bx,
 static inline bool pdgn_aligned(const void *p, uintptr_t to) { return !((uintptr_t)p & (to - 1)); }
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (PDGN_WAVE - 1); }
+
+// Host-side launchers one kernel file offers another (defined once, linked by name; each enqueues on `s` and allocates nothing).
+// det.hip: CSR transpose of idx (b, E) over nt targets in ws = [cnt b*nt][rowptr b*(nt+1)][edges b*E] (det_ints(b, nt, E) ints, b <= 65535);
+// every row lists its edges in INCREASING edge id, an index outside [0, nt) is in no row.
+long long det_ints(long long b, long long nt, long long E);
+int det_transpose(int b, int nt, long long E, const int32_t *idx, int *ws, int **rowptr, int **edges, hipStream_t s);
+// repulsion.hip: the fixed-order means of a (b, n) array (that file's header block: one wave per cloud, the xor tree, fp64 across clouds)
+void rp_reduce_launch(int b, int n, const float *s, float *loss, float *per_cloud, hipStream_t st);

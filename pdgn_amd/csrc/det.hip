@@ -130,10 +130,10 @@ __global__ __launch_bounds__(DET_THREADS) void det_nndist_grad_kernel(
     }
 }
 
-static long long det_ints(long long b, long long nt, long long E) { return b * (2 * nt + 1 + E); }
+long long det_ints(long long b, long long nt, long long E) { return b * (2 * nt + 1 + E); }
 
 // CSR transpose of idx (b, E) over nt targets in ws: [cnt b*nt][rowptr b*(nt+1)][edges b*E].
-static int det_transpose(int b, int nt, long long E, const int32_t *idx, int *ws, int **rowptr, int **edges, hipStream_t s) {
+int det_transpose(int b, int nt, long long E, const int32_t *idx, int *ws, int **rowptr, int **edges, hipStream_t s) {
     int *cnt = ws;
     *rowptr = ws + (size_t)b * nt;
     *edges = *rowptr + (size_t)b * (nt + 1);

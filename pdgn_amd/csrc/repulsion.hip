@@ -121,6 +121,10 @@ __global__ __launch_bounds__(256) void repulsion_bwd_kernel(long long count, con
 }
 
 
+void rp_reduce_launch(int b, int n, const float *s, float *loss, float *per_cloud, hipStream_t st) {
+    hipLaunchKernelGGL(repulsion_reduce_kernel, dim3(1), dim3(RP_RED_THREADS), 0, st, b, n, s, loss, per_cloud);
+}
+
 extern "C" int pdgn_repulsion_chunk(void) { return RP_CHUNK; }
 
 extern "C" int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, float coef, float *s, float *loss, float *per_cloud,
@@ -147,7 +151,7 @@ extern "C" int pdgn_repulsion(int b, int n, const float *xyz, float inv_h2, floa
         else
             hipLaunchKernelGGL(repulsion_kernel<64>, grid, dim3(64), lds, (hipStream_t)stream, n, x0, inv_h2, coef, s0, g0, n0);
     }
-    hipLaunchKernelGGL(repulsion_reduce_kernel, dim3(1), dim3(RP_RED_THREADS), 0, (hipStream_t)stream, b, n, s, loss, per_cloud);
+    rp_reduce_launch(b, n, s, loss, per_cloud, (hipStream_t)stream);
     return pdgn_launch_status();
 }
 

@@ -1,8 +1,8 @@
 """The training loop behind `PDGNTrainer.fit` (models/PDGNet_v2.py:157-269) and its host-side parts: the side logs
-(grad_norms.csv, lr.csv, aug.csv, repulsion.csv), the two-slot read-back of the losses, and the gradient guard's stop rule.
+(grad_norms.csv, lr.csv, aug.csv, repulsion.csv, flatness.csv), the two-slot read-back of the losses, and the gradient guard's stop rule.
 
 Everything here takes the trainer as an argument and asks it only for what the feature in use needs, so `fit` also runs on a
-duck-typed stand-in without `guards`, `lr_table`, `per_network_lr`, `aug` or `repulsion` (tests/test_fit_host.py).  This module imports
+duck-typed stand-in without `guards`, `lr_table`, `per_network_lr`, `aug`, `repulsion` or `flatness` (tests/test_fit_host.py).  This module imports
 nothing from `trainer`; `trainer` re-exports the names below that were defined there.
 """
 import contextlib
@@ -157,8 +157,14 @@ def _repulsion_row(trainer, ep):
     return ["%d" % ep, "%.9g" % state["weight"], "%.9g" % state["radius"], "%.9g" % state["total"]] + ["%.9g" % v for v in state["per_level"]]
 
 
+def _flatness_row(trainer, ep):
+    state = trainer.flatness_state()
+    return (["%d" % ep, "%.9g" % state["weight"], "%d" % state["k"], "%.9g" % state["eps"], "%.9g" % state["total"]]
+            + ["%.9g" % v for v in state["per_level"]] + ["%d" % state["degenerate"]])
+
+
 def fit(trainer, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-        on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None, repulsion_log=None):
+        on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None, repulsion_log=None, flatness_log=None):
     """`PDGNTrainer.fit`: its docstring is the contract."""
     if issue not in ("list", "eager"):
         raise ValueError("issue: 'list' or 'eager', got %r" % (issue,))
@@ -187,6 +193,8 @@ def fit(trainer, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None
 
         repel = side(repulsion_log, "repulsion.csv", getattr(trainer, "repulsion", None) is not None,
                      ["epoch", "weight", "radius", "total"] + ["level%d" % l for l in (1, 2, 3, 4)])
+        flat = side(flatness_log, "flatness.csv", getattr(trainer, "flatness", None) is not None,
+                    ["epoch", "weight", "k", "eps", "total"] + ["level%d" % l for l in (1, 2, 3, 4)] + ["degenerate"])
 
         def epoch_rows(ep):                                      # one row per epoch: the last epoch's checkpoint may be written twice
             ada.row(lambda: _ada_row(trainer, ep), key=ep)
@@ -220,6 +228,7 @@ def fit(trainer, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None
                 on_epoch(epoch)
                 epoch_rows(epoch)
             repel.row(lambda: _repulsion_row(trainer, epoch), key=epoch)     # every epoch: the last iteration's values (one synchronise)
+            flat.row(lambda: _flatness_row(trainer, epoch), key=epoch)
         if back is not None:
             back.flush()
         if save_to is not None:

@@ -275,6 +275,104 @@ def repulsion_radii(radius, sizes):
     return [radius * (float(finest) / float(n)) ** 0.5 for n in sizes]
 
 
+FLATNESS_MAX_K = 64                                              # PDGN_NORMALS_MAX_K
+
+
+def _flatness_eps(eps):
+    eps = float(eps)
+    if not (0.0 <= eps < float("inf")):
+        raise ValueError("eps must be finite and not negative, got %r" % (eps,))
+    return eps
+
+
+def flatness_pass(x, idx, eps=0.0, grad=True, per_cloud=False, degenerate=None):
+    """pdgn_flatness on x (B,N,3), point-major and contiguous, with the neighbour lists idx (B,N,k) int32: (loss 0-dim, per_cloud (B) |
+    None, grad (B,N,3) | None, sigma (B,N), degenerate (B) int32 -- the caller's tensor where one is given); without `grad` no record is
+    written and nothing is transposed.  No autograd (losses.flatness is the differentiable form; evaluation.surface_stats the metric)."""
+    eps = _flatness_eps(eps)
+    require(x, "x", F32, 3)
+    require(idx, "idx", I32, 3)
+    b, n, three = x.shape
+    if three != 3:
+        raise ValueError("x must be (B,N,3), got %s" % (tuple(x.shape),))
+    k = idx.shape[2]
+    if tuple(idx.shape[:2]) != (b, n) or not 1 <= k <= FLATNESS_MAX_K or idx.device != x.device:
+        raise ValueError("idx must be (B,N,k) = (%d,%d,1..%d) on %s, got %s" % (b, n, FLATNESS_MAX_K, x.device, tuple(idx.shape)))
+    L = _lib.lib()
+    size = L.pdgn_flatness_workspace_bytes(b, n, k, 1 if grad else 0)
+    if size < 0:
+        raise _lib.PdgnHipError("pdgn_flatness_workspace_bytes: argument outside the supported range")
+    sigma = torch.empty((b, n), dtype=F32, device=x.device)
+    loss = torch.empty((), dtype=F32, device=x.device)
+    pc = torch.empty((b,), dtype=F32, device=x.device) if per_cloud else None
+    if degenerate is None:
+        deg = torch.empty((b,), dtype=I32, device=x.device)
+    else:
+        deg = require(degenerate, "degenerate", I32, 1)
+        if deg.shape[0] != b or deg.device != x.device:
+            raise ValueError("degenerate must be (B) = (%d) int32 on %s" % (b, x.device))
+    g = torch.empty((b, n, 3), dtype=F32, device=x.device) if grad else None
+    ws = torch.empty((size // 4,), dtype=I32, device=x.device) if grad else None
+    check(L.pdgn_flatness(b, n, k, ptr(x), ptr(idx), eps, 1.0 / (float(b) * float(n)), ptr(sigma), ptr(loss), ptr(pc), ptr(deg), ptr(g),
+                          ptr(ws), stream_of(x)), "pdgn_flatness")
+    return loss, pc, g, sigma, deg
+
+
+class Flatness(Function):
+    """x (B,N,3), idx (B,N,k) -> the batch mean of the surface variation as ONE autograd node (csrc/flatness.hip): the forward computes the
+    gradient too and saves it, the backward multiplies it by the upstream scalar (pdgn_repulsion_backward).  Nothing flows to idx."""
+
+    @staticmethod
+    def forward(ctx, x, idx, eps, degenerate=None):
+        loss, _, g, _, _ = flatness_pass(x, idx, eps, degenerate=degenerate)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, up):
+        g, = ctx.saved_tensors
+        dx = torch.empty_like(g)
+        up = up.contiguous()
+        check(_lib.lib().pdgn_repulsion_backward(g.numel(), ptr(g), ptr(up), ptr(dx), stream_of(g)), "pdgn_repulsion_backward")
+        return dx, None, None, None
+
+
+def flatness(cloud, k=16, idx=None, eps=0.0, degenerate=None):
+    """The flatness regulariser of a batch of clouds: the batch MEAN over clouds and points of Pauly's surface
+    variation sigma_i = l0 / (l0 + l1 + l2 + eps) of the covariance of point i's k neighbours -- zero where every neighbourhood is flat.
+    cloud: (B,3,N) as the generator returns it, or point-major (B,N,3); (B,3,3) reads as (B,3,N).  idx: the neighbour lists (B,N,k)
+    int32, or None: pointops.knnquery(k, x, x) of the detached cloud (k <= N).  The lists are data: the neighbour choice is not
+    differentiated.  degenerate: None, or a (B) int32 tensor that receives every cloud's number of degenerate points (sigma = 0: coincident
+    points, an exactly flat neighbourhood).  Every sum in a fixed order (bitwise repeatable, no float atomics); a NaN coordinate gives a NaN loss and NaN
+    gradients on its neighbourhoods' points."""
+    if not isinstance(cloud, torch.Tensor) or cloud.dim() != 3 or 3 not in cloud.shape[1:]:
+        raise ValueError("cloud must be a (B,3,N) or (B,N,3) tensor")
+    eps = _flatness_eps(eps)
+    x = cloud.transpose(1, 2) if cloud.shape[1] == 3 else cloud
+    n = x.shape[1]
+    if idx is None:
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(FLATNESS_MAX_K, n):
+            raise ValueError("k must be an integer from 1 to min(%d, N = %d), got %r" % (FLATNESS_MAX_K, n, k))
+    elif not isinstance(idx, torch.Tensor) or idx.dtype != I32 or idx.dim() != 3 or tuple(idx.shape[:2]) != (x.shape[0], n) or not 1 <= idx.shape[2] <= FLATNESS_MAX_K:
+        raise ValueError("idx must be an int32 tensor (B,N,k) = (%d,%d,1..%d)" % (x.shape[0], n, FLATNESS_MAX_K))
+    x = x.contiguous()
+    if idx is None:
+        with torch.no_grad():
+            idx = pointops.knnquery(k, x.detach(), x.detach())
+    return Flatness.apply(x, idx.contiguous(), eps, degenerate)
+
+
+def flatness_floors(eps, sizes):
+    """The floor per level: eps * N_finest / N_l for the point counts `sizes` -- `eps` is the finest level's, and a neighbourhood's trace
+    scales with the squared spacing, about 1 / N."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 1:
+        raise ValueError("sizes: at least one positive point count, got %r" % (sizes,))
+    eps = _flatness_eps(eps)
+    finest = max(sizes)
+    return [eps * float(finest) / float(n) for n in sizes]
+
+
 class SurfaceDistance(Function):
     """xyz (B,N,3) -> d2 (B,N), the squared distance of every point to the surface of its shape, as ONE autograd node over
     meshes.point_to_mesh (csrc/meshdist.hip): the forward launch returns the closest points and saves them, the backward is the tensor

@@ -76,8 +76,8 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
     (`k` is then ignored); None: knnquery(k, xyz, xyz), which needs k <= N.  orient: None (the component of largest magnitude is made
     non-negative), ("direction", v) (n . v >= 0), ("towards", p) (n . (p - x) >= 0) or ("away", p) (n . (x - p) >= 0), v / p three
     numbers, or "consistent" (the estimate with orient=None, then orient_normals with the same lists: N <= 4096, k <= 64).  A point with
-    an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no graph (a flatness loss is
-    a request of its own)."""
+    an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no graph (the differentiable
+    flatness loss on the same eigenvalues is losses.flatness)."""
     require(xyz, "xyz", F32, 3)
     if xyz.shape[2] != 3:
         raise ValueError("xyz must be (B,N,3), got %s" % (tuple(xyz.shape),))

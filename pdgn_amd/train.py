@@ -40,7 +40,11 @@ evenly spread duplicates where it stores fewer (data.RaggedFeeder, pdgn_feed_bat
 --repulsion W (train): the generator's loss gains W times a repulsion term on every generated cloud of --repulsion_levels (default 1,2,3,4), which
 is zero when no two points of a cloud are closer than the level's radius (losses.repulsion); --repulsion_radius H is the radius at
 --num_point points -- without it the radius is calibrated once before training, --repulsion_radius_factor (1) times the mean nearest-neighbour distance
-of up to 64 clouds the feeder itself produces, and printed; repulsion.csv beside the log.  --report_spacing (needs --report_every): the reports also
+of up to 64 clouds the feeder itself produces, and printed; repulsion.csv beside the log.  --flatness W (train): the generator's loss gains W times a flatness term on every
+generated cloud of --flatness_levels (default 1,2,3,4): the batch mean of the surface variation l0 / (l0 + l1 + l2 + eps) of every point's --flatness_k (16)
+nearest neighbours, zero on a flat neighbourhood (losses.flatness); --flatness_eps E is the floor under the trace at --num_point
+points -- without it the floor is calibrated once before training, --flatness_eps_factor (1e-2) times the mean trace of the k-neighbourhoods of up to 64
+clouds the feeder itself produces, and printed; flatness.csv beside the log.  --report_spacing (needs --report_every): the reports also
 append nearest-neighbour spacing statistics of the generated and the val clouds to report/spacing.csv.  --report_lit: the preview sheets are shaded by
 surface normals estimated from each cloud's 16 nearest neighbours; --report_surface: the reports also append the surface
 variation of the generated and the val clouds to report/surface.csv (both need --report_every).
@@ -143,6 +147,18 @@ def build_parser():
                    "calibrated radius is K times the mean nearest-neighbour distance (default 1)")
     p.add_argument("--repulsion_levels", type=str, default=argparse.SUPPRESS, metavar="L,..", help="--repulsion: the levels that carry the term, 1 (the "
                    "coarsest) .. 4 (--num_point points), comma separated (default 1,2,3,4)")
+    p.add_argument("--flatness", type=float, default=argparse.SUPPRESS, metavar="W", help="flatness regulariser: the generator's loss gains W times the "
+                   "sum over the levels of the batch mean of the surface variation l0 / (l0 + l1 + l2 + eps) of every generated point's k-neighbourhood "
+                   "(losses.flatness, DESIGN.md section 7x); flatness.csv beside the log")
+    p.add_argument("--flatness_k", type=int, default=argparse.SUPPRESS, metavar="K", help="--flatness: the number of nearest neighbours, 1 .. 64 and at most "
+                   "the coarsest named level's point count (default 16)")
+    p.add_argument("--flatness_eps", type=float, default=argparse.SUPPRESS, metavar="E", help="--flatness: the floor under the trace at --num_point points (a "
+                   "coarser level of N points gets E num_point / N); default: calibrated once before training, --flatness_eps_factor times the mean "
+                   "trace of the k-neighbourhoods of up to 64 clouds the feeder produces")
+    p.add_argument("--flatness_eps_factor", type=float, default=argparse.SUPPRESS, metavar="F", help="--flatness without --flatness_eps: the calibrated "
+                   "floor is F times the mean neighbourhood trace (default 1e-2)")
+    p.add_argument("--flatness_levels", type=str, default=argparse.SUPPRESS, metavar="L,..", help="--flatness: the levels that carry the term, 1 (the "
+                   "coarsest) .. 4 (--num_point points), comma separated (default 1,2,3,4)")
     p.add_argument("--report_spacing", action="store_true", default=argparse.SUPPRESS, help="reports also append the nearest-neighbour spacing statistics of "
                    "the generated and of the val clouds to report/spacing.csv (evaluation.spacing_stats); needs --report_every")
     p.add_argument("--report_lit", action="store_true", default=argparse.SUPPRESS, help="preview sheets shaded by surface normals (two-sided headlight "
@@ -216,6 +232,11 @@ class Args(argparse.Namespace):
     repulsion_radius = None                                      # (None: calibrated from the feeder's clouds)
     repulsion_radius_factor = 1.0
     repulsion_levels = "1,2,3,4"
+    flatness = None
+    flatness_k = 16
+    flatness_eps = None                                          # (None: calibrated from the feeder's clouds)
+    flatness_eps_factor = 1e-2
+    flatness_levels = "1,2,3,4"
     report_spacing = False
     report_lit = False
     report_surface = False
@@ -316,6 +337,26 @@ def parse_args(argv=None):
             p.error("--repulsion_levels: %s" % e)
         if args.num_point > 8192:
             p.error("--repulsion: --num_point %d, the all-pairs kernel holds at most 8192 points" % args.num_point)
+    if args.flatness is None:
+        for flag in ("flatness_k", "flatness_eps", "flatness_eps_factor", "flatness_levels"):
+            if flag in given:
+                p.error("--%s needs --flatness" % flag)
+    else:
+        if not (args.flatness >= 0.0 and args.flatness != float("inf")):
+            p.error("--flatness %r: a finite weight, not negative" % args.flatness)
+        if args.flatness_eps is not None and not (args.flatness_eps >= 0.0 and args.flatness_eps != float("inf")):
+            p.error("--flatness_eps %r: a finite floor, not negative" % args.flatness_eps)
+        if args.flatness_eps is not None and "flatness_eps_factor" in given:
+            p.error("--flatness_eps_factor scales the CALIBRATED floor: it does not go with --flatness_eps")
+        if not (args.flatness_eps_factor >= 0.0 and args.flatness_eps_factor != float("inf")):
+            p.error("--flatness_eps_factor %r: a finite factor, not negative" % args.flatness_eps_factor)
+        try:
+            levels = flatness_levels(args)
+        except ValueError as e:
+            p.error("--flatness_levels: %s" % e)
+        coarsest = args.num_point >> (3 - levels[0])
+        if not 1 <= args.flatness_k <= min(64, coarsest):
+            p.error("--flatness_k %d: 1 .. 64 and at most the %d points of level %d" % (args.flatness_k, coarsest, levels[0] + 1))
     if args.report_spacing and not args.report_every:
         p.error("--report_spacing needs --report_every")
     for flag in ("report_lit", "report_surface", "report_fidelity"):
@@ -349,6 +390,48 @@ def repulsion_levels(args):
     if not levels or len(set(levels)) != len(levels) or min(levels) < 1 or max(levels) > 4:
         raise ValueError("%r: distinct levels from 1 (the coarsest) to 4 (the finest)" % (args.repulsion_levels,))
     return tuple(sorted(l - 1 for l in levels))
+
+
+def flatness_levels(args):
+    """--flatness_levels, read as --repulsion_levels is."""
+    try:
+        levels = [int(w) for w in str(args.flatness_levels).split(",")]
+    except ValueError:
+        raise ValueError("%r: comma-separated integers 1 .. 4" % (args.flatness_levels,)) from None
+    if not levels or len(set(levels)) != len(levels) or min(levels) < 1 or max(levels) > 4:
+        raise ValueError("%r: distinct levels from 1 (the coarsest) to 4 (the finest)" % (args.flatness_levels,))
+    return tuple(sorted(l - 1 for l in levels))
+
+
+def calibrate_flatness_eps(feeder, k=16, factor=1e-2, clouds=64):
+    """The floor of --flatness without --flatness_eps: `factor` times the mean trace l0 + l1 + l2 of the k-neighbourhoods
+    (pointops.estimate_normals' eigenvalues) of up to `clouds` finest-resolution clouds that the feeder itself produces -- the leading
+    batches of epoch 1, into buffers of its own.  Under data parallelism rank 0's value goes to every rank."""
+    import torch.distributed as dist
+    from .pointops import estimate_normals
+    reals, z1, z2 = feeder.buffers()
+    got = []
+    for i in range(min(feeder.batches_per_epoch, -(-int(clouds) // reals[3].shape[0]))):
+        feeder.fill(1, i, reals, z1, z2)
+        got.append(reals[3].transpose(1, 2).contiguous())
+    pcs = torch.cat(got)[:int(clouds)].contiguous()
+    _, eig = estimate_normals(pcs, k=int(k), return_eig=True)
+    eps = float(factor) * float(eig.double().sum(dim=2).mean().item())
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        t = torch.tensor([eps], dtype=torch.float64, device=pcs.device)
+        dist.broadcast(t, 0)
+        eps = float(t.item())
+    if not (eps >= 0.0 and eps != float("inf")):
+        raise SystemExit("--flatness: the calibrated floor is %r (the feeder's clouds have no finite neighbourhood trace); give --flatness_eps" % eps)
+    return eps, pcs.shape[0]
+
+
+def flatness_arg(args, eps=None):
+    """PDGNTrainer's `flatness` from the command line (None without --flatness); eps: the calibrated one where --flatness_eps was not given."""
+    if args.flatness is None:
+        return None
+    return {"weight": args.flatness, "k": args.flatness_k, "eps": args.flatness_eps if args.flatness_eps is not None else eps,
+            "levels": flatness_levels(args)}
 
 
 def calibrate_repulsion_radius(feeder, factor=1.0, clouds=64):
@@ -596,7 +679,7 @@ def init_dist(device):
     return 0, 1, torch.device(device)
 
 
-def make_trainer(args, device, batches_per_epoch=None, repulsion=None):
+def make_trainer(args, device, batches_per_epoch=None, repulsion=None, flatness=None):
     from .generator import PointGenerator
     from .trainer import PDGNTrainer
     base = args.num_point // 16
@@ -609,7 +692,8 @@ def make_trainer(args, device, batches_per_epoch=None, repulsion=None):
                        lr_g=args.lr_g if args.phase == "train" else None, lr_d=args.lr_d if args.phase == "train" else None,
                        lr_schedule=schedule_knots(args, batches_per_epoch) if args.phase == "train" and batches_per_epoch else None,
                        augment=_augment_arg(args) if args.phase == "train" else None, gan_loss=args.gan_loss,
-                       repulsion=repulsion if args.phase == "train" else None)
+                       repulsion=repulsion if args.phase == "train" else None,
+                       **({"flatness": flatness} if flatness is not None and args.phase == "train" else {}))
 
 
 def _augment_arg(args):
@@ -690,14 +774,24 @@ def train(args):
         if rank == 0:
             print("# repulsion radius: %.9g (%g x the mean nearest-neighbour distance of %d clouds of %d points)"
                   % (radius, args.repulsion_radius_factor, used, n))
+    floor = None
+    if args.flatness is not None and args.flatness_eps is None:
+        floor, used = calibrate_flatness_eps(feeder, args.flatness_k, args.flatness_eps_factor)
+        if rank == 0:
+            print("# flatness eps: %.9g (%g x the mean trace of the %d-neighbourhoods of %d clouds of %d points)"
+                  % (floor, args.flatness_eps_factor, args.flatness_k, used, n))
     try:
-        trainer = make_trainer(args, device, feeder.batches_per_epoch, repulsion_arg(args, radius))
+        trainer = make_trainer(args, device, feeder.batches_per_epoch, repulsion_arg(args, radius),
+                               **({"flatness": flatness_arg(args, floor)} if args.flatness is not None else {}))
     except ValueError as e:                                      # (a schedule that does not fit this run's number of updates)
         raise SystemExit(str(e))
     trainer.train()
     if rank == 0 and trainer.repulsion is not None:
         print("# repulsion: weight %g, radius %.9g, levels %s" % (trainer.repulsion["weight"], trainer.repulsion["radius"],
                                                                   ",".join(str(l + 1) for l in trainer.repulsion["levels"])))
+    if rank == 0 and getattr(trainer, "flatness", None) is not None:
+        print("# flatness: weight %g, k %d, eps %.9g, levels %s" % (trainer.flatness["weight"], trainer.flatness["k"], trainer.flatness["eps"],
+                                                                    ",".join(str(l + 1) for l in trainer.flatness["levels"])))
     if rank == 0 and trainer.gan_loss != "lsgan":
         print("# adversarial objective: %s (scores are logits; decision boundary 0)" % trainer.gan_loss)
     start = _resume(args, trainer, ckpt) or 1
@@ -732,7 +826,8 @@ def train(args):
                        category=args.choice or "full", log=log, on_epoch=reporter, guard_max_skips=args.guard_max_skips,
                        grad_norms=os.path.join(run_dir, "grad_norms.csv") if args.grad_guard else None,
                        lr_log=os.path.join(run_dir, "lr.csv"), aug_log=os.path.join(run_dir, "aug.csv"),
-                       **({"repulsion_log": os.path.join(run_dir, "repulsion.csv")} if trainer.repulsion is not None else {}))
+                       **({"repulsion_log": os.path.join(run_dir, "repulsion.csv")} if trainer.repulsion is not None else {}),
+                       **({"flatness_log": os.path.join(run_dir, "flatness.csv")} if getattr(trainer, "flatness", None) is not None else {}))
     torch.cuda.synchronize(device)
     if world > 1:
         torch.distributed.barrier()

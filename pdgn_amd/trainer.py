@@ -84,15 +84,25 @@ class PDGNTrainer:
     for it.  `out["g_loss"]` includes it, `out["repulsion_loss"]` is the unweighted sum over the levels, `repulsion_state()` reads the
     per-level values; `set_repulsion(weight=...)` overwrites the weight in place (a captured list follows), a new radius needs a
     recapture.  Every sum of the term runs in a fixed order: under `set_deterministic` it adds no non-determinism of its own (the
-    step's other sums still warn).  None: `repulsion` is None, no buffer, no launch, the same list and the same six `out` keys."""
+    step's other sums still warn).  None: `repulsion` is None, no buffer, no launch, the same list and the same six `out` keys.
+
+    flatness: None, or {"weight": w, "k": 16, "eps": e, "levels": (0, 1, 2, 3)} (k, eps and levels optional).  With one, the generator's
+    loss gains w * sum_l losses.flatness(gen_l, k, eps=e_l) over the named levels of pass #2's clouds: the batch
+    mean of the surface variation of every point's k nearest neighbours (one pdgn_knnquery per level, on the detached cloud); e is the
+    finest level's floor, e_l = losses.flatness_floors'.  A batch MEAN like repulsion: no world-size factor.  `out["g_loss"]` includes
+    it, `out["flatness_loss"]` is the unweighted sum over the levels, `flatness_state()` reads the per-level values and the number of
+    degenerate points; `set_flatness(weight=...)` overwrites the weight in place (a captured list follows), a new k or eps needs a
+    recapture.  Fixed-order sums, no float atomics.  May be combined with `repulsion`.  None: `flatness` is None, no buffer, no launch,
+    the same list and the same `out` keys."""
 
     def __init__(self, device="cuda", lr=1e-4, num_k=20, base_points=128, generator=None,
                  discriminators=None, distributed=None, ema_decay=0.0, grad_guard=False, clip_grad_norm=None,
-                 lr_g=None, lr_d=None, lr_schedule=None, augment=None, gan_loss="lsgan", repulsion=None):
+                 lr_g=None, lr_d=None, lr_schedule=None, augment=None, gan_loss="lsgan", repulsion=None, flatness=None):
         if gan_loss not in losses.GAN_LOSSES:                    # (raises before anything is allocated)
             raise ValueError("gan_loss must be one of %s, got %r" % (", ".join(losses.GAN_LOSSES), gan_loss))
         self.gan_loss = gan_loss
         self.repulsion = None if repulsion is None else self._check_repulsion(repulsion)     # (raises before anything is allocated)
+        self.flatness = None if flatness is None else self._check_flatness(flatness)
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be in [0, 1), got %r" % (ema_decay,))
         self.ema_decay = float(ema_decay)
@@ -160,6 +170,10 @@ class PDGNTrainer:
         if self.repulsion is not None:
             self._rep_buf = torch.zeros(4, dtype=torch.float32, device=self.device)       # the last iteration's value per level
             self._rep_zero = torch.zeros((), dtype=torch.float32, device=self.device)     # (a level that is not in `levels`)
+        if self.flatness is not None:
+            self._flat_buf = torch.zeros(4, dtype=torch.float32, device=self.device)      # the last iteration's value per level
+            self._flat_zero = torch.zeros((), dtype=torch.float32, device=self.device)
+            self._flat_deg = {}                                  # level -> (B) int32: the last iteration's degenerate points per cloud
         for ws in {1, world_size() if self.distributed else 1}:
             self._loss_weights(ws)
         self._early_tail = os.environ.get("PDGN_EARLY_TAIL", "1") == "1"
@@ -211,7 +225,7 @@ class PDGNTrainer:
         self.repulsion = fresh
         with torch.no_grad():
             for w in self._lw.values():
-                w[5:].fill_(fresh["weight"])
+                w[5:6].fill_(fresh["weight"])
 
     def repulsion_state(self):
         """{weight, radius, levels, radii, per_level, total}: the parameters, the radius of each of the four levels for the last
@@ -237,6 +251,75 @@ class PDGNTrainer:
         vals = torch.stack([r if r is not None else self._rep_zero for r in rep])
         # (an elementwise launch, not copy_: a captured 16-byte copy_ is a memcpy node of a shape the launch list does not re-issue)
         torch.add(vals.detach(), self._rep_zero, out=self._rep_buf)
+        return vals.sum()
+
+    @staticmethod
+    def _check_flatness(cfg):
+        """{"weight", "k", "eps", "levels"} validated: weight finite and >= 0, k an integer in [1, 64], eps finite and >= 0, levels a
+        non-empty ascending subset of (0, 1, 2, 3)."""
+        if not isinstance(cfg, dict) or set(cfg) - {"weight", "k", "eps", "levels"} or "weight" not in cfg:
+            raise ValueError("flatness: None or {'weight': w, 'k': 16, 'eps': e, 'levels': (0, 1, 2, 3)}, got %r" % (cfg,))
+        weight, eps, k = float(cfg["weight"]), float(cfg.get("eps", 0.0)), cfg.get("k", 16)
+        if not (0.0 <= weight < float("inf")):
+            raise ValueError("flatness weight must be finite and not negative, got %r" % (cfg["weight"],))
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= losses.FLATNESS_MAX_K:
+            raise ValueError("flatness k must be an integer from 1 to %d, got %r" % (losses.FLATNESS_MAX_K, k))
+        if not (0.0 <= eps < float("inf")):
+            raise ValueError("flatness eps must be finite and not negative, got %r" % (cfg.get("eps"),))
+        levels = tuple(int(l) for l in cfg.get("levels", (0, 1, 2, 3)))
+        if not levels or list(levels) != sorted(set(levels)) or levels[0] < 0 or levels[-1] > 3:
+            raise ValueError("flatness levels: a non-empty ascending subset of (0, 1, 2, 3), got %r" % (cfg.get("levels"),))
+        return {"weight": weight, "k": k, "eps": eps, "levels": levels}
+
+    def set_flatness(self, weight=None, k=None, eps=None):
+        """Change the flatness term.  weight: written INTO the loss-weight vectors -- the tensors a launch list has baked in: the next
+        `step_list()` (or eager step) uses it, with no recapture.  k, eps: launch ARGUMENTS, so a captured list or graph keeps the ones
+        it was captured with: raises while one exists.  Raises on a trainer built without `flatness`."""
+        if self.flatness is None:
+            raise RuntimeError("set_flatness(): this trainer was built without flatness; build it with one (e.g. weight 0.0)")
+        fresh = self._check_flatness({"weight": self.flatness["weight"] if weight is None else weight,
+                                      "k": self.flatness["k"] if k is None else k,
+                                      "eps": self.flatness["eps"] if eps is None else eps, "levels": self.flatness["levels"]})
+        if (fresh["k"], fresh["eps"]) != (self.flatness["k"], self.flatness["eps"]) and (
+                getattr(self, "_list", None) is not None or getattr(self, "_graphs", None)):
+            raise RuntimeError("set_flatness(k=..., eps=...): k and eps are arguments of the captured launches; capture again with the new ones")
+        self.flatness = fresh
+        with torch.no_grad():
+            for w in self._lw.values():
+                w[self._flat_at:self._flat_at + 1].fill_(fresh["weight"])
+
+    def flatness_state(self):
+        """{weight, k, eps, levels, floors, per_level, total, degenerate}: the parameters, the floor of each of the four levels for the
+        last iteration's cloud sizes (None before the first), the last iteration's unweighted value per level (0 for a level that is
+        not in `levels`) with their sum, and its number of degenerate points over the levels.  Synchronises the device."""
+        if self.flatness is None:
+            raise RuntimeError("flatness_state(): this trainer was built without flatness")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        per = [float(v) for v in self._flat_buf.cpu()]
+        return dict(self.flatness, floors=self.__dict__.get("_flat_floors"), per_level=per, total=float(sum(per)),
+                    degenerate=int(sum(int(d.sum()) for d in self._flat_deg.values())))
+
+    def _flatness_floors(self, sizes):
+        """The four levels' floors for these point counts (cached: the same sizes every iteration)."""
+        key = (self.flatness["eps"],) + tuple(int(n) for n in sizes)
+        if self.__dict__.get("_flat_key") != key:
+            self._flat_key, self._flat_floors = key, losses.flatness_floors(key[0], key[1:])
+        return self._flat_floors
+
+    def _flatness_level(self, level, cloud, floors):
+        """Level l's term (0-dim, differentiable), or None where the level is off; the degenerate counts go to the level's own buffer."""
+        if level not in self.flatness["levels"]:
+            return None
+        deg = self._flat_deg.get(level)
+        if deg is None or deg.shape[0] != cloud.shape[0]:
+            deg = self._flat_deg[level] = torch.zeros(cloud.shape[0], dtype=torch.int32, device=self.device)
+        return losses.flatness(cloud, self.flatness["k"], eps=floors[level], degenerate=deg)
+
+    def _flatness_total(self, flat):
+        """As `_repulsion_total`: the four per-level values -> their unweighted sum, kept in the 4-float buffer for `flatness_state`."""
+        vals = torch.stack([f if f is not None else self._flat_zero for f in flat])
+        torch.add(vals.detach(), self._flat_zero, out=self._flat_buf)
         return vals.sum()
 
     def set_lr_schedule(self, knots):
@@ -475,6 +558,9 @@ class PDGNTrainer:
             base = [1.2, 1.2, 1.2, 1.0, 0.1 * ws]
             if self.repulsion is not None:                       # one more entry of the weighted sum: a batch mean, no world-size factor
                 base.append(self.repulsion["weight"])
+            if self.flatness is not None:                        # and one more: a batch mean as well
+                self._flat_at = len(base)
+                base.append(self.flatness["weight"])
             w = self._lw[ws] = torch.tensor(base, dtype=torch.float32, device=self.device)
         return w
 
@@ -581,6 +667,11 @@ class PDGNTrainer:
                 rep = self._repulsion_total([losses.repulsion(gen[l], radii[l]) if l in self.repulsion["levels"] else None for l in range(4)])
                 adv = adv + self._lw[1][5] * rep                 # (the weight as the device holds it: set_repulsion reaches a captured graph)
                 st["out"]["repulsion_loss"] = rep.detach()
+            if self.flatness is not None:
+                floors = self._flatness_floors([c.shape[2] for c in gen])
+                flat = self._flatness_total([self._flatness_level(l, gen[l], floors) for l in range(4)])
+                adv = adv + self._lw[1][self._flat_at] * flat    # (the weight as the device holds it, as above)
+                st["out"]["flatness_loss"] = flat.detach()
             lossG = adv + 0.1 * similar
             # MSE is a batch MEAN, the shape loss a batch SUM (chamfer_loss.py:16-20): to reproduce
             # one reference step at the global batch, scale the sum term by world_size before the
@@ -740,6 +831,8 @@ class PDGNTrainer:
         rep, rep_on = [None] * 4, self.repulsion is not None
         # (the levels arrive one at a time; the generator's clouds have the real batch's point counts -- D_k sees both)
         radii = self._repulsion_radii([r.shape[2] for r in st["reals"]]) if rep_on else None
+        flat, flat_on = [None] * 4, self.flatness is not None
+        floors = self._flatness_floors([r.shape[2] for r in st["reals"]]) if flat_on else None
 
         def repel(level, cloud):                            # level l's all-pairs launch, on the local-pair stream (which has waited for `main`)
             if level in self.repulsion["levels"]:
@@ -753,13 +846,15 @@ class PDGNTrainer:
 
         def tail(level, cloud):
             gen_so_far.append(cloud)
-            if level >= 1 or rep_on:
+            if level >= 1 or rep_on or flat_on:
                 self._side_lp.wait_stream(main)
                 with torch.cuda.stream(self._side_lp):
                     if level >= 1:
                         terms.update(self.similar_terms(gen_so_far, [(a, level) for a in range(level)], own))
                     if rep_on:
                         repel(level, cloud)
+                    if flat_on:                             # level l's neighbour search and flatness launches, on the same stream
+                        flat[level] = self._flatness_level(level, cloud, floors)
             d_gen(level, cloud)
 
         gen = self.G(self._z(st, "z2"), stage_hook=tail if early else None)
@@ -771,6 +866,9 @@ class PDGNTrainer:
                 if rep_on:
                     for level in range(4):
                         repel(level, gen[level])
+                if flat_on:
+                    for level in range(4):
+                        flat[level] = self._flatness_level(level, gen[level], floors)
             for i, side in enumerate(self._side):
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
@@ -786,7 +884,10 @@ class PDGNTrainer:
         if rep_on:                                          # one more entry of the weighted sum; its weight is the vector's last element
             repulsion = self._repulsion_total(rep)
             st["out"]["repulsion_loss"] = repulsion.detach()
-        terms = torch.stack(g_loss + [similar] + ([repulsion] if rep_on else []))
+        if flat_on:                                         # and one more, behind it
+            flatness = self._flatness_total(flat)
+            st["out"]["flatness_loss"] = flatness.detach()
+        terms = torch.stack(g_loss + [similar] + ([repulsion] if rep_on else []) + ([flatness] if flat_on else []))
         lossG = (terms * self._loss_weights(1)).sum()
         (lossG if ws == 1 else (terms * self._loss_weights(ws)).sum()).backward()
         mark("backward")
@@ -966,7 +1067,7 @@ class PDGNTrainer:
     LOG_FORMAT, LOSS_KEYS = _fit.LOG_FORMAT, _fit.LOSS_KEYS
 
     def fit(self, feeder, epochs, start_epoch=1, snapshot=20, checkpoint_dir=None, category="chair", issue="list", log=None,
-            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None, repulsion_log=None):
+            on_epoch=None, guard_max_skips=50, grad_norms=None, lr_log=None, aug_log=None, repulsion_log=None, flatness_log=None):
         """PDGNet_v2.train (:157-269): epochs start_epoch .. epochs over `feeder` (data.BatchFeeder: `batches_per_epoch` and
         `fill(epoch, i, reals, z1, z2)`), a checkpoint every `snapshot` epochs and after the last one (:266-268; rank 0 writes
         them), one log line per iteration in the reference's format (:259).  Returns the last epoch.  Resuming: pass what
@@ -1001,9 +1102,12 @@ class PDGNTrainer:
 
         With the repulsion term `repulsion_log` (a path; default: repulsion.csv beside a log given as a path, else
         none) gets one row per EPOCH -- epoch, weight, radius, total, level1 .. level4: `repulsion_state()` after the epoch's last
-        iteration, one synchronise per epoch.  Rank 0 only; without the term, no file and no synchronise."""
+        iteration, one synchronise per epoch.  Rank 0 only; without the term, no file and no synchronise.
+
+        With the flatness term `flatness_log` (default: flatness.csv beside a log given as a path) gets one row per
+        EPOCH in the same way -- epoch, weight, k, eps, total, level1 .. level4, degenerate: `flatness_state()`."""
         return _fit.fit(self, feeder, epochs, start_epoch, snapshot, checkpoint_dir, category, issue, log, on_epoch, guard_max_skips,
-                        grad_norms, lr_log, aug_log, repulsion_log)
+                        grad_norms, lr_log, aug_log, repulsion_log, flatness_log)
 
     def _sync(self):
         torch.cuda.current_stream(self.device).synchronize()
