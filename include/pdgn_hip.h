@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 49
+#define PDGN_ABI_VERSION 50
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1257,6 +1257,22 @@ int pdgn_mesh_visibility_bias_cover(void);
 int pdgn_mesh_visibility_bias_small(int R);
 int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off, const float *frame,
                          const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ face orientation from visibility (csrc/visible.hip)
+ * Which SIDE of every face the views see: pdgn_mesh_visibility's depth pass, then per (face, view) the count of the face's covered pixel
+ * centres that pass the depth test, added to the face's front or back column by the sign of its snapped 2D area in the stored vertex
+ * order.  A face with more back votes than front votes is stored the wrong way round (Takayama et al. 2014).  The second header block of
+ * csrc/visible.hip is the normative definition; tests/face_orient_mirror.py spells it in numpy.  No reference counterpart.
+ * The arguments are pdgn_mesh_visibility's, with the same ranges, and
+ *   votes  (F,2) uint32, cleared here on `stream`: votes[f][0] the centres (or the one fallback test) that passed in views that see the
+ *          front of f -- the side its stored vertices run counter-clockwise from --, votes[f][1] those in views that see its back.  A
+ *          dead face, and a face edge-on in a view, have no vote.  At most NV R^2 per word.
+ *   mask   (F) uint32 or NULL: where given, cleared and then set to exactly the bits pdgn_mesh_visibility gives on the same arguments
+ * A pure function of the arguments, bit for bit: integer minima, integer sums and ORs only.  One or two memsets and one launch of S NV
+ * workgroups on `stream`, after the same read-back of the radii.  PDGN_ERR_INVALID, with nothing launched and nothing written: as
+ * pdgn_mesh_visibility, with votes in the place of mask as the pointer that must not be null. */
+int pdgn_mesh_face_votes(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off, const float *frame,
+                         const float *views, int NV, int R, uint32_t *mask, uint32_t *votes, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ repulsion regulariser and spacing statistics (csrc/repulsion.hip)
  * Every point of a cloud against every other point of the SAME cloud, in one launch: the repulsion term of the point-upsampling

@@ -93,9 +93,11 @@ __device__ __forceinline__ bool raster_scan(const RasterFace &t, int start, int 
 // every thread of the workgroup calls, and the last thing the call does is a barrier.  load(f, t) gathers and sets up face f and says
 // whether it is alive; visit is raster_scan's; done(f, t, covered, stopped) runs once per live face after its scan, in one lane, with
 // whether any of its centres was covered and whether any visit stopped.  The counter of the last turn is left holding its count: a caller
-// that sweeps again clears both first.
-template <int SUB, class Index, class Load, class Visit, class Done>
-__device__ __forceinline__ void raster_sweep(Index f0, Index f1, Index stride, int *s_list, int *s_cnt, Load load, Visit visit, Done done) {
+// that sweeps again clears both first.  fold() is the one hook that every lane of a wave reaches after it has scanned its share of a large
+// face, before lane 0 calls done: a caller whose visit keeps a per-lane partial (a count) folds the 64 of them there; a lane-per-face
+// scan has nothing to fold and does not call it.
+template <int SUB, class Index, class Load, class Visit, class Done, class Fold>
+__device__ __forceinline__ void raster_sweep(Index f0, Index f1, Index stride, int *s_list, int *s_cnt, Load load, Visit visit, Done done, Fold fold) {
     const int tid = threadIdx.x, lane = tid & (PDGN_WAVE - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int par = 0;
     for (Index base = f0; base < f1; base += stride, par ^= 1) {
@@ -122,8 +124,22 @@ __device__ __forceinline__ void raster_sweep(Index f0, Index f1, Index stride, i
             bool covered = false;
             const bool stopped = raster_scan<SUB>(t, lane, PDGN_WAVE, covered, visit);
             const bool any_stopped = __any(stopped), any_covered = __any(covered);
+            fold();
             if (lane == 0) done(g, t, any_covered, any_stopped);
         }
         __syncthreads();
     }
+}
+
+// The sweep of a caller without per-lane partials.
+template <int SUB, class Index, class Load, class Visit, class Done>
+__device__ __forceinline__ void raster_sweep(Index f0, Index f1, Index stride, int *s_list, int *s_cnt, Load load, Visit visit, Done done) {
+    raster_sweep<SUB>(f0, f1, stride, s_list, s_cnt, load, visit, done, [] {});
+}
+
+// The sum of one unsigned per lane over the 64 lanes of a wave, in every lane (all 64 call).
+__device__ __forceinline__ unsigned raster_wave_sum(unsigned v) {
+#pragma unroll
+    for (int d = PDGN_WAVE / 2; d > 0; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, PDGN_WAVE);
+    return v;
 }

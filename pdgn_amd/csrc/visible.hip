@@ -33,6 +33,24 @@
 // CU; 144 KB at R = 192: one), beside the sweep's static 1 KB.  The two passes are the same sweep of the shape's faces (csrc/raster.h,
 // THE SWEEP: a lane per small face, a wave per large one, the exact division) with atomicMin (ds_min_u32) in the first and a compare in
 // the second.
+//
+// pdgn_mesh_face_votes: WHICH SIDE of a face the views see (tests/face_orient_mirror.py spells it in numpy).  A face
+// seen mostly from its back is stored the wrong way round (Takayama et al. 2014, orientation of facets by ray casting).
+// THE DEFINITION (normative).  Snap, Dead and Pass 1 are the ones above, word for word: the same depth buffer.
+//   Side.   For a live face in view v, S = edge(P0, P1, P2) on the snapped integers in the STORED vertex order, before Pass 1's swap.
+//           S < 0: the view sees the FRONT, the side from which the stored vertices run counter-clockwise, the side the normal e1 x e2
+//           points to (the view looks along +e_z of a right-handed basis, so such a face has e_z . n < 0 and a negative edge function).
+//           S > 0: the view sees the BACK.  S = 0: the face is edge-on in this view and has no vote here.
+//   Pass 2. After one barrier.  A face that covers centres counts n = the number of ALL its covered centres with Zp <= buf +
+//           PDGN_VISIBLE_BIAS_COVER (no early stop).  A face with S != 0 that covers none counts n = 1 when it passes the fallback test
+//           above, else 0.  votes[f][S > 0] += n: column 0 the front, column 1 the back.
+//   Mask.   Where mask is given it receives pdgn_mesh_visibility's bits exactly: bit v when n > 0, or when the fallback passes (S = 0
+//           included).
+// Everything the result depends on is an integer minimum, an integer sum or an OR: two runs agree bit for bit and a permutation of a
+// shape's faces permutes its rows.  A count is at most NV R^2 < 2^21: uint32 holds it.
+// THE KERNEL is the one above with another second pass (vis_vote_pass): the per-lane counts of a large face are summed over the wave in
+// the sweep's fold hook, and one lane per (face, view) adds the face's n to its word with one integer atomicAdd (global_atomic_add_u32,
+// no return); the LDS buffer is only read in this pass.  Same grid, same LDS, same occupancy as the visibility kernel.
 #include "raster.h"
 
 #define VIS_THREADS RASTER_THREADS
@@ -42,7 +60,7 @@ struct VisArgs {
     const float *verts;
     const int32_t *faces, *face_off;
     const float *frame, *views;
-    uint32_t *mask;
+    uint32_t *mask, *votes;                                      // votes: pdgn_mesh_face_votes' (F,2); there mask may be null
     int V, F, NV, R, bias_small;
 };
 
@@ -68,8 +86,9 @@ __device__ __forceinline__ void vis_snap(const VisView &w, const float *p, int &
     Z = vis_quant(vis_dot(w.ez, d0, d1, d2), w.rho, 1048576.f);
 }
 
-// Gather and snap face f.  False: the face is dead (zero area in 3D, or an index outside the vertices).
-__device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int f, RasterFace &t) {
+// Gather and snap face f.  False: the face is dead (zero area in 3D, or an index outside the vertices).  side: the sign of S =
+// edge(P0, P1, P2) in the stored vertex order, before the set-up's swap (-1: the view sees the front, +1: the back, 0: edge-on).
+__device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int f, RasterFace &t, int &side) {
     const int i0 = a.faces[3 * (size_t)f], i1 = a.faces[3 * (size_t)f + 1], i2 = a.faces[3 * (size_t)f + 2];
     if ((unsigned)i0 >= (unsigned)a.V || (unsigned)i1 >= (unsigned)a.V || (unsigned)i2 >= (unsigned)a.V) return false;
     const float *q0 = a.verts + 3 * (size_t)i0, *q1 = a.verts + 3 * (size_t)i1, *q2 = a.verts + 3 * (size_t)i2;
@@ -85,6 +104,8 @@ __device__ __forceinline__ bool vis_load(const VisArgs &a, const VisView &w, int
     vis_snap(w, p0, t.x0, t.y0, t.z0);
     vis_snap(w, p1, t.x1, t.y1, t.z1);
     vis_snap(w, p2, t.x2, t.y2, t.z2);
+    const long long stored = raster_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+    side = (stored > 0) - (stored < 0);
     raster_setup<8>(t, 0, w.R - 1);
     return true;
 }
@@ -101,8 +122,9 @@ extern __shared__ unsigned vis_buf[];
 template <bool TEST>
 __device__ __forceinline__ void vis_pass(const VisArgs &a, const VisView &w, int f0, int f1, unsigned bit, int *s_list, int *s_cnt) {
     const int R = w.R;
+    int side;
     raster_sweep<8>(
-        f0, f1, VIS_THREADS, s_list, s_cnt, [&](int f, RasterFace &t) { return vis_load(a, w, f, t); },
+        f0, f1, VIS_THREADS, s_list, s_cnt, [&](int f, RasterFace &t) { return vis_load(a, w, f, t, side); },
         [&](int px, int py, long long zp) {
             if (TEST) return zp <= (long long)vis_buf[py * R + px] + PDGN_VISIBLE_BIAS_COVER;
             atomicMin(vis_buf + py * R + px, (unsigned)zp);
@@ -115,6 +137,36 @@ __device__ __forceinline__ void vis_pass(const VisArgs &a, const VisView &w, int
     __syncthreads();
 }
 
+// Pass 2 of pdgn_mesh_face_votes over the faces [f0, f1): every covered centre that passes the depth test is counted, in the lane that
+// looked at it (no visit stops the scan); the 64 partials of a large face are summed in the sweep's fold, so that `done` -- one lane per
+// face on either path -- holds the face's n and adds it to the column its stored order names.  Integer adds to distinct words per face:
+// the NV workgroups of a shape meet on a face's two words in any order, with one result.
+__device__ __forceinline__ void vis_vote_pass(const VisArgs &a, const VisView &w, int f0, int f1, unsigned bit, int *s_list, int *s_cnt) {
+    const int R = w.R;
+    int side;
+    unsigned n;
+    raster_sweep<8>(
+        f0, f1, VIS_THREADS, s_list, s_cnt,
+        [&](int f, RasterFace &t) {
+            n = 0;
+            return vis_load(a, w, f, t, side);
+        },
+        [&](int px, int py, long long zp) {
+            n += zp <= (long long)vis_buf[py * R + px] + PDGN_VISIBLE_BIAS_COVER;
+            return false;
+        },
+        [&](int f, const RasterFace &t, bool covered, bool) {
+            const bool fell = !covered && vis_fallback(t, vis_buf, R, a.bias_small);
+            const unsigned count = covered ? n : (unsigned)(fell && side != 0);
+            if (count) atomicAdd(a.votes + 2 * (size_t)f + (side > 0), count);
+            if (a.mask && (count || fell)) atomicOr(a.mask + f, bit);
+        },
+        [&] { n = raster_wave_sum(n); });
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+template <bool VOTES>
 __global__ __launch_bounds__(VIS_THREADS) void visible_kernel(VisArgs a) {
     __shared__ int s_list[VIS_THREADS];
     __shared__ int s_cnt[2];
@@ -130,7 +182,8 @@ __global__ __launch_bounds__(VIS_THREADS) void visible_kernel(VisArgs a) {
     if (tid < 2) s_cnt[tid] = 0;
     __syncthreads();
     vis_pass<false>(a, w, f0, f1, 0u, s_list, s_cnt);            // (its last sweep ends with the barrier between the passes)
-    vis_pass<true>(a, w, f0, f1, 1u << view, s_list, s_cnt);
+    if (VOTES) vis_vote_pass(a, w, f0, f1, 1u << view, s_list, s_cnt);
+    else vis_pass<true>(a, w, f0, f1, 1u << view, s_list, s_cnt);
 }
 
 extern "C" int pdgn_mesh_visibility_bias_cover(void) { return PDGN_VISIBLE_BIAS_COVER; }
@@ -140,14 +193,17 @@ extern "C" int pdgn_mesh_visibility_bias_small(int R) {
     return (3 << 20) / R;
 }
 
-extern "C" int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off,
-                                    const float *frame, const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream) {
+// Both entry points: the checks, the memsets and the launch.  votes null: pdgn_mesh_visibility (mask required); else pdgn_mesh_face_votes
+// (mask optional).
+template <bool VOTES>
+static int vis_launch(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off, const float *frame,
+                      const float *views, int NV, int R, uint32_t *mask, uint32_t *votes, pdgn_stream_t stream) {
     // host-side checks: nothing is launched and nothing written before all of them have passed
     if (S < 1 || V < 1 || F < 1 || NV < 1 || NV > PDGN_VISIBLE_MAX_VIEWS || R < PDGN_VISIBLE_MIN_RES || R > PDGN_VISIBLE_MAX_RES)
         return PDGN_ERR_INVALID;
     if (3LL * V > 0x7fffffffLL || 3LL * F > 0x7fffffffLL || (long long)S * NV > 0x7fffffffLL) return PDGN_ERR_INVALID;
-    if (!verts || !faces || !face_off || !frame || !views || !mask) return PDGN_ERR_INVALID;
-    if (((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)face_off | (uintptr_t)frame | (uintptr_t)views | (uintptr_t)mask) & 3)
+    if (!verts || !faces || !face_off || !frame || !views || (VOTES ? !votes : !mask)) return PDGN_ERR_INVALID;
+    if (((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)face_off | (uintptr_t)frame | (uintptr_t)views | (uintptr_t)mask | (uintptr_t)votes) & 3)
         return PDGN_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     {   // the radii, read back once (16 S bytes; the stream is waited for): a frame the snap would divide by is refused here
@@ -162,15 +218,27 @@ extern "C" int pdgn_mesh_visibility(int S, int V, int F, const float *verts, con
         if (!ok) return PDGN_ERR_INVALID;
     }
     VisArgs a;
-    a.verts = verts, a.faces = faces, a.face_off = face_off, a.frame = frame, a.views = views, a.mask = mask;
+    a.verts = verts, a.faces = faces, a.face_off = face_off, a.frame = frame, a.views = views, a.mask = mask, a.votes = votes;
     a.V = V, a.F = F, a.NV = NV, a.R = R, a.bias_small = (3 << 20) / R;
     const size_t lds = (size_t)R * R * 4;
     if (lds > 48 * 1024) {                                       // (beside it the kernel's static 1 KB: the attribute is the dynamic part alone)
-        hipError_t e = hipFuncSetAttribute((const void *)visible_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)visible_kernel<VOTES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipError_t e = hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)F, s);
+    hipError_t e = mask ? hipMemsetAsync(mask, 0, sizeof(uint32_t) * (size_t)F, s) : hipSuccess;
+    if (e == hipSuccess && VOTES) e = hipMemsetAsync(votes, 0, sizeof(uint32_t) * 2 * (size_t)F, s);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(visible_kernel, dim3(S * NV), dim3(VIS_THREADS), lds, s, a);
+    hipLaunchKernelGGL(visible_kernel<VOTES>, dim3(S * NV), dim3(VIS_THREADS), lds, s, a);
     return pdgn_launch_status();
+}
+
+extern "C" int pdgn_mesh_visibility(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off,
+                                    const float *frame, const float *views, int NV, int R, uint32_t *mask, pdgn_stream_t stream) {
+    return vis_launch<false>(S, V, F, verts, faces, face_off, frame, views, NV, R, mask, nullptr, stream);
+}
+
+extern "C" int pdgn_mesh_face_votes(int S, int V, int F, const float *verts, const int32_t *faces, const int32_t *face_off,
+                                    const float *frame, const float *views, int NV, int R, uint32_t *mask, uint32_t *votes,
+                                    pdgn_stream_t stream) {
+    return vis_launch<true>(S, V, F, verts, faces, face_off, frame, views, NV, R, mask, votes, stream);
 }

@@ -10,6 +10,10 @@ Visible-surface sampling: `face_visibility` asks the devi
 (csrc/visible.hip: pdgn_mesh_visibility); a `MeshSet` built with `visible=mask` gives the others weight zero wherever the area is used,
 so they are never drawn.  `pack --visible` stores the masks beside the meshes.
 
+Face orientation: `face_orientation` asks the same depth pass which SIDE of every face the views see
+(pdgn_mesh_face_votes); a face seen mostly from its back is stored the wrong way round.  A `MeshSet` carries the answer as `flip`,
+`MeshSet.oriented()` applies it, and the signed quantities below then mean something on raw CAD meshes.  `pack --orient` stores the flips.
+
 Distances and sides (DESIGN.md sections 7t and 7u): `point_to_mesh` is the closest point of a shape's faces (csrc/meshdist.hip),
 `winding_number` the generalized winding number about them (csrc/winding.hip) -- 1 inside a closed, consistently oriented shape, 0
 outside -- and on the two `signed_distance`, `occupancy_grid` and `winding_report`; the commands `distance`, `occupancy` and `check`.
@@ -161,10 +165,9 @@ def shape_frames(verts, faces, face_off):
     return out.astype(np.float32)
 
 
-def face_visibility(verts, faces, face_off, views=26, resolution=128, device=None):
-    """mask (F) uint32 numpy: bit v set where face f passes the depth test of view v (pdgn_mesh_visibility; the definition is the header
-    block of csrc/visible.hip).  views: 6 / 14 / 26 (`default_views`), an (NV,3) array of directions to look from, or an (NV,3,3) table
-    of bases; raw or normalised geometry alike (the frame of `shape_frames` makes the result the same up to the snap)."""
+def _view_arguments(verts, faces, face_off, views, device, what):
+    """The front of `face_visibility` and `face_orientation`: the checks, the view table and the frames, and everything on the device
+    -> (S, V, F, NV, [verts, faces, face_off, frame, views] device tensors)."""
     import torch
     from . import _lib
     verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
@@ -172,23 +175,68 @@ def face_visibility(verts, faces, face_off, views=26, resolution=128, device=Non
     face_off = np.ascontiguousarray(face_off, dtype=np.int32).reshape(-1)
     S, V, F = face_off.shape[0] - 1, verts.shape[0], faces.shape[0]
     if S < 1 or face_off[0] != 0 or face_off[-1] != F or np.any(np.diff(face_off) < 0):
-        raise ValueError("face_visibility: face_off must ascend from 0 to the number of faces over at least one shape")
+        raise ValueError("%s: face_off must ascend from 0 to the number of faces over at least one shape" % what)
     if F and (faces.min() < 0 or faces.max() >= V):
-        raise ValueError("face_visibility: a face names a vertex outside the %d vertices" % V)
+        raise ValueError("%s: a face names a vertex outside the %d vertices" % (what, V))
     table = default_views(views) if np.ndim(views) == 0 else np.asarray(views)
     table = view_bases(table) if table.ndim == 2 else np.ascontiguousarray(table, dtype=np.float32)
     if table.ndim != 3 or table.shape[1:] != (3, 3):
-        raise ValueError("face_visibility: views are a count, (NV,3) directions or (NV,3,3) bases, got %s" % (table.shape,))
+        raise ValueError("%s: views are a count, (NV,3) directions or (NV,3,3) bases, got %s" % (what, table.shape,))
     frame = shape_frames(verts, faces, face_off)
     dev = torch.device("cuda" if device is None else device)
-    t = lambda a: torch.from_numpy(a).to(dev)
-    d_verts, d_faces, d_off, d_frame, d_views = t(verts), t(faces), t(face_off), t(frame), t(table)
-    _lib.require(d_verts, "the vertices", torch.float32, 2)
-    mask = torch.zeros(F, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().pdgn_mesh_visibility(S, V, F, _lib.ptr(d_verts), _lib.ptr(d_faces), _lib.ptr(d_off), _lib.ptr(d_frame),
-                                               _lib.ptr(d_views), int(table.shape[0]), int(resolution), _lib.ptr(mask),
-                                               _lib.stream_of(d_verts)), "pdgn_mesh_visibility")
+    tensors = [torch.from_numpy(a).to(dev) for a in (verts, faces, face_off, frame, table)]
+    _lib.require(tensors[0], "the vertices", torch.float32, 2)
+    return S, V, F, int(table.shape[0]), tensors
+
+
+def face_visibility(verts, faces, face_off, views=26, resolution=128, device=None):
+    """mask (F) uint32 numpy: bit v set where face f passes the depth test of view v (pdgn_mesh_visibility; the definition is the header
+    block of csrc/visible.hip).  views: 6 / 14 / 26 (`default_views`), an (NV,3) array of directions to look from, or an (NV,3,3) table
+    of bases; raw or normalised geometry alike (the frame of `shape_frames` makes the result the same up to the snap)."""
+    import torch
+    from . import _lib
+    S, V, F, NV, d = _view_arguments(verts, faces, face_off, views, device, "face_visibility")
+    mask = torch.zeros(F, dtype=torch.int32, device=d[0].device)
+    _lib.check(_lib.lib().pdgn_mesh_visibility(S, V, F, *[_lib.ptr(x) for x in d], NV, int(resolution), _lib.ptr(mask),
+                                               _lib.stream_of(d[0])), "pdgn_mesh_visibility")
     return mask.cpu().numpy().view(np.uint32)
+
+
+# ---------------------------------------------------------------------------- face orientation from visibility (csrc/visible.hip, DESIGN.md section 7y)
+def orientation_from_votes(front, back, face_off=None):
+    """The decision rule on the votes of pdgn_mesh_face_votes, front and back (F) counts: {"front", "back" (F) uint32, "flip" (F) bool:
+    back > front -- a tie, a dead face and an unseen face keep their order --, "undecided" (F): front == back, "two_sided" (F): both sides
+    were seen and the rarer one at least a quarter as often as the other (min > 0 and 4 min >= max: a sheet, an open table top; no flip
+    gives it a sign)[, with face_off (S+1): "flipped", "undecided_count", "two_sided_count" (S) int64 per shape]}."""
+    front, back = (np.ascontiguousarray(np.asarray(x).astype(np.uint32, copy=False)).reshape(-1) for x in (front, back))
+    if front.shape != back.shape:
+        raise ValueError("orientation_from_votes: %d front and %d back counts" % (front.shape[0], back.shape[0]))
+    lo, hi = np.minimum(front, back).astype(np.int64), np.maximum(front, back).astype(np.int64)
+    out = {"front": front, "back": back, "flip": back > front, "undecided": front == back, "two_sided": (lo > 0) & (4 * lo >= hi)}
+    if face_off is not None:
+        off = np.asarray(face_off, dtype=np.int64).reshape(-1)
+        per = lambda flag: np.diff(np.concatenate([[0], np.cumsum(flag.astype(np.int64))])[off])     # (an empty shape counts 0)
+        out.update(flipped=per(out["flip"]), undecided_count=per(out["undecided"]), two_sided_count=per(out["two_sided"]))
+    return out
+
+
+def face_orientation(verts, faces, face_off, views=26, resolution=128, device=None, return_mask=False):
+    """Which way round every face is stored, from which of its sides a ring of views sees (pdgn_mesh_face_votes; the definition is the
+    second header block of csrc/visible.hip; Takayama et al. 2014): `orientation_from_votes` of the device's votes, with the per-shape
+    counts[, and "mask" (F) uint32, exactly `face_visibility`'s masks for the same arguments, from the same depth pass].  The arguments
+    are `face_visibility`'s."""
+    import torch
+    from . import _lib
+    S, V, F, NV, d = _view_arguments(verts, faces, face_off, views, device, "face_orientation")
+    votes = torch.zeros(F, 2, dtype=torch.int32, device=d[0].device)
+    mask = torch.zeros(F, dtype=torch.int32, device=d[0].device) if return_mask else None
+    _lib.check(_lib.lib().pdgn_mesh_face_votes(S, V, F, *[_lib.ptr(x) for x in d], NV, int(resolution), _lib.ptr(mask), _lib.ptr(votes),
+                                               _lib.stream_of(d[0])), "pdgn_mesh_face_votes")
+    votes = votes.cpu().numpy().view(np.uint32)
+    out = orientation_from_votes(votes[:, 0], votes[:, 1], d[2].cpu().numpy())
+    if return_mask:
+        out["mask"] = mask.cpu().numpy().view(np.uint32)
+    return out
 
 
 class MeshSet:
@@ -197,18 +245,20 @@ class MeshSet:
     to the shape); shift (S,3) / scale (S) fp32: the normalisation that was applied ((raw - shift) / scale).  Built by `from_meshes` /
     `from_arrays`, which guarantee what the kernels trust: every shape owns a face of positive area, every index is inside the vertex
     array, every alias inside its shape.  visible (F) or None: the view masks the set was built with -- a face whose mask is 0 has
-    weight zero in the table (threshold 0, nobody's alias: never drawn) and in the normalisation."""
+    weight zero in the table (threshold 0, nobody's alias: never drawn) and in the normalisation.  flip (F) bool or None: the faces
+    `face_orientation` found stored the wrong way round; carried only -- the geometry stays as given until `oriented()` applies it."""
 
-    def __init__(self, verts, faces, face_off, alias, shift, scale, normalize=None, visible=None):
+    def __init__(self, verts, faces, face_off, alias, shift, scale, normalize=None, visible=None, flip=None):
         self.verts, self.faces, self.face_off, self.alias, self.shift, self.scale = verts, faces, face_off, alias, shift, scale
         self.normalize = normalize
         self.visible = visible                                   # (F) int32, the bits of the uint32 masks of `face_visibility`, or None
+        self.flip = flip                                         # (F) bool: `face_orientation`'s "flip", or None
         self.S, self.V, self.F = int(face_off.shape[0]) - 1, int(verts.shape[0]), int(faces.shape[0])
 
     # ------------------------------------------------------------------ construction (host, numpy)
     @classmethod
-    def from_meshes(cls, meshes, normalize=None, names=None, visible=None):
-        """meshes: a list of (verts (V_c,3), faces (F_c,3) indices into that shape's own vertices); visible: as `from_arrays`."""
+    def from_meshes(cls, meshes, normalize=None, names=None, visible=None, flip=None):
+        """meshes: a list of (verts (V_c,3), faces (F_c,3) indices into that shape's own vertices); visible, flip: as `from_arrays`."""
         meshes = list(meshes)
         if not meshes:
             raise ValueError("MeshSet: no shapes")
@@ -226,12 +276,13 @@ class MeshSet:
             faces.append(f.astype(np.int64) + at)
             at += v.shape[0]
             face_off.append(face_off[-1] + f.shape[0])
-        return cls.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.asarray(face_off), normalize, names, visible)
+        return cls.from_arrays(np.concatenate(verts, 0), np.concatenate(faces, 0), np.asarray(face_off), normalize, names, visible, flip)
 
     @classmethod
-    def from_arrays(cls, verts, faces, face_off, normalize=None, names=None, visible=None):
+    def from_arrays(cls, verts, faces, face_off, normalize=None, names=None, visible=None, flip=None):
         """From the concatenated form (what `pack` stores): verts (V,3), faces (F,3) GLOBAL indices, face_off (S+1).  visible: (F) masks
-        (`face_visibility`); a face whose mask is 0 counts as a face of area zero in the table, the normalisation and the vertex box."""
+        (`face_visibility`); a face whose mask is 0 counts as a face of area zero in the table, the normalisation and the vertex box.
+        flip: (F) booleans (`face_orientation`), stored with the set and nothing else: the faces keep the order they came in."""
         import torch
         if normalize not in NORMALIZE:
             raise ValueError("MeshSet: normalize %r -- meshes take None, 'shape_unit' or 'shape_bbox' (global_unit, shape_half and shape_34 "
@@ -294,6 +345,10 @@ class MeshSet:
             area = face_areas(verts, faces)                      # (a uniform scale per shape: the same table up to rounding; built from what is drawn from)
             if visible is not None:
                 area = np.where(visible != 0, area, 0.0)
+        if flip is not None:
+            flip = np.ascontiguousarray(np.asarray(flip).astype(bool, copy=False)).reshape(-1)
+            if flip.shape[0] != F:
+                raise ValueError("MeshSet: %d orientation flips for %d faces" % (flip.shape[0], F))
         alias = np.empty((F, 2), dtype=np.uint32)
         for c in range(S):
             a, b = face_off[c], face_off[c + 1]
@@ -301,13 +356,15 @@ class MeshSet:
         t = torch.from_numpy
         return cls(t(verts), t(faces.astype(np.int32)), t(face_off.astype(np.int32)), t(alias.view(np.int32)),
                    t(np.asarray(shift, np.float32)), t(np.asarray(scale, np.float32)), normalize,
-                   None if visible is None else t(visible.view(np.int32).copy()))
+                   None if visible is None else t(visible.view(np.int32).copy()), None if flip is None else t(flip.copy()))
 
     # ------------------------------------------------------------------ storage and placement
     _FIELDS = ("verts", "faces", "face_off", "alias", "shift", "scale")
 
     def save(self, path):
         extra = {} if self.visible is None else {"visible": self.visible.cpu().numpy()}
+        if self.flip is not None:
+            extra["flip"] = self.flip.cpu().numpy()
         np.savez(path, normalize=np.asarray("" if self.normalize is None else self.normalize),
                  **{k: getattr(self, k).cpu().numpy() for k in self._FIELDS}, **extra)
 
@@ -317,11 +374,13 @@ class MeshSet:
         with np.load(path) as f:
             mode = str(f["normalize"])
             return cls(*(torch.from_numpy(f[k]) for k in cls._FIELDS), normalize=mode or None,
-                       visible=torch.from_numpy(f["visible"]) if "visible" in f.files else None)
+                       visible=torch.from_numpy(f["visible"]) if "visible" in f.files else None,
+                       flip=torch.from_numpy(f["flip"].astype(bool, copy=False)) if "flip" in f.files else None)
 
     def to(self, device):
         return MeshSet(*(getattr(self, k).to(device).contiguous() for k in self._FIELDS), normalize=self.normalize,
-                       visible=None if self.visible is None else self.visible.to(device).contiguous())
+                       visible=None if self.visible is None else self.visible.to(device).contiguous(),
+                       flip=None if self.flip is None else self.flip.to(device).contiguous())
 
     def in_frame(self, shift, scale):
         """The same shapes with every vertex v of shape s at (v - shift[s]) / scale[s], in fp32 as data.normalize_clouds moves points:
@@ -340,8 +399,21 @@ class MeshSet:
         own = owner.clamp_min(0)
         verts = torch.where(used[:, None], (self.verts - shift[own]) / scale[own][:, None], self.verts).contiguous()
         return MeshSet(verts, self.faces, self.face_off, self.alias, self.shift + self.scale[:, None] * shift, self.scale * scale,
-                       normalize=self.normalize, visible=self.visible)
+                       normalize=self.normalize, visible=self.visible, flip=self.flip)
 
+    def oriented(self):
+        """The set with its stored flips applied: a face whose `flip` is set has its second and third vertex exchanged, so that its
+        normal points the other way (`winding_number` and everything signed read the order).  Vertices, alias table, masks, shift and
+        scale are shared -- the area of a face read backwards is the same fp64 number, so the table is the table --, flip is None, and
+        nothing prepared for the old order (`mesh_dist_records`) is carried over.  `sample()` on the result draws from the same faces in
+        the same proportions, the same face index for every point, but not the same points: the barycentric pair of a flipped face is
+        mirrored."""
+        import torch
+        if self.flip is None:
+            raise ValueError("MeshSet.oriented: the set holds no orientation flips (face_orientation computes them, pack --orient stores them)")
+        flip = self.flip.to(self.faces.device).bool()
+        faces = torch.where(flip[:, None], self.faces[:, [0, 2, 1]], self.faces).contiguous()
+        return MeshSet(self.verts, faces, self.face_off, self.alias, self.shift, self.scale, normalize=self.normalize, visible=self.visible)
     def visible_stats(self):
         """What the masks leave out: {"faces", "hidden" (S) int64, "kept" (S) the share of every shape's area that is still drawn from,
         "total_faces", "total_hidden", "total_kept" (of the summed area)}; without masks nothing is hidden."""
@@ -710,16 +782,33 @@ def read_obj_root(root, synsetids=None):
     return out
 
 
-def pack(root, out_path, visible=None):
+def _masks_and_flips(verts, faces, face_off, visible, orient):
+    """(mask or None, orientation dict or None) of `pack` and `split_meshset`, visible and orient each None or a dict of options: where
+    both are asked for with the same options, one `face_orientation` call -- one depth pass per view -- serves both."""
+    if visible is not None and orient is not None and visible == orient:
+        result = face_orientation(verts, faces, face_off, return_mask=True, **orient)
+        return result["mask"], result
+    return (None if visible is None else face_visibility(verts, faces, face_off, **visible),
+            None if orient is None else face_orientation(verts, faces, face_off, **orient))
+
+
+def pack(root, out_path, visible=None, orient=None, report=None):
     """Write the directory's meshes as one .npz with the keys "<synsetid>/<split>/{verts,faces,face_off}" (raw, un-normalised).
     visible: a dict of `face_visibility` options (views, resolution, device) -- one more array "<synsetid>/<split>/visible" per split,
-    the (F) uint32 masks, computed on the device; None: the file is what it was before the masks existed."""
+    the (F) uint32 masks, computed on the device; orient: a dict of `face_orientation` options -- "<synsetid>/<split>/flip", the (F)
+    booleans, the geometry stays as read; both None: the file is what it was before either existed.  report: a callable that gets
+    (synsetid, split, orientation dict) per split oriented."""
     arrays = {}
     for sid, splits in read_obj_root(root).items():
         for split, (v, f, off) in splits.items():
             arrays["%s/%s/verts" % (sid, split)], arrays["%s/%s/faces" % (sid, split)], arrays["%s/%s/face_off" % (sid, split)] = v, f, off
-            if visible is not None:
-                arrays["%s/%s/visible" % (sid, split)] = face_visibility(v, f, off, **visible)
+            mask, result = _masks_and_flips(v, f, off, visible, orient)
+            if mask is not None:
+                arrays["%s/%s/visible" % (sid, split)] = mask
+            if result is not None:
+                arrays["%s/%s/flip" % (sid, split)] = result["flip"]
+                if report is not None:
+                    report(sid, split, result)
     np.savez(out_path, **arrays)
     return sorted(arrays)
 
@@ -746,6 +835,17 @@ def load_packed_visible(path, synsetids=None):
     return out
 
 
+def load_packed_flip(path, synsetids=None):
+    """{synsetid: {split: (F) bool flips}} of the splits of a packed file that `pack --orient` stored flips for (empty: none)."""
+    out = {}
+    with np.load(path) as f:
+        for key in f.files:
+            sid, split, what = key.split("/")
+            if what == "flip" and (synsetids is None or sid in synsetids):
+                out.setdefault(sid, {})[split] = f[key].astype(bool, copy=False)
+    return out
+
+
 def is_mesh_root(path):
     """Whether a --data_root holds meshes: an .npz with "<synsetid>/<split>/verts" keys, or a directory with a <synsetid>/<split>/*.obj."""
     path = str(path)
@@ -763,8 +863,10 @@ def is_mesh_root(path):
 
 
 class MeshRoot(dict):
-    """The mapping `open_mesh_root` returns; `visible`: what `load_packed_visible` found beside the meshes ({} for a directory)."""
+    """The mapping `open_mesh_root` returns; `visible`, `flip`: what `load_packed_visible` and `load_packed_flip` found beside the
+    meshes ({} for a directory)."""
     visible = {}
+    flip = {}
 
 
 def open_mesh_root(path, synsetids=None):
@@ -772,6 +874,7 @@ def open_mesh_root(path, synsetids=None):
         return MeshRoot(read_obj_root(str(path), synsetids))
     root = MeshRoot(load_packed(path, synsetids))
     root.visible = load_packed_visible(path, synsetids)
+    root.flip = load_packed_flip(path, synsetids)
     return root
 
 
@@ -782,10 +885,19 @@ def has_stored_visible(root, split):
     return bool(sids) and all(split in stored.get(sid, {}) for sid in sids)
 
 
-def split_meshset(root, split, normalize=None, visible=None):
+def has_stored_flip(root, split):
+    """Whether every category of an opened root that has the split has stored orientation flips for it."""
+    stored = getattr(root, "flip", {})
+    sids = [sid for sid in sorted(root) if split in root[sid]]
+    return bool(sids) and all(split in stored.get(sid, {}) for sid in sids)
+
+
+def split_meshset(root, split, normalize=None, visible=None, orient=None):
     """One MeshSet of a split over every category of an opened root (`open_mesh_root`, or the path of one), categories in sorted order.
     visible: None (every face is drawn from), a dict of `face_visibility` options (views, resolution, device: the masks are computed
-    now) or "stored" (the masks `pack --visible` wrote; an error where the data holds none)."""
+    now) or "stored" (the masks `pack --visible` wrote; an error where the data holds none).  orient: the same three for the set's
+    `flip` -- None, a dict of `face_orientation` options or "stored" (what `pack --orient` wrote); two equal dicts share one device pass.
+    The flips are carried, not applied: `.oriented()` applies them."""
     if isinstance(root, (str, os.PathLike)):
         root = open_mesh_root(root)
     parts = [root[sid][split] for sid in sorted(root) if split in root[sid]]
@@ -793,6 +905,11 @@ def split_meshset(root, split, normalize=None, visible=None):
         raise ValueError("the mesh data has no %r split" % split)
     if visible is not None and not isinstance(visible, dict) and visible != "stored":
         raise ValueError("split_meshset: visible is None, a dict of face_visibility options or 'stored', got %r" % (visible,))
+    if orient is not None and not isinstance(orient, dict) and orient != "stored":
+        raise ValueError("split_meshset: orient is None, a dict of face_orientation options or 'stored', got %r" % (orient,))
+    if orient == "stored" and not has_stored_flip(root, split):
+        raise ValueError("orient='stored': the mesh data holds no orientation flips for its %r split (python -m pdgn_amd.meshes pack DIR "
+                         "OUT.npz --orient writes them)" % split)
     if visible == "stored" and not has_stored_visible(root, split):
         raise ValueError("visible='stored': the mesh data holds no visibility masks for its %r split (python -m pdgn_amd.meshes pack DIR "
                          "OUT.npz --visible writes them)" % split)
@@ -803,20 +920,24 @@ def split_meshset(root, split, normalize=None, visible=None):
         face_off.append(off[1:].astype(np.int64) + fat)
         at, fat = at + v.shape[0], fat + int(off[-1])
     verts, faces, face_off = np.concatenate(verts, 0), np.concatenate(faces, 0), np.concatenate(face_off, 0)
-    mask = None
+    mask, result = _masks_and_flips(verts, faces, face_off, visible if isinstance(visible, dict) else None,
+                                    orient if isinstance(orient, dict) else None)
+    flip = None if result is None else result["flip"]
     if visible == "stored":
         mask = np.concatenate([root.visible[sid][split] for sid in sorted(root) if split in root[sid]], 0)
-    elif visible is not None:
-        mask = face_visibility(verts, faces, face_off, **visible)
-    return MeshSet.from_arrays(verts, faces, face_off, normalize, visible=mask)
+    if orient == "stored":
+        flip = np.concatenate([root.flip[sid][split] for sid in sorted(root) if split in root[sid]], 0)
+    return MeshSet.from_arrays(verts, faces, face_off, normalize, visible=mask, flip=flip)
 
 
-USAGE = ("usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible [--views 6|14|26] [--resolution R]]\n"
-         "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--signed] [--split val] [--device cuda]\n"
-         "       python -m pdgn_amd.meshes occupancy MESHES.npz OUT.npz --resolution R [--shape I,J,...] [--visible] [--split val] [--device cuda]\n"
-         "       python -m pdgn_amd.meshes check MESHES.npz [--samples N] [--split val] [--device cuda]\n"
+USAGE = ("usage: python -m pdgn_amd.meshes pack DIR OUT.npz [--visible] [--orient] [--views 6|14|26] [--resolution R]\n"
+         "       python -m pdgn_amd.meshes distance CLOUDS.npy MESHES.npz [--shape I,J,...] [--visible] [--signed] [--orient] [--split val] "
+         "[--device cuda]\n"
+         "       python -m pdgn_amd.meshes occupancy MESHES.npz OUT.npz --resolution R [--shape I,J,...] [--visible] [--orient] [--split val] "
+         "[--device cuda]\n"
+         "       python -m pdgn_amd.meshes check MESHES.npz [--samples N] [--orient] [--split val] [--device cuda]\n"
          "       python -m pdgn_amd.meshes render MESHES.npz -o sheet.png [--split val] [--shape I,J,...] [--rows N] [--cols N] [--cell C] "
-         "[--visible] [--shade flat|depth] [--device cuda]")
+         "[--visible] [--orient] [--shade flat|depth] [--device cuda]")
 
 
 def distance_table(result):
@@ -853,17 +974,23 @@ def _shape_option(text):
         raise SystemExit("--shape takes integers separated by commas\n" + USAGE) from None
 
 
-def _open_meshset(path, split, visible):
-    """MESHES.npz of the commands: a file `pack` wrote (one split of it, raw geometry) or one `MeshSet.save` wrote."""
+def _open_meshset(path, split, visible, orient=False):
+    """MESHES.npz of the commands: a file `pack` wrote (one split of it, raw geometry) or one `MeshSet.save` wrote.  orient: the set must
+    carry orientation flips (the caller applies them: `.oriented()`)."""
     with np.load(path) as f:
         packed = any(k.count("/") == 2 for k in f.files)
     if not packed:
-        return MeshSet.load(path)
+        ms = MeshSet.load(path)
+        if orient and ms.flip is None:
+            raise SystemExit("--orient: %s holds no orientation flips (pack --orient writes them)" % (path,))
+        return ms
     root = open_mesh_root(path)
     if visible and not has_stored_visible(root, split):
         raise SystemExit("--visible: %s holds no visibility masks for its %r split (pack --visible writes them)" % (path, split))
+    if orient and not has_stored_flip(root, split):
+        raise SystemExit("--orient: %s holds no orientation flips for its %r split (pack --orient writes them)" % (path, split))
     try:
-        return split_meshset(root, split, visible="stored" if visible else None)
+        return split_meshset(root, split, visible="stored" if visible else None, orient="stored" if orient else None)
     except ValueError as e:
         raise SystemExit(str(e)) from None
 
@@ -872,14 +999,16 @@ def _distance_main(argv):
     """distance CLOUDS.npy MESHES.npz: CLOUDS (S,N,3) or (S,3,N), in the meshes' frame."""
     import torch
     from .evaluation import surface_fidelity
-    opts = _options(argv[2:], {"shape": None, "visible": False, "signed": False, "split": "val", "device": "cuda"}, ("--visible", "--signed"))
+    opts = _options(argv[2:], {"shape": None, "visible": False, "signed": False, "orient": False, "split": "val", "device": "cuda"},
+                    ("--visible", "--signed", "--orient"))
     clouds = np.load(argv[0])
     if clouds.ndim != 3 or 3 not in clouds.shape[1:]:
         raise SystemExit("%s: clouds are (S,N,3) or (S,3,N), got %s" % (argv[0], clouds.shape))
     if clouds.shape[2] != 3:
         clouds = clouds.transpose(0, 2, 1)
     shape = _shape_option(opts["shape"])
-    ms = _open_meshset(argv[1], opts["split"], opts["visible"])
+    ms = _open_meshset(argv[1], opts["split"], opts["visible"], opts["orient"])
+    ms = ms.oriented() if opts["orient"] else ms
     dev = torch.device(opts["device"])
     try:
         result = surface_fidelity(torch.from_numpy(np.ascontiguousarray(clouds, dtype=np.float32)).to(dev), ms.to(dev), shape,
@@ -893,12 +1022,13 @@ def _occupancy_main(argv):
     """occupancy MESHES.npz OUT.npz --resolution R: OUT holds "occupancy" (S',ceil(R^3 / 8)) uint8 -- np.packbits of every shape's (R,R,R)
     grid in (x, y, z) order -- with "resolution", "origin" (S',3), "voxel" (S') and "shape" (S')."""
     import torch
-    opts = _options(argv[2:], {"shape": None, "visible": False, "resolution": None, "split": "val", "device": "cuda"}, ("--visible",),
-                    ("--shape", "--split", "--device", "--resolution"))
+    opts = _options(argv[2:], {"shape": None, "visible": False, "orient": False, "resolution": None, "split": "val", "device": "cuda"},
+                    ("--visible", "--orient"), ("--shape", "--split", "--device", "--resolution"))
     if opts["resolution"] is None or not opts["resolution"].isdigit():
         raise SystemExit("occupancy takes --resolution R\n" + USAGE)
     shape = _shape_option(opts["shape"])
-    ms = _open_meshset(argv[0], opts["split"], opts["visible"]).to(torch.device(opts["device"]))
+    ms = _open_meshset(argv[0], opts["split"], opts["visible"], opts["orient"]).to(torch.device(opts["device"]))
+    ms = ms.oriented() if opts["orient"] else ms
     try:
         occ, origin, voxel = occupancy_grid(ms, shape, int(opts["resolution"]), visible_only=opts["visible"])
     except ValueError as e:
@@ -911,18 +1041,31 @@ def _occupancy_main(argv):
 
 
 def _check_main(argv):
-    """check MESHES.npz: `winding_report`, one row per shape."""
+    """check MESHES.npz: `winding_report`, one row per shape; --orient: as stored and with the stored flips applied, side by side."""
     import torch
-    opts = _options(argv[1:], {"samples": "4096", "split": "val", "device": "cuda"}, (), ("--samples", "--split", "--device"))
+    opts = _options(argv[1:], {"samples": "4096", "orient": False, "split": "val", "device": "cuda"}, ("--orient",),
+                    ("--samples", "--split", "--device"))
     if not opts["samples"].isdigit():
         raise SystemExit(USAGE)
-    ms = _open_meshset(argv[0], opts["split"], False).to(torch.device(opts["device"]))
+    ms = _open_meshset(argv[0], opts["split"], False, opts["orient"]).to(torch.device(opts["device"]))
+    verdict = lambda r: ("closed and consistently oriented" if r["fractional"].max() <= 0.01
+                         else "open, self-intersecting or inconsistently oriented shapes: signs are not to be trusted")
     rep = winding_report(ms, int(opts["samples"]))
-    print("shape %12s %12s %12s" % ("w_min", "w_max", "fractional"))
+    if not opts["orient"]:
+        print("shape %12s %12s %12s" % ("w_min", "w_max", "fractional"))
+        for c in range(ms.S):
+            print("%5d %12.6f %12.6f %12.4f" % (c, rep["w_min"][c], rep["w_max"][c], rep["fractional"][c]))
+        print("worst fractional share %.4f: %s" % (rep["fractional"].max(), verdict(rep)))
+        return
+    after = winding_report(ms.oriented(), int(opts["samples"]))
+    flipped = _per_shape(ms.flip.cpu().numpy().astype(np.int64), ms.face_off.cpu().numpy().astype(np.int64))
+    print("shape %8s | %12s %12s %12s | %12s %12s %12s" % ("flipped", "w_min", "w_max", "fractional", "w_min", "w_max", "fractional"))
+    print("      %8s | %38s | %38s" % ("", "as stored", "oriented"))
     for c in range(ms.S):
-        print("%5d %12.6f %12.6f %12.4f" % (c, rep["w_min"][c], rep["w_max"][c], rep["fractional"][c]))
-    print("worst fractional share %.4f: %s" % (rep["fractional"].max(), "closed and consistently oriented" if rep["fractional"].max() <= 0.01
-                                               else "open, self-intersecting or inconsistently oriented shapes: signs are not to be trusted"))
+        print("%5d %8d | %12.6f %12.6f %12.4f | %12.6f %12.6f %12.4f" % (c, flipped[c], rep["w_min"][c], rep["w_max"][c], rep["fractional"][c],
+                                                                       after["w_min"][c], after["w_max"][c], after["fractional"][c]))
+    print("as stored: worst fractional share %.4f: %s" % (rep["fractional"].max(), verdict(rep)))
+    print("oriented:  worst fractional share %.4f: %s" % (after["fractional"].max(), verdict(after)))
 
 
 def _render_main(argv):
@@ -931,11 +1074,12 @@ def _render_main(argv):
     import torch
     from .report import MAX_COLUMNS, MESH_SHADES, MeshColumn, render_sheet, write_png
     opts = _options(argv[1:], {"o": "sheet.png", "shape": None, "visible": False, "split": "val", "device": "cuda", "rows": "8",
-                               "cols": str(MAX_COLUMNS), "cell": "128", "shade": "flat"}, ("--visible",),
+                               "cols": str(MAX_COLUMNS), "cell": "128", "shade": "flat", "orient": False}, ("--visible", "--orient"),
                     ("--shape", "--split", "--device", "--rows", "--cols", "--cell", "--shade", "--o"))
     if not all(opts[k].isdigit() and int(opts[k]) > 0 for k in ("rows", "cols", "cell")) or opts["shade"] not in MESH_SHADES:
         raise SystemExit(USAGE)
-    ms = _open_meshset(argv[0], opts["split"], opts["visible"])
+    ms = _open_meshset(argv[0], opts["split"], opts["visible"], opts["orient"])
+    ms = ms.oriented() if opts["orient"] else ms
     if opts["visible"] and ms.visible is None:
         raise SystemExit("--visible: %s holds no visibility masks" % argv[0])
     try:
@@ -972,18 +1116,22 @@ def main(argv=None):
         return _check_main(argv[1:])
     if len(argv) < 3 or argv[0] != "pack":
         raise SystemExit(USAGE)
-    opts, rest, given = {"views": 26, "resolution": 128}, argv[3:], False
+    opts, rest, given, orient = {"views": 26, "resolution": 128}, argv[3:], False, False
     while rest:
         flag = rest.pop(0)
         if flag == "--visible":
             given = True
+        elif flag == "--orient":
+            orient = True
         elif flag in ("--views", "--resolution") and rest and rest[0].isdigit():
             opts[flag[2:]] = int(rest.pop(0))
         else:
             raise SystemExit(USAGE)
-    if not given and opts != {"views": 26, "resolution": 128}:
-        raise SystemExit("--views and --resolution go with --visible\n" + USAGE)
-    keys = pack(argv[1], argv[2], opts if given else None)
+    if not (given or orient) and opts != {"views": 26, "resolution": 128}:
+        raise SystemExit("--views and --resolution go with --visible or --orient\n" + USAGE)
+    said = lambda sid, split, r: print("%s/%s: %d of %d faces flipped, %d undecided, %d two-sided" % (
+        sid, split, int(r["flip"].sum()), r["flip"].shape[0], int(r["undecided"].sum()), int(r["two_sided"].sum())))
+    keys = pack(argv[1], argv[2], opts if given else None, dict(opts) if orient else None, said)
     print("packed %d arrays into %s" % (len(keys), argv[2]))
 
 
