@@ -36,7 +36,7 @@ typedef void *pdgn_stream_t; /* hipStream_t */
  * (csrc/abi.hip) and pdgn_amd/_lib.py reads it, together with the ctypes signature of every prototype below, from this
  * file: keep the prototypes to `int` / `long long` results and `int`, `long long`, `unsigned [int]`,
  * `unsigned long long`, `float`, `double`, pointer and pdgn_stream_t parameters, each with a name. */
-#define PDGN_ABI_VERSION 50
+#define PDGN_ABI_VERSION 51
 int pdgn_abi_version(void);
 
 /* ------------------------------------------------------------------ pointops
@@ -1386,6 +1386,52 @@ int pdgn_flatness(int b, int n, int k, const float *xyz, const int32_t *idx, flo
 long long pdgn_orient_workspace_ints(int b, int n, int k);
 int pdgn_orient_normals(int b, int n, int k, const float *xyz, const int32_t *idx, const float *normals_in, float *normals_out,
                         int32_t *parent, int32_t *stats, int32_t *workspace, pdgn_stream_t stream);
+
+/* ------------------------------------------------------------------ normal orientation from visibility (csrc/cloudvis.hip)
+ * The sign of a cloud's normals from which side of every point a ring of orthographic views sees (hidden point removal by a splatted
+ * depth buffer, Katz et al. 2007; the votes of Takayama et al. 2014, as pdgn_mesh_face_votes casts them for faces), then a pooling of
+ * the votes over each point's neighbours in its tangent plane.  Thin sheets, whose two sides fall into one neighbourhood, and clouds of
+ * any size: nothing here is sequential.  The header block of csrc/cloudvis.hip is the normative statement of both sets of rules;
+ * tests/cloudvis_mirror.py spells them in numpy and the two agree bit for bit.  No reference counterpart.
+ *
+ * pdgn_cloud_normal_votes: per (cloud, view) a depth buffer of R x R pixels in LDS (4 R^2 bytes), every live point's depth written by
+ * integer minima into the pixel that holds it and into every pixel whose centre lies within `splat` of it; then a point passes where its
+ * depth is at most its own pixel's minimum plus `bias`, and a point that passes adds w = (uint32)(min(|s|, 1) 256), s = g . e_z, to its
+ * front (s < 0) or back (s > 0) count.
+ *   xyz, normals  (b,n,3); a point with a value that is not finite among its six is dead: it splats nothing and gets no votes
+ *   frame   (b,4) float, device: per cloud the centre and the radius rho of a ball that holds it (pdgn_mesh_visibility's frame; a rho
+ *           that is not positive and finite snaps every point to a corner or the middle of the image: defined, and useless)
+ *   views   (NV,3,3) float, device: pdgn_mesh_visibility's table, 1 <= NV <= PDGN_VISIBLE_MAX_VIEWS
+ *   R       PDGN_CLOUDVIS_MIN_RES .. PDGN_VISIBLE_MAX_RES
+ *   splat   >= 0, in pixel units with 8 sub-pixel bits (256 = one pixel): the radius of a point's disc; 0 writes the own pixel only
+ *   bias    >= 0, in depth quanta of rho 2^-20
+ *   votes   (b,n,2) uint32, cleared here on `stream`: front, back; at most NV 256 per word
+ * One memset and one launch of b NV workgroups on `stream`, no host synchronisation, nothing allocated; integer minima and integer sums
+ * only: a pure function of the arguments bit for bit, and a permutation of a cloud's points permutes its rows.
+ *
+ * pdgn_orient_pool: v_i = front_i - back_i, then `rounds` Jacobi rounds v'_i = 2 v_i + sum over the slots of c_ij v_j, c_ij in {-1, 0, 1}
+ * the sign of g_i . g_j where j lies in the tangent planes of both points and the two normal lines are within 60 degrees, and
+ * o_i = -g_i iff the final v_i < 0.
+ *   idx         (b,n,k) int32 as pdgn_orient_normals takes them: out of range (never dereferenced), self and dead entries are ignored,
+ *               a repeated entry counts as often as it occurs
+ *   normals_in  (b,n,3); normals_out (b,n,3): normals_in with the sign bit of all three components flipped or kept; may be normals_in
+ *   votes       (b,n,2) uint32: pdgn_cloud_normal_votes'
+ *   rounds      0 .. PDGN_CLOUDVIS_MAX_ROUNDS
+ *   pooled      (b,n) int64 or NULL: the final v_i (0 for a dead point)
+ *   stats       (b,4) int32 or NULL, cleared here on `stream`: normals flipped, live points undecided (final v_i == 0: they keep their
+ *               bits), live points unseen (front + back == 0 before any pooling), dead points
+ *   workspace   2 b n int64 of the caller's (16 b n bytes, 8-byte aligned; the rounds ping-pong through it); contents undefined on return
+ * rounds + 1 launches (and the memset of stats) on `stream`, one thread per point, integer atomics on stats only, nothing allocated;
+ * repeatable bit for bit.
+ * PDGN_ERR_INVALID, with nothing launched and nothing written: b < 1, n < 1, b n beyond 2^28, NV, R, k (1 .. PDGN_NORMALS_MAX_K) or rounds
+ * outside their ranges, a negative splat or bias, a null pointer (pooled and stats excepted), a pointer not 4-byte (pooled, workspace:
+ * 8-byte) aligned. */
+#define PDGN_CLOUDVIS_MIN_RES 1
+#define PDGN_CLOUDVIS_MAX_ROUNDS 4
+int pdgn_cloud_normal_votes(int b, int n, const float *xyz, const float *normals, const float *frame, const float *views, int NV, int R,
+                            int splat, int bias, uint32_t *votes, pdgn_stream_t stream);
+int pdgn_orient_pool(int b, int n, int k, const float *xyz, const int32_t *idx, const float *normals_in, const uint32_t *votes, int rounds,
+                     float *normals_out, long long *pooled, int32_t *stats, long long *workspace, pdgn_stream_t stream);
 
 /* ------------------------------------------------------------------ surface reconstruction (csrc/reconstruct.hip)
  * From oriented points to a triangle mesh: a signed-distance field on a regular grid by implicit moving least squares with the compact

@@ -4,11 +4,12 @@ reconstruction, MeshLab and Blender take).
     write_ply("chair.ply", xyz, normals)
     python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient outward
     python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient consistent
+    python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --normals 16 --orient visible
     python -m pdgn_amd.export results/GEN_Ours_chair_<time>/out.npy -o plys --count 16 --mesh 64
     write_ply("chair_mesh.ply", verts, faces=faces);  write_obj("chair_mesh.obj", verts, faces)
 
 The writers are struct and numpy only, as report.write_png is; only the command line's --normals and --mesh touch the device
-(pointops.estimate_normals; --orient consistent: pointops.orient_normals, section 7r; --mesh: reconstruct.imls_field and
+(pointops.estimate_normals; --orient consistent: pointops.orient_normals, section 7r; --orient visible: pointops.orient_normals_visible, section 7z; --mesh: reconstruct.imls_field and
 reconstruct.surface_nets, section 7s)."""
 import argparse
 import os
@@ -19,6 +20,7 @@ import numpy as np
 
 PLY_PROPERTIES = ("x", "y", "z", "nx", "ny", "nz")
 CONSISTENT_MAX_POINTS = 4096                                       # PDGN_ORIENT_MAX_N
+VISIBLE_MAX_POINTS = 8192                                          # PDGN_REPULSION_MAX_N: the spacing behind --orient_radius_factor
 MESH_FORMATS = ("ply", "obj")
 MESH_BATCH_NODES = 1 << 24                                         # --mesh: clouds per field launch so that B R^3 floats stay at 64 MB
 
@@ -101,11 +103,19 @@ def build_parser():
     p.add_argument("--count", type=int, default=None, help="clouds written (default: all from --first on)")
     p.add_argument("--normals", type=int, default=None, metavar="K", help="add per-point normals estimated from the K nearest neighbours "
                    "(pointops.estimate_normals; needs the device)")
-    p.add_argument("--orient", choices=["outward", "consistent", "none"], default="outward", action=_Given, help="--normals: outward (default) turns every "
+    p.add_argument("--orient", choices=["outward", "consistent", "visible", "none"], default="outward", action=_Given, help="--normals: outward (default) turns every "
                    "normal away from its cloud's centroid -- a heuristic that is right for roughly convex shapes and wrong inside concavities; "
                    "consistent propagates the sign along a minimum spanning tree of the neighbour graph from each component's highest point "
-                   "(what Poisson reconstruction needs; clouds of at most %d points); none leaves the sign convention of the estimate "
+                   "(what Poisson reconstruction needs; clouds of at most %d points); visible asks a ring of orthographic views which side of "
+                   "every point they see and pools the answers over each point's tangent plane (thin sheets -- seats, table tops --, which "
+                   "consistent gets wrong; needs views that reach the surface); none leaves the sign convention of the estimate "
                    "(largest component non-negative)" % CONSISTENT_MAX_POINTS)
+    p.add_argument("--orient_views", type=int, choices=[6, 14, 26], default=None, help="--orient visible: the number of views (default 26)")
+    p.add_argument("--orient_resolution", type=int, default=None, metavar="R", help="--orient visible: pixels per side of a view's depth "
+                   "buffer, 1 .. 192 (default 64)")
+    p.add_argument("--orient_radius_factor", type=float, default=None, metavar="F", help="--orient visible: a point is splatted as a disc "
+                   "of F times its cloud's mean nearest-neighbour distance (default 2)")
+    p.add_argument("--orient_rounds", type=int, default=None, metavar="N", help="--orient visible: pooling rounds, 0 .. 4 (default 1)")
     p.add_argument("--mesh", type=int, default=None, metavar="R", help="also reconstruct every cloud's surface on a grid of R nodes per axis "
                    "(reconstruct.imls_field and surface_nets; needs the device) and write mesh_<index>.<ext> beside the cloud; implies "
                    "--normals 16 --orient consistent unless they are given, and refuses --orient none")
@@ -127,7 +137,7 @@ def main(argv=None):
             p.error("--mesh_radius, --mesh_radius_factor and --mesh_format go with --mesh")
     else:
         if args.orient == "none":
-            p.error("--mesh needs oriented normals: --orient outward or consistent, not none")
+            p.error("--mesh needs oriented normals: --orient outward, consistent or visible, not none")
         if not 2 <= args.mesh <= 256:
             p.error("--mesh %d: between 2 and 256 nodes per axis" % args.mesh)
         if args.mesh_radius is not None and args.mesh_radius_factor is not None:
@@ -139,6 +149,16 @@ def main(argv=None):
             args.normals = 16
         if not getattr(args, "orient_given", False):
             args.orient = "consistent"
+    visible_opts = ("orient_views", "orient_resolution", "orient_radius_factor", "orient_rounds")
+    if args.orient != "visible" and any(getattr(args, name) is not None for name in visible_opts):
+        p.error("--orient_views, --orient_resolution, --orient_radius_factor and --orient_rounds go with --orient visible")
+    if args.orient == "visible":
+        if args.orient_resolution is not None and not 1 <= args.orient_resolution <= 192:
+            p.error("--orient_resolution %d: between 1 and 192 pixels per side" % args.orient_resolution)
+        if args.orient_radius_factor is not None and not args.orient_radius_factor > 0:
+            p.error("--orient_radius_factor must be positive")
+        if args.orient_rounds is not None and not 0 <= args.orient_rounds <= 4:
+            p.error("--orient_rounds %d: between 0 and 4" % args.orient_rounds)
     pcs = np.load(args.clouds)
     if pcs.ndim != 3 or 3 not in pcs.shape[1:]:
         raise SystemExit("%s: expected (S, N, 3) or (S, 3, N), got %s" % (args.clouds, pcs.shape))
@@ -153,6 +173,11 @@ def main(argv=None):
             p.error("--orient consistent: clouds of at most %d points, the file's have %d" % (CONSISTENT_MAX_POINTS, pcs.shape[1]))
         if args.normals > 64:
             p.error("--orient consistent: --normals at most 64, got %d" % args.normals)
+    if args.normals is not None and args.orient == "visible":
+        if pcs.shape[1] > VISIBLE_MAX_POINTS:
+            p.error("--orient visible: the spacing is measured on clouds of at most %d points, the file's have %d" % (VISIBLE_MAX_POINTS, pcs.shape[1]))
+        if args.normals > 64:
+            p.error("--orient visible: --normals at most 64, got %d" % args.normals)
     stop = pcs.shape[0] if args.count is None else min(pcs.shape[0], args.first + args.count)
     pcs = np.ascontiguousarray(pcs[args.first:stop], dtype=np.float32)
     normals = [None] * pcs.shape[0]
@@ -168,6 +193,16 @@ def main(argv=None):
             oriented, _, stats = orient_normals(x, estimate_normals(x, idx=idx), idx=idx, return_tree=True)
             normals = list(oriented.cpu().numpy())
             tree = " (%d components, %d weak tree edges)" % tuple(stats[:, [0, 2]].sum(dim=0).tolist())
+        elif args.orient == "visible":                            # (every cloud in one batched call)
+            from .pointops import knnquery, orient_normals_visible
+            x = torch.from_numpy(pcs).to(dev)
+            idx = knnquery(args.normals, x, x)
+            opts = {"views": args.orient_views, "resolution": args.orient_resolution, "radius_factor": args.orient_radius_factor,
+                    "rounds": args.orient_rounds}
+            oriented, stats = orient_normals_visible(x, estimate_normals(x, idx=idx), idx=idx, return_stats=True,
+                                                     **{name: v for name, v in opts.items() if v is not None})
+            normals = list(oriented.cpu().numpy())
+            tree = " (%d points undecided, %d unseen by every view)" % tuple(stats[:, [1, 2]].sum(dim=0).tolist())
         else:
             for i in range(pcs.shape[0]):                        # (a cloud at a time: the centroid is an argument of the launch)
                 x = torch.from_numpy(pcs[i:i + 1]).to(dev)

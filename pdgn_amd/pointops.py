@@ -75,7 +75,9 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
     (normals, eig (B,N,3)), the neighbourhood covariance's eigenvalues ascending.  idx: (B,N,k') int32 neighbour lists of the caller's
     (`k` is then ignored); None: knnquery(k, xyz, xyz), which needs k <= N.  orient: None (the component of largest magnitude is made
     non-negative), ("direction", v) (n . v >= 0), ("towards", p) (n . (p - x) >= 0) or ("away", p) (n . (x - p) >= 0), v / p three
-    numbers, or "consistent" (the estimate with orient=None, then orient_normals with the same lists: N <= 4096, k <= 64).  A point with
+    numbers, or "consistent" (the estimate with orient=None, then orient_normals with the same lists: N <= 4096, k <= 64), or "visible"
+    (the estimate with orient=None, then orient_normals_visible at its defaults with the same lists: any N, k <= 64; thin sheets, which
+    "consistent" gets wrong).  A point with
     an index outside the cloud or a non-finite neighbour gets NaNs.  NOT differentiable: the results carry no graph (the differentiable
     flatness loss on the same eigenvalues is losses.flatness)."""
     require(xyz, "xyz", F32, 3)
@@ -92,8 +94,9 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
             raise ValueError("idx must be (B,N,k) on xyz's device, got %s for xyz %s" % (tuple(idx.shape), tuple(xyz.shape)))
     mode, o = 0, (0.0, 0.0, 0.0)
     consistent = isinstance(orient, str) and orient == "consistent"
-    if orient is not None and not consistent:
-        bad = "orient must be None, \"consistent\" or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,)
+    visible = isinstance(orient, str) and orient == "visible"
+    if orient is not None and not consistent and not visible:
+        bad = "orient must be None, \"consistent\", \"visible\" or (\"direction\" | \"towards\" | \"away\", three numbers), got %r" % (orient,)
         try:
             kind, o = orient
             mode, o = _ORIENT[kind], tuple(float(v) for v in o)
@@ -109,6 +112,8 @@ def estimate_normals(xyz, k=16, idx=None, orient=None, return_eig=False):
                                            stream_of(xyz)), "pdgn_estimate_normals")
     if consistent:
         normals = orient_normals(xyz, normals, idx=idx)
+    if visible:
+        normals = orient_normals_visible(xyz, normals, idx=idx)
     return (normals, eig) if return_eig else normals
 
 
@@ -152,6 +157,135 @@ def orient_normals(xyz, normals, k=16, idx=None, return_tree=False):
     check(L.pdgn_orient_normals(b, n, idx.shape[2], ptr(xyz), ptr(idx), ptr(normals), ptr(out), ptr(parent), ptr(stats), ptr(work),
                                 stream_of(xyz)), "pdgn_orient_normals")
     return (out, parent, stats) if return_tree else out
+
+
+VISIBLE_MAX_VIEWS, VISIBLE_MAX_RESOLUTION = 32, 192                # PDGN_VISIBLE_MAX_VIEWS, PDGN_VISIBLE_MAX_RES
+VISIBLE_SPACING_MAX_N = 8192                                       # PDGN_REPULSION_MAX_N: the all-pairs launch behind radius=None
+POOL_MAX_ROUNDS = 4                                                # PDGN_CLOUDVIS_MAX_ROUNDS
+
+
+def _cloud_pair(xyz, normals, what):
+    require(xyz, "xyz", F32, 3)
+    require(normals, "normals", F32, 3)
+    if xyz.shape[2] != 3 or xyz.shape[0] < 1 or xyz.shape[1] < 1:
+        raise ValueError("%s: xyz must be (B,N,3) with B, N >= 1, got %s" % (what, tuple(xyz.shape)))
+    if normals.shape != xyz.shape or normals.device != xyz.device:
+        raise ValueError("%s: normals must be (B,N,3) on xyz's device, got %s for xyz %s" % (what, tuple(normals.shape), tuple(xyz.shape)))
+    return xyz.shape[0], xyz.shape[1]
+
+
+@torch.no_grad()
+def cloud_frames(xyz):
+    """(B,4) fp32 (centre, radius) per cloud: the centre of the box of its points and the largest distance of a point from it times
+    (1 + 2^-10), in fp64 torch ops on the device, rounded once -- meshes.shape_frames' rule for points.  Points with a non-finite
+    coordinate do not count; a cloud without a finite point, or of one repeated point, gets the radius 1."""
+    require(xyz, "xyz", F32, 3)
+    if xyz.shape[2] != 3 or xyz.shape[0] < 1 or xyz.shape[1] < 1:
+        raise ValueError("cloud_frames: xyz must be (B,N,3) with B, N >= 1, got %s" % (tuple(xyz.shape),))
+    x = xyz.double()
+    ok = torch.isfinite(x).all(dim=2, keepdim=True)
+    lo = torch.where(ok, x, torch.full_like(x, float("inf"))).amin(dim=1)
+    hi = torch.where(ok, x, torch.full_like(x, float("-inf"))).amax(dim=1)
+    ctr = torch.where(ok.any(dim=1), (lo + hi) / 2, torch.zeros_like(lo))
+    d2 = torch.where(ok[:, :, 0], ((x - ctr[:, None, :]) ** 2).sum(dim=2), torch.zeros_like(x[:, :, 0])).amax(dim=1)
+    rho = d2.sqrt() * (1.0 + 2.0 ** -10)
+    rho = torch.where(rho > 0, rho, torch.ones_like(rho))
+    return torch.cat([ctr, rho[:, None]], dim=1).float().contiguous()
+
+
+def _view_table(views, what):
+    from .meshes import default_views, view_bases
+    table = default_views(views) if np.ndim(views) == 0 else np.asarray(views.cpu() if isinstance(views, torch.Tensor) else views)
+    table = view_bases(table) if table.ndim == 2 else np.ascontiguousarray(table, dtype=np.float32)
+    if table.ndim != 3 or table.shape[1:] != (3, 3) or not 1 <= table.shape[0] <= VISIBLE_MAX_VIEWS:
+        raise ValueError("%s: views are a count, (NV,3) directions or (NV,3,3) bases, at most %d, got %s" % (what, VISIBLE_MAX_VIEWS, table.shape,))
+    return table
+
+
+@torch.no_grad()
+def normal_votes(xyz, normals, views=26, resolution=64, radius=None, radius_factor=2.0, bias=None, bias_factor=0.25, return_quanta=False):
+    """From which side a ring of orthographic views sees every point (pdgn_cloud_normal_votes, csrc/cloudvis.hip; no
+    reference counterpart): per (cloud, view) a depth buffer into which every point is splatted as a disc, then every point that is at
+    most `bias` behind its own pixel's nearest depth votes with the weight (int)(256 min(|n . e_z|, 1)) for the side of it the view sees.
+    xyz, normals (B,N,3) fp32 on the device -> (front, back) (B,N) int32: front counts the views the normal faces.  views as in
+    meshes.face_visibility: 6 / 14 / 26, (NV,3) directions to look from, or (NV,3,3) bases.  resolution: pixels per image side, 1 .. 192.
+    radius: the disc's, in the units of xyz, a number or (B); None: radius_factor times each cloud's mean nearest-neighbour distance (the
+    all-pairs launch of reconstruct.mean_spacing: clouds of at most 8192 points then; a given radius has no limit).  bias: a depth in the
+    units of xyz, a number or (B); None: bias_factor times the radius.  The launch takes ONE disc radius in sub-pixel units (256 to the
+    pixel) and ONE bias in depth quanta (2^-20 of a frame's radius) for the whole batch: the batch means of radius / rho R 2^7 and of
+    bias / rho 2^20 over the clouds' frames (cloud_frames), in fp64, each rounded once.  return_quanta=True appends {"splat", "bias"
+    (those two integers), "frame" (B,4), "views" (NV,3,3) device tensors}: what a restatement of the kernel is fed.  NOT differentiable."""
+    b, n = _cloud_pair(xyz, normals, "normal_votes")
+    R = int(resolution)
+    if not 1 <= R <= VISIBLE_MAX_RESOLUTION:
+        raise ValueError("normal_votes: resolution %r, between 1 and %d pixels per side" % (resolution, VISIBLE_MAX_RESOLUTION))
+    table = torch.from_numpy(_view_table(views, "normal_votes")).to(xyz.device)
+    frame = cloud_frames(xyz)
+    if radius is None:
+        if not float(radius_factor) > 0:
+            raise ValueError("normal_votes: radius_factor must be positive, got %r" % (radius_factor,))
+        if n > VISIBLE_SPACING_MAX_N:
+            raise ValueError("normal_votes: radius=None measures the spacing of clouds of at most %d points, got %d: give a radius"
+                             % (VISIBLE_SPACING_MAX_N, n))
+        from .reconstruct import mean_spacing
+        radius = float(radius_factor) * mean_spacing(xyz)
+    radius = torch.as_tensor(radius, dtype=torch.float64, device=xyz.device).expand(b)
+    if bias is None:
+        if not float(bias_factor) >= 0:
+            raise ValueError("normal_votes: bias_factor must not be negative, got %r" % (bias_factor,))
+        bias = float(bias_factor) * radius
+    bias = torch.as_tensor(bias, dtype=torch.float64, device=xyz.device).expand(b)
+    rho = frame[:, 3].double()
+    splat_q, bias_q = float((radius / rho).mean() * (R * 128.0)), float((bias / rho).mean() * 1048576.0)
+    if not (0 <= splat_q < 2 ** 30 and 0 <= bias_q < 2 ** 30):
+        raise ValueError("normal_votes: radius and bias must be finite and not negative (a disc of %r sub-pixel units, a bias of %r quanta)" % (splat_q, bias_q))
+    splat_q, bias_q = int(np.rint(splat_q)), int(np.rint(bias_q))
+    votes = torch.empty((b, n, 2), dtype=I32, device=xyz.device)
+    check(_lib.lib().pdgn_cloud_normal_votes(b, n, ptr(xyz), ptr(normals), ptr(frame), ptr(table), int(table.shape[0]), R, splat_q, bias_q,
+                                             ptr(votes), stream_of(xyz)), "pdgn_cloud_normal_votes")
+    front, back = votes[:, :, 0].contiguous(), votes[:, :, 1].contiguous()
+    if return_quanta:
+        return front, back, {"splat": splat_q, "bias": bias_q, "frame": frame, "views": table}
+    return front, back
+
+
+@torch.no_grad()
+def orient_normals_visible(xyz, normals, k=16, idx=None, rounds=1, views=26, resolution=64, radius=None, radius_factor=2.0, bias=None,
+                           bias_factor=0.25, return_votes=False, return_stats=False):
+    """The sign of every normal from visibility (pdgn_cloud_normal_votes and pdgn_orient_pool, csrc/cloudvis.hip; no
+    reference counterpart): `normal_votes`, then `rounds` (0 .. 4) Jacobi rounds in which a point adds to twice its own balance
+    front - back the balances of its neighbours that lie in its tangent plane and agree with its normal line, then a negative balance turns
+    the normal round.  Where orient_normals propagates a sign along a tree -- across a thin sheet at no cost, to 4096 points at most --
+    this asks the outside directly: sheets thinner than a neighbourhood and clouds of any size.  It needs views that can see the surface:
+    the inside of a cavity no view reaches stays undecided, or takes its neighbours' sign.  xyz, normals (B,N,3) fp32 on the device
+    (estimate_normals' with orient=None) -> normals (B,N,3), a new tensor that differs from the input in sign bits alone (a point with
+    balance 0 keeps its bits)[, with return_votes=True (front, back (B,N) int32, pooled (B,N) int64: the final balance)][, with
+    return_stats=True stats (B,4) int32: normals flipped, live points undecided, live points no view saw, dead points (a non-finite
+    coordinate or normal)].  idx as in orient_normals: (B,N,k') int32 lists, or None: knnquery(k, xyz, xyz); k' <= 64.  The remaining
+    arguments are normal_votes'.  NOT differentiable."""
+    b, n = _cloud_pair(xyz, normals, "orient_normals_visible")
+    if not 0 <= int(rounds) <= POOL_MAX_ROUNDS:
+        raise ValueError("orient_normals_visible: rounds between 0 and %d, got %r" % (POOL_MAX_ROUNDS, rounds))
+    if idx is None:
+        if not 1 <= int(k) <= min(n, ORIENT_MAX_K):
+            raise ValueError("orient_normals_visible: k = %r neighbours of a cloud of %d points (at most %d)" % (k, n, ORIENT_MAX_K))
+        idx = knnquery(int(k), xyz, xyz)
+    else:
+        require(idx, "idx", I32, 3)
+        if tuple(idx.shape[:2]) != (b, n) or idx.device != xyz.device:
+            raise ValueError("idx must be (B,N,k) on xyz's device, got %s for xyz %s" % (tuple(idx.shape), tuple(xyz.shape)))
+        if not 1 <= idx.shape[2] <= ORIENT_MAX_K:
+            raise ValueError("orient_normals_visible: lists of 1 .. %d neighbours, got %d" % (ORIENT_MAX_K, idx.shape[2]))
+    front, back = normal_votes(xyz, normals, views, resolution, radius, radius_factor, bias, bias_factor)
+    votes = torch.stack([front, back], dim=2).contiguous()
+    out = torch.empty_like(normals)
+    pooled = torch.empty((b, n), dtype=torch.int64, device=xyz.device) if return_votes else None
+    stats = torch.empty((b, 4), dtype=I32, device=xyz.device) if return_stats else None
+    work = torch.empty((2, b, n), dtype=torch.int64, device=xyz.device)
+    check(_lib.lib().pdgn_orient_pool(b, n, idx.shape[2], ptr(xyz), ptr(idx), ptr(normals), ptr(votes), int(rounds), ptr(out), ptr(pooled),
+                                      ptr(stats), ptr(work), stream_of(xyz)), "pdgn_orient_pool")
+    result = (out,) + (((front, back, pooled),) if return_votes else ()) + ((stats,) if return_stats else ())
+    return result if len(result) > 1 else out
 
 
 class Grouping(Function):

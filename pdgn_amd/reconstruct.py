@@ -18,6 +18,7 @@ from ._lib import check, ptr, require, stream_of
 
 F32, I32 = torch.float32, torch.int32
 MIN_RESOLUTION, MAX_RESOLUTION = 2, 256                            # PDGN_RECON_MIN_R, PDGN_RECON_MAX_R
+VISIBLE_DISC_OF_SUPPORT = 0.4                                      # orient="visible" with a given support h: the disc's radius is 0.4 h (2 of the default 5 spacings)
 
 
 def _clouds(xyz, name="xyz"):
@@ -140,16 +141,24 @@ def surface_nets(field, origin, voxel):
 
 
 @torch.no_grad()
-def reconstruct(xyz, normals=None, k=16, resolution=64, radius=None, radius_factor=5.0):
+def reconstruct(xyz, normals=None, k=16, resolution=64, radius=None, radius_factor=5.0, orient="consistent"):
     """Clouds to meshes: xyz (B,N,3) -> surface_nets' five results.  normals: oriented normals (B,N,3); None: knnquery(k),
-    estimate_normals and orient_normals first (clouds of at most 4096 points, k at most 64, then)."""
+    estimate_normals and, by `orient`, "consistent": orient_normals (clouds of at most 4096 points, k at most 64, then) or "visible":
+    orient_normals_visible at its defaults (k at most 64; no limit on the points where `radius` is given, and where it is given the
+    discs of the depth pass take 0.4 of it: two of the five spacings the default support spans)."""
     _clouds(xyz)
+    if orient not in ("consistent", "visible"):
+        raise ValueError("reconstruct: orient is \"consistent\" or \"visible\", got %r" % (orient,))
     if normals is None:
-        from .pointops import estimate_normals, knnquery, orient_normals
+        from .pointops import estimate_normals, knnquery, orient_normals, orient_normals_visible
         if not 1 <= int(k) <= xyz.shape[1]:
             raise ValueError("reconstruct: k = %r neighbours of a cloud of %d points" % (k, xyz.shape[1]))
         idx = knnquery(int(k), xyz, xyz)
-        normals = orient_normals(xyz, estimate_normals(xyz, idx=idx), idx=idx)
+        if orient == "visible":
+            disc = None if radius is None else torch.as_tensor(radius, dtype=torch.float64, device=xyz.device) * VISIBLE_DISC_OF_SUPPORT
+            normals = orient_normals_visible(xyz, estimate_normals(xyz, idx=idx), idx=idx, radius=disc)
+        else:
+            normals = orient_normals(xyz, estimate_normals(xyz, idx=idx), idx=idx)
     field, origin, voxel = imls_field(xyz, normals, resolution, radius, radius_factor)
     return surface_nets(field, origin, voxel)
 
